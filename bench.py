@@ -7,11 +7,14 @@ GP_Utils.cpp:130-157, 1138-1162): fused Gram/B fill, blocked Cholesky, two trian
 f = K*alpha, log-det and the nlZ reductions.  X and y are resident in HBM before the timed
 region; parameters (10 doubles) are the only per-step host input.
 
-Prints ONE JSON line (see the driver contract): metric/value/unit + `roofline` for the
-dominant kernel (the MFMA trailing update of the Cholesky) + `cpu_baseline` (the oracle's
-reference-sequence on the host cores, bounded sample).
+Prints ONE JSON line (see the driver contract): metric/value/unit/ms_per_step + `roofline` for the
+dominant kernel (the MFMA trailing update of the Cholesky), from the timed steps' own phase times.
+A plain run does only that; `--full` adds the sub-runs and reference points: calibration, N=65536,
+configs 2 / 3 / 5, the vendor Cholesky and `cpu_baseline` (the oracle's reference sequence on the
+host cores, bounded sample).  `--dump-outputs DIR` writes what the last timed step computed.
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -40,6 +43,25 @@ def params_for_step(i):
     return e, synth.DEFAULT_BIAS, synth.DEFAULT_SN2 * (1.0 + 1e-3 * (i % 3))
 
 
+@functools.lru_cache(maxsize=None)
+def _openblas_pool():
+    """Threads of the OpenBLAS that oracle.use_lapack() binds (SciPy's wheel), None without it.  Read once, at the first
+    call -- before this process changes the count with use_lapack() -- and remembered: the pool it started with."""
+    import ctypes
+    import glob
+    try:
+        import scipy
+    except ImportError:
+        return None
+    root = os.path.join(os.path.dirname(os.path.dirname(scipy.__file__)), "scipy.libs")
+    cands = sorted(glob.glob(os.path.join(root, "libscipy_openblas*.so")))
+    if not cands:
+        return None
+    lib = ctypes.CDLL(cands[0])     # the same file, hence the same loaded instance, as the oracle's
+    get = getattr(lib, "scipy_openblas_get_num_threads", None) or getattr(lib, "openblas_get_num_threads", None)
+    return int(get()) if get else None
+
+
 def cpu_baseline(n_full, sample_n):
     """Reference operation sequence on the host cores through the CPU oracle (kind: port)."""
     from gp_ss_ak_amd import synth
@@ -49,14 +71,20 @@ def cpu_baseline(n_full, sample_n):
         cores = len(os.sched_getaffinity(0))
     except AttributeError:
         pass
+    # OpenBLAS sizes its thread pool once, when it is loaded (OPENBLAS_NUM_THREADS / OMP_NUM_THREADS, else the CPUs it
+    # sees, at most its MAX_THREADS); asked later for more threads than that pool holds, its dpotrf segfaults.  A host
+    # that shows more CPUs than it grants (OMP_NUM_THREADS set to the grant) made the probe below start far above it.
+    pool = _openblas_pool()
+    if pool:
+        cores = min(cores, pool)
     X, y = synth.drillholes(sample_n)
     e, bias, sn2 = params_for_step(0)
     t0 = time.perf_counter()
     K = orc.gram(X, X, e, bias, orc.DIST_EXPANSION)
     t_gram = time.perf_counter() - t0
     # give the CPU its best shot: OpenBLAS on all visible hardware threads is often slower than on the
-    # physical cores, and a container may see many more cores than its CPU share (256 visible, 16 granted
-    # on the GPU box) -- a small probe picks the thread count, the timed run uses it
+    # physical cores, and a container may see many more cores than its CPU share -- a small probe picks the
+    # thread count (never above the pool OpenBLAS started with), the timed run uses it
     lapack, best = False, (None, cores)
     for thr in sorted({t for t in (cores, cores // 2, cores // 4, 32, 16, 8) if 1 <= t <= cores}, reverse=True):
         lapack = orc.use_lapack(thr)
@@ -122,6 +150,13 @@ def _timed_steps(g, mode, steps, warmup):
             phases[k] += t[k]
         launches += t["trailing_launches"]
     return time.perf_counter() - t0, nlz, phases, launches
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one float64 DIR/<name>.npy per array, so that two builds can be compared output for output."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _sources_sha16():
@@ -321,6 +356,11 @@ def run_single(args):
             out["roofline"]["peak_at_in_situ_clock"] = PEAK_F64_MFMA_TFLOPS * ghz / 2.4
             out["roofline"]["mfma_busy_frac"] = (pm["mfma_busy_cycles_per_launch"] / (256 * 4) /
                                                  (pm["grbm_gui_active_per_launch"] / 8.0))
+    if args.dump_outputs:
+        # what the last timed step left in the context, before any sub-run below changes it: nothing is recomputed
+        quad, sumlp, logdet = g.nlz_terms()
+        dump_outputs(args.dump_outputs, {"nlz": np.array([nlz]), "nlz_terms": np.array([quad, sumlp, logdet]),
+                                         "alpha": g.solve_alpha()})
     if args.grad:
         # config 3 of BASELINE.json: what one Grad_Values() of the L-BFGS loop costs on top of ObjVal()
         t0 = time.perf_counter()
@@ -537,7 +577,15 @@ def launch_multi(args, argv):
                      (N, time.perf_counter() - t_all, json.dumps(attempts)))
 
 
-def main():
+# options that select or shape a sub-run beyond the headline, with their values under --full (the defaults of the
+# options) and in a plain run (every sub-run off)
+FULL_DEFAULTS = {"cpu_n": 16384, "grad": 0, "calibrate": True, "vendor": 1, "config2": 8192, "config3": 3,
+                 "config5": 1000000, "grid": "auto"}
+PLAIN_VALUES = {"cpu_n": 16384, "grad": 0, "calibrate": False, "vendor": 0, "config2": 0, "config3": 0, "config5": 0,
+                "grid": "none", "no_cpu": True, "no_n65536": True}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -546,25 +594,50 @@ def main():
     ap.add_argument("--n", "--size", dest="n", type=int, default=32768)
     ap.add_argument("--dist", choices=["direct", "expansion"], default="direct")
     ap.add_argument("--nb-outer", type=int, default=0)
-    ap.add_argument("--cpu-n", type=int, default=16384, help="sample size of the CPU baseline (~15 s of CPU work)")
+    ap.add_argument("--cpu-n", type=int, help="sample size of the CPU baseline (~15 s of CPU work)")
     ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--grad", type=int, default=0, help="also time this many GradLL evaluations (config 3)")
-    ap.add_argument("--calibrate", action="store_true", default=True)
+    ap.add_argument("--grad", type=int, help="also time this many GradLL evaluations (config 3)")
+    ap.add_argument("--calibrate", action="store_true", default=None)
     ap.add_argument("--no-n65536", action="store_true", help="skip the N=65536 sub-run (north_star's scaling size)")
-    ap.add_argument("--vendor", type=int, default=1, help="1: time torch.linalg.cholesky (hipSOLVER / rocSOLVER) on the same matrix as a "
+    ap.add_argument("--vendor", type=int, help="1: time torch.linalg.cholesky (hipSOLVER / rocSOLVER) on the same matrix as a "
                     "reference point (N=32768 and the config-2 size)")
-    ap.add_argument("--config2", type=int, default=8192, help="size of the configs[1] sub-run (GPU step and the CPU "
-                                                               "reference sequence at full size; 0 = skip)")
-    ap.add_argument("--config3", type=int, default=3, help="L-BFGS iterations of the configs[2] sub-run through the CLI "
-                                                            "(N=32768 only; 0 = skip)")
-    ap.add_argument("--config5", type=int, default=1000000, help="test points of the configs[4] sub-run (N=32768 fp32 "
-                                                                  "prediction; 0 = skip)")
-    ap.add_argument("--grid", default="auto", help="N > 1: also time the row-block x column-block layouts: PrxPc, 'auto' "
-                                                    "(every Pr in 2, 4, 8 dividing N) or 'none'")
+    ap.add_argument("--config2", type=int, help="size of the configs[1] sub-run (GPU step and the CPU "
+                    "reference sequence at full size; 0 = skip)")
+    ap.add_argument("--config3", type=int, help="L-BFGS iterations of the configs[2] sub-run through the CLI "
+                    "(N=32768 only; 0 = skip)")
+    ap.add_argument("--config5", type=int, help="test points of the configs[4] sub-run (N=32768 fp32 "
+                    "prediction; 0 = skip)")
+    ap.add_argument("--grid", help="N > 1: also time the row-block x column-block layouts: PrxPc, 'auto' "
+                    "(every Pr in 2, 4, 8 dividing N) or 'none'")
     ap.add_argument("--inproc", action="store_true", help="N > 1: one process, one host thread per GPU (gpak_create_multi)")
     ap.add_argument("--profile-tag", default=os.environ.get("GPAK_PROFILE_TAG", "r03"),
                     help="profiles/<tag>_pmc_summary_N<N>.json supplies `traffic` and the in-situ clock")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every sub-run and reference point beyond the headline: "
+                    "calibration, N=65536, configs 2 / 3 / 5, --grad, the vendor Cholesky, the CPU baseline, the grid "
+                    "layouts (the options above that ask for one of them are refused without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed "
+                    "(nlZ, its three terms, alpha) as DIR/<name>.npy, float64 (one GPU, single-context path)")
+    args = ap.parse_args(argv)
+    if args.full:
+        for k, v in FULL_DEFAULTS.items():
+            if getattr(args, k) is None:
+                setattr(args, k, v)
+    else:
+        # a plain run is the headline alone: set-up, warm-up, the timed steps, the outputs, the line.  An option that asks
+        # for a sub-run is refused rather than dropped (switching one off, e.g. --config2 0 or --grid none, is accepted)
+        asked = ["--" + k.replace("_", "-") for k in FULL_DEFAULTS if getattr(args, k) not in (None, 0, False, "none")]
+        if asked:
+            ap.error(f"{', '.join(asked)}: sub-runs beyond the headline run only with --full")
+        for k, v in PLAIN_VALUES.items():
+            setattr(args, k, v)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (args.gpus > 1 or args.inproc or world > 1 or os.environ.get("GPAK_FORCE_DIST")):
+        ap.error("--dump-outputs is implemented for the single-context path (--gpus 1) only")
+    return args
+
+
+def main():
+    args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.inproc and args.gpus > 1:
         print(json.dumps(run_inproc(args)))

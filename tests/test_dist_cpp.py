@@ -368,7 +368,7 @@ def _bench(world, extra_env, size, timeout=900):
     env = dict(os.environ, **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world),
-           "--steps", "2", "--warmup", "1", "--size", str(size), "--no-cpu", "--no-n65536"]
+           "--steps", "2", "--warmup", "1", "--size", str(size), "--no-cpu", "--no-n65536", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -437,7 +437,7 @@ def _bench_as_typed(world, size, extra_env, extra_args=()):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(extra_env)
     out = subprocess.run([sys.executable, "bench.py", "--gpus", str(world), "--size", str(size), "--steps", "2",
-                          "--warmup", "1", "--no-n65536", "--no-cpu", *extra_args], env=env, cwd=ROOT,
+                          "--warmup", "1", "--no-n65536", "--no-cpu", "--full", *extra_args], env=env, cwd=ROOT,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]

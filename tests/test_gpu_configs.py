@@ -225,7 +225,7 @@ def test_config4_n65536_sharded_over_four_ranks(gp):
     the C++ schedule on this box's one GPU (gpak_create_multi, in-process peer-copy transport; RCCL refuses several
     ranks per device), against the single-context path at the same size and against the LAPACK golden
     (tests/golden/golden_N65536.json: direct distances only, the expansion form does not fit the generator's host).
-    The real 8-GPU run is the driver's (bench.py --gpus 8, `n65536` sub-object)."""
+    The real 8-GPU run is the driver's (bench.py --gpus 8 --full, `n65536` sub-object)."""
     N = 65536
     z = golden(N)["direct"]
     X, y = synth.drillholes(N)

@@ -309,6 +309,38 @@ def test_alternative_kernels_give_the_same_step():
         assert abs(v - vals["default"]) <= 1e-11 * abs(vals["default"]), (name, vals)
 
 
+def test_bench_plain_run_dumps_the_last_timed_step(gp, orc, tmp_path):
+    """A plain `bench.py` run is the headline alone (no sub-run rides along), and --dump-outputs writes what the LAST
+    timed step computed -- nlZ, its three terms, alpha -- for that step's parameters: against the oracle and against a
+    context of this process given the same inputs."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    N, warmup, steps = 2048, 1, 3
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                          str(warmup), "--size", str(N), "--dump-outputs", str(tmp_path)], cwd=root,
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    d = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1])
+    # the sub-runs due at this size under --full (the N=32768-only ones are pinned in tests/test_bench_cli.py)
+    assert "cpu_baseline" not in d and "n65536" not in d and "calibrated_mfma_f64_tflops" not in d["roofline"]
+    nlz, terms, alpha = (np.load(tmp_path / f"{k}.npy") for k in ("nlz", "nlz_terms", "alpha"))
+    assert nlz.dtype == terms.dtype == alpha.dtype == np.float64
+    assert nlz.shape == (1,) and terms.shape == (3,) and alpha.shape == (N,) and nlz[0] == d["nlz"]
+    X, y = synth.drillholes(N)
+    e, bias, sn2 = bench.params_for_step(warmup + steps - 1)
+    info, alpha_o, _ = orc.nlz_refseq(orc.gram(X, X, e, bias, orc.DIST_DIRECT), y, sn2)
+    assert abs(nlz[0] - info.nlz) <= 1e-9 * abs(info.nlz)
+    assert rel(alpha, alpha_o) <= 1e-8
+    gp.set_train(X, y)
+    gp.set_params(e, bias, sn2, gpak.DIST_DIRECT)
+    assert abs(gp.logLikelihood() - nlz[0]) <= 1e-12 * abs(nlz[0])
+    assert rel(gp.nlz_terms(), terms) <= 1e-12
+    assert rel(gp.solve_alpha(), alpha) <= 1e-12
+
+
 _BLOCK_KERNEL_SCRIPT = r'''
 import hashlib, json, sys
 import numpy as np, torch
