@@ -67,6 +67,8 @@ static GpakTuning read_tuning_env() {
   geti("GPAK_GEMM_SMALL", t.gemm_small);
   geti("GPAK_GEMM_SMALL_ROWS", t.gemm_small_rows);
   geti("GPAK_SUPER_LR", t.super_lr);
+  getb("GPAK_BULK_TICKETS", t.bulk_tickets);
+  geti("GPAK_BULK_SURPLUS", t.bulk_surplus);
   getb("GPAK_FILL_FAST", t.fill_fast);
   getb("GPAK_KMV_SYM", t.kmv_sym);
   if (const char *e = getenv("GPAK_F32_ACC")) t.f32_wide = strcmp(e, "plain") != 0;
@@ -319,6 +321,7 @@ void gpak_destroy(gpak_ctx *ctx) {
   gpak_predict_release(ctx);
   if (ctx->dRed) hipFree(ctx->dRed);
   if (ctx->dInfo) hipFree(ctx->dInfo);
+  if (ctx->dTickets) hipFree(ctx->dTickets);
   for (int i = 0; i < 10; i++) hipEventDestroy(ctx->ev[i]);
   for (auto e : ctx->ev_pool) hipEventDestroy(e);
   for (auto e : ctx->ev_sync) hipEventDestroy(e);

@@ -42,45 +42,91 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // latency (an L2-resident operand set runs no faster) but the barrier per stage and the LDS-DMA /
 // ds_read issue slots next to the MFMAs.
 // ---------------------------------------------------------------------------------------
+// Super-tile walk shared by the static map and the ticketed one: tile slot `slot` (0..63) of super-tile `ssel`, in the
+// order of the super-tiles of the lower triangle (lower_skip == 1) or of the whole grid; false for a slot with no tile.
+__device__ __forceinline__ bool gpak_super_tile(int ssel, int slot, int lr, int lower_skip, int mt, int nt, int rb0,
+                                                int cb0, int &ti, int &tj) {
+  // super-tile = 2^lr rows x 2^(6 - lr) columns of tiles (64 workgroups: what one XCD keeps resident);
+  // 3 = 8 x 8, the default (4 x 16 and 16 x 4 measured in round 3: profiles/r03_supertile_shapes.txt)
+  const int lc = 6 - lr;
+  const int SR = (mt + (1 << lr) - 1) >> lr, SC = (nt + (1 << lc) - 1) >> lc;
+  int si, sj = 0;
+  if (lower_skip == 1) {   // 1: super-tiles that touch the lower triangle only; 2: all super-tiles, per-tile rule below
+    int rem = ssel;
+    int first = 0;
+    for (; sj < SC; sj++) {   // first super row of column sj whose last tile row reaches the diagonal: (sj << lc) >> lr
+      first = (sj << lc) >> lr;
+      const int cnt = SR - first;
+      if (cnt <= 0) { sj = SC; break; }
+      if (rem < cnt) break;
+      rem -= cnt;
+    }
+    si = first + rem;
+  } else {
+    sj = ssel / SR;
+    si = ssel - sj * SR;
+  }
+  if (sj >= SC) return false;
+  ti = (si << lr) + (slot & ((1 << lr) - 1));
+  tj = (sj << lc) + (slot >> lr);
+  if (ti >= mt || tj >= nt) return false;
+  if (lower_skip && (rb0 + ti) < (cb0 + tj)) return false;
+  return true;
+}
+
 // TRAILING only names the instantiation (the bulk trailing update gets its own line in rocprofv3 statistics).
 // K0MAP (the distributed gradient's B^-1 = G G^T on row-cyclic slabs of G): the k-loop of tile row ti starts at global
 // row block ti * cyc_tpb + cyc_lt0 (the cyc_* parameters are reused; no cyclic column map in that instantiation).
-template <int RS_D, int RS_OCC, bool TRAILING, bool K0MAP = false, bool SBASE = false>
+// TICKET (the bulk update of the factorisation, GpakTuning::bulk_tickets): which workgroup computes which tile is
+// decided at run time instead of by blockIdx.  The static map takes workgroup b to XCD b & 7 and gives it slot
+// (b >> 3) & 63 of that XCD's super-tiles, so every XCD has to finish exactly its eighth of the launch however many of its
+// slots a CU mask or a co-resident panel kernel has taken.  With tickets, XCD x (read from HW_REG_XCC_ID) owns the same
+// list -- super-tiles x, x + 8, ..., 64 slots each, in the static order -- and its workgroups claim entries from the
+// front of it; once it is used up they claim entries from the back of the other XCDs' lists, so an XCD with more free
+// slots computes more tiles.  Front and back counts of a list share one 64-bit word (tk[x]: front in the low half, back
+// in the high half), so one returning atomic add decides every claim: entry front / share - 1 - back is taken iff
+// front + back < share before the add.  The launcher starts a few more workgroups than there are tiles; one that finds
+// every list used up exits.  Every tile is still computed by one workgroup, by the same instructions in the same k order.
+template <int RS_D, int RS_OCC, bool TRAILING, bool K0MAP = false, bool SBASE = false, bool TICKET = false>
 __global__ __launch_bounds__(256, RS_OCC) void gpak_gemm_nt_f64_rs(int K, double alpha, const double *A, long lda,
                                                                const double *B, long ldb, double beta, double *C,
                                                                long ldc, int rb0, int cb0, int lower_skip, int mt,
                                                                int nt, int k0_by_row, int cyc_P, int cyc_rank,
-                                                               int cyc_tpb, int cyc_lt0, int super_lr) {
+                                                               int cyc_tpb, int cyc_lt0, int super_lr,
+                                                               unsigned long long *tk, int nsuper) {
   int ti, tj;
-  {
-    // super-tile = 2^super_lr rows x 2^(6 - super_lr) columns of tiles (64 workgroups: what one XCD keeps resident);
-    // 3 = 8 x 8, the default (4 x 16 and 16 x 4 measured in round 3: profiles/r03_supertile_shapes.txt)
-    const int lr = super_lr, lc = 6 - super_lr;
-    const int b = blockIdx.x, q = b >> 3;
-    const int slot = q & 63;
-    const int ssel = (q >> 6) * 8 + (b & 7);
-    const int SR = (mt + (1 << lr) - 1) >> lr, SC = (nt + (1 << lc) - 1) >> lc;
-    int si, sj = 0;
-    if (lower_skip == 1) {   // 1: super-tiles that touch the lower triangle only; 2: all super-tiles, per-tile rule below
-      int rem = ssel;
-      int first = 0;
-      for (; sj < SC; sj++) {   // first super row of column sj whose last tile row reaches the diagonal: (sj << lc) >> lr
-        first = (sj << lc) >> lr;
-        const int cnt = SR - first;
-        if (cnt <= 0) { sj = SC; break; }
-        if (rem < cnt) break;
-        rem -= cnt;
+  if constexpr (TICKET) {
+    __shared__ int tile_sh;
+    if (threadIdx.x == 0) {
+      // HW_REG_XCC_ID (hardware register 20), bits 3:0
+      const int x = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7;
+      int got = -1;
+      for (int i = 0; i < 8 && got < 0; i++) {
+        const int y = (x + i) & 7;
+        const unsigned share = nsuper > y ? 64u * (unsigned)((nsuper - 1 - y) / 8 + 1) : 0u;
+        while (true) {
+          // a vector global atomic (one lane), device scope: the lists are shared by all XCDs
+          const unsigned long long old = atomicAdd(tk + y, i == 0 ? 1ull : (1ull << 32));
+          const unsigned f = (unsigned)old, bk = (unsigned)(old >> 32);
+          if (f + bk >= share) break;   // list y used up
+          const unsigned e = i == 0 ? f : share - 1 - bk;
+          int a, c;
+          if (gpak_super_tile((int)(e >> 6) * 8 + y, (int)(e & 63), super_lr, lower_skip, mt, nt, rb0, cb0, a, c)) {
+            got = a | (c << 16);
+            break;
+          }
+        }
       }
-      si = first + rem;
-    } else {
-      sj = ssel / SR;
-      si = ssel - sj * SR;
+      tile_sh = got;
     }
-    if (sj >= SC) return;
-    ti = (si << lr) + (slot & ((1 << lr) - 1));
-    tj = (sj << lc) + (slot >> lr);
-    if (ti >= mt || tj >= nt) return;
-    if (lower_skip && (rb0 + ti) < (cb0 + tj)) return;
+    __syncthreads();
+    const int got = __builtin_amdgcn_readfirstlane(tile_sh);
+    if (got < 0) return;
+    ti = got & 0xffff;
+    tj = got >> 16;
+  } else {
+    const int b = blockIdx.x, q = b >> 3;
+    if (!gpak_super_tile((q >> 6) * 8 + (b & 7), q & 63, super_lr, lower_skip, mt, nt, rb0, cb0, ti, tj)) return;
   }
   int gct = tj, art = ti;
   if (!K0MAP && cyc_P) {
@@ -327,7 +373,7 @@ void gpak_launch_gemm_cyclic(hipStream_t st, int mt, int nt, int K, const double
   const long nsuper = (long)SR * SC;
   dim3 grid((unsigned)((nsuper + 7) / 8 * 8 * 64)), block(256);
   hipLaunchKernelGGL((gpak_gemm_nt_f64_rs<4, 2, true>), grid, block, 0, st, K, -1.0, Pv, ldp, Pv, ldp, 1.0, Clocal, ldc,
-                     rt0, 0, 0, mt, nt, 0, P, rank, tpb, lt0, 3);
+                     rt0, 0, 0, mt, nt, 0, P, rank, tpb, lt0, 3, nullptr, 0);
 }
 
 // C (mt x nt tiles) = alpha * A * B^T with the k-loop of tile row ti started at global row block ti*k0_mul + k0_add
@@ -341,12 +387,13 @@ void gpak_launch_gemm_nt_k0map(hipStream_t st, int mt, int nt, int K, double alp
   dim3 grid((unsigned)((nsuper + 7) / 8 * 8 * 64)), block(256);
   // lower_skip = 0 in the super-tile walk (every super-tile is visited); the per-tile rule is rb0 + ti < cb0 + tj
   hipLaunchKernelGGL((gpak_gemm_nt_f64_rs<4, 2, false, true>), grid, block, 0, st, K, alpha, A, lda, B, ldb, 0.0, C, ldc, 0,
-                     skip_shift, 2, mt, nt, 0, 0, 0, k0_mul, k0_add, 3);
+                     skip_shift, 2, mt, nt, 0, 0, 0, k0_mul, k0_add, 3, nullptr, 0);
 }
 
 void gpak_launch_gemm_nt(hipStream_t st, int mt, int nt, int K, double alpha, const double *A, long lda,
                          const double *B, long ldb, double beta, double *C, long ldc, int row_block0,
-                         int col_block0, bool lower_skip, bool trailing, bool k0_by_row) {
+                         int col_block0, bool lower_skip, bool trailing, bool k0_by_row, unsigned long long *tickets,
+                         int surplus_pct) {
   if (mt <= 0 || nt <= 0) return;
   // super-tile shape: 8 x 8 unless the bulk trailing update was asked for another one (GpakTuning::super_lr)
   int lr = 3;
@@ -402,16 +449,23 @@ void gpak_launch_gemm_nt(hipStream_t st, int mt, int nt, int K, double alpha, co
   const bool long_k = K >= 2048;
   if (trailing && (long_k || (sbase_rows > 0 && (long)mt * TM > sbase_rows)))
     hipLaunchKernelGGL((gpak_gemm_nt_f64_rs<4, 2, true, false, true>), grid, block, 0, st, K, alpha, A, lda, B, ldb, beta, C,
-                       ldc, row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr);
+                       ldc, row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr, nullptr, 0);
   else if (long_k)
     hipLaunchKernelGGL((gpak_gemm_nt_f64_rs<4, 2, false, false, true>), grid, block, 0, st, K, alpha, A, lda, B, ldb, beta, C,
-                       ldc, row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr);
-  else if (trailing)
+                       ldc, row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr, nullptr, 0);
+  else if (trailing && tickets && lower_skip && row_block0 == col_block0 && !k0_by_row) {
+    // ticketed map (the factorisation's bulk update): one workgroup per tile plus surplus_pct % more, spread evenly over
+    // the XCDs, so that an XCD with more free slots can run more tiles than its eighth; 8 list words at `tickets`, zero
+    const long extra = (tiles * (surplus_pct > 0 ? surplus_pct : 0) + 799) / 800;   // per XCD
+    hipLaunchKernelGGL((gpak_gemm_nt_f64_rs<4, 2, true, false, false, true>), dim3((unsigned)(tiles + 8 * extra)), block, 0,
+                       st, K, alpha, A, lda, B, ldb, beta, C, ldc, row_block0, col_block0, 1, mt, nt, 0, 0, 0, 1, 0, lr,
+                       tickets, (int)nsuper);
+  } else if (trailing)
     hipLaunchKernelGGL((gpak_gemm_nt_f64_rs<4, 2, true>), grid, block, 0, st, K, alpha, A, lda, B, ldb, beta, C, ldc,
-                       row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr);
+                       row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr, nullptr, 0);
   else
     hipLaunchKernelGGL((gpak_gemm_nt_f64_rs<4, 2, false>), grid, block, 0, st, K, alpha, A, lda, B, ldb, beta, C, ldc,
-                       row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr);
+                       row_block0, col_block0, lower_skip ? 1 : 0, mt, nt, k0_by_row ? 1 : 0, 0, 0, 1, 0, lr, nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------------------

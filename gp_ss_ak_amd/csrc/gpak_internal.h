@@ -83,6 +83,8 @@ struct GpakTuning {
   int gemm_small = 160;        // GPAK_GEMM_SMALL      tile grids up to this size take the latency kernel
   int gemm_small_rows = 16;    // GPAK_GEMM_SMALL_ROWS rows per workgroup of that kernel: 16 / 32 / 64
   int super_lr = 3;            // GPAK_SUPER_LR      bulk update: super-tiles of 2^lr x 2^(6-lr) tiles per XCD (3 = 8 x 8)
+  bool bulk_tickets = true;    // GPAK_BULK_TICKETS  factorisation's bulk update: tiles claimed per XCD at run time (0: static blockIdx map)
+  int bulk_surplus = 6;        // GPAK_BULK_SURPLUS  ... with this many percent more workgroups than tiles
   bool fill_fast = true;       // GPAK_FILL_FAST     table exp + in-line sqrt fill / Gram-matvec
   bool kmv_sym = true;         // GPAK_KMV_SYM       symmetric Gram-matvec from 32 macro blocks on
   // fp32 prediction (GPAK_F32 contexts)
@@ -142,6 +144,8 @@ struct gpak_ctx {
   double *dWork = nullptr;   // 4*Np scratch vectors
   double *dRed = nullptr;    // small reduction scratch
   int *dInfo = nullptr;      // first failing column (1-based) or 0
+  unsigned long long *dTickets = nullptr;   // ticketed bulk updates: 8 list words per bulk launch, zeroed per factorisation
+  int tickets_cap = 0;       // bulk launches dTickets has room for
   enum { M_NONE, M_B, M_L } mstate = M_NONE;
   bool alpha_ok = false, nlz_ok = false;
   int failed_col = 0;
@@ -309,9 +313,12 @@ int gpak_ensure_U(gpak_ctx *ctx);
 // C[mt x nt tiles of 128] = beta*C + alpha * A (m x K) * B (n x K)^T, all column-major.
 // lower_skip: skip tile (ti,tj) when row_block0+ti < col_block0+tj.
 // trailing=true selects the instantiation gpak_gemm_nt_f64_rs<4, 2, true> (its own line in profiles).
+// tickets (the factorisation's bulk update, lower_skip with row_block0 == col_block0): the ticketed tile map -- eight
+// zeroed 64-bit list words of this launch's own, surplus_pct % more workgroups than tiles (gemm.hip, TICKET).
 void gpak_launch_gemm_nt(hipStream_t st, int mt, int nt, int K, double alpha, const double *A, long lda,
                          const double *B, long ldb, double beta, double *C, long ldc, int row_block0,
-                         int col_block0, bool lower_skip, bool trailing, bool k0_by_row = false);
+                         int col_block0, bool lower_skip, bool trailing, bool k0_by_row = false,
+                         unsigned long long *tickets = nullptr, int surplus_pct = 0);
 
 void gpak_launch_gemm_nt_k0map(hipStream_t st, int mt, int nt, int K, double alpha, const double *A, long lda,
                                const double *B, long ldb, double *C, long ldc, int skip_shift, int k0_mul, int k0_add);

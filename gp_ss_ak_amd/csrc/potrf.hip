@@ -572,14 +572,16 @@ static int factor_panel_tail(gpak_ctx *ctx, hipStream_t sp, hipStream_t sx, int 
 }
 
 // Update of the columns [c0, c1) (and all rows >= c0) with the factored panel [J, J+W).
-static void update_cols(gpak_ctx *ctx, hipStream_t st, int J, int W, int c0, int c1, bool trailing) {
+// tk: the ticketed tile map's eight list words for this launch (bulk updates only; nullptr: static map)
+static void update_cols(gpak_ctx *ctx, hipStream_t st, int J, int W, int c0, int c1, bool trailing,
+                        unsigned long long *tk = nullptr) {
   const long ld = ctx->ld;
   double *M = ctx->dM;
   const int mt = (ctx->Np - c0) / PB, nt = (c1 - c0) / PB;
   if (mt <= 0 || nt <= 0) return;
   const double *P = M + c0 + (size_t)J * ld;
   gpak_launch_gemm_nt(st, mt, nt, W, -1.0, P, ld, P, ld, 1.0, M + c0 + (size_t)c0 * ld, ld, 0, 0, true,
-                      trailing);
+                      trailing, false, tk, ctx->tune.bulk_surplus);
 }
 
 // Right-looking blocked factorisation with one panel of look-ahead:
@@ -621,6 +623,19 @@ int gpak_potrf_blocked(gpak_ctx *ctx) {
   Js.push_back(Np);
   const int init = 0x7fffffff;
   GPAK_HIP(hipMemcpyAsync(ctx->dInfo, &init, sizeof(int), hipMemcpyHostToDevice, su));
+  // ticketed bulk updates (GpakTuning::bulk_tickets): a ring of eight list words per bulk launch, zeroed here once for
+  // the whole factorisation (one command; a memset in front of every bulk launch would cost a hand-off each)
+  const bool tickets = ctx->tune.bulk_tickets;
+  if (tickets) {
+    if (ctx->tickets_cap < nJ) {
+      if (ctx->dTickets) GPAK_HIP(hipFree(ctx->dTickets));
+      ctx->dTickets = nullptr;
+      ctx->tickets_cap = 0;
+      GPAK_HIP(hipMalloc(&ctx->dTickets, sizeof(unsigned long long) * 8 * (size_t)nJ));
+      ctx->tickets_cap = nJ;
+    }
+    GPAK_HIP(hipMemsetAsync(ctx->dTickets, 0, sizeof(unsigned long long) * 8 * (size_t)nJ, su));
+  }
 
   while ((int)ctx->ev_sync.size() < 2 * nJ + 4 + 5) {
     hipEvent_t e;
@@ -730,7 +745,7 @@ int gpak_potrf_blocked(gpak_ctx *ctx) {
         }
         GPAK_HIP(hipEventRecord(ctx->ev_pool[ev_used], su));
       }
-      update_cols(ctx, su, J, W, J2, Np, true);
+      update_cols(ctx, su, J, W, J2, Np, true, tickets ? ctx->dTickets + 8 * (size_t)tl : nullptr);
       if (ctx->profile) {
         GPAK_HIP(hipEventRecord(ctx->ev_pool[ev_used + 1], su));
         ev_used += 2;
