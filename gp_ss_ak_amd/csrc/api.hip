@@ -39,9 +39,16 @@ int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng);
 
 static std::string g_global_err;
 
-// ---- the tuning set (gpak_internal.h): defaults, overridden once by the GPAK_* environment ------------------
-static GpakTuning read_tuning_env() {
-  GpakTuning t;
+// ---- the two tuning sets (GpakSchedule in potrf_plan.h: copied by every context; GpakKernelTuning in gpak_internal.h:
+// process-wide): defaults, overridden once by the GPAK_* environment ------------------
+struct Tuning {
+  GpakSchedule sched;
+  GpakKernelTuning kern;
+};
+static Tuning read_tuning_env() {
+  Tuning tn;
+  GpakSchedule &t = tn.sched;
+  GpakKernelTuning &k = tn.kern;
   auto geti = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
   auto getb = [](const char *name, bool &v) { if (const char *e = getenv(name)) v = atoi(e) != 0; };
   geti("GPAK_NB_OUTER", t.nb_outer);
@@ -55,25 +62,25 @@ static GpakTuning read_tuning_env() {
   geti("GPAK_NEXT_SPLIT_ROWS", t.next_split_rows);
   getb("GPAK_INV512", t.inv512);
   geti("GPAK_BWD_FUSED", t.bwd_fused);
-  geti("GPAK_SBASE_ROWS", t.sbase_rows);
+  geti("GPAK_SBASE_ROWS", k.sbase_rows);
   geti("GPAK_BWD_BLOCK", t.bwd_block);
   getb("GPAK_LOOKAHEAD", t.lookahead);
   getb("GPAK_FWD_IN_FACTOR", t.fwd_in_factor);
-  geti("GPAK_POTRF_CO", t.potrf_co);
+  geti("GPAK_POTRF_CO", t.potrf_co); k.potrf_co = t.potrf_co;
   geti("GPAK_TAIL_MASK", t.tail_mask);
   geti("GPAK_TAIL_MASK_STRIDE", t.tail_mask_stride);
   getb("GPAK_BULK_QUEUE", t.bulk_queue);
   if (const char *e = getenv("GPAK_LD_PAD")) t.ld_pad = atol(e) / 2 * 2;
-  geti("GPAK_GEMM_SMALL", t.gemm_small);
-  geti("GPAK_GEMM_SMALL_ROWS", t.gemm_small_rows);
-  geti("GPAK_SUPER_LR", t.super_lr);
+  geti("GPAK_GEMM_SMALL", k.gemm_small);
+  geti("GPAK_GEMM_SMALL_ROWS", k.gemm_small_rows);
+  geti("GPAK_SUPER_LR", k.super_lr);
   getb("GPAK_BULK_TICKETS", t.bulk_tickets);
   geti("GPAK_BULK_SURPLUS", t.bulk_surplus);
-  getb("GPAK_FILL_FAST", t.fill_fast);
-  getb("GPAK_KMV_SYM", t.kmv_sym);
-  if (const char *e = getenv("GPAK_F32_ACC")) t.f32_wide = strcmp(e, "plain") != 0;
-  geti("GPAK_F32_RSD", t.f32_rsd);
-  geti("GPAK_F32_TILE", t.f32_tile);
+  getb("GPAK_FILL_FAST", k.fill_fast);
+  getb("GPAK_KMV_SYM", k.kmv_sym);
+  if (const char *e = getenv("GPAK_F32_ACC")) k.f32_wide = strcmp(e, "plain") != 0;
+  geti("GPAK_F32_RSD", k.f32_rsd);
+  geti("GPAK_F32_TILE", k.f32_tile);
   geti("GPAK_PRED_BATCH", t.pred_batch);
   geti("GPAK_PRED_LD_SKEW", t.pred_ld_skew);
   if (const char *e = getenv("GPAK_FS_LEVELS_F32")) {   // "128,512,...": ascending, each a multiple of the one before
@@ -86,13 +93,13 @@ static GpakTuning read_tuning_env() {
     }
     if (n > 0) memcpy(t.fs_levels, lv, sizeof(lv));
   }
+  return tn;
+}
+static Tuning &tuning_storage() {
+  static Tuning t = read_tuning_env();
   return t;
 }
-static GpakTuning &tuning_storage() {
-  static GpakTuning t = read_tuning_env();
-  return t;
-}
-const GpakTuning &gpak_tuning() { return tuning_storage(); }
+const GpakKernelTuning &gpak_tuning() { return tuning_storage().kern; }
 extern "C" void gpak_reload_tuning(void) { tuning_storage() = read_tuning_env(); }
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -230,7 +237,7 @@ int gpak_create(gpak_ctx **out, int device, int precision) {
     return GPAK_EHIP;
   }
   gpak_ctx *ctx = new gpak_ctx();
-  ctx->tune = gpak_tuning();
+  ctx->sched = tuning_storage().sched;
   ctx->device = device;
   ctx->precision = precision;
   memset(&ctx->times, 0, sizeof(ctx->times));
@@ -245,10 +252,10 @@ int gpak_create(gpak_ctx **out, int device, int precision) {
   // a copy of the main stream that may not use the first GPAK_TAIL_MASK (default 8) compute units; the bulk
   // updates of the chain-bound tail of the factorisation go there so that the panel chain finds idle CUs
   {
-    const int skip = ctx->tune.tail_mask;            // 0 switches it off; measured: 8 CUs, rows <= 12288: 183.4 -> 181.2 ms
+    const int skip = ctx->sched.tail_mask;           // 0 switches it off; measured: 8 CUs, rows <= 12288: 183.4 -> 181.2 ms
     if (skip > 0 && skip < prop.multiProcessorCount) {
       std::vector<uint32_t> mask((prop.multiProcessorCount + 31) / 32, 0xffffffffu);
-      const int stride = ctx->tune.tail_mask_stride;
+      const int stride = ctx->sched.tail_mask_stride;
       for (int c = 0; c < skip; c++) { const int bit = (c * stride) % prop.multiProcessorCount; mask[bit / 32] &= ~(1u << (bit % 32)); }
       if (hipExtStreamCreateWithCUMask(&ctx->stream_tail, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
         ctx->stream_tail = nullptr;
@@ -262,7 +269,7 @@ int gpak_create(gpak_ctx **out, int device, int precision) {
   // the middle of the factorisation with nothing else running, on a queue created by hipExtStreamCreateWithCUMask
   // 23 us: 175.1 -> 172.8 ms per factorisation at N = 32768 (same-box A/B).  The same for the panel stream (which then
   // loses its priority): 203 ms; for the forward-substitution or the main stream: +1.3 ms.  GPAK_BULK_QUEUE=0: off.
-  if (ctx->tune.bulk_queue) {
+  if (ctx->sched.bulk_queue) {
     std::vector<uint32_t> mask((prop.multiProcessorCount + 31) / 32, 0xffffffffu);
     if (hipExtStreamCreateWithCUMask(&ctx->stream_bulk, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
       ctx->stream_bulk = nullptr;
@@ -272,9 +279,6 @@ int gpak_create(gpak_ctx **out, int device, int precision) {
   for (int i = 0; i < 10; i++) hipEventCreate(&ctx->ev[i]);
   hipMalloc(&ctx->dRed, sizeof(double) * 64);
   hipMalloc(&ctx->dInfo, sizeof(int) * 4);
-  ctx->fwd_in_factor = ctx->tune.fwd_in_factor;
-  ctx->lookahead = ctx->tune.lookahead;   // diagnostics: 0 = one stream
-  ctx->nb_outer = ctx->tune.nb_outer;
   *out = ctx;
   return GPAK_OK;
 }
@@ -343,26 +347,26 @@ int gpak_set_option(gpak_ctx *ctx, int option, long value) {
     case GPAK_OPT_MEMOISE: ctx->memoise = value != 0; return GPAK_OK;
     case GPAK_OPT_NB_OUTER:
       if (value < 128 || value % 128) { ctx->err = "nb_outer must be a positive multiple of 128"; return GPAK_EINVAL; }
-      ctx->nb_outer = (int)value;
+      ctx->sched.nb_outer = (int)value;
       return GPAK_OK;
     case GPAK_OPT_PROFILE: ctx->profile = value != 0; return GPAK_OK;
-    case GPAK_OPT_LOOKAHEAD: ctx->lookahead = value != 0; return GPAK_OK;
+    case GPAK_OPT_LOOKAHEAD: ctx->sched.lookahead = value != 0; return GPAK_OK;
     case GPAK_OPT_NB_WIDE:
       if (value < 0 || value % 128) { ctx->err = "nb_wide must be 0 or a multiple of 128"; return GPAK_EINVAL; }
-      ctx->tune.nb_wide = (int)value;
+      ctx->sched.nb_wide = (int)value;
       return GPAK_OK;
-    case GPAK_OPT_NB_WIDE_ROWS: ctx->tune.nb_wide_rows = (int)value; return GPAK_OK;
-    case GPAK_OPT_TAIL_ROWS: ctx->tune.tail_rows = (int)value; return GPAK_OK;
-    case GPAK_OPT_FIRST_NARROW: ctx->tune.first_narrow = value != 0; return GPAK_OK;
-    case GPAK_OPT_INV512: ctx->tune.inv512 = value != 0; return GPAK_OK;
+    case GPAK_OPT_NB_WIDE_ROWS: ctx->sched.nb_wide_rows = (int)value; return GPAK_OK;
+    case GPAK_OPT_TAIL_ROWS: ctx->sched.tail_rows = (int)value; return GPAK_OK;
+    case GPAK_OPT_FIRST_NARROW: ctx->sched.first_narrow = value != 0; return GPAK_OK;
+    case GPAK_OPT_INV512: ctx->sched.inv512 = value != 0; return GPAK_OK;
     case GPAK_OPT_POTRF_CO:
       if (value < 0 || value > 2) { ctx->err = "potrf_co must be 0, 1 or 2"; return GPAK_EINVAL; }
-      ctx->tune.potrf_co = (int)value;
+      ctx->sched.potrf_co = (int)value;
       return GPAK_OK;
-    case GPAK_OPT_PRED_BATCH: ctx->tune.pred_batch = (int)value; return GPAK_OK;
+    case GPAK_OPT_PRED_BATCH: ctx->sched.pred_batch = (int)value; return GPAK_OK;
     case GPAK_OPT_BWD_FUSED:
       if (value < 0 || value > 2) { ctx->err = "bwd_fused must be 0, 1 or 2"; return GPAK_EINVAL; }
-      ctx->tune.bwd_fused = (int)value;
+      ctx->sched.bwd_fused = (int)value;
       return GPAK_OK;
   }
   ctx->err = "unknown option";
@@ -378,7 +382,7 @@ int gpak_set_train(gpak_ctx *ctx, const double *X, const double *y, int N, int d
   release_train(ctx);
   const int Np = round_up(N, GPAK_TILE);
   long pad = Np >= 1024 ? 32 : 0;
-  if (ctx->tune.ld_pad >= 0) pad = ctx->tune.ld_pad;
+  if (ctx->sched.ld_pad >= 0) pad = ctx->sched.ld_pad;
   const long ld = Np + pad;
   ctx->N = N; ctx->Np = Np; ctx->ld = (int)ld; ctx->d = d;
   ctx->hX.assign(X, X + (size_t)N * d);
@@ -390,7 +394,7 @@ int gpak_set_train(gpak_ctx *ctx, const double *X, const double *y, int N, int d
   }
   const int T = Np / GPAK_TILE;
   // width of the back substitution's explicit diagonal-block inverses (fixed per training set: it sizes dInv512)
-  int bw = ctx->tune.bwd_block;
+  int bw = ctx->sched.bwd_block;
   if (bw != 512 && bw != 1024 && bw != 2048) bw = 512;
   ctx->bwd_bw = bw;
   if (hipMalloc(&ctx->dX, sizeof(double) * 4 * (size_t)Np) != hipSuccess ||
@@ -499,6 +503,13 @@ int gpak_ensure_U(gpak_ctx *ctx) {
   return GPAK_OK;
 }
 
+// dM is about to hold another factor: nothing that was derived from the old one is valid any more
+static void factor_changed(gpak_ctx *ctx) {
+  ctx->z_ok = false;                          // dWork does not hold L^-1 (y/sn2)
+  ctx->backsolve = gpak_ctx::BS_BLOCKS128;    // no explicit inverses of wider diagonal blocks
+  ctx->lf_ok = false;                         // the fp32 image (GPAK_F32 prediction) is rebuilt on first use
+}
+
 static int ensure_factor(gpak_ctx *ctx) {
   if (ctx->mstate == gpak_ctx::M_L) return GPAK_OK;
   int rc = gpak_ensure_U(ctx);
@@ -510,11 +521,8 @@ static int ensure_factor(gpak_ctx *ctx) {
   gpak_launch_fill(st, ctx->U, ctx->U, ctx->Np, ctx->Np, ctx->kp, 1.0 / ctx->sn2, 1.0, 1.0, 1, ctx->dM,
                    ctx->ld, nullptr);
   ctx->mstate = gpak_ctx::M_B;
-  ctx->z_ok = false;
-  ctx->inv512_ok = false;
-  ctx->t512_mode = 0;
-  ctx->lf_ok = false;
-  if (ctx->fwd_in_factor) gpak_launch_scale(st, ctx->Np, ctx->dy, 1.0 / ctx->sn2, ctx->dWork);  // rhs = y/sn2
+  factor_changed(ctx);
+  if (ctx->sched.fwd_in_factor) gpak_launch_scale(st, ctx->Np, ctx->dy, 1.0 / ctx->sn2, ctx->dWork);  // rhs = y/sn2
   GPAK_HIP(hipEventRecord(ctx->ev[1], st));
   rc = gpak_potrf_blocked(ctx);
   GPAK_HIP(hipEventRecord(ctx->ev[2], st));
@@ -535,9 +543,13 @@ static int ensure_factor(gpak_ctx *ctx) {
   }
   if (rc) return rc;
   ctx->mstate = gpak_ctx::M_L;
-  ctx->z_ok = ctx->fwd_in_factor;
-  ctx->t512_mode = ctx->fwd_in_factor && ctx->tune.inv512 ? ctx->tune.bwd_fused : 0;
-  ctx->inv512_ok = ctx->fwd_in_factor && ctx->tune.inv512 && ctx->t512_mode != 2;   // mode 2 builds [R ; T] elsewhere
+  const GpakSchedule &sc = ctx->sched;
+  ctx->z_ok = sc.fwd_in_factor;
+  // the explicit inverses are built beside the forward substitution only (gpak_potrf_plan)
+  ctx->backsolve = !(sc.fwd_in_factor && sc.inv512) ? gpak_ctx::BS_BLOCKS128
+                   : sc.bwd_fused == 2              ? gpak_ctx::BS_RT
+                   : sc.bwd_fused == 1              ? gpak_ctx::BS_INV_FAR
+                                                    : gpak_ctx::BS_INV_STEP;
   return GPAK_OK;
 }
 
@@ -554,14 +566,7 @@ static int ensure_alpha(gpak_ctx *ctx) {
     gpak_launch_trsv_fwd(st, ctx->Np, ctx->dM, ctx->ld, ctx->dInv, w0, w1);
   }
   ctx->z_ok = false;  // the back substitution consumes w1
-  if (ctx->t512_mode)
-    gpak_launch_trsv_bwd3(st, ctx->Np, ctx->dM, ctx->ld, w1, ctx->dAlpha, ctx->dWork + 2 * (size_t)ctx->Np,
-                          ctx->t512_mode == 2 ? ctx->dT512 : ctx->dInv512,
-                          (size_t)(ctx->t512_mode == 2 ? 2 : 1) * ctx->bwd_bw * ctx->bwd_bw,
-                          (ctx->t512_mode == 2 ? 2 : 1) * ctx->bwd_bw, ctx->t512_mode == 2, ctx->bwd_bw);
-  else
-    gpak_launch_trsv_bwd2(st, ctx->Np, ctx->dM, ctx->ld, ctx->dInv, w1, ctx->dAlpha, ctx->dWork + 2 * (size_t)ctx->Np,
-                          ctx->inv512_ok ? ctx->dInv512 : nullptr, ctx->bwd_bw);
+  gpak_backsolve(ctx, st, w1, ctx->dAlpha, ctx->dWork + 2 * (size_t)ctx->Np);
   GPAK_HIP(hipEventRecord(ctx->ev[4], st));
   GPAK_HIP(hipEventSynchronize(ctx->ev[4]));
   float ms = 0;
@@ -627,10 +632,7 @@ int gpak_import_factor(gpak_ctx *ctx, const gpak_dist_factor_view *v) {
   GPAK_HIP(hipMemcpyAsync(ctx->dF, v->f, sizeof(double) * Np, hipMemcpyDeviceToDevice, st));
   GPAK_HIP(hipStreamSynchronize(st));
   ctx->mstate = gpak_ctx::M_L;
-  ctx->z_ok = false;         // dWork does not hold L^-1 (y/sn2)
-  ctx->inv512_ok = false;    // the 512-block inverses were not imported: back substitutions use the 128-blocks
-  ctx->t512_mode = 0;
-  ctx->lf_ok = false;        // the fp32 image (GPAK_F32 prediction) is rebuilt from this factor on first use
+  factor_changed(ctx);       // in particular the 512-block inverses were not imported: back substitutions use the 128-blocks
   ctx->alpha_ok = true; ctx->nlz_ok = true;
   ctx->failed_col = 0;
   ctx->quad = v->quad; ctx->sumlp = v->sumlp; ctx->logdet = v->logdet; ctx->nlz = v->nlz;

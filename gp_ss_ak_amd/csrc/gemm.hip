@@ -77,7 +77,7 @@ __device__ __forceinline__ bool gpak_super_tile(int ssel, int slot, int lr, int 
 // TRAILING only names the instantiation (the bulk trailing update gets its own line in rocprofv3 statistics).
 // K0MAP (the distributed gradient's B^-1 = G G^T on row-cyclic slabs of G): the k-loop of tile row ti starts at global
 // row block ti * cyc_tpb + cyc_lt0 (the cyc_* parameters are reused; no cyclic column map in that instantiation).
-// TICKET (the bulk update of the factorisation, GpakTuning::bulk_tickets): which workgroup computes which tile is
+// TICKET (the bulk update of the factorisation, GpakSchedule::bulk_tickets): which workgroup computes which tile is
 // decided at run time instead of by blockIdx.  The static map takes workgroup b to XCD b & 7 and gives it slot
 // (b >> 3) & 63 of that XCD's super-tiles, so every XCD has to finish exactly its eighth of the launch however many of its
 // slots a CU mask or a co-resident panel kernel has taken.  With tickets, XCD x (read from HW_REG_XCC_ID) owns the same
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, RS_OCC) void gpak_gemm_nt_f64_rs(int K, double
   // loop with the two v_lshl_add_u64 per k-step the compiler makes of per-lane pointers 146 TFLOP/s, with v_add_co
   // pairs 142, with scalar bases 155.6 of 157).  RS_LAUNDER keeps loop-strength reduction from turning base + offset
   // back into per-lane 64-bit pointers.
-  // SBASE is chosen by the launcher for the bulk update while the trailing matrix is large (GpakTuning::sbase_rows):
+  // SBASE is chosen by the launcher for the bulk update while the trailing matrix is large (GpakKernelTuning::sbase_rows):
   // alone the kernel gains 1.2-1.6 % at K >= 512 and LOSES 4-13 % at K = 128 / 256 (more issue-stall cycles per wave
   // around the short loop, tools/ab_pmc.sh), and in situ the tighter loop starves the panel chain beside it -- with
   // scalar bases in every bulk update the step was 2 ms SLOWER at N = 32768 and 10 % slower at N = 8192, where the chain
@@ -395,7 +395,7 @@ void gpak_launch_gemm_nt(hipStream_t st, int mt, int nt, int K, double alpha, co
                          int col_block0, bool lower_skip, bool trailing, bool k0_by_row, unsigned long long *tickets,
                          int surplus_pct) {
   if (mt <= 0 || nt <= 0) return;
-  // super-tile shape: 8 x 8 unless the bulk trailing update was asked for another one (GpakTuning::super_lr)
+  // super-tile shape: 8 x 8 unless the bulk trailing update was asked for another one (GpakKernelTuning::super_lr)
   int lr = 3;
   if (trailing && lower_skip && row_block0 == col_block0) {
     lr = gpak_tuning().super_lr;
@@ -444,7 +444,7 @@ void gpak_launch_gemm_nt(hipStream_t st, int mt, int nt, int K, double alpha, co
   }
   // Scalar-base build (SBASE): for the long products that only occur OUTSIDE the factorisation -- K >= 2048: the upper
   // levels of the prediction's substitution ladder, the gradient's G G^T -- where nothing runs beside the kernel and it
-  // is 1.2-1.6 % faster; inside the factorisation (K <= 1024) only on request (GpakTuning::sbase_rows, measured slower).
+  // is 1.2-1.6 % faster; inside the factorisation (K <= 1024) only on request (GpakKernelTuning::sbase_rows, measured slower).
   const int sbase_rows = gpak_tuning().sbase_rows;
   const bool long_k = K >= 2048;
   if (trailing && (long_k || (sbase_rows > 0 && (long)mt * TM > sbase_rows)))

@@ -313,9 +313,9 @@ void gpak_launch_gemm_nt_f32(hipStream_t st, int mt, int nt, int K, float alpha,
   // Products longer than one chunk take the wide-accumulation kernel (fp32 MFMA chunks of K = 128 summed in fp64):
   // measured at N = 32768, M = 65536 against the fp64 context, variance error 7.4e-7 of the largest variance instead
   // of 6.8e-6, for 118 instead of 120.5 TFLOP/s (profiles/r03_f32_accumulation.txt).  A K = 128 product IS one chunk:
-  // the 128 x 64-tile kernel below computes the same sum faster.  GpakTuning::f32_wide = false (GPAK_F32_ACC=plain): the
+  // the 128 x 64-tile kernel below computes the same sum faster.  GpakKernelTuning::f32_wide = false (GPAK_F32_ACC=plain): the
   // round-2 kernels everywhere.
-  const GpakTuning &tn = gpak_tuning();
+  const GpakKernelTuning &tn = gpak_tuning();
   const bool wide = tn.f32_wide && K > 128 && K % 128 == 0;
   if (wide) {
     const int v = tn.f32_rsd;

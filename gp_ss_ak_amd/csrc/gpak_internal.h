@@ -6,8 +6,7 @@
 #include <vector>
 
 #include "../../include/gpak.h"
-
-#define GPAK_TILE 128  // every matrix dimension on the device is padded to this
+#include "potrf_plan.h"  // GPAK_TILE, GpakSchedule and the factorisation's schedule (HIP-free)
 
 // The covariance function as the device sees it: a SUM of up to three stationary terms (the
 // children of the reference's HybKerns, Kernel.cpp:140-154), a constant and a white-noise diagonal.
@@ -47,56 +46,26 @@ struct DevPoints {
   int cap = 0;  // allocated points (multiple of GPAK_TILE)
 };
 
-// ---- tuning ------------------------------------------------------------------------------------------------
-// Every schedule / kernel-selection knob of the library in ONE place.  gpak_tuning() is the process-wide set: the
-// defaults below (each the measured best at N = 32768 on MI355X, DESIGN.md sections 4.1-4.4), overridden ONCE, at the
-// first call, by the GPAK_* environment variables of the same names (A/B tooling; gpak_reload_tuning() re-reads
-// them).  A context copies the set at gpak_create; gpak_set_option changes the copy of that context only.
-struct GpakTuning {
-  // gpak_potrf_blocked
-  int nb_outer = 512;          // GPAK_NB_OUTER      outer panel width
-  int nb_wide = 1024;          // GPAK_NB_WIDE       panel width while more than nb_wide_rows rows are left (0: off)
-  int nb_wide_rows = 16384;    // GPAK_NB_WIDE_ROWS
-  int nb_xwide = 2048;         // GPAK_NB_XWIDE      ... and while more than nb_xwide_rows rows are left (0: off)
-  int nb_xwide_rows = 32768;   // GPAK_NB_XWIDE_ROWS
-  bool first_narrow = true;    // GPAK_FIRST_NARROW  the very first panel is nb_outer wide
-  int tail_rows = 12288;       // GPAK_TAIL_ROWS     rows left from which the bulk updates use the CU-masked queue
-  bool sub_next = false;       // GPAK_SUB_NEXT      tail: next block column updated sub-panel by sub-panel
-  int next_split_rows = 0;     // GPAK_NEXT_SPLIT_ROWS  rows left from which only the first 128 columns of the next block column are
-                               //                    updated in the panel chain, the others beside the next panel's first step (0: off)
-  bool inv512 = true;          // GPAK_INV512        explicit diagonal-block inverses for the back substitution
-  int bwd_fused = 2;           // GPAK_BWD_FUSED     back substitution: 0 three launches per step, 1 far column dots under the diagonal
-                               //                    step (two launches), 2 one launch (coupling blocks T_b): solve.hip
-  int bwd_block = 512;         // GPAK_BWD_BLOCK     ... of this width: 512, 1024 or 2048 columns per back-substitution step
-                               //                    (measured round 3: solve 1.72 / 1.42 / 1.33 ms at N = 32768, but the wider inverses cost
-                               //                    the factorisation as much or more: profiles/r03_bwd_block.txt)
-  bool lookahead = true;       // GPAK_LOOKAHEAD     0: everything on one stream
-  bool fwd_in_factor = true;   // GPAK_FWD_IN_FACTOR forward substitution of y/sn2 rides along with the factorisation
-  int potrf_co = 1;            // GPAK_POTRF_CO      0 always the 8-wave block kernel, 2 always the 4-wave one, 1 as asked
-  int tail_mask = 8;           // GPAK_TAIL_MASK     compute units the tail's bulk queue leaves idle (0: no such queue)
-  int tail_mask_stride = 1;    // GPAK_TAIL_MASK_STRIDE
-  bool bulk_queue = true;      // GPAK_BULK_QUEUE    bulk updates on a queue made by hipExtStreamCreateWithCUMask
-  long ld_pad = -1;            // GPAK_LD_PAD        leading-dimension skew in doubles (-1: 32 from Np = 1024 on)
-  // kernel selection
+// ---- tuning, part 2: kernel selection ------------------------------------------------------------------------
+// Part 1, the schedule set that a context copies and gpak_set_option changes, is GpakSchedule in potrf_plan.h.
+// What the launchers of gemm.hip / gemm_f32.hip / gram.hip / potrf.hip read has no context to live in: this set is
+// process-wide and read only through gpak_tuning().  Same rules for the values: the defaults below, overridden once,
+// at the first call, by the GPAK_* environment variables of the same names; gpak_reload_tuning() re-reads them.
+struct GpakKernelTuning {
   int sbase_rows = 0;          // GPAK_SBASE_ROWS      bulk updates of more rows than this use the scalar-base build of the kernel (0: never;
                                //                      measured slower in situ at every threshold: profiles/r03_scalar_base.txt)
   int gemm_small = 160;        // GPAK_GEMM_SMALL      tile grids up to this size take the latency kernel
   int gemm_small_rows = 16;    // GPAK_GEMM_SMALL_ROWS rows per workgroup of that kernel: 16 / 32 / 64
   int super_lr = 3;            // GPAK_SUPER_LR      bulk update: super-tiles of 2^lr x 2^(6-lr) tiles per XCD (3 = 8 x 8)
-  bool bulk_tickets = true;    // GPAK_BULK_TICKETS  factorisation's bulk update: tiles claimed per XCD at run time (0: static blockIdx map)
-  int bulk_surplus = 6;        // GPAK_BULK_SURPLUS  ... with this many percent more workgroups than tiles
+  int potrf_co = 1;            // GPAK_POTRF_CO      as GpakSchedule::potrf_co, for panels factored without a context (gpak_dev.h)
   bool fill_fast = true;       // GPAK_FILL_FAST     table exp + in-line sqrt fill / Gram-matvec
   bool kmv_sym = true;         // GPAK_KMV_SYM       symmetric Gram-matvec from 32 macro blocks on
   // fp32 prediction (GPAK_F32 contexts)
   bool f32_wide = true;        // GPAK_F32_ACC=plain switches the fp64 accumulation of the fp32 products off
   int f32_rsd = 4;             // GPAK_F32_RSD       operand prefetch depth of the wide-accumulation kernel: 2 / 4 / 8
   int f32_tile = 128;          // GPAK_F32_TILE      wave tile rows of the plain fp32 kernel: 128 / 64
-  int fs_levels[8] = {128, 512, 2048, 8192, 0, 0, 0, 0};   // GPAK_FS_LEVELS_F32  ladder of the substitution with many right-hand sides (fp32 and fp64 prediction)
-  int pred_batch = 0;          // GPAK_PRED_BATCH    test points per batch (0: 16384 fp64, 65536 fp32)
-  int pred_ld_skew = 1;        // GPAK_PRED_LD_SKEW  leading dimensions of the test-major batch and of the fp32 factor image
-                               //                    are skewed by this many 256-byte units (0: powers of two, as in round 2)
 };
-const GpakTuning &gpak_tuning();
+const GpakKernelTuning &gpak_tuning();
 int gpak_build_kp(int nterms, const int *kinds, const double *pars, double bias, double white, int dist_mode,
                   KernParams *out, double *kdiag_out);
 
@@ -138,8 +107,14 @@ struct gpak_ctx {
   double *dInv512 = nullptr; // explicit (L_bb^-1)^T of the bw x bw diagonal blocks (bw = bwd_bw; back substitution)
   int bwd_bw = 512;          // block width dInv512 was sized and is being built for
   double *dT512 = nullptr;   // bwd_fused = 2: per block column the stacked [R_b ; T_b], T_b = L[b, b-1]^T R_b (2 bw x bw: solve.hip)
-  bool inv512_ok = false;
-  int t512_mode = 0;         // fused back substitution of the current factor: 0 no, 1 from dInv512, 2 from dT512
+  // what gpak_backsolve (solve.hip) may use with the current factor: set by ensure_factor after a successful
+  // factorisation, reset by factor_changed (api.hip)
+  enum Backsolve {
+    BS_BLOCKS128,            // the inverted 128-blocks only
+    BS_INV_STEP,             // explicit inverses in dInv512, three launches per step (bwd_fused 0)
+    BS_INV_FAR,              // ... far column dots under the diagonal step (bwd_fused 1)
+    BS_RT                    // [R_b ; T_b] in dT512, one launch per step (bwd_fused 2)
+  } backsolve = BS_BLOCKS128;
   double *dAlpha = nullptr;  // Np
   double *dWork = nullptr;   // 4*Np scratch vectors
   double *dRed = nullptr;    // small reduction scratch
@@ -172,12 +147,9 @@ struct gpak_ctx {
   size_t gpart_elems = 0;
 
   // options
-  GpakTuning tune;            // this context's copy of the tuning set (gpak_set_option changes it)
+  GpakSchedule sched;         // this context's copy of the schedule set (gpak_set_option changes it)
   bool memoise = false;
-  int nb_outer = 512;
   bool profile = false;
-  bool lookahead = true;
-  bool fwd_in_factor = true;  // L^-1 (y/sn2) is computed block column by block column during the factorisation
   bool z_ok = false;          // dWork[Np..2Np) holds L^-1 (y/sn2) of the current factor
 
   // timing
@@ -360,8 +332,9 @@ void gpak_launch_trsv_bwd2(hipStream_t st, int Np, const double *L, long ld, con
 // OP = per block column R_b (and, with_T, T_b in the rows below it: gpak_launch_diag_inverse with extra = NB)
 void gpak_launch_trsv_bwd3(hipStream_t st, int Np, const double *L, long ld, const double *z, double *out, double *scratch,
                            const double *OP, size_t op_stride, int RL, bool with_T, int NB);
-void gpak_launch_trsv_bwd(hipStream_t st, int Np, const double *L, long ld, const double *inv, double *x,
-                          double *out);
+// out = L^-T z with whatever the context's current factor supports (gpak_ctx::backsolve); z is read-only, scratch
+// holds what the launcher it picks asks for: at most max(8 + bw / 32, 18) * bw doubles, bw = ctx->bwd_bw
+void gpak_backsolve(gpak_ctx *ctx, hipStream_t st, const double *z, double *out, double *scratch);
 void gpak_launch_trsv_fwd_block(hipStream_t st, int Np, int J, int W, const double *L, long ld,
                                 const double *inv, double *x, double *out);
 void gpak_launch_trsv_bwd_block(hipStream_t st, int J, int W, const double *L, long ld, const double *inv,

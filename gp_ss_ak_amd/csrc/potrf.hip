@@ -482,7 +482,7 @@ void gpak_launch_potrf128(hipStream_t st, double *A, long ld, double *inv, int c
       done_mask.fetch_or(bit, std::memory_order_release);
     }
   }
-  // co_mode (GpakTuning::potrf_co): 0 = always the 8-wave build, 2 = always the co-resident 4-wave build, 1 = as the
+  // co_mode (GpakSchedule::potrf_co): 0 = always the 8-wave build, 2 = always the co-resident 4-wave build, 1 = as the
   // caller asks; -1 = the process-wide setting
   if (co_mode < 0) co_mode = gpak_tuning().potrf_co;
   if (co_mode != 1) co = co_mode == 2;
@@ -517,7 +517,6 @@ static void factor_panel_128(hipStream_t st, double *M, long ld, int Np, int J, 
 }
 // Panels wider than GPAK_PANEL_MID columns are factored in GPAK_PANEL_MID-column pieces with a K=MID update
 // of the rest of the panel in between (three-level blocking: 128 / MID / W).
-#define GPAK_PANEL_MID 512
 void gpak_factor_panel(hipStream_t st, double *M, long ld, int Np, int J, int W, double *inv_base, int *info,
                        bool zero_inv, bool co, int co_mode, hipEvent_t gate) {
   for (int j = J; j < J + W; j += GPAK_PANEL_MID) {
@@ -532,7 +531,7 @@ void gpak_factor_panel(hipStream_t st, double *M, long ld, int Np, int J, int W,
 }
 static void factor_panel(gpak_ctx *ctx, hipStream_t st, int J, int W, bool co, hipEvent_t gate = nullptr) {
   // ctx->dInv is zeroed once in gpak_set_train and only ever written inside its triangles
-  gpak_factor_panel(st, ctx->dM, ctx->ld, ctx->Np, J, W, ctx->dInv, ctx->dInfo, false, co, ctx->tune.potrf_co, gate);
+  gpak_factor_panel(st, ctx->dM, ctx->ld, ctx->Np, J, W, ctx->dInv, ctx->dInfo, false, co, ctx->sched.potrf_co, gate);
 }
 
 // Chain-bound tail: the same panel factorisation (W <= 512), but the update of the NEXT block column [J1, J2) is
@@ -549,7 +548,7 @@ static int factor_panel_tail(gpak_ctx *ctx, hipStream_t sp, hipStream_t sx, int 
   int k = 0;
   for (int j = J; j < J + W; j += PB, k++) {
     double *inv = ctx->dInv + (size_t)(j / PB) * 2 * PB * PB;
-    gpak_launch_potrf128(sp, M + j + (size_t)j * ld, ld, inv, j, ctx->dInfo, false, false, ctx->tune.potrf_co);
+    gpak_launch_potrf128(sp, M + j + (size_t)j * ld, ld, inv, j, ctx->dInfo, false, false, ctx->sched.potrf_co);
     const int mt = (Np - j - PB) / PB;
     if (mt <= 0) continue;
     double *P = M + (j + PB) + (size_t)j * ld;
@@ -581,7 +580,7 @@ static void update_cols(gpak_ctx *ctx, hipStream_t st, int J, int W, int c0, int
   if (mt <= 0 || nt <= 0) return;
   const double *P = M + c0 + (size_t)J * ld;
   gpak_launch_gemm_nt(st, mt, nt, W, -1.0, P, ld, P, ld, 1.0, M + c0 + (size_t)c0 * ld, ld, 0, 0, true,
-                      trailing, false, tk, ctx->tune.bulk_surplus);
+                      trailing, false, tk, ctx->sched.bulk_surplus);
 }
 
 // Right-looking blocked factorisation with one panel of look-ahead:
@@ -591,41 +590,25 @@ static void update_cols(gpak_ctx *ctx, hipStream_t st, int J, int W, int c0, int
 // T(b,b+1) waits for the previous bulk update (which touched column b+1); the bulk update
 // T(b,b+2..) waits for F(b).  While the MFMA-bound bulk update of step b runs, the latency-
 // bound panel work of step b+1 proceeds beside it.
+// WHAT is done per panel -- widths, queues, which variant of each hand-off -- is decided by gpak_potrf_plan
+// (potrf_plan.h); this function turns each step of the plan into its launches and event edges.
 int gpak_potrf_blocked(gpak_ctx *ctx) {
   const int Np = ctx->Np;
+  const GpakSchedule &sc = ctx->sched;
+  PotrfCaps caps;
+  caps.tail_queue = ctx->stream_tail != nullptr;
+  caps.bulk_queue = ctx->stream_bulk != nullptr;
+  caps.side_stream = ctx->stream_x != nullptr;
+  const std::vector<PotrfStep> plan = gpak_potrf_plan(Np, sc, caps, ctx->bwd_bw);
+  const int nJ = (int)plan.size();
   // without look-ahead everything is queued on the one main stream, in the classical order
-  hipStream_t su = ctx->stream, sp = ctx->lookahead ? ctx->stream_hi : ctx->stream;
-  hipStream_t sf = ctx->lookahead ? ctx->stream_fs : ctx->stream;
-  int NB = ctx->nb_outer;
-  if (NB < PB) NB = PB;
-  NB = NB / PB * PB;
-  // Panel boundaries.  While the trailing matrix is large the bulk update hides any panel chain, and a wider
-  // panel makes it more efficient (K = 1024: 73.7 TFLOP/s in the kernel, K = 512: 71.4); later the narrower
-  // panel keeps the chain short (N=32768: 180.8 -> 178.5 ms).  GPAK_NB_WIDE / GPAK_NB_WIDE_ROWS: width and
-  // "rows left" threshold; only applies when nb_outer is narrower than the wide width.
-  const int nb_wide = ctx->tune.nb_wide / PB * PB;   // 0: off
-  const int nb_wide_rows = ctx->tune.nb_wide_rows;
-  // a third tier for trailing matrices beyond N = 32768: 2048-column panels while more than 32768 rows are left
-  // (N=65536: 1295.0 -> 1285.5 ms with 2048 / 32768 alone, tools/time_sizes.py; nothing changes at N <= 32768)
-  const int nb_xwide = ctx->tune.nb_xwide / PB * PB, nb_xwide_rows = ctx->tune.nb_xwide_rows;
-  std::vector<int> Js;
-  // the very first panel has nothing to hide behind: keep it narrow so that the first bulk update starts early
-  // (measured at N=32768, 30-step A/B inside one box: 182.46 -> 181.90 ms)
-  const bool first_narrow = ctx->tune.first_narrow;
-  for (int J = 0; J < Np;) {
-    Js.push_back(J);
-    const bool first = first_narrow && J == 0;
-    J += (nb_xwide > NB && nb_xwide > nb_wide && Np - J > nb_xwide_rows && !first) ? nb_xwide
-         : (nb_wide > NB && Np - J > nb_wide_rows && !first)                        ? nb_wide
-                                                                                    : NB;
-  }
-  const int nJ = (int)Js.size();
-  Js.push_back(Np);
+  hipStream_t su = ctx->stream, sp = sc.lookahead ? ctx->stream_hi : ctx->stream;
+  hipStream_t sf = sc.lookahead ? ctx->stream_fs : ctx->stream, sx = ctx->stream_x;
   const int init = 0x7fffffff;
   GPAK_HIP(hipMemcpyAsync(ctx->dInfo, &init, sizeof(int), hipMemcpyHostToDevice, su));
-  // ticketed bulk updates (GpakTuning::bulk_tickets): a ring of eight list words per bulk launch, zeroed here once for
+  // ticketed bulk updates (GpakSchedule::bulk_tickets): a ring of eight list words per bulk launch, zeroed here once for
   // the whole factorisation (one command; a memset in front of every bulk launch would cost a hand-off each)
-  const bool tickets = ctx->tune.bulk_tickets;
+  const bool tickets = sc.bulk_tickets;
   if (tickets) {
     if (ctx->tickets_cap < nJ) {
       if (ctx->dTickets) GPAK_HIP(hipFree(ctx->dTickets));
@@ -646,114 +629,75 @@ int gpak_potrf_blocked(gpak_ctx *ctx) {
   hipEvent_t Estart = ctx->ev_sync[2 * nJ], Eend = ctx->ev_sync[2 * nJ + 1], Efs = ctx->ev_sync[2 * nJ + 2];
   hipEvent_t Eorder = ctx->ev_sync[2 * nJ + 3];
   hipEvent_t *EX = ctx->ev_sync.data() + 2 * nJ + 4, EXdone = ctx->ev_sync[2 * nJ + 8];
+  while (ctx->profile && ctx->ev_pool.size() < 2 * (size_t)nJ) {
+    hipEvent_t e;
+    GPAK_HIP(hipEventCreate(&e));
+    ctx->ev_pool.push_back(e);
+  }
   // the panel stream starts after everything queued so far on the main stream (the fill)
   GPAK_HIP(hipEventRecord(Estart, su));
   GPAK_HIP(hipStreamWaitEvent(sp, Estart, 0));
 
-  size_t ev_used = 0;
-  int done512 = 0;
-  double tflops = 0.0, tbytes = 0.0;
-  int tl = 0;
-  const int tail_rows = ctx->tune.tail_rows;
-  // sub-panel updates of the next block column in the tail (factor_panel_tail): measured 183.07 -> 183.73 ms at
-  // N=32768 -- the four K=128 products re-read and re-write the column four times and the chain gains nothing
-  // measurable; off unless GPAK_SUB_NEXT=1 (kept: the multi-GPU schedule is built the same way and tests compare)
-  const bool sub_next = ctx->tune.sub_next;
-  bool next_col_done = false;   // the next block column already has this panel's update (applied per sub-panel)
-  // GPAK_NEXT_SPLIT_ROWS: in the chain-bound tail only the first 128 columns of the next block column take this panel's
-  // K = W update on the panel stream; the others get it on the side stream while the next panel's first block kernel
-  // and panel solve run, and that panel's first in-panel update waits for it (`gate`)
-  const int next_split_rows = ctx->stream_x && ctx->lookahead ? ctx->tune.next_split_rows : 0;
-  hipEvent_t gate = nullptr;
+  size_t ev_used = 0;   // profiling: a pair of timing events around every bulk update
   for (int b = 0; b < nJ; b++) {
-    const int J = Js[b], W = Js[b + 1] - J;
-    const int J1n = J + W, J2n = J1n < Np ? Js[b + 2] : Np;
-    const bool tail_step = sub_next && ctx->lookahead && ctx->stream_x && W <= 512 && J1n < Np && Np - J1n <= tail_rows;
-    if (tail_step) {
+    const PotrfStep &s = plan[b];
+    const int J = s.J, W = s.W, J1 = J + W, J2 = s.J2, bw = ctx->bwd_bw;
+    hipEvent_t EUprev = b > 0 ? EU[b - 1] : nullptr;   // the previous bulk update touched the columns [J1, Np)
+    // the part of the previous panel's update of this one that ran on the side stream (NEXT_SPLIT)
+    hipEvent_t gate = b > 0 && plan[b - 1].next == PotrfStep::NEXT_SPLIT ? EXdone : nullptr;
+    if (s.tail_panel) {
       if (gate) GPAK_HIP(hipStreamWaitEvent(sp, gate, 0));
-      int rc = factor_panel_tail(ctx, sp, ctx->stream_x, J, W, J1n, J2n, b > 0 ? EU[b - 1] : nullptr, EX, EXdone);
+      int rc = factor_panel_tail(ctx, sp, sx, J, W, J1, J2, EUprev, EX, EXdone);
       if (rc) return rc;
-      next_col_done = true;
     } else {
-      // panel b is factored while the bulk update of panel b-1 (rows >= J + W) runs: on the unmasked stream that
-      // update holds two 210-VGPR waves on every SIMD of the chip, and only the 4-wave, 80-VGPR potrf128 fits beside it
-      const bool beside_bulk = ctx->lookahead && b > 0 && !(ctx->stream_tail && Np - (J + W) <= tail_rows);
-      factor_panel(ctx, sp, J, W, beside_bulk, gate);
-      next_col_done = false;
+      factor_panel(ctx, sp, J, W, s.beside_bulk, gate);
     }
     GPAK_HIP(hipEventRecord(EF[b], sp));
     // forward substitution of the right-hand side y/sn2 rides along: block column b of L is final
     // here and the solve touches only the two work vectors.  It has its own stream so that its four
     // small launches (~45 us) are not part of the serial panel chain
-    if (ctx->fwd_in_factor) {
+    if (sc.fwd_in_factor) {
       if (sf != sp) GPAK_HIP(hipStreamWaitEvent(sf, EF[b], 0));
       gpak_launch_trsv_fwd_block(sf, Np, J, W, ctx->dM, ctx->ld, ctx->dInv, ctx->dWork, ctx->dWork + Np);
-      // explicit inverses of the 512-column diagonal blocks completed by this panel, for the back substitution
-      // (same stream: off the panel chain, hidden behind the bulk updates)
-      const bool inv512 = ctx->tune.inv512;
-      const int bw = ctx->bwd_bw;
-      while (inv512 && done512 * bw < Np && (std::min(Np, (done512 + 1) * bw) <= J + W)) {
-        const int j5 = done512 * bw;
-        const int w5 = std::min(bw, Np - j5);
-        // bwd_fused = 2: with the block that couples it to the block column on its left riding along (solve.hip)
-        if (ctx->tune.bwd_fused == 2)
-          gpak_launch_diag_inverse(sf, j5, w5, ctx->dM, ctx->ld, ctx->dInv, ctx->dT512 + (size_t)done512 * 2 * bw * bw, 2 * bw,
-                                   j5 > 0 ? bw : 0);
-        else
-          gpak_launch_diag_inverse(sf, j5, w5, ctx->dM, ctx->ld, ctx->dInv, ctx->dInv512 + (size_t)done512 * bw * bw, bw);
-        done512++;
-      }
     }
-    const int J1 = J + W;
-    if (J1 >= Np) break;
-    const int J2 = Js[b + 2];
+    // explicit inverses of the bw-column diagonal blocks completed by this panel, for the back substitution (same
+    // stream: off the panel chain, hidden behind the bulk updates)
+    for (int i = s.inv_begin; i < s.inv_end; i++) {
+      const int j5 = i * bw, w5 = std::min(bw, Np - j5);
+      // bwd_fused = 2: with the block that couples it to the block column on its left riding along (solve.hip)
+      if (sc.bwd_fused == 2)
+        gpak_launch_diag_inverse(sf, j5, w5, ctx->dM, ctx->ld, ctx->dInv, ctx->dT512 + (size_t)i * 2 * bw * bw, 2 * bw, j5 > 0 ? bw : 0);
+      else
+        gpak_launch_diag_inverse(sf, j5, w5, ctx->dM, ctx->ld, ctx->dInv, ctx->dInv512 + (size_t)i * bw * bw, bw);
+    }
+    if (s.next == PotrfStep::NEXT_NONE) break;
     // next panel's columns first, on the panel stream (after the previous bulk update)
-    gate = nullptr;
-    if (next_col_done) {
+    if (s.next == PotrfStep::NEXT_DONE) {
       GPAK_HIP(hipStreamWaitEvent(sp, EXdone, 0));
-    } else if (next_split_rows > 0 && Np - J1 <= next_split_rows && J2 - J1 > PB && J2 - J1 <= GPAK_PANEL_MID) {
-      hipStream_t sx = ctx->stream_x;
+    } else if (s.next == PotrfStep::NEXT_SPLIT) {
       GPAK_HIP(hipStreamWaitEvent(sx, EF[b], 0));
-      if (b > 0) {
-        GPAK_HIP(hipStreamWaitEvent(sx, EU[b - 1], 0));
-        GPAK_HIP(hipStreamWaitEvent(sp, EU[b - 1], 0));
+      if (EUprev) {
+        GPAK_HIP(hipStreamWaitEvent(sx, EUprev, 0));
+        GPAK_HIP(hipStreamWaitEvent(sp, EUprev, 0));
       }
       update_cols(ctx, sp, J, W, J1, J1 + PB, false);
       update_cols(ctx, sx, J, W, J1 + PB, J2, false);
       GPAK_HIP(hipEventRecord(EXdone, sx));
-      gate = EXdone;
     } else {
-      if (b > 0) GPAK_HIP(hipStreamWaitEvent(sp, EU[b - 1], 0));
+      if (EUprev) GPAK_HIP(hipStreamWaitEvent(sp, EUprev, 0));
       update_cols(ctx, sp, J, W, J1, J2, false);
     }
-    if (J2 < Np) {
-      // chain-bound tail: the bulk update is off the critical path there; on the CU-masked stream it leaves
-      // idle compute units to potrf128 and the small panel products
-      hipStream_t su_b = (ctx->stream_tail && ctx->lookahead && Np - J2 <= tail_rows) ? ctx->stream_tail
-                         : (ctx->stream_bulk && ctx->lookahead) ? ctx->stream_bulk : ctx->stream;
-      if (su_b != su) {                       // keep the order of successive bulk updates across the two streams
+    if (s.bulk != PotrfStep::Q_NONE) {
+      hipStream_t su_b = s.bulk == PotrfStep::Q_TAIL ? ctx->stream_tail : s.bulk == PotrfStep::Q_BULK ? ctx->stream_bulk : ctx->stream;
+      if (su_b != su) {                       // keep the order of successive bulk updates across the queues
         GPAK_HIP(hipEventRecord(Eorder, su));
         GPAK_HIP(hipStreamWaitEvent(su_b, Eorder, 0));
         su = su_b;
       }
       GPAK_HIP(hipStreamWaitEvent(su, EF[b], 0));
-      if (ctx->profile) {
-        while (ctx->ev_pool.size() < ev_used + 2) {
-          hipEvent_t e;
-          GPAK_HIP(hipEventCreate(&e));
-          ctx->ev_pool.push_back(e);
-        }
-        GPAK_HIP(hipEventRecord(ctx->ev_pool[ev_used], su));
-      }
-      update_cols(ctx, su, J, W, J2, Np, true, tickets ? ctx->dTickets + 8 * (size_t)tl : nullptr);
-      if (ctx->profile) {
-        GPAK_HIP(hipEventRecord(ctx->ev_pool[ev_used + 1], su));
-        ev_used += 2;
-      }
-      const double mt = (Np - J2) / PB;
-      tflops += mt * (mt + 1) / 2.0 * 2.0 * PB * PB * W;  // lower tiles only
-      tbytes += mt * (mt + 1) / 2.0 * 2.0 * PB * PB * 8.0; // each C tile read once and written once
-      tl++;
+      if (ctx->profile) GPAK_HIP(hipEventRecord(ctx->ev_pool[ev_used++], su));
+      update_cols(ctx, su, J, W, J2, Np, true, tickets ? ctx->dTickets + 8 * (size_t)s.ticket : nullptr);
+      if (ctx->profile) GPAK_HIP(hipEventRecord(ctx->ev_pool[ev_used++], su));
     }
     GPAK_HIP(hipEventRecord(EU[b], su));
   }
@@ -766,9 +710,16 @@ int gpak_potrf_blocked(gpak_ctx *ctx) {
   }
   GPAK_HIP(hipMemcpyAsync(&info, ctx->dInfo, sizeof(int), hipMemcpyDeviceToHost, su));
   GPAK_HIP(hipStreamSynchronize(su));
-  ctx->times.trailing_flops = tflops;
-  ctx->times.trailing_bytes = tbytes;
-  ctx->times.trailing_launches = tl;
+  // what the bulk updates amount to: lower tiles only, each C tile read once and written once
+  ctx->times.trailing_flops = ctx->times.trailing_bytes = 0.0;
+  ctx->times.trailing_launches = 0;
+  for (const PotrfStep &s : plan) {
+    if (s.bulk == PotrfStep::Q_NONE) continue;
+    const double mt = (Np - s.J2) / PB, tiles = mt * (mt + 1) / 2.0;
+    ctx->times.trailing_flops += tiles * 2.0 * PB * PB * s.W;
+    ctx->times.trailing_bytes += tiles * 2.0 * PB * PB * 8.0;
+    ctx->times.trailing_launches++;
+  }
   ctx->times.trailing_ms = 0.0;
   if (ctx->profile) {
     double ms = 0.0;

@@ -68,7 +68,7 @@ static int ensure_predict_bufs(gpak_ctx *ctx, int cap, bool want_var) {
   int rc = gpak_alloc_points(ctx, ctx->Upred, ctx->Np);
   if (rc) return rc;
   // (pred_cap + skew) x Np: the batch is stored with a skewed leading dimension (gpak_predict_impl)
-  size_t need = want_var ? ((size_t)ctx->pred_cap + 64 * (size_t)std::max(0, ctx->tune.pred_ld_skew)) * ctx->Np : 0;
+  size_t need = want_var ? ((size_t)ctx->pred_cap + 64 * (size_t)std::max(0, ctx->sched.pred_ld_skew)) * ctx->Np : 0;
   if (need > ctx->wt_elems) {
     if (ctx->dWt) hipFree(ctx->dWt);
     ctx->dWt = nullptr; ctx->wt_elems = 0;
@@ -82,7 +82,7 @@ static int ensure_predict_bufs(gpak_ctx *ctx, int cap, bool want_var) {
 }
 
 // blocked forward substitution on the test-major batch: Wt (mbp x Np, ld ldw) := Wt * L^-T.
-// A ladder of block widths like the fp32 path below (GpakTuning::fs_levels, 128 / 512 / 2048 / 8192): a block of width
+// A ladder of block widths like the fp32 path below (GpakSchedule::fs_levels, 128 / 512 / 2048 / 8192): a block of width
 // lv[k] is solved by its children of width lv[k-1], each followed by ONE K = lv[k-1] update of the rest of the block.
 // Round 3: the two-level form (128-column steps inside 512 columns, then a K = 512 update of everything to the
 // right) left 75 % of the flops in K = 512 products (70.7 TFLOP/s alone); with the ladder they sit in K = 8192 / 2048
@@ -109,7 +109,7 @@ static void fs_block_f64(gpak_ctx *ctx, double *Wt, long ldw, int mt, int J0, in
 }
 static void forward_subst_batch(gpak_ctx *ctx, double *Wt, long ldw, int mbp) {
   std::vector<int> lv;
-  for (int v : ctx->tune.fs_levels) if (v > 0) lv.push_back(v);
+  for (int v : ctx->sched.fs_levels) if (v > 0) lv.push_back(v);
   if (lv.empty()) lv = {PB, 512};
   lv.push_back(ctx->Np > lv.back() ? ctx->Np : lv.back() + 1);   // the whole matrix is the top block
   fs_block_f64(ctx, Wt, ldw, mbp / PB, 0, ctx->Np, lv, (int)lv.size() - 1);
@@ -121,7 +121,7 @@ static int ensure_f32_factor(gpak_ctx *ctx) {
   const int Np = ctx->Np, T = Np / PB;
   // k-columns 128 KiB apart (Np = 32768 floats) would all fall on the same L2 channel / HBM bank group: skew the
   // leading dimension by 256 B like the fp64 matrix (gpak_set_train)
-  ctx->ldLf = Np + 64L * std::max(0, ctx->tune.pred_ld_skew);
+  ctx->ldLf = Np + 64L * std::max(0, ctx->sched.pred_ld_skew);
   if (!ctx->dLf) {
     if (hipMalloc(&ctx->dLf, sizeof(float) * (size_t)ctx->ldLf * Np) != hipSuccess ||
         hipMalloc(&ctx->dInvf, sizeof(float) * (size_t)T * 2 * PB * PB) != hipSuccess) {
@@ -164,7 +164,7 @@ static void fs_block_f32(gpak_ctx *ctx, float *Wt, long ldw, int mt, int J0, int
 }
 static void forward_subst_batch_f32(gpak_ctx *ctx, float *Wt, long ldw, int mbp) {
   std::vector<int> lv;
-  for (int v : ctx->tune.fs_levels) if (v > 0) lv.push_back(v);
+  for (int v : ctx->sched.fs_levels) if (v > 0) lv.push_back(v);
   if (lv.empty()) lv = {PB, 512};
   lv.push_back(ctx->Np > lv.back() ? ctx->Np : lv.back() + 1);   // the whole matrix is the top block
   // the top block's width need not be a multiple of its children's: fs_block_f32 clips the last child
@@ -182,7 +182,7 @@ int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, do
   // 32768 -> 71.7 / 118.7, 65536 -> 71.8 / 119.7: the fp32 path takes the larger batch
   const bool f32 = ctx->precision == GPAK_F32;
   int batch = f32 ? 65536 : 16384;
-  if (ctx->tune.pred_batch > 0) batch = std::max(2 * PB, ctx->tune.pred_batch / (2 * PB) * (2 * PB));
+  if (ctx->sched.pred_batch > 0) batch = std::max(2 * PB, ctx->sched.pred_batch / (2 * PB) * (2 * PB));
   // keep the cross-kernel batch under ~8 GiB
   while (batch > 2 * PB && (size_t)batch * Np * (f32 ? sizeof(float) : sizeof(double)) > ((size_t)8 << 30)) batch /= 2;
   batch = batch / (2 * PB) * (2 * PB);
@@ -223,7 +223,7 @@ int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, do
     if (var) {
       // test-major batch, k-columns `ldw` apart: a power-of-two stride (cap = 65536 floats = 256 KiB) puts every k-column
       // of a row tile on the same L2 channel -- skewed by 256 B like the fp64 matrix
-      const long ldw = cap + (f32 ? 64L : 32L) * std::max(0, ctx->tune.pred_ld_skew);
+      const long ldw = cap + (f32 ? 64L : 32L) * std::max(0, ctx->sched.pred_ld_skew);
       int vs = std::max(1, std::min(64, Np / 512));
       int cps = (Np + vs - 1) / vs;
       if (f32) {
@@ -266,14 +266,7 @@ int gpak_solve_chol_impl(gpak_ctx *ctx, double *X_host, int k) {
     GPAK_HIP(hipMemsetAsync(w0, 0, sizeof(double) * Np, st));
     GPAK_HIP(hipMemcpyAsync(w0, X_host + (size_t)c * N, sizeof(double) * N, hipMemcpyHostToDevice, st));
     gpak_launch_trsv_fwd(st, Np, ctx->dM, ctx->ld, ctx->dInv, w0, w1);
-    if (ctx->t512_mode)
-      gpak_launch_trsv_bwd3(st, Np, ctx->dM, ctx->ld, w1, w2, ctx->dWork + 3 * (size_t)Np,
-                            ctx->t512_mode == 2 ? ctx->dT512 : ctx->dInv512,
-                            (size_t)(ctx->t512_mode == 2 ? 2 : 1) * ctx->bwd_bw * ctx->bwd_bw,
-                            (ctx->t512_mode == 2 ? 2 : 1) * ctx->bwd_bw, ctx->t512_mode == 2, ctx->bwd_bw);
-    else
-      gpak_launch_trsv_bwd2(st, Np, ctx->dM, ctx->ld, ctx->dInv, w1, w2, ctx->dWork + 3 * (size_t)Np,
-                            ctx->inv512_ok ? ctx->dInv512 : nullptr, ctx->bwd_bw);
+    gpak_backsolve(ctx, st, w1, w2, ctx->dWork + 3 * (size_t)Np);
     GPAK_HIP(hipMemcpyAsync(X_host + (size_t)c * N, w2, sizeof(double) * N, hipMemcpyDeviceToHost, st));
   }
   GPAK_HIP(hipStreamSynchronize(st));

@@ -98,17 +98,6 @@ void gpak_launch_trsv_fwd(hipStream_t st, int Np, const double *L, long ld, cons
   }
 }
 
-void gpak_launch_trsv_bwd(hipStream_t st, int Np, const double *L, long ld, const double *inv, double *x,
-                          double *out) {
-  const int T = Np / SB;
-  for (int jb = T - 1; jb >= 0; jb--) {
-    int cols = jb * SB;
-    int cpw = 32;
-    int grid = cols > 0 ? (cols + cpw - 1) / cpw : 1;
-    hipLaunchKernelGGL(gpak_trsv_bwd_f64, dim3(grid), dim3(256), 0, st, jb, L, ld, inv, x, out, cpw, 0);
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // Two-level back substitution  out = L^-T z  (the second solve of solve_chol, GP_Utils.cpp:844):
 // per 512-column block column J, from the last to the first,
@@ -461,6 +450,26 @@ void gpak_launch_trsv_bwd3(hipStream_t st, int Np, const double *L, long ld, con
     if (!with_T && b > 0)
       hipLaunchKernelGGL(gpak_bwd_near_f64, dim3(Wp / 4), dim3(256), 0, st, J, W, Jp, L, ld, out, nearb[(b + 1) & 1]);
     nsplit_in = Rs;
+  }
+}
+
+// The back substitution of a context: whichever of the above its current factor supports (gpak_ctx::backsolve)
+void gpak_backsolve(gpak_ctx *ctx, hipStream_t st, const double *z, double *out, double *scratch) {
+  const int Np = ctx->Np, bw = ctx->bwd_bw;
+  const size_t blk = (size_t)bw * bw;
+  switch (ctx->backsolve) {
+    case gpak_ctx::BS_RT:
+      gpak_launch_trsv_bwd3(st, Np, ctx->dM, ctx->ld, z, out, scratch, ctx->dT512, 2 * blk, 2 * bw, true, bw);
+      break;
+    case gpak_ctx::BS_INV_FAR:
+      gpak_launch_trsv_bwd3(st, Np, ctx->dM, ctx->ld, z, out, scratch, ctx->dInv512, blk, bw, false, bw);
+      break;
+    case gpak_ctx::BS_INV_STEP:
+      gpak_launch_trsv_bwd2(st, Np, ctx->dM, ctx->ld, ctx->dInv, z, out, scratch, ctx->dInv512, bw);
+      break;
+    case gpak_ctx::BS_BLOCKS128:
+      gpak_launch_trsv_bwd2(st, Np, ctx->dM, ctx->ld, ctx->dInv, z, out, scratch, nullptr, bw);
+      break;
   }
 }
 

@@ -1,5 +1,5 @@
 // Which XCD (and shader engine / CU) each bit of a hipExtStreamCreateWithCUMask mask selects, and how the tail queue's
-// mask (GpakTuning::tail_mask CUs from bit 0, every tail_mask_stride-th) falls on the XCDs.  Every workgroup writes its
+// mask (GpakSchedule::tail_mask CUs from bit 0, every tail_mask_stride-th) falls on the XCDs.  Every workgroup writes its
 // HW_REG_XCC_ID and HW_REG_HW_ID through an ordinary vector store; nothing else runs.
 //   hipcc -O2 --offload-arch=gfx950 tools/xcc_cu_map.hip -o tools/bin/xcc_cu_map && tools/bin/xcc_cu_map [skip stride]
 #include <hip/hip_ext.h>
