@@ -58,6 +58,7 @@ static Tuning read_tuning_env() {
   geti("GPAK_NB_XWIDE_ROWS", t.nb_xwide_rows);
   getb("GPAK_FIRST_NARROW", t.first_narrow);
   geti("GPAK_TAIL_ROWS", t.tail_rows);
+  geti("GPAK_TAIL_MAX_NP", t.tail_queue_max_np);
   getb("GPAK_SUB_NEXT", t.sub_next);
   geti("GPAK_NEXT_SPLIT_ROWS", t.next_split_rows);
   getb("GPAK_INV512", t.inv512);
@@ -245,10 +246,14 @@ int gpak_create(gpak_ctx **out, int device, int precision) {
   hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);  // numerically lower = higher priority
   if ((e = hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio_lo)) != hipSuccess ||
       (e = hipStreamCreateWithPriority(&ctx->stream_hi, hipStreamNonBlocking, prio_hi)) != hipSuccess ||
-      (e = hipStreamCreateWithPriority(&ctx->stream_fs, hipStreamNonBlocking, prio_hi)) != hipSuccess ||
-      (e = hipStreamCreateWithPriority(&ctx->stream_x, hipStreamNonBlocking, prio_hi)) != hipSuccess) {
+      (e = hipStreamCreateWithPriority(&ctx->stream_fs, hipStreamNonBlocking, prio_hi)) != hipSuccess) {
     g_global_err = hipGetErrorString(e); delete ctx; return GPAK_EHIP;
   }
+  ctx->cu_count = prop.multiProcessorCount;
+  // ORDER OF CREATION MATTERS: the two CU-masked queues below are made before the side stream, so that they are the
+  // device's 4th and 5th queue.  Measured (profiles/r06_tail_before.txt): whichever of them was the
+  // 6th queue of the process handed work over in 60-800 us instead of 13 (the bulk queue until round 5: N = 32768
+  // 2 ms slower than without any tail queue; the tail queue when the two are swapped: N = 8192 twice as slow).
   // a copy of the main stream that may not use the first GPAK_TAIL_MASK (default 8) compute units; the bulk
   // updates of the chain-bound tail of the factorisation go there so that the panel chain finds idle CUs
   {
@@ -275,6 +280,10 @@ int gpak_create(gpak_ctx **out, int device, int precision) {
       ctx->stream_bulk = nullptr;
       (void)hipGetLastError();
     }
+  }
+  // the side stream (GPAK_SUB_NEXT, GPAK_NEXT_SPLIT_ROWS: unused by the default schedule) comes last
+  if ((e = hipStreamCreateWithPriority(&ctx->stream_x, hipStreamNonBlocking, prio_hi)) != hipSuccess) {
+    g_global_err = hipGetErrorString(e); delete ctx; return GPAK_EHIP;
   }
   for (int i = 0; i < 10; i++) hipEventCreate(&ctx->ev[i]);
   hipMalloc(&ctx->dRed, sizeof(double) * 64);
@@ -364,6 +373,10 @@ int gpak_set_option(gpak_ctx *ctx, int option, long value) {
       ctx->sched.potrf_co = (int)value;
       return GPAK_OK;
     case GPAK_OPT_PRED_BATCH: ctx->sched.pred_batch = (int)value; return GPAK_OK;
+    case GPAK_OPT_TAIL_MAX_NP:
+      if (value < 0) { ctx->err = "tail_queue_max_np must be 0 (no limit) or a size"; return GPAK_EINVAL; }
+      ctx->sched.tail_queue_max_np = (int)value;
+      return GPAK_OK;
     case GPAK_OPT_BWD_FUSED:
       if (value < 0 || value > 2) { ctx->err = "bwd_fused must be 0, 1 or 2"; return GPAK_EINVAL; }
       ctx->sched.bwd_fused = (int)value;

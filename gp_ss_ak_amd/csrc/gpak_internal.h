@@ -74,6 +74,7 @@ struct gpak_multi;   // multi.hip: one process driving several GPUs (gpak_create
 struct gpak_ctx {
   gpak_multi *multi = nullptr;   // set: every call is forwarded to the group, the fields below are unused
   int device = 0;
+  int cu_count = 0;                 // compute units of the device (gpak_potrf_block_co)
   int precision = GPAK_F64;
   hipStream_t stream = nullptr;     // main stream: fill, bulk trailing updates, solves
   hipStream_t stream_hi = nullptr;  // high-priority stream: panel factorisation (look-ahead)

@@ -595,10 +595,7 @@ static void update_cols(gpak_ctx *ctx, hipStream_t st, int J, int W, int c0, int
 int gpak_potrf_blocked(gpak_ctx *ctx) {
   const int Np = ctx->Np;
   const GpakSchedule &sc = ctx->sched;
-  PotrfCaps caps;
-  caps.tail_queue = ctx->stream_tail != nullptr;
-  caps.bulk_queue = ctx->stream_bulk != nullptr;
-  caps.side_stream = ctx->stream_x != nullptr;
+  const PotrfCaps caps = gpak_potrf_caps(Np, sc, ctx->stream_tail != nullptr, ctx->stream_bulk != nullptr, ctx->stream_x != nullptr);
   const std::vector<PotrfStep> plan = gpak_potrf_plan(Np, sc, caps, ctx->bwd_bw);
   const int nJ = (int)plan.size();
   // without look-ahead everything is queued on the one main stream, in the classical order
@@ -650,7 +647,10 @@ int gpak_potrf_blocked(gpak_ctx *ctx) {
       int rc = factor_panel_tail(ctx, sp, sx, J, W, J1, J2, EUprev, EX, EXdone);
       if (rc) return rc;
     } else {
-      factor_panel(ctx, sp, J, W, s.beside_bulk, gate);
+      // the bulk update that runs beside this panel is panel b-1's
+      const long beside = b > 0 && plan[b - 1].bulk != PotrfStep::Q_NONE
+                              ? gpak_bulk_workgroups((Np - plan[b - 1].J2) / PB, tickets ? sc.bulk_surplus : 0) : 0;
+      factor_panel(ctx, sp, J, W, gpak_potrf_block_co(s, sc.potrf_co, beside, ctx->cu_count), gate);
     }
     GPAK_HIP(hipEventRecord(EF[b], sp));
     // forward substitution of the right-hand side y/sn2 rides along: block column b of L is final

@@ -43,6 +43,8 @@ struct GpakSchedule {
   long ld_pad = -1;            // GPAK_LD_PAD        leading-dimension skew in doubles (-1: 32 from Np = 1024 on)
   bool bulk_tickets = true;    // GPAK_BULK_TICKETS  factorisation's bulk update: tiles claimed per XCD at run time (0: static blockIdx map)
   int bulk_surplus = 6;        // GPAK_BULK_SURPLUS  ... with this many percent more workgroups than tiles
+  int tail_queue_max_np = 0;   // GPAK_TAIL_MAX_NP   padded sizes above this factor without the CU-masked tail queue (0: no limit);
+                               //                    read by gpak_potrf_caps, not by the plan
   // prediction
   int fs_levels[8] = {128, 512, 2048, 8192, 0, 0, 0, 0};   // GPAK_FS_LEVELS_F32  ladder of the substitution with many right-hand sides (fp32 and fp64 prediction)
   int pred_batch = 0;          // GPAK_PRED_BATCH    test points per batch (0: 16384 fp64, 65536 fp32)
@@ -57,6 +59,17 @@ struct PotrfCaps {
   bool bulk_queue = false;   // the bulk updates' own queue (gpak_ctx::stream_bulk)
   bool side_stream = false;  // gpak_ctx::stream_x
 };
+
+// What gpak_potrf_blocked hands to the plan as "the queues the context has": the streams that exist, less the tail
+// queue where the schedule set withholds it by matrix size (GpakSchedule::tail_queue_max_np).  Without the tail queue
+// the plan keeps every bulk update on the bulk queue and every later panel beside_bulk.  The only place this rule lives.
+inline PotrfCaps gpak_potrf_caps(int Np, const GpakSchedule &s, bool have_tail, bool have_bulk, bool have_side) {
+  PotrfCaps caps;
+  caps.tail_queue = have_tail && (s.tail_queue_max_np <= 0 || Np <= s.tail_queue_max_np);
+  caps.bulk_queue = have_bulk;
+  caps.side_stream = have_side;
+  return caps;
+}
 
 // One panel b = columns [J, J + W) and everything its factorisation triggers.  With J1 = J + W:
 //   panel stream :  F(b) | update of the next panel's columns [J1, J2) | F(b+1) ...
@@ -138,4 +151,22 @@ inline std::vector<PotrfStep> gpak_potrf_plan(int Np, const GpakSchedule &s, con
     }
   }
   return plan;
+}
+
+// Workgroups of the bulk update of a trailing matrix of mt tile rows: one per lower tile plus, with the ticketed map,
+// surplus_pct percent more, rounded up per XCD (the grid gpak_launch_gemm_nt makes for it; pass 0 for the static map,
+// whose workgroups beyond the tiles exit at once).
+inline long gpak_bulk_workgroups(int mt, int surplus_pct) {
+  if (mt <= 0) return 0;
+  const long tiles = (long)mt * (mt + 1) / 2;
+  return tiles + 8 * ((tiles * (surplus_pct > 0 ? surplus_pct : 0) + 799) / 800);
+}
+
+// Which 128 x 128 block kernel the panel takes: true = the co-resident 4-wave build.  A beside_bulk panel needs it
+// while the bulk update beside it (panel b-1's, bulk_workgroups_beside workgroups) fills the chip; once that launch has
+// no more workgroups than the chip has compute units, whole CUs are free or hold one bulk workgroup, and the 8-wave
+// build fits there (2 x 134 + 210 VGPRs per SIMD; the bulk kernel uses no LDS to speak of).  potrf_co 0 / 2 force one build.
+inline bool gpak_potrf_block_co(const PotrfStep &st, int potrf_co, long bulk_workgroups_beside, int cu_count) {
+  if (potrf_co != 1) return potrf_co == 2;
+  return st.beside_bulk && !(cu_count > 0 && bulk_workgroups_beside <= cu_count);
 }

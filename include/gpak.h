@@ -117,6 +117,7 @@ int gpak_set_kernel(gpak_ctx *ctx, int nterms, const int *kinds, const double *p
 #define GPAK_OPT_PRED_BATCH  11  /* test points per prediction batch (0: 16384 fp64, 65536 fp32)                    */
 #define GPAK_OPT_BWD_FUSED   12  /* back substitution (needs INV512): 0 three launches per 512 columns, 1 the far column
                                     dots of the next block under this block's diagonal step, 2 (default) one launch  */
+#define GPAK_OPT_TAIL_MAX_NP 13  /* padded sizes above this factor without the CU-masked tail queue (0: no limit)       */
 int gpak_set_option(gpak_ctx *ctx, int option, long value);
 
 /* ---- hot path --------------------------------------------------------------------------- */
