@@ -1,6 +1,8 @@
 // dist.hip -- the multi-GPU hot path in C++ (include/gpak_dist.h): one rank of the block-column-cyclic
 // factorisation / solves / nlZ of GP_utils::ldB2_exact, solve_chol and logLikelihood
-// (GP_Utils.cpp:841-845, 872-915, 1138-1162; the reference itself is single-process).
+// (GP_Utils.cpp:841-845, 872-915, 1138-1162; the reference itself is single-process).  Also here: the
+// built-in HIP engine, the RCCL binding and the functions over RankCore (dist_core.h) that this schedule shares with
+// the row-block x column-block one of grid.hip.
 //
 // Streams of a rank:
 //   bulk  (kind 0)  fill, bulk trailing updates, forward substitution riding along, back substitution, nlZ;
@@ -19,7 +21,6 @@
 // the inverted diagonal blocks, so both triangular solves run locally with no communication.
 #include <dlfcn.h>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -27,14 +28,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <string>
-#include <vector>
 
-#include "../../include/gpak_dev.h"
-#include "../../include/gpak_dist.h"
-#include "gpak_internal.h"
+#include "dist_core.h"
 
 // ------------------------------------------------------------------------------------------------
 // small vector kernels of the built-in engine
@@ -60,12 +55,6 @@ extern "C" int gpak_dev_vec_sum(void *stream, int n, const double *in, double *o
 // built-in HIP engine
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-struct HipEngineState {
-  int device = 0;
-  int cu_mask_skip = 8;
-  bool mask_failed = false;
-};
 
 void *he_alloc(void *, size_t bytes) {
   void *p = nullptr;
@@ -160,6 +149,7 @@ struct Rccl {
   int (*GetUniqueId)(rccl_uid *) = nullptr;
   int (*CommInitRank)(void **, int, rccl_uid, int) = nullptr;
   int (*CommInitAll)(void **, int, const int *) = nullptr;
+  int (*CommSplit)(void *, int, int, void **, void *) = nullptr;
   int (*CommAbort)(void *) = nullptr;
   int (*CommDestroy)(void *) = nullptr;
   int (*Broadcast)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
@@ -180,6 +170,7 @@ struct Rccl {
     CommInitRank = (int (*)(void **, int, rccl_uid, int))dlsym(lib, "ncclCommInitRank");
     CommDestroy = (int (*)(void *))dlsym(lib, "ncclCommDestroy");
     CommInitAll = (int (*)(void **, int, const int *))dlsym(lib, "ncclCommInitAll");
+    CommSplit = (int (*)(void *, int, int, void **, void *))dlsym(lib, "ncclCommSplit");   // the grid's groups only
     CommAbort = (int (*)(void *))dlsym(lib, "ncclCommAbort");
     Broadcast = (int (*)(const void *, void *, size_t, int, int, void *, hipStream_t))dlsym(lib, "ncclBroadcast");
     AllReduce = (int (*)(const void *, void *, size_t, int, int, void *, hipStream_t))dlsym(lib, "ncclAllReduce");
@@ -194,63 +185,337 @@ struct Rccl {
 Rccl g_rccl;
 const int kNcclInt = 2, kNcclDouble = 8, kNcclSum = 0, kNcclMin = 3;
 
-struct RcclTransport {
-  void *comm = nullptr;
-  int world = 1;
-};
-int rt_bcast(void *self, void *st, double *buf, size_t count, int root) {
+// The communicator of `group` (0: the world).  GPAK_OK with none: a one-rank world, where a collective has nothing to
+// do (a one-rank communicator exists only when a test asked for it).
+int rt_comm(void *self, int group, void **comm) {
   RcclTransport *t = (RcclTransport *)self;
-  if (t->world == 1 && !t->comm) return GPAK_OK;   // (a one-rank communicator exists only when a test asked for it)
-  if (!t->comm) return GPAK_ESTATE;
-  return g_rccl.Broadcast(buf, buf, count, kNcclDouble, root, t->comm, (hipStream_t)st) == 0 ? GPAK_OK : GPAK_EHIP;
+  *comm = t->comm[group == GPAK_GROUP_ROW || group == GPAK_GROUP_COL ? group : 0];
+  return *comm || t->world == 1 ? GPAK_OK : GPAK_ESTATE;
 }
-int rt_allreduce_sum(void *self, void *st, double *buf, size_t count) {
-  RcclTransport *t = (RcclTransport *)self;
-  if (t->world == 1 && !t->comm) return GPAK_OK;
-  if (!t->comm) return GPAK_ESTATE;
-  return g_rccl.AllReduce(buf, buf, count, kNcclDouble, kNcclSum, t->comm, (hipStream_t)st) == 0 ? GPAK_OK : GPAK_EHIP;
+int rt_bcast_group(void *self, void *st, double *buf, size_t count, int root, int group) {
+  void *c = nullptr;
+  const int rc = rt_comm(self, group, &c);
+  if (rc != GPAK_OK || !c) return rc;
+  return g_rccl.Broadcast(buf, buf, count, kNcclDouble, root, c, (hipStream_t)st) == 0 ? GPAK_OK : GPAK_EHIP;
+}
+int rt_allreduce_sum_group(void *self, void *st, double *buf, size_t count, int group) {
+  void *c = nullptr;
+  const int rc = rt_comm(self, group, &c);
+  if (rc != GPAK_OK || !c) return rc;
+  return g_rccl.AllReduce(buf, buf, count, kNcclDouble, kNcclSum, c, (hipStream_t)st) == 0 ? GPAK_OK : GPAK_EHIP;
 }
 int rt_allreduce_min_int(void *self, void *st, int *buf, size_t count) {
-  RcclTransport *t = (RcclTransport *)self;
-  if (t->world == 1 && !t->comm) return GPAK_OK;
-  if (!t->comm) return GPAK_ESTATE;
-  return g_rccl.AllReduce(buf, buf, count, kNcclInt, kNcclMin, t->comm, (hipStream_t)st) == 0 ? GPAK_OK : GPAK_EHIP;
+  void *c = nullptr;
+  const int rc = rt_comm(self, 0, &c);
+  if (rc != GPAK_OK || !c) return rc;
+  return g_rccl.AllReduce(buf, buf, count, kNcclInt, kNcclMin, c, (hipStream_t)st) == 0 ? GPAK_OK : GPAK_EHIP;
 }
+int rt_bcast(void *self, void *st, double *buf, size_t count, int root) { return rt_bcast_group(self, st, buf, count, root, 0); }
+int rt_allreduce_sum(void *self, void *st, double *buf, size_t count) { return rt_allreduce_sum_group(self, st, buf, count, 0); }
+int rt_grid_setup(void *, int, int) { return GPAK_OK; }   // the communicators are split in core_init_rccl
 
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+// Gives the communicators back, the groups before the world they were split from.  After a failure ncclCommAbort,
+// where the library has it: it does not wait for peers that may never come.
+void rccl_release(RcclTransport *t, bool failed) {
+  for (int g : {GPAK_GROUP_ROW, GPAK_GROUP_COL, 0}) {
+    if (!t->comm[g]) continue;
+    if (failed && g_rccl.CommAbort) g_rccl.CommAbort(t->comm[g]);
+    else g_rccl.CommDestroy(t->comm[g]);
+    t->comm[g] = nullptr;
+  }
 }
 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// one rank
+// the rank core (dist_core.h): what does not depend on the layout
 // ------------------------------------------------------------------------------------------------
-struct gpak_dist {
-  int rank = 0, P = 1, device = 0;
-  gpak_dist_engine E;
-  gpak_dist_transport T;
-  HipEngineState hip_state;
-  RcclTransport rccl_state;
-  bool builtin_engine = false, builtin_transport = false;
-  std::string err;
+int core_attach(RankCore *h, int rank, int world, int device, const gpak_dist_engine *engine,
+                const gpak_dist_transport *transport, bool cu_mask) {
+  h->rank = rank; h->P = world; h->device = device;
+  memset(&h->stats, 0, sizeof(h->stats));
+  if (engine) {
+    h->E = *engine;
+  } else {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || hipSetDevice(device) != hipSuccess)
+      return GPAK_EHIP;   // no CPU fallback: the built-in engine needs a gfx950 device
+    h->hip_state.device = device;
+    const char *m = getenv("GPAK_DIST_MASK");
+    h->hip_state.cu_mask_skip = cu_mask ? (m ? atoi(m) : 8) : 0;
+    fill_hip_engine(h->E, &h->hip_state);
+    h->builtin_engine = true;
+  }
+  if (transport) {
+    h->T = *transport;
+  } else {
+    h->rccl_state.world = world;
+    h->T.self = &h->rccl_state;
+    h->T.bcast = rt_bcast; h->T.allreduce_sum = rt_allreduce_sum; h->T.allreduce_min_int = rt_allreduce_min_int;
+    h->T.grid_setup = rt_grid_setup; h->T.bcast_group = rt_bcast_group; h->T.allreduce_sum_group = rt_allreduce_sum_group;
+    h->builtin_transport = true;
+  }
+  return GPAK_OK;
+}
 
-  // streams
-  void *s_bulk = nullptr, *s_panel = nullptr, *s_comm = nullptr, *s_aux = nullptr;
+void core_set_device(RankCore *h) {
+  if (h->builtin_engine) hipSetDevice(h->device);
+}
+
+void core_release(RankCore *h) {
+  gpak_dist_engine &E = h->E;
+  auto rel = [&](double *&p) { if (p) E.release(E.self, p); p = nullptr; };
+  rel(h->x_soa); rel(h->y); rel(h->u); rel(h->scratch); rel(h->small); rel(h->alpha); rel(h->rhs); rel(h->f);
+  rel(h->ld_slots); rel(h->bwd_scratch);
+  if (h->info) E.release(E.self, h->info);
+  h->info = nullptr;
+  h->N = h->Np = 0;
+  h->have_result = false;
+}
+
+void core_detach(RankCore *h) {
+  for (void *e : h->ev_sync) h->E.event_destroy(h->E.self, e);
+  for (void *e : h->ev_time) h->E.event_destroy(h->E.self, e);
+  if (h->builtin_transport) rccl_release(&h->rccl_state, false);
+}
+
+int core_init_rccl(RankCore *h, const char *id, int Pr) {
+  if (!h || !id) return GPAK_EINVAL;
+  if (!h->builtin_transport) { h->err = "this handle uses a caller-supplied transport"; return GPAK_ESTATE; }
+  RcclTransport &t = h->rccl_state;
+  if (t.comm[0]) return GPAK_OK;
+  if (!g_rccl.load()) { h->err = g_rccl.err; return GPAK_EHIP; }
+  if (Pr > 0 && !g_rccl.CommSplit) { h->err = "librccl lacks ncclCommSplit (needed for the row / column communicators)"; return GPAK_EHIP; }
+  core_set_device(h);
+  // ncclCommInitRank is a rendezvous of ALL ranks: when one of them never arrives (its start-up failed, its device is
+  // not usable) the others would sit in the bootstrap for ever.  The call therefore runs on a helper thread and this
+  // one waits a bounded time (GPAK_RCCL_INIT_TIMEOUT_S, default 90 s); on a time-out the helper is abandoned (it
+  // holds only the shared state below) and the caller gets an error it can act on -- every host in this repository
+  // then switches ALL ranks to another transport, it never retries RCCL on a subset.
+  struct Shared { std::mutex m; std::condition_variable cv; bool done = false; int rc = -1; void *comm = nullptr; };
+  auto sh = std::make_shared<Shared>();
+  rccl_uid u;
+  memcpy(u.internal, id, GPAK_DIST_ID_BYTES);
+  const int P = h->P, rank = h->rank, dev = h->device;
+  const bool own_dev = h->builtin_engine;
+  std::thread([sh, u, P, rank, dev, own_dev]() {
+    if (own_dev) hipSetDevice(dev);
+    void *c = nullptr;
+    const int rc = g_rccl.CommInitRank(&c, P, u, rank);
+    std::lock_guard<std::mutex> lk(sh->m);
+    sh->rc = rc; sh->comm = c; sh->done = true;
+    sh->cv.notify_all();
+  }).detach();
+  double limit = 90.0;
+  if (const char *e = getenv("GPAK_RCCL_INIT_TIMEOUT_S")) limit = atof(e) > 0 ? atof(e) : limit;
+  {
+    std::unique_lock<std::mutex> lk(sh->m);
+    if (!sh->cv.wait_for(lk, std::chrono::duration<double>(limit), [&] { return sh->done; })) {
+      h->err = "ncclCommInitRank did not return within " + std::to_string((int)limit) + " s (a rank is missing from the rendezvous)";
+      return GPAK_EHIP;
+    }
+  }
+  if (sh->rc != 0) {
+    h->err = std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(sh->rc) : "failed");
+    return GPAK_EHIP;
+  }
+  t.comm[0] = sh->comm;
+  if (Pr > 0) {
+    // row communicator: colour = pr, member index (key) = pc; column communicator: colour = pc, key = pr
+    const int pr = h->rank % Pr, pc = h->rank / Pr;
+    if (g_rccl.CommSplit(t.comm[0], pr, pc, &t.comm[GPAK_GROUP_ROW], nullptr) != 0 ||
+        g_rccl.CommSplit(t.comm[0], pc, pr, &t.comm[GPAK_GROUP_COL], nullptr) != 0) {
+      rccl_release(&t, true);   // a later call starts again from the rendezvous
+      h->err = "ncclCommSplit failed";
+      return GPAK_EHIP;
+    }
+  }
+  return GPAK_OK;
+}
+
+int core_train_check(RankCore *h, const double *X, const double *y, int N, int d, int *nb) {
+  if (!h || !X || !y || N <= 0) return GPAK_EINVAL;
+  if (d != 3 && d != 4) { h->err = "inputs must have 3 or 4 columns"; return GPAK_ENOTIMPL; }
+  if (*nb == 0) *nb = 512;
+  if (*nb < GPAK_TILE || *nb % GPAK_TILE || *nb > 512) { h->err = "nb must be 128, 256, 384 or 512"; return GPAK_EINVAL; }
+  core_set_device(h);
+  h->d = d;
+  return GPAK_OK;
+}
+
+bool core_train_alloc(RankCore *h, int N, int nb) {
+  gpak_dist_engine &E = h->E;
+  h->N = N;
+  h->Np = (N + GPAK_TILE - 1) / GPAK_TILE * GPAK_TILE;
+  h->nb = nb;
+  h->nJ = (h->Np + nb - 1) / nb;
+  h->cap = h->Np;
+  const size_t Np = h->Np;
+  auto dalloc = [&](size_t n) { return (double *)E.alloc(E.self, sizeof(double) * (n ? n : 1)); };
+  h->x_soa = dalloc(4 * Np); h->y = dalloc(Np);   // four raw columns, the 4th zero for d = 3
+  h->u = dalloc(5 * GPAK_MAX_TERMS * Np);          // 5 arrays per child of the composition
+  h->scratch = dalloc(64 * Np); h->small = dalloc(16); h->alpha = dalloc(Np); h->rhs = dalloc(Np); h->f = dalloc(Np);
+  h->ld_slots = dalloc(h->nJ + 1);                 // one per diagonal block of this rank: nJ at the most
+  h->bwd_scratch = dalloc(24 * 512);
+  h->info = (int *)E.alloc(E.self, sizeof(int) * 4);
+  return h->x_soa && h->y && h->u && h->scratch && h->small && h->alpha && h->rhs && h->f && h->ld_slots &&
+         h->bwd_scratch && h->info;
+}
+
+int core_train_upload(RankCore *h, const double *X, const double *y) {
+  gpak_dist_engine &E = h->E;
+  const int N = h->N;
+  const size_t Np = h->Np;
+  std::vector<double> xs(4 * Np, 0.0), yp(Np, 0.0);
+  h->xsum[3] = 0.0;
+  for (int k = 0; k < h->d; k++) {
+    double s = 0.0;
+    for (int i = 0; i < N; i++) { xs[k * Np + i] = X[i + (size_t)k * N]; s += X[i + (size_t)k * N]; }
+    h->xsum[k] = s;
+  }
+  for (int i = 0; i < N; i++) yp[i] = y[i];
+  RCHK(E.upload(E.self, h->s_bulk, h->x_soa, xs.data(), sizeof(double) * 4 * Np));
+  RCHK(E.upload(E.self, h->s_bulk, h->y, yp.data(), sizeof(double) * Np));
+  RCHK(E.zero(E.self, h->s_bulk, h->alpha, sizeof(double) * Np));
+  RCHK(E.zero(E.self, h->s_bulk, h->small, sizeof(double) * 16));
+  memset(&h->stats, 0, sizeof(h->stats));
+  h->stats.rank = h->rank; h->stats.world = h->P; h->stats.n = N; h->stats.n_padded = h->Np; h->stats.nb = h->nb;
+  h->stats.n_panels = h->nJ;
+  return GPAK_OK;
+}
+
+int core_set_params(RankCore *h, const double *expans, double bias, double sn2, int dist_mode) {
+  if (!h || !expans) return GPAK_EINVAL;
+  if (dist_mode != GPAK_DIST_EXPANSION && dist_mode != GPAK_DIST_DIRECT) { h->err = "bad dist_mode"; return GPAK_EINVAL; }
+  memcpy(h->expans, expans, sizeof(double) * 8);
+  h->bias = bias; h->sn2 = sn2; h->mode = dist_mode;
+  h->hyb = false; h->white = 0.0;
+  h->have_params = true;
+  h->have_result = false;   // GP_Utils.cpp:132-133: always invalidates
+  return GPAK_OK;
+}
+
+int core_step_transform(RankCore *h) {
+  gpak_dist_engine &E = h->E;
+  h->t_start = now_ms();
+  h->sync_used = 0; h->time_used = 0; h->spans.clear();
+  h->stats.bytes_broadcast = 0; h->stats.bulk_flops = 0; h->stats.bulk_bytes = 0; h->stats.bulk_launches = 0;
+  h->stats.flags = h->flags;
+  h->tp[0] = h->time_event(h->s_bulk);
+  double mu[4];
+  gpak_pooled_mean(h->xsum, h->N, h->xsum, h->N, mu);   // of X u X, as Kernel.cpp:1391-1392 computes it
+  if (h->hyb) RCHK(E.transform_k(h->s_bulk, h->x_soa, h->Np, h->N, h->cap, h->kern, h->kmode(), mu, h->u));
+  else RCHK(E.transform(h->s_bulk, h->x_soa, h->Np, h->N, h->cap, h->expans, mu, h->u));
+  return GPAK_OK;
+}
+
+int core_step_factored(RankCore *h, int failed_col) {
+  h->failed_col = failed_col;
+  h->tp[2] = h->time_event(h->s_bulk);
+  if (failed_col) {
+    h->err = "B = I + K/sn2 is not positive definite";
+    RCHK(h->E.stream_sync(h->E.self, h->s_bulk));
+    return GPAK_ENOTPD;   // Chol_fail -> quiet NaN (GP_Utils.cpp:1145-1158)
+  }
+  return GPAK_OK;
+}
+
+// Every collective of a rank goes through ONE stream in one global issue order: RCCL serialises the operations of a
+// communicator, and two streams feeding the same communicator concurrently is the classic way to deadlock it.  Where
+// that stream is not the bulk stream, a hop orders it behind the bulk stream and another one back.
+int core_hop(RankCore *h, void *from, void *to) {
+  if (from == to) return GPAK_OK;
+  void *e = h->sync_event();
+  RCHK(h->E.event_record(h->E.self, e, from));
+  RCHK(h->E.stream_wait_event(h->E.self, to, e));
+  return GPAK_OK;
+}
+
+int core_step_finish(RankCore *h, void *s_coll, const std::vector<DiagBlock> &diag, double *nlz) {
+  gpak_dist_engine &E = h->E;
+  gpak_dist_transport &T = h->T;
+  const int N = h->N, Np = h->Np, P = h->P;
+  // ---- f = K alpha: each rank sums over its slice of source points, then one all-reduce (GP_Utils.cpp:1147)
+  int per = (N + P - 1) / P;
+  per = (per + 1) / 2 * 2;
+  const int i0 = std::min(N, h->rank * per), i1 = std::min(N, (h->rank + 1) * per);
+  RCHK(E.zero(E.self, h->s_bulk, h->f, sizeof(double) * Np));
+  const size_t tk0 = h->time_event(h->s_bulk);
+  if (i1 > i0)
+    RCHK(E.kmatvec(h->s_bulk, h->u, h->cap, N, i0, i1, h->alpha, h->kpars(), h->bias, h->kmode(), h->scratch, h->f));
+  // Kern_White is the diagonal Sigma_White I (Kernel.cpp:256-263): its share of K alpha, once (rank 0's partial sum)
+  if (h->hyb && h->white != 0.0 && h->rank == 0) RCHK(E.vec_axpy(h->s_bulk, N, h->white, h->alpha, h->f));
+  const size_t tk1 = h->time_event(h->s_bulk);
+  RCHK(core_hop(h, h->s_bulk, s_coll));
+  RCHK(T.allreduce_sum(T.self, s_coll, h->f, (size_t)Np));
+  RCHK(core_hop(h, s_coll, h->s_bulk));
+  // ---- log-determinant: this rank's diagonal blocks, summed in a fixed order, then over the ranks
+  for (size_t i = 0; i < diag.size(); i++)
+    RCHK(E.logdiag_block(h->s_bulk, diag[i].a, diag[i].ld, diag[i].J, diag[i].W, N, h->ld_slots + i));
+  RCHK(E.zero(E.self, h->s_bulk, h->small, sizeof(double) * 16));
+  if (!diag.empty()) RCHK(E.vec_sum(h->s_bulk, (int)diag.size(), h->ld_slots, h->small + 2));
+  RCHK(core_hop(h, h->s_bulk, s_coll));
+  RCHK(T.allreduce_sum(T.self, s_coll, h->small + 2, 1));
+  RCHK(core_hop(h, s_coll, h->s_bulk));
+  RCHK(E.nlz_terms(h->s_bulk, N, h->y, h->f, h->alpha, h->sn2, h->small));
+  h->tp[4] = h->time_event(h->s_bulk);
+  double vals[3];
+  RCHK(E.download(E.self, h->s_bulk, vals, h->small, sizeof(vals)));
+  h->quad = vals[0]; h->sumlp = vals[1]; h->logdet = vals[2];
+  h->nlz = h->quad - h->sumlp + h->logdet;   // GP_Utils.cpp:1159
+  h->have_result = true;
+  *nlz = h->nlz;
+  // ---- per-phase split
+  gpak_dist_stats &S = h->stats;
+  S.step_ms = now_ms() - h->t_start;
+  auto el = [&](size_t a, size_t b) { double ms = 0; E.event_elapsed_ms(E.self, h->ev_time[a], h->ev_time[b], &ms); return ms; };
+  const size_t *tp = h->tp;
+  S.fill_ms = el(tp[0], tp[1]); S.factor_ms = el(tp[1], tp[2]); S.solve_ms = el(tp[2], tp[3]); S.nlz_ms = el(tp[3], tp[4]);
+  S.kmatvec_ms = el(tk0, tk1);
+  S.bulk_ms = S.chain_ms = S.comm_ms = 0;
+  if (h->profile) {
+    RCHK(E.stream_sync(E.self, h->s_panel));
+    if (s_coll != h->s_bulk) RCHK(E.stream_sync(E.self, s_coll));
+    for (const RankCore::Span &sp : h->spans) {
+      const double ms = el(sp.e0, sp.e1);
+      if (sp.kind == 0) S.bulk_ms += ms; else if (sp.kind == 1) S.chain_ms += ms; else S.comm_ms += ms;
+    }
+  }
+  S.wait_ms = S.factor_ms - S.bulk_ms;
+  return GPAK_OK;
+}
+
+int core_nlz_terms(RankCore *h, double *quad, double *sumlp, double *logdet) {
+  if (quad) *quad = h->quad;
+  if (sumlp) *sumlp = h->sumlp;
+  if (logdet) *logdet = h->logdet;
+  return GPAK_OK;
+}
+
+int core_get_alpha(RankCore *h, double *alpha_host) {
+  core_set_device(h);
+  RCHK(h->E.download(h->E.self, h->s_bulk, alpha_host, h->alpha, sizeof(double) * h->N));
+  return GPAK_OK;
+}
+
+int core_get_stats(RankCore *h, gpak_dist_stats *out) {
+  if (!h || !out) return GPAK_EINVAL;
+  *out = h->stats;
+  out->flags = h->flags;
+  return GPAK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// one rank of the block-column-cyclic layout
+// ------------------------------------------------------------------------------------------------
+struct gpak_dist : RankCore {
+  void *s_comm = nullptr, *s_aux = nullptr;
   bool own_comm_stream = false;
-  int flags = 0;
   bool checked = false;
 
-  // problem
-  int N = 0, Np = 0, nb = 512, nJ = 0, cap = 0;
   long ld = 0;
   std::vector<int> owned;
-  double xsum[4] = {0, 0, 0, 0};
-  int d = 3;                          // input columns: 3, or 4 with a rock-type column
-  double *x_soa = nullptr, *y = nullptr, *u = nullptr, *local = nullptr, *scratch = nullptr, *small = nullptr;
-  double *alpha = nullptr, *fwd_x = nullptr, *fwd_z = nullptr, *rhs = nullptr, *f = nullptr, *bwd_scratch = nullptr;
-  double *ld_slots = nullptr;
-  int *info = nullptr;
+  double *local = nullptr, *fwd_x = nullptr, *fwd_z = nullptr;
   // gradient workspaces (allocated on the first gpak_dist_grad)
   std::vector<double *> slabs;        // [0] own rows of L^-T (rows_a x Np), [1..2] receive buffers (gpak_dist_grad)
   double *binv = nullptr, *gpart = nullptr, *gred = nullptr;
@@ -261,65 +526,14 @@ struct gpak_dist {
   std::vector<double *> rinv;         // per block column: explicit (L_bb^-1)^T, 512 x 512
   std::vector<char> rinv_ok;
 
-  // parameters
-  bool have_params = false;
-  double expans[8] = {0}, bias = 0, sn2 = 0;
-  int mode = GPAK_DIST_DIRECT;
-  bool hyb = false;                         // a general composition (gpak_dist_set_kernel): `kern` is what the engine gets
-  double kern[GPAK_KERN_SERIAL_MAX] = {0};  // serialized: children, kinds, Sigma_White, parameters (gpak_dev.h)
-  double white = 0;
-
-  // results
-  bool have_result = false;
-  double quad = 0, sumlp = 0, logdet = 0, nlz = 0;
-  int failed_col = 0;                 // 1-based failing column of the last factorisation, min-reduced: the same on every rank
-  gpak_dist_stats stats;
-
-  // event pools
-  std::vector<void *> ev_sync, ev_time;
-  size_t sync_used = 0, time_used = 0;
-  struct Span { size_t e0, e1; int kind; };   // kind 0 bulk, 1 chain, 2 comm
-  std::vector<Span> spans;
-  bool profile = true;
-
-  int kmode() const { return mode | (d == 4 ? GPAK_DIST_D4 : 0) | (hyb ? GPAK_DIST_HYB : 0); }   // what the engine calls get
-  const double *kpars() const { return hyb ? kern : expans; }
-  int width(int b) const { return std::min(nb, Np - b * nb); }
-  int start(int b) const { return b * nb; }
   int owner(int b) const { return b % P; }
   double *blk(int b) const { return local + (size_t)(b / P) * nb * ld; }
-
-  void *sync_event() {
-    if (sync_used == ev_sync.size()) ev_sync.push_back(E.event_create(E.self, 0));
-    return ev_sync[sync_used++];
-  }
-  size_t time_event(void *stream) {
-    if (time_used == ev_time.size()) ev_time.push_back(E.event_create(E.self, 1));
-    E.event_record(E.self, ev_time[time_used], stream);
-    return time_used++;
-  }
 };
-
-#define DCHK(call)                                                                    \
-  do {                                                                                \
-    int rc_ = (call);                                                                 \
-    if (rc_ != GPAK_OK) {                                                             \
-      h->err = std::string(#call) + " failed with status " + std::to_string(rc_);     \
-      return rc_ < 0 ? rc_ : GPAK_EHIP;                                               \
-    }                                                                                 \
-  } while (0)
-
-static void set_device(gpak_dist *h) {
-  if (h->builtin_engine) hipSetDevice(h->device);
-}
 
 static void release_problem(gpak_dist *h) {
   gpak_dist_engine &E = h->E;
   auto rel = [&](double *&p) { if (p) E.release(E.self, p); p = nullptr; };
-  rel(h->x_soa); rel(h->y); rel(h->u); rel(h->local); rel(h->scratch); rel(h->small); rel(h->alpha);
-  rel(h->fwd_x); rel(h->fwd_z); rel(h->rhs); rel(h->f); rel(h->bwd_scratch); rel(h->ld_slots);
-  if (h->info) E.release(E.self, h->info);
-  h->info = nullptr;
+  rel(h->local); rel(h->fwd_x); rel(h->fwd_z);
   for (size_t b = 0; b < h->panels.size(); b++) {
     if (h->panels[b]) E.release(E.self, h->panels[b]);
     if (h->invs[b] && h->owner((int)b) != h->rank) E.release(E.self, h->invs[b]);
@@ -331,18 +545,13 @@ static void release_problem(gpak_dist *h) {
   rel(h->binv); rel(h->gpart); rel(h->gred);
   h->panels.clear(); h->invs.clear(); h->rinv.clear(); h->rinv_ok.clear(); h->inv_own.clear();
   h->owned.clear();
-  h->N = h->Np = 0;
-  h->have_result = false;
+  core_release(h);
 }
 
 static int ensure_streams(gpak_dist *h) {
   if (h->s_bulk) return GPAK_OK;
   gpak_dist_engine &E = h->E;
-  if (h->builtin_engine) {
-    const char *m = getenv("GPAK_DIST_MASK");
-    h->hip_state.cu_mask_skip = (h->P > 1) ? (m ? atoi(m) : 8) : 0;   // one rank: the single-GPU numbers say no mask
-    if (h->flags & GPAK_DIST_FLAG_CU_MASK_OFF) h->hip_state.cu_mask_skip = 0;
-  }
+  if (h->flags & GPAK_DIST_FLAG_CU_MASK_OFF) h->hip_state.cu_mask_skip = 0;
   h->s_bulk = E.stream_create(E.self, 0);
   h->s_panel = E.stream_create(E.self, 1);
   h->s_aux = E.stream_create(E.self, 3);
@@ -375,28 +584,8 @@ int gpak_dist_create(gpak_dist **out, int rank, int world, int device, const gpa
   if (!out || world < 1 || rank < 0 || rank >= world) return GPAK_EINVAL;
   *out = nullptr;
   gpak_dist *h = new gpak_dist();
-  h->rank = rank; h->P = world; h->device = device;
-  memset(&h->stats, 0, sizeof(h->stats));
-  if (engine) {
-    h->E = *engine;
-  } else {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || hipSetDevice(device) != hipSuccess) {
-      delete h;
-      return GPAK_EHIP;   // no CPU fallback: the built-in engine needs a gfx950 device
-    }
-    h->hip_state.device = device;
-    fill_hip_engine(h->E, &h->hip_state);
-    h->builtin_engine = true;
-  }
-  if (transport) {
-    h->T = *transport;
-  } else {
-    h->rccl_state.world = world;
-    h->T.self = &h->rccl_state;
-    h->T.bcast = rt_bcast; h->T.allreduce_sum = rt_allreduce_sum; h->T.allreduce_min_int = rt_allreduce_min_int;
-    h->builtin_transport = true;
-  }
+  int rc = core_attach(h, rank, world, device, engine, transport, world > 1);   // one rank: the single-GPU numbers say no mask
+  if (rc) { delete h; return rc; }
   if (getenv("GPAK_DIST_PROFILE")) h->profile = atoi(getenv("GPAK_DIST_PROFILE")) != 0;
   if (getenv("GPAK_DIST_PLAIN_STREAMS") && atoi(getenv("GPAK_DIST_PLAIN_STREAMS")))
     h->flags |= GPAK_DIST_FLAG_CU_MASK_OFF | GPAK_DIST_FLAG_COMM_INLINE;
@@ -406,14 +595,12 @@ int gpak_dist_create(gpak_dist **out, int rank, int world, int device, const gpa
 
 void gpak_dist_destroy(gpak_dist *h) {
   if (!h) return;
-  set_device(h);
+  core_set_device(h);
   gpak_dist_engine &E = h->E;
   if (h->s_bulk) { E.stream_sync(E.self, h->s_bulk); E.stream_sync(E.self, h->s_panel); E.stream_sync(E.self, h->s_comm); E.stream_sync(E.self, h->s_aux); }
   release_problem(h);
-  for (void *e : h->ev_sync) E.event_destroy(E.self, e);
-  for (void *e : h->ev_time) E.event_destroy(E.self, e);
   drop_streams(h);
-  if (h->builtin_transport && h->rccl_state.comm) g_rccl.CommDestroy(h->rccl_state.comm);
+  core_detach(h);
   delete h;
 }
 
@@ -428,45 +615,7 @@ int gpak_dist_rccl_unique_id(char *id) {
   return GPAK_OK;
 }
 
-int gpak_dist_init_rccl(gpak_dist *h, const char *id) {
-  if (!h || !id) return GPAK_EINVAL;
-  if (!h->builtin_transport) { h->err = "this handle uses a caller-supplied transport"; return GPAK_ESTATE; }
-  if (h->rccl_state.comm) return GPAK_OK;
-  if (!g_rccl.load()) { h->err = g_rccl.err; return GPAK_EHIP; }
-  set_device(h);
-  // ncclCommInitRank is a rendezvous of ALL ranks: when one of them never arrives (its start-up failed, its device is
-  // not usable) the others would sit in the bootstrap for ever.  The call therefore runs on a helper thread and this
-  // one waits a bounded time (GPAK_RCCL_INIT_TIMEOUT_S, default 90 s); on a time-out the helper is abandoned (it
-  // holds only the shared state below) and the caller gets an error it can act on -- every host in this repository
-  // then switches ALL ranks to another transport, it never retries RCCL on a subset.
-  struct Shared { std::mutex m; std::condition_variable cv; bool done = false; int rc = -1; void *comm = nullptr; };
-  auto sh = std::make_shared<Shared>();
-  rccl_uid u;
-  memcpy(u.internal, id, GPAK_DIST_ID_BYTES);
-  const int P = h->P, rank = h->rank, dev = h->device;
-  const bool own_dev = h->builtin_engine;
-  std::thread([sh, u, P, rank, dev, own_dev]() {
-    if (own_dev) hipSetDevice(dev);
-    void *c = nullptr;
-    const int rc = g_rccl.CommInitRank(&c, P, u, rank);
-    std::lock_guard<std::mutex> lk(sh->m);
-    sh->rc = rc; sh->comm = c; sh->done = true;
-    sh->cv.notify_all();
-  }).detach();
-  double limit = 90.0;
-  if (const char *e = getenv("GPAK_RCCL_INIT_TIMEOUT_S")) limit = atof(e) > 0 ? atof(e) : limit;
-  std::unique_lock<std::mutex> lk(sh->m);
-  if (!sh->cv.wait_for(lk, std::chrono::duration<double>(limit), [&] { return sh->done; })) {
-    h->err = "ncclCommInitRank did not return within " + std::to_string((int)limit) + " s (a rank is missing from the rendezvous)";
-    return GPAK_EHIP;
-  }
-  if (sh->rc != 0) {
-    h->err = std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(sh->rc) : "failed");
-    return GPAK_EHIP;
-  }
-  h->rccl_state.comm = sh->comm;
-  return GPAK_OK;
-}
+int gpak_dist_init_rccl(gpak_dist *h, const char *id) { return core_init_rccl(h, id, 0); }
 
 // One process, all devices (multi.hip): the communicators of ALL ranks are made by ONE call from ONE thread
 // (ncclCommInitAll) -- it either yields n communicators or fails as a whole, there is no rendezvous a rank can
@@ -482,7 +631,7 @@ void gpak_dist_rccl_destroy(void *comm) { if (comm && g_rccl.CommDestroy) g_rccl
 int gpak_dist_adopt_rccl(gpak_dist *h, void *comm) {
   if (!h || !comm) return GPAK_EINVAL;
   if (!h->builtin_transport) { h->err = "this handle uses a caller-supplied transport"; return GPAK_ESTATE; }
-  h->rccl_state.comm = comm;
+  h->rccl_state.comm[0] = comm;
   return GPAK_OK;
 }
 int gpak_dist_failed_column(const gpak_dist *h) { return h ? h->failed_col : 0; }
@@ -492,10 +641,10 @@ int gpak_dist_failed_column(const gpak_dist *h) { return h ? h->failed_col : 0; 
 // makes ALL ranks fall back to plain streams with the collectives in line on the panel stream.
 int gpak_dist_selfcheck(gpak_dist *h, int *flags_out) {
   if (!h) return GPAK_EINVAL;
-  set_device(h);
+  core_set_device(h);
   gpak_dist_engine &E = h->E;
   gpak_dist_transport &T = h->T;
-  if (h->builtin_transport && h->P > 1 && !h->rccl_state.comm) { h->err = "gpak_dist_init_rccl has not been called"; return GPAK_ESTATE; }
+  if (h->builtin_transport && h->P > 1 && !h->rccl_state.comm[0]) { h->err = "gpak_dist_init_rccl has not been called"; return GPAK_ESTATE; }
   int rc = ensure_streams(h);
   if (rc) return rc;
   const int n = 4096;
@@ -560,37 +709,23 @@ int gpak_dist_selfcheck(gpak_dist *h, int *flags_out) {
 }
 
 int gpak_dist_set_train(gpak_dist *h, const double *X, const double *y, int N, int d, int nb) {
-  if (!h || !X || !y || N <= 0) return GPAK_EINVAL;
-  if (d != 3 && d != 4) { h->err = "inputs must have 3 or 4 columns"; return GPAK_ENOTIMPL; }
-  if (nb == 0) nb = 512;
-  if (nb < GPAK_TILE || nb % GPAK_TILE || nb > 512) { h->err = "nb must be 128, 256, 384 or 512"; return GPAK_EINVAL; }
-  set_device(h);
-  h->d = d;
+  int rc = core_train_check(h, X, y, N, d, &nb);
+  if (rc) return rc;
   if (!h->checked) {
-    int rc = gpak_dist_selfcheck(h, nullptr);
+    rc = gpak_dist_selfcheck(h, nullptr);
     if (rc) return rc;
   }
   gpak_dist_engine &E = h->E;
   E.stream_sync(E.self, h->s_bulk); E.stream_sync(E.self, h->s_panel); E.stream_sync(E.self, h->s_comm);
   release_problem(h);
-  h->N = N;
-  h->Np = (N + GPAK_TILE - 1) / GPAK_TILE * GPAK_TILE;
+  bool ok = core_train_alloc(h, N, nb);
   h->ld = h->Np + (h->Np >= 1024 ? 32 : 0);
-  h->nb = nb;
-  h->nJ = (h->Np + nb - 1) / nb;
-  h->cap = h->Np;
   for (int b = 0; b < h->nJ; b++) if (h->owner(b) == h->rank) h->owned.push_back(b);
   const size_t Np = h->Np;
   auto dalloc = [&](size_t n) { return (double *)E.alloc(E.self, sizeof(double) * (n ? n : 1)); };
-  h->x_soa = dalloc(4 * Np); h->y = dalloc(Np);   // four raw columns, the 4th zero for d = 3
-  h->u = dalloc(5 * GPAK_MAX_TERMS * Np);          // 5 arrays per child of the composition
   h->local = dalloc(std::max<size_t>(1, h->owned.size()) * nb * h->ld);
-  h->scratch = dalloc(64 * Np); h->small = dalloc(16); h->alpha = dalloc(Np);
-  h->fwd_x = dalloc(Np); h->fwd_z = dalloc(Np); h->rhs = dalloc(Np); h->f = dalloc(Np);
-  h->bwd_scratch = dalloc(24 * 512); h->ld_slots = dalloc(h->owned.size() + 1);
-  h->info = (int *)E.alloc(E.self, sizeof(int) * 4);
-  bool ok = h->x_soa && h->y && h->u && h->local && h->scratch && h->small && h->alpha && h->fwd_x && h->fwd_z &&
-            h->rhs && h->f && h->bwd_scratch && h->ld_slots && h->info;
+  h->fwd_x = dalloc(Np); h->fwd_z = dalloc(Np);
+  ok = ok && h->local && h->fwd_x && h->fwd_z;
   h->panels.assign(h->nJ, nullptr); h->invs.assign(h->nJ, nullptr); h->rinv.assign(h->nJ, nullptr);
   h->rinv_ok.assign(h->nJ, 0);
   h->inv_own.assign(h->owned.size(), nullptr);
@@ -608,34 +743,14 @@ int gpak_dist_set_train(gpak_dist *h, const double *X, const double *y, int N, i
     ok = h->panels[b] && h->rinv[b] && h->invs[b];
   }
   if (!ok) { h->err = "device allocation failed for the distributed training set"; release_problem(h); return GPAK_ENOMEM; }
-  std::vector<double> xs(4 * Np, 0.0), yp(Np, 0.0);
-  h->xsum[3] = 0.0;
-  for (int k = 0; k < d; k++) {
-    double s = 0.0;
-    for (int i = 0; i < N; i++) { xs[k * Np + i] = X[i + (size_t)k * N]; s += X[i + (size_t)k * N]; }
-    h->xsum[k] = s;
-  }
-  for (int i = 0; i < N; i++) yp[i] = y[i];
-  DCHK(E.upload(E.self, h->s_bulk, h->x_soa, xs.data(), sizeof(double) * 4 * Np));
-  DCHK(E.upload(E.self, h->s_bulk, h->y, yp.data(), sizeof(double) * Np));
-  DCHK(E.zero(E.self, h->s_bulk, h->alpha, sizeof(double) * Np));
-  DCHK(E.zero(E.self, h->s_bulk, h->small, sizeof(double) * 16));
-  DCHK(E.stream_sync(E.self, h->s_bulk));
-  memset(&h->stats, 0, sizeof(h->stats));
-  h->stats.rank = h->rank; h->stats.world = h->P; h->stats.n = N; h->stats.n_padded = h->Np; h->stats.nb = nb;
-  h->stats.n_panels = h->nJ;
+  rc = core_train_upload(h, X, y);
+  if (rc) return rc;
+  RCHK(E.stream_sync(E.self, h->s_bulk));
   return GPAK_OK;
 }
 
 int gpak_dist_set_params(gpak_dist *h, const double *expans, double bias, double sn2, int dist_mode) {
-  if (!h || !expans) return GPAK_EINVAL;
-  if (dist_mode != GPAK_DIST_EXPANSION && dist_mode != GPAK_DIST_DIRECT) { h->err = "bad dist_mode"; return GPAK_EINVAL; }
-  memcpy(h->expans, expans, sizeof(double) * 8);
-  h->bias = bias; h->sn2 = sn2; h->mode = dist_mode;
-  h->hyb = false; h->white = 0.0;
-  h->have_params = true;
-  h->have_result = false;   // GP_Utils.cpp:132-133: always invalidates
-  return GPAK_OK;
+  return core_set_params(h, expans, bias, sn2, dist_mode);
 }
 
 int gpak_dist_set_kernel(gpak_dist *h, int nterms, const int *kinds, const double *pars, double bias, double white,
@@ -683,76 +798,62 @@ static int produce(gpak_dist *h, int b, void **done) {
     double *chunk = buf + (size_t)s * GPAK_TILE * rows;
     if (own) {
       double *sub = h->blk(b) + (size_t)s * GPAK_TILE * ld;
-      DCHK(E.factor_panel(h->s_panel, sub, ld, Np, J + s * GPAK_TILE, GPAK_TILE,
+      RCHK(E.factor_panel(h->s_panel, sub, ld, Np, J + s * GPAK_TILE, GPAK_TILE,
                           h->invs[b] + (size_t)s * 2 * GPAK_TILE * GPAK_TILE, h->info));
       // the pack runs on the communication stream, in front of the broadcast it feeds: the sub-panel is final once
       // it is solved, and the panel chain goes straight on with the rest of the owner's own block column
       if (h->s_comm != h->s_panel) {
         void *e = h->sync_event();
-        DCHK(E.event_record(E.self, e, h->s_panel));
-        DCHK(E.stream_wait_event(E.self, h->s_comm, e));
+        RCHK(E.event_record(E.self, e, h->s_panel));
+        RCHK(E.stream_wait_event(E.self, h->s_comm, e));
       }
-      DCHK(E.pack(h->s_comm, sub, ld, J, rows, GPAK_TILE, chunk));
+      RCHK(E.pack(h->s_comm, sub, ld, J, rows, GPAK_TILE, chunk));
       const int rem = W - (s + 1) * GPAK_TILE;
       if (rem > 0)   // the rest of the owner's own block column
-        DCHK(E.update_block(h->s_panel, sub, ld, 0, GPAK_TILE, h->blk(b) + (size_t)(s + 1) * GPAK_TILE * ld, ld, Np,
+        RCHK(E.update_block(h->s_panel, sub, ld, 0, GPAK_TILE, h->blk(b) + (size_t)(s + 1) * GPAK_TILE * ld, ld, Np,
                             J + (s + 1) * GPAK_TILE, rem));
     }
     size_t c0 = 0;
     if (h->profile && h->P > 1) c0 = h->time_event(h->s_comm);
-    DCHK(T.bcast(T.self, h->s_comm, chunk, (size_t)GPAK_TILE * rows, h->owner(b)));
+    RCHK(T.bcast(T.self, h->s_comm, chunk, (size_t)GPAK_TILE * rows, h->owner(b)));
     if (h->profile && h->P > 1) h->spans.push_back({c0, h->time_event(h->s_comm), 2});
     h->stats.bytes_broadcast += 8.0 * GPAK_TILE * rows;
     if (next_owner) {
       if (h->s_comm != h->s_panel) {
         void *e = h->sync_event();
-        DCHK(E.event_record(E.self, e, h->s_comm));
-        DCHK(E.stream_wait_event(E.self, h->s_panel, e));
+        RCHK(E.event_record(E.self, e, h->s_comm));
+        RCHK(E.stream_wait_event(E.self, h->s_panel, e));
       }
-      DCHK(E.update_block(h->s_panel, chunk, rows, J, GPAK_TILE, h->blk(nxt), ld, Np, h->start(nxt), h->width(nxt)));
+      RCHK(E.update_block(h->s_panel, chunk, rows, J, GPAK_TILE, h->blk(nxt), ld, Np, h->start(nxt), h->width(nxt)));
     }
   }
   if (own && h->profile) h->spans.push_back({t0, h->time_event(h->s_panel), 1});
   const size_t inv_n = (size_t)W / GPAK_TILE * 2 * GPAK_TILE * GPAK_TILE;
-  DCHK(T.bcast(T.self, h->s_comm, h->invs[b], inv_n, h->owner(b)));   // the owner's last factor is already ordered
+  RCHK(T.bcast(T.self, h->s_comm, h->invs[b], inv_n, h->owner(b)));   // the owner's last factor is already ordered
   h->stats.bytes_broadcast += 8.0 * inv_n;                            // in front of it by the last pack's event
   *done = h->sync_event();
-  DCHK(E.event_record(E.self, *done, h->s_comm));
+  RCHK(E.event_record(E.self, *done, h->s_comm));
   return GPAK_OK;
 }
 
-// Every collective of a rank goes through ONE stream (the communication stream) in one global issue order: RCCL
-// serialises the operations of a communicator, and two streams feeding the same communicator concurrently is the
-// classic way to deadlock it.  `hop_in` orders the communication stream behind the bulk stream, `hop_out` back.
-static int hop_in(gpak_dist *h) {
-  if (h->s_comm == h->s_bulk) return GPAK_OK;
-  void *e = h->sync_event();
-  DCHK(h->E.event_record(h->E.self, e, h->s_bulk));
-  DCHK(h->E.stream_wait_event(h->E.self, h->s_comm, e));
-  return GPAK_OK;
-}
-static int hop_out(gpak_dist *h) {
-  if (h->s_comm == h->s_bulk) return GPAK_OK;
-  void *e = h->sync_event();
-  DCHK(h->E.event_record(h->E.self, e, h->s_comm));
-  DCHK(h->E.stream_wait_event(h->E.self, h->s_bulk, e));
-  return GPAK_OK;
-}
+// the collectives of this layout go through the communication stream (core_hop): behind the bulk stream, and back
+static int hop_in(gpak_dist *h) { return core_hop(h, h->s_bulk, h->s_comm); }
+static int hop_out(gpak_dist *h) { return core_hop(h, h->s_comm, h->s_bulk); }
 
 static int factor(gpak_dist *h, int *failed_col) {
   gpak_dist_engine &E = h->E;
   gpak_dist_transport &T = h->T;
   const int Np = h->Np, nJ = h->nJ, P = h->P;
   const int init = 0x7fffffff;
-  DCHK(E.upload(E.self, h->s_bulk, h->info, &init, sizeof(int)));
+  RCHK(E.upload(E.self, h->s_bulk, h->info, &init, sizeof(int)));
   std::fill(h->rinv_ok.begin(), h->rinv_ok.end(), 0);
   // the panel and communication streams start behind the fill -- and behind whatever the bulk stream still reads
   // of the previous step's panels (the receive buffers are reused)
   void *e_fill = h->sync_event();
-  DCHK(E.event_record(E.self, e_fill, h->s_bulk));
-  DCHK(E.stream_wait_event(E.self, h->s_panel, e_fill));
-  if (h->s_comm != h->s_panel) DCHK(E.stream_wait_event(E.self, h->s_comm, e_fill));
-  DCHK(E.stream_wait_event(E.self, h->s_aux, e_fill));
+  RCHK(E.event_record(E.self, e_fill, h->s_bulk));
+  RCHK(E.stream_wait_event(E.self, h->s_panel, e_fill));
+  if (h->s_comm != h->s_panel) RCHK(E.stream_wait_event(E.self, h->s_comm, e_fill));
+  RCHK(E.stream_wait_event(E.self, h->s_aux, e_fill));
   void *done = nullptr, *done_next = nullptr, *e_bulk_prev = nullptr;
   int rc = produce(h, 0, &done);
   if (rc) return rc;
@@ -760,14 +861,14 @@ static int factor(gpak_dist *h, int *failed_col) {
     const int J = h->start(b), W = h->width(b), rows = Np - J;
     const int nxt = b + 1, nn = b + 2;
     double *panel = h->panels[b];
-    DCHK(E.stream_wait_event(E.self, h->s_bulk, done));            // panel b and its inverses are complete here
+    RCHK(E.stream_wait_event(E.self, h->s_bulk, done));            // panel b and its inverses are complete here
     if (nxt < nJ) {
       // look-ahead on the panel stream: column b+2 gets panel b as one K=nb update, then column b+1 is factored
       // (it received panel b sub-panel by sub-panel inside produce(b))
-      if (h->s_panel != h->s_comm) DCHK(E.stream_wait_event(E.self, h->s_panel, done));
-      if (e_bulk_prev) DCHK(E.stream_wait_event(E.self, h->s_panel, e_bulk_prev));   // bulk update b-1 touched column b+2
+      if (h->s_panel != h->s_comm) RCHK(E.stream_wait_event(E.self, h->s_panel, done));
+      if (e_bulk_prev) RCHK(E.stream_wait_event(E.self, h->s_panel, e_bulk_prev));   // bulk update b-1 touched column b+2
       if (nn < nJ && h->rank == h->owner(nn))
-        DCHK(E.update_block(h->s_panel, panel, rows, J, W, h->blk(nn), h->ld, Np, h->start(nn), h->width(nn)));
+        RCHK(E.update_block(h->s_panel, panel, rows, J, W, h->blk(nn), h->ld, Np, h->start(nn), h->width(nn)));
       rc = produce(h, nxt, &done_next);
       if (rc) return rc;
       // bulk update of every owned block column beyond b+2, one launch
@@ -776,7 +877,7 @@ static int factor(gpak_dist *h, int *failed_col) {
       if (lb0 >= 0) {
         size_t t0 = 0;
         if (h->profile) t0 = h->time_event(h->s_bulk);
-        DCHK(E.update_cyclic(h->s_bulk, panel, rows, J, W, h->local, h->ld, Np, h->nb, P, h->rank, lb0,
+        RCHK(E.update_cyclic(h->s_bulk, panel, rows, J, W, h->local, h->ld, Np, h->nb, P, h->rank, lb0,
                              (int)h->owned.size(), h->width(h->owned.back())));
         if (h->profile) h->spans.push_back({t0, h->time_event(h->s_bulk), 0});
         for (size_t i = lb0; i < h->owned.size(); i++) {   // algorithmic flops: lower tiles of the owned columns
@@ -788,13 +889,13 @@ static int factor(gpak_dist *h, int *failed_col) {
         h->stats.bulk_launches += 1;
       }
       e_bulk_prev = h->sync_event();
-      DCHK(E.event_record(E.self, e_bulk_prev, h->s_bulk));
+      RCHK(E.event_record(E.self, e_bulk_prev, h->s_bulk));
     }
     // forward substitution L^-1 (y/sn2) rides along on the aux stream, and the explicit inverse of the diagonal
     // block for the back substitution
-    DCHK(E.stream_wait_event(E.self, h->s_aux, done));
-    DCHK(E.trsv_fwd_block(h->s_aux, panel - J, rows, Np, J, W, h->invs[b], h->fwd_x, h->fwd_z));
-    DCHK(E.diag_inverse(h->s_aux, panel, rows, J, J, W, h->invs[b], h->rinv[b]));
+    RCHK(E.stream_wait_event(E.self, h->s_aux, done));
+    RCHK(E.trsv_fwd_block(h->s_aux, panel - J, rows, Np, J, W, h->invs[b], h->fwd_x, h->fwd_z));
+    RCHK(E.diag_inverse(h->s_aux, panel, rows, J, J, W, h->invs[b], h->rinv[b]));
     h->rinv_ok[b] = 1;
     if (nxt >= nJ) break;
     done = done_next;
@@ -802,16 +903,16 @@ static int factor(gpak_dist *h, int *failed_col) {
   // everything of the panel stream has been waited for through `done` except trailing look-ahead work of the last
   // step, which does not exist (nxt >= nJ); the failing column travels as an int min-reduce
   void *e_end = h->sync_event();
-  DCHK(E.event_record(E.self, e_end, h->s_panel));
-  DCHK(E.stream_wait_event(E.self, h->s_bulk, e_end));
+  RCHK(E.event_record(E.self, e_end, h->s_panel));
+  RCHK(E.stream_wait_event(E.self, h->s_bulk, e_end));
   void *e_aux = h->sync_event();
-  DCHK(E.event_record(E.self, e_aux, h->s_aux));
-  DCHK(E.stream_wait_event(E.self, h->s_bulk, e_aux));
-  DCHK(hop_in(h));
-  DCHK(T.allreduce_min_int(T.self, h->s_comm, h->info, 1));
-  DCHK(hop_out(h));
+  RCHK(E.event_record(E.self, e_aux, h->s_aux));
+  RCHK(E.stream_wait_event(E.self, h->s_bulk, e_aux));
+  RCHK(hop_in(h));
+  RCHK(T.allreduce_min_int(T.self, h->s_comm, h->info, 1));
+  RCHK(hop_out(h));
   int info = init;
-  DCHK(E.download(E.self, h->s_bulk, &info, h->info, sizeof(int)));
+  RCHK(E.download(E.self, h->s_bulk, &info, h->info, sizeof(int)));
   *failed_col = info == init ? 0 : info;
   return GPAK_OK;
 }
@@ -824,121 +925,48 @@ int gpak_dist_nlz(gpak_dist *h, double *nlz) {
   if (!h->N) { h->err = "no training set (gpak_dist_set_train)"; return GPAK_ESTATE; }
   if (!h->have_params) { h->err = "no parameters (gpak_dist_set_params)"; return GPAK_ESTATE; }
   if (h->have_result) { *nlz = h->nlz; return GPAK_OK; }
-  set_device(h);
+  core_set_device(h);
   gpak_dist_engine &E = h->E;
-  gpak_dist_transport &T = h->T;
-  const int N = h->N, Np = h->Np, P = h->P;
-  const double t_start = now_ms();
-  h->sync_used = 0; h->time_used = 0; h->spans.clear();
-  h->stats.bytes_broadcast = 0; h->stats.bulk_flops = 0; h->stats.bulk_bytes = 0; h->stats.bulk_launches = 0;
-  h->stats.flags = h->flags;
-  size_t tp[6] = {0, 0, 0, 0, 0, 0};
-  tp[0] = h->time_event(h->s_bulk);
+  const int Np = h->Np;
   // ---- fill: HybKerns::computeK + "(sW sW') % K + I" of ldB2_exact, owned columns only, no communication
-  {
-    const double n = (double)N;
-    double mu[4];
-    for (int k = 0; k < 4; k++) {   // pooled mean of X u X exactly as Kernel.cpp:1391-1392 computes it
-      const double mX1 = n / (n + n) * h->xsum[k] / n;
-      mu[k] = n / (n + n) * h->xsum[k] / n + mX1;
-    }
-    if (h->hyb) DCHK(E.transform_k(h->s_bulk, h->x_soa, Np, N, h->cap, h->kern, h->kmode(), mu, h->u));
-    else DCHK(E.transform(h->s_bulk, h->x_soa, Np, N, h->cap, h->expans, mu, h->u));
+  int rc = core_step_begin(h, [&]() -> int {
     for (int b : h->owned)
-      DCHK(E.fill_b(h->s_bulk, h->u, h->cap, N, Np, h->start(b), h->width(b), h->kpars(), h->bias, h->sn2, h->kmode(),
+      RCHK(E.fill_b(h->s_bulk, h->u, h->cap, h->N, Np, h->start(b), h->width(b), h->kpars(), h->bias, h->sn2, h->kmode(),
                     h->blk(b), h->ld));
-  }
-  DCHK(E.vec_scale(h->s_bulk, Np, h->y, 1.0 / h->sn2, h->rhs));            // rhs = y / sn2
-  DCHK(E.copy(E.self, h->s_bulk, h->fwd_x, h->rhs, sizeof(double) * Np));
-  DCHK(E.zero(E.self, h->s_bulk, h->fwd_z, sizeof(double) * Np));
-  tp[1] = h->time_event(h->s_bulk);
-  int bad = 0;
-  int rc = factor(h, &bad);
+    return GPAK_OK;
+  });
   if (rc) return rc;
-  h->failed_col = bad;
-  tp[2] = h->time_event(h->s_bulk);
-  if (bad) {
-    h->err = "B = I + K/sn2 is not positive definite";
-    DCHK(E.stream_sync(E.self, h->s_bulk));
-    return GPAK_ENOTPD;   // Chol_fail -> quiet NaN (GP_Utils.cpp:1145-1158)
-  }
+  RCHK(E.copy(E.self, h->s_bulk, h->fwd_x, h->rhs, sizeof(double) * Np));
+  RCHK(E.zero(E.self, h->s_bulk, h->fwd_z, sizeof(double) * Np));
+  h->tp[1] = h->time_event(h->s_bulk);
+  int bad = 0;
+  rc = factor(h, &bad);
+  if (!rc) rc = core_step_factored(h, bad);
+  if (rc) return rc;
   // ---- back substitution: every rank holds every packed panel, no collective (solve_chol, GP_Utils.cpp:841-845)
-  DCHK(E.zero(E.self, h->s_bulk, h->alpha, sizeof(double) * Np));
+  RCHK(E.zero(E.self, h->s_bulk, h->alpha, sizeof(double) * Np));
   for (int b = h->nJ - 1; b >= 0; b--) {
     const int J = h->start(b), W = h->width(b);
-    DCHK(E.trsv_bwd_packed(h->s_bulk, h->panels[b], Np - J, J, Np, J, W, h->invs[b], h->fwd_z, h->bwd_scratch, h->alpha,
+    RCHK(E.trsv_bwd_packed(h->s_bulk, h->panels[b], Np - J, J, Np, J, W, h->invs[b], h->fwd_z, h->bwd_scratch, h->alpha,
                            h->rinv_ok[b] ? h->rinv[b] : nullptr));
   }
-  tp[3] = h->time_event(h->s_bulk);
-  // ---- f = K alpha: each rank sums over its slice of source points, then one all-reduce (GP_Utils.cpp:1147)
-  int per = (N + P - 1) / P;
-  per = (per + 1) / 2 * 2;
-  const int i0 = std::min(N, h->rank * per), i1 = std::min(N, (h->rank + 1) * per);
-  DCHK(E.zero(E.self, h->s_bulk, h->f, sizeof(double) * Np));
-  const size_t tk0 = h->time_event(h->s_bulk);
-  if (i1 > i0)
-    DCHK(E.kmatvec(h->s_bulk, h->u, h->cap, N, i0, i1, h->alpha, h->kpars(), h->bias, h->kmode(), h->scratch, h->f));
-  // Kern_White is the diagonal Sigma_White I (Kernel.cpp:256-263): its share of K alpha, once (rank 0's partial sum)
-  if (h->hyb && h->white != 0.0 && h->rank == 0) DCHK(E.vec_axpy(h->s_bulk, N, h->white, h->alpha, h->f));
-  const size_t tk1 = h->time_event(h->s_bulk);
-  DCHK(hop_in(h));
-  DCHK(T.allreduce_sum(T.self, h->s_comm, h->f, (size_t)Np));
-  DCHK(hop_out(h));
-  for (size_t i = 0; i < h->owned.size(); i++) {
-    const int b = h->owned[i];
-    DCHK(E.logdiag_block(h->s_bulk, h->blk(b), h->ld, h->start(b), h->width(b), N, h->ld_slots + i));
-  }
-  DCHK(E.zero(E.self, h->s_bulk, h->small, sizeof(double) * 16));
-  if (!h->owned.empty()) DCHK(E.vec_sum(h->s_bulk, (int)h->owned.size(), h->ld_slots, h->small + 2));
-  DCHK(hop_in(h));
-  DCHK(T.allreduce_sum(T.self, h->s_comm, h->small + 2, 1));
-  DCHK(hop_out(h));
-  DCHK(E.nlz_terms(h->s_bulk, N, h->y, h->f, h->alpha, h->sn2, h->small));
-  tp[4] = h->time_event(h->s_bulk);
-  double vals[3];
-  DCHK(E.download(E.self, h->s_bulk, vals, h->small, sizeof(vals)));
-  h->quad = vals[0]; h->sumlp = vals[1]; h->logdet = vals[2];
-  h->nlz = h->quad - h->sumlp + h->logdet;   // GP_Utils.cpp:1159
-  h->have_result = true;
-  *nlz = h->nlz;
-  // ---- per-phase split
-  gpak_dist_stats &S = h->stats;
-  S.step_ms = now_ms() - t_start;
-  auto el = [&](size_t a, size_t b) { double ms = 0; E.event_elapsed_ms(E.self, h->ev_time[a], h->ev_time[b], &ms); return ms; };
-  S.fill_ms = el(tp[0], tp[1]); S.factor_ms = el(tp[1], tp[2]); S.solve_ms = el(tp[2], tp[3]); S.nlz_ms = el(tp[3], tp[4]);
-  S.kmatvec_ms = el(tk0, tk1);
-  S.bulk_ms = S.chain_ms = S.comm_ms = 0;
-  if (h->profile) {
-    DCHK(E.stream_sync(E.self, h->s_panel));
-    DCHK(E.stream_sync(E.self, h->s_comm));
-    for (const gpak_dist::Span &sp : h->spans) {
-      const double ms = el(sp.e0, sp.e1);
-      if (sp.kind == 0) S.bulk_ms += ms; else if (sp.kind == 1) S.chain_ms += ms; else S.comm_ms += ms;
-    }
-  }
-  S.wait_ms = S.factor_ms - S.bulk_ms;
-  return GPAK_OK;
+  h->tp[3] = h->time_event(h->s_bulk);
+  // ---- f = K alpha, the log-determinant from the owned block columns, nlZ; the collectives on the communication stream
+  std::vector<DiagBlock> diag;
+  for (int b : h->owned) diag.push_back({h->blk(b), h->ld, h->start(b), h->width(b)});
+  return core_step_finish(h, h->s_comm, diag, nlz);
 }
 
 int gpak_dist_nlz_terms(gpak_dist *h, double *quad, double *sumlp, double *logdet) {
-  if (!h) return GPAK_EINVAL;
   double v;
   int rc = gpak_dist_nlz(h, &v);
-  if (rc) return rc;
-  if (quad) *quad = h->quad;
-  if (sumlp) *sumlp = h->sumlp;
-  if (logdet) *logdet = h->logdet;
-  return GPAK_OK;
+  return rc ? rc : core_nlz_terms(h, quad, sumlp, logdet);
 }
 
 int gpak_dist_get_alpha(gpak_dist *h, double *alpha_host) {
-  if (!h || !alpha_host) return GPAK_EINVAL;
   double v;
-  int rc = gpak_dist_nlz(h, &v);
-  if (rc) return rc;
-  set_device(h);
-  DCHK(h->E.download(h->E.self, h->s_bulk, alpha_host, h->alpha, sizeof(double) * h->N));
-  return GPAK_OK;
+  int rc = alpha_host ? gpak_dist_nlz(h, &v) : (int)GPAK_EINVAL;
+  return rc ? rc : core_get_alpha(h, alpha_host);
 }
 
 int gpak_dist_grad(gpak_dist *h, double *g) {
@@ -947,7 +975,7 @@ int gpak_dist_grad(gpak_dist *h, double *g) {
   if (h->hyb) { h->err = "gpak_dist_grad handles the ExpAns(+Bias) composition"; return GPAK_ENOTIMPL; }
   int rc = gpak_dist_nlz(h, &v);   // GradLL re-enters logLikelihood(): GP_Utils.cpp:1173-1174
   if (rc) return rc;
-  set_device(h);
+  core_set_device(h);
   gpak_dist_engine &E = h->E;
   gpak_dist_transport &T = h->T;
   const int Np = h->Np, P = h->P, Tn = Np / GPAK_TILE;
@@ -969,7 +997,7 @@ int gpak_dist_grad(gpak_dist *h, double *g) {
   h->sync_used = 0; h->time_used = 0;
   const size_t t0 = h->time_event(h->s_bulk);
   double *own = h->slabs[0];
-  DCHK(E.grad_g_rows(h->s_bulk, Np, h->nb, P, h->rank, h->panels.data(), h->invs.data(), own));
+  RCHK(E.grad_g_rows(h->s_bulk, Np, h->nb, P, h->rank, h->panels.data(), h->invs.data(), own));
   // The slabs go round one at a time: rank q's is broadcast into one of two receive buffers while the product against
   // the previous one runs out of the other, so a rank never holds more than its own slab and two in flight.
   void *e_read[2] = {nullptr, nullptr};   // recorded behind the product that last read the receive buffer
@@ -978,38 +1006,33 @@ int gpak_dist_grad(gpak_dist *h, double *g) {
     if (tiles_of(q) == 0) continue;
     double *buf = own;
     if (q == h->rank) {
-      DCHK(hop_in(h));                     // the slab is this rank's to send once grad_g_rows has written it
+      RCHK(hop_in(h));                     // the slab is this rank's to send once grad_g_rows has written it
     } else {
       buf = h->slabs[1 + slot];
-      if (e_read[slot] && h->s_comm != h->s_bulk) DCHK(E.stream_wait_event(E.self, h->s_comm, e_read[slot]));
+      if (e_read[slot] && h->s_comm != h->s_bulk) RCHK(E.stream_wait_event(E.self, h->s_comm, e_read[slot]));
     }
-    DCHK(T.bcast(T.self, h->s_comm, buf, (size_t)tiles_of(q) * GPAK_TILE * Np, q));
-    DCHK(hop_out(h));
-    DCHK(E.grad_binv_rows(h->s_bulk, Np, P, h->rank, q, own, buf, h->binv));
+    RCHK(T.bcast(T.self, h->s_comm, buf, (size_t)tiles_of(q) * GPAK_TILE * Np, q));
+    RCHK(hop_out(h));
+    RCHK(E.grad_binv_rows(h->s_bulk, Np, P, h->rank, q, own, buf, h->binv));
     if (q != h->rank) {
       e_read[slot] = h->sync_event();
-      DCHK(E.event_record(E.self, e_read[slot], h->s_bulk));
+      RCHK(E.event_record(E.self, e_read[slot], h->s_bulk));
       slot ^= 1;
     }
   }
-  DCHK(E.grad_pairs_rows(h->s_bulk, h->u, h->cap, h->x_soa, Np, h->N, Np, h->y, h->f, h->alpha, h->binv, P, h->rank,
+  RCHK(E.grad_pairs_rows(h->s_bulk, h->u, h->cap, h->x_soa, Np, h->N, Np, h->y, h->f, h->alpha, h->binv, P, h->rank,
                          h->expans, h->bias, h->sn2, h->kmode(), h->gpart, h->gred));
-  DCHK(hop_in(h));
-  DCHK(T.allreduce_sum(T.self, h->s_comm, h->gred, 16));
-  DCHK(hop_out(h));
+  RCHK(hop_in(h));
+  RCHK(T.allreduce_sum(T.self, h->s_comm, h->gred, 16));
+  RCHK(hop_out(h));
   const size_t t1 = h->time_event(h->s_bulk);
   double red[17];
-  DCHK(E.download(E.self, h->s_bulk, red, h->gred, sizeof(red)));
+  RCHK(E.download(E.self, h->s_bulk, red, h->gred, sizeof(red)));
   E.event_elapsed_ms(E.self, h->ev_time[t0], h->ev_time[t1], &h->grad_ms);
   return gpak_dev_grad_finish_d(h->expans, h->bias, h->sn2, h->N, h->d, red, g);
 }
 
-int gpak_dist_get_stats(gpak_dist *h, gpak_dist_stats *out) {
-  if (!h || !out) return GPAK_EINVAL;
-  *out = h->stats;
-  out->flags = h->flags;
-  return GPAK_OK;
-}
+int gpak_dist_get_stats(gpak_dist *h, gpak_dist_stats *out) { return core_get_stats(h, out); }
 
 }  // extern "C"
 
@@ -1035,5 +1058,3 @@ int gpak_dist_factor_view_get(gpak_dist *h, gpak_dist_factor_view *out) {
   return GPAK_OK;
 }
 double gpak_dist_grad_ms(const gpak_dist *h) { return h ? h->grad_ms : 0.0; }
-
-#include "grid.inc"

@@ -313,7 +313,7 @@ class DistRank:
 
 
 class GridRank:
-    """One rank of the row-block x column-block layout (gpak_grid_* of include/gpak_dist.h, csrc/grid.inc) on a Pr x Pc
+    """One rank of the row-block x column-block layout (gpak_grid_* of include/gpak_dist.h, csrc/grid.hip) on a Pr x Pc
     process grid, rank = pr + Pr * pc.  engine / transport: None = built-in HIP engine / built-in RCCL transport (world
     communicator + ncclCommSplit row and column communicators)."""
 
@@ -584,7 +584,7 @@ def bench(args):
         # along as a sub-object; it needs 32 GiB / P + 17 GB per GPU
         state["phase"] = "N=65536"
         extra = _one_size(args, 65536, dist, rank, world, local, make_rank, max(1, min(args.steps, 3)), 1, bench_mod)
-    # the row-block x column-block layouts of the same world size (north_star's 2-D sharding, csrc/grid.inc) ride along:
+    # the row-block x column-block layouts of the same world size (north_star's 2-D sharding, csrc/grid.hip) ride along:
     # a short run per grid, so that one line holds both layouts' step time and bytes received per rank
     state["extra"] = extra
     grids = state["grids"]

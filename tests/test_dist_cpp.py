@@ -308,7 +308,7 @@ def test_other_compositions_on_a_multi_gpu_context(orc):
         g.close()
 
 
-# ---- the row-block x column-block layout (gpak_grid_*, csrc/grid.inc) ----------------------------------------------
+# ---- the row-block x column-block layout (gpak_grid_*, csrc/grid.hip) ----------------------------------------------
 @pytest.mark.parametrize("grid,n,nb", [((2, 2), 700, 128), ((2, 3), 1300, 128), ((3, 2), 1500, 256), ((2, 2), 600, 256),
                                         ((2, 4), 1200, 128), ((4, 2), 1100, 128), ((2, 1), 500, 128), ((4, 1), 900, 128)])
 def test_grid_layout_over_gloo_matches_oracle(orc, grid, n, nb):
