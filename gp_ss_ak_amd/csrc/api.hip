@@ -36,6 +36,7 @@ int gpak_multi_n(gpak_multi *g);
 #define GPAK_MULTI_ERR(rc_) do { int v_ = (rc_); if (v_) ctx->err = gpak_multi_error(ctx->multi); return v_; } while (0)
 int gpak_solve_chol_impl(gpak_ctx *ctx, double *X_host, int k);
 int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng);
+int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng);
 
 static std::string g_global_err;
 
@@ -450,6 +451,7 @@ int gpak_set_params(gpak_ctx *ctx, const double *expans, double bias, double sn2
   bool same = ctx->have_params && memcmp(expans, ctx->expans, sizeof(double) * 8) == 0 && bias == ctx->bias &&
               sn2 == ctx->sn2 && dist_mode == ctx->dist_mode;
   memcpy(ctx->expans, expans, sizeof(double) * 8);
+  memcpy(ctx->tpars[0], expans, sizeof(double) * 8);
   ctx->bias = bias; ctx->sn2 = sn2; ctx->dist_mode = dist_mode;
   ctx->have_params = true;
   ctx->expans_only = true;
@@ -488,7 +490,9 @@ int gpak_set_kernel(gpak_ctx *ctx, int nterms, const int *kinds, const double *p
     const double *p = pars;
     for (int t = 0; t < nterms; t++) {
       if (kinds[t] == GPAK_KERN_EXPANS) memcpy(ctx->expans, p, sizeof(double) * 8);  // the (single) ExpAns child, wherever it sits
-      p += kinds[t] == GPAK_KERN_EXPANS ? 8 : kinds[t] == GPAK_KERN_EXP ? 2 : 3;
+      const int np = kinds[t] == GPAK_KERN_EXPANS ? 8 : kinds[t] == GPAK_KERN_EXP ? 2 : 3;
+      memcpy(ctx->tpars[t], p, sizeof(double) * np);
+      p += np;
       ctx->kinds[t] = kinds[t];
     }
   }
@@ -857,6 +861,17 @@ int gpak_grad_hyb(gpak_ctx *ctx, double *g, int ng) {
   int rc = ensure_nlz(ctx);
   if (rc) return rc;
   return gpak_grad_impl(ctx, g, ng);
+}
+
+int gpak_grad_exact(gpak_ctx *ctx, double *g, int ng) {
+  if (!ctx || !g) return GPAK_EINVAL;
+  if (ctx->multi) {
+    ctx->err = "gpak_grad_exact is built for the single-GPU context (gpak_create) only; a multi-GPU context has gpak_grad / gpak_grad_hyb";
+    return GPAK_ENOTIMPL;
+  }
+  int rc = ensure_nlz(ctx);
+  if (rc) return rc;
+  return gpak_grad_exact_impl(ctx, g, ng);
 }
 
 int gpak_timing(gpak_ctx *ctx, gpak_phase_times *out) {

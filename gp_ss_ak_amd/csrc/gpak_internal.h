@@ -96,6 +96,7 @@ struct gpak_ctx {
   double expans[8] = {0};   // ExpAns parameters when the kernel is the reference's default composition
   bool expans_only = true;  // kernel == ExpAns(+Bias): the composition of the fixed-length gpak_grad
   int kinds[GPAK_MAX_TERMS] = {0, 0, 0};  // GPAK_KERN_* of each stationary term
+  double tpars[GPAK_MAX_TERMS][8] = {{0}};  // raw parameters of each stationary term, the reference's order (gpak_grad_exact)
   double bias = 0, sn2 = 0;
   int dist_mode = GPAK_DIST_DIRECT;
   KernParams kp;

@@ -13,6 +13,7 @@
 //   2. B^-1 = G G^T, lower tiles, k-loop started at the row tile (N^3/3 flops, MFMA);
 //   3. ONE fused pass over the pairs i >= j that recomputes K_ij from the coordinates and
 //      accumulates the nine sums the ten gradient entries are made of.
+// gpak_grad_exact (further down) is the derivative of nlZ itself: steps 1-2 shared, a pair pass of its own.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -232,13 +233,10 @@ void gpak_grad_release(gpak_ctx *ctx) {
   ctx->gpart_elems = 0;
 }
 
-// S, S_alpha.. as written at Kernel.cpp:955-1166 (the (0,0) z-term of the angle derivatives lacks
-// its factor 2, :1003-1011) and M_p = S % S_p
-static void build_grad_consts(const double *e, GradConsts &gc) {
+// Rot (Kernel.cpp:1399-1410) and its true derivatives D[a] = dRot / d angle_a, a = 0..2 = AngleX, AngleY, AngleZ
+static void rot_tables(const double *e, double R[3][3], double D[3][3][3]) {
   const double al = e[0], be = e[2], te = e[4];
-  const double iw[3] = {e[1], e[3], e[5]};
   const double ca = cos(al), sa = sin(al), cb = cos(be), sb = sin(be), ct = cos(te), st = sin(te);
-  double R[3][3], D[3][3][3];
   R[0][0] = ca * ct + sa * sb * st;   D[0][0][0] = -sa * ct + ca * sb * st;
   D[1][0][0] = sa * cb * st;          D[2][0][0] = -ca * st + sa * sb * ct;
   R[0][1] = -sa * ct + ca * sb * st;  D[0][0][1] = -ca * ct - sa * sb * st;
@@ -257,6 +255,14 @@ static void build_grad_consts(const double *e, GradConsts &gc) {
   D[1][2][1] = -ca * cb * ct;         D[2][2][1] = -sa * ct + ca * sb * st;
   R[2][2] = cb * ct;                  D[0][2][2] = 0.0;
   D[1][2][2] = -sb * ct;              D[2][2][2] = -cb * st;
+}
+
+// S, S_alpha.. as written at Kernel.cpp:955-1166 (the (0,0) z-term of the angle derivatives lacks
+// its factor 2, :1003-1011) and M_p = S % S_p
+static void build_grad_consts(const double *e, GradConsts &gc) {
+  const double iw[3] = {e[1], e[3], e[5]};
+  double R[3][3], D[3][3][3];
+  rot_tables(e, R, D);
   double S[3][3], Sp[6][3][3];
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) {
@@ -313,27 +319,12 @@ void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *ex
   g[go] = -1.0 * sum_dW * (2.0 / sn2) - red[NSUM];               // GP_Utils.cpp:1226
 }
 
-// kinds of the current composition (set by gpak_set_params / gpak_set_kernel)
-int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) {
-  GPAK_HIP(hipSetDevice(ctx->device));
+// steps 1 and 2, shared by the as-written and the exact gradient: allocates the two N x N workspaces on first use,
+// records ev[7] (the start of grad_ms) and leaves B^-1 (lower tiles) in ctx->dBinv
+static int grad_binv(gpak_ctx *ctx) {
   hipStream_t st = ctx->stream;
-  const int N = ctx->N, Np = ctx->Np;
+  const int Np = ctx->Np;
   const long ld = ctx->ld;
-  // expected length: children in order (8 / 2 / 3), bias, sn2
-  int need = 2, te = -1;
-  for (int t = 0; t < ctx->kp.nterms; t++) {
-    need += ctx->kinds[t] == GPAK_KERN_EXPANS ? 8 : ctx->kinds[t] == GPAK_KERN_EXP ? 2 : 3;
-    if (ctx->kinds[t] == GPAK_KERN_EXPANS) {
-      if (te >= 0) { ctx->err = "gpak_grad: at most one ExpAns child"; return GPAK_ENOTIMPL; }
-      te = t;
-    }
-  }
-  if (ng != need) { ctx->err = "gpak_grad: gradient vector has the wrong length"; return GPAK_EINVAL; }
-  if (ctx->kp.white != 0.0) {
-    // Kern_White has no getGradients upstream (Kernel.h:257-283: the base method calls itself)
-    ctx->err = "gpak_grad: compositions with a White child have no gradient in the reference either";
-    return GPAK_ENOTIMPL;
-  }
   if (!ctx->dG) {
     if (hipMalloc(&ctx->dG, sizeof(double) * (size_t)ld * Np) != hipSuccess ||
         hipMalloc(&ctx->dBinv, sizeof(double) * (size_t)ld * Np) != hipSuccess) {
@@ -371,6 +362,45 @@ int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) {
   }
   // 2. B^-1 = G G^T (lower tiles); G[i,k] = 0 for k < i, so the k-loop starts at the row tile
   gpak_launch_gemm_nt(st, Np / PB, Np / PB, Np, 1.0, G, ld, G, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, true);
+  return GPAK_OK;
+}
+
+// per-workgroup partial sums of a pair pass: at least `elems` doubles in ctx->dGpart
+static int grad_partials(gpak_ctx *ctx, size_t elems) {
+  if (ctx->gpart_elems >= elems) return GPAK_OK;
+  if (ctx->dGpart) hipFree(ctx->dGpart);
+  ctx->dGpart = nullptr; ctx->gpart_elems = 0;
+  if (hipMalloc(&ctx->dGpart, sizeof(double) * elems) != hipSuccess) {
+    ctx->err = "device allocation failed for gradient partial sums";
+    return GPAK_ENOMEM;
+  }
+  ctx->gpart_elems = elems;
+  return GPAK_OK;
+}
+
+// kinds of the current composition (set by gpak_set_params / gpak_set_kernel)
+int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np;
+  const long ld = ctx->ld;
+  // expected length: children in order (8 / 2 / 3), bias, sn2
+  int need = 2, te = -1;
+  for (int t = 0; t < ctx->kp.nterms; t++) {
+    need += ctx->kinds[t] == GPAK_KERN_EXPANS ? 8 : ctx->kinds[t] == GPAK_KERN_EXP ? 2 : 3;
+    if (ctx->kinds[t] == GPAK_KERN_EXPANS) {
+      if (te >= 0) { ctx->err = "gpak_grad: at most one ExpAns child"; return GPAK_ENOTIMPL; }
+      te = t;
+    }
+  }
+  if (ng != need) { ctx->err = "gpak_grad: gradient vector has the wrong length"; return GPAK_EINVAL; }
+  if (ctx->kp.white != 0.0) {
+    // Kern_White has no getGradients upstream (Kernel.h:257-283: the base method calls itself)
+    ctx->err = "gpak_grad: compositions with a White child have no gradient in the reference either";
+    return GPAK_ENOTIMPL;
+  }
+  int rc = grad_binv(ctx);
+  if (rc) return rc;
   // 3. fused pair pass
   GradConsts gc;
   memset(&gc, 0, sizeof(gc));
@@ -380,16 +410,9 @@ int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) {
   for (int t = 0; t < GPAK_MAX_TERMS; t++) gc.kinds[t] = t < ctx->kp.nterms ? ctx->kinds[t] : -1;
   dim3 grid(Np / GT_ROWS, Np / GT_COLS);
   const size_t nblocks = (size_t)grid.x * grid.y;
-  if (ctx->gpart_elems < nblocks * NSUM) {
-    if (ctx->dGpart) hipFree(ctx->dGpart);
-    ctx->dGpart = nullptr; ctx->gpart_elems = 0;
-    if (hipMalloc(&ctx->dGpart, sizeof(double) * nblocks * NSUM) != hipSuccess) {
-      ctx->err = "device allocation failed for gradient partial sums";
-      return GPAK_ENOMEM;
-    }
-    ctx->gpart_elems = nblocks * NSUM;
-  }
-  int rc = gpak_ensure_U(ctx);
+  rc = grad_partials(ctx, nblocks * NSUM);
+  if (rc) return rc;
+  rc = gpak_ensure_U(ctx);
   if (rc) return rc;
   hipLaunchKernelGGL(gpak_grad_pairs_f64, grid, dim3(256), 0, st, ctx->U.base, ctx->U.cap, ctx->dX, ctx->dX + Np,
                      ctx->dX + 2 * (size_t)Np, ctx->d == 4 ? ctx->dX + 3 * (size_t)Np : (const double *)nullptr,
@@ -404,6 +427,229 @@ int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) {
   GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[3]));
   ctx->times.grad_ms = ms;
   gpak_grad_assemble(ctx->kp, ctx->kinds, ctx->expans, ctx->d, N, ctx->sn2, red, g);
+  return GPAK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The EXACT gradient of nlZ (gpak_grad_exact): d nlZ / d theta = 1/2 sum_ij W_ij dK_ij / d theta with
+// W = (K + sn2 I)^-1 - alpha alpha^T, the `qw` of the pass above.  Steps 1-2 are shared (grad_binv); the pair pass
+// below accumulates sums that do not depend on which parameter is differentiated, and the host contracts them with
+// the 3 x 3 matrices dA / d theta (gpak_grad_exact_assemble).
+// ---------------------------------------------------------------------------------------
+#define NSX 16
+// part[block][NSX], sums over i >= j with weight 2 off the diagonal:
+//   [0] sum W   [1] trace W   [2+t] sum W e_t   [5+t] sum W e'_t d2_t for an Exp (e' = dk) or RBF (e' = e) child, on the
+//   child's OWN d2   [8..13] sum W dk D_a D_b, (a, b) = 00 01 02 11 12 22, D = x_i - x_j on the raw columns, ExpAns term
+//   [14] sum W dk D_4^2 (raw 4th column)
+// e_t = exp(-sqrt(d2_t)) or exp(-iw d2_t / 2), dk = -e / (2 sqrt(d2)) and 0 where d2 = 0 or i == j; d2_t from the
+// transformed points by differences whatever dist_mode is (a gradient has no use for the expansion's cancellation noise)
+struct ExactConsts {
+  double inv_sn2;
+  double iw[GPAK_MAX_TERMS];
+  int profile[GPAK_MAX_TERMS];
+  int nterms;
+  int te;   // index of the ExpAns term (-1: none)
+};
+
+__global__ __launch_bounds__(256) void gpak_grad_exact_pairs_f64(
+    const double *__restrict__ U, int cap, const double *__restrict__ x0, const double *__restrict__ x1,
+    const double *__restrict__ x2, const double *__restrict__ x3, const double *__restrict__ alpha,
+    const double *__restrict__ Binv, long ld, int N, ExactConsts xc, double *__restrict__ part) {
+  const int row0 = blockIdx.x * GT_ROWS, col0 = blockIdx.y * GT_COLS;
+  const int bid = blockIdx.y * gridDim.x + blockIdx.x;
+  __shared__ double cq[GPAK_MAX_TERMS][4][GT_COLS];  // transformed column points per term: u0, u1, u2, u3 (array 4 of U)
+  __shared__ double cx[4][GT_COLS];                  // raw columns of the column points (the 4th 0 for 3-D)
+  __shared__ double cal[GT_COLS];                    // alpha of the column points
+  __shared__ double red[4][NSX];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int nterms = xc.nterms, te = xc.te;
+  double acc[NSX];
+#pragma unroll
+  for (int k = 0; k < NSX; k++) acc[k] = 0.0;
+  if (row0 + GT_ROWS > col0) {  // tile touches the lower triangle
+    if (t < GT_COLS) {
+      const int j = col0 + t;
+      const bool ok = j < N;
+      for (int m = 0; m < nterms; m++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) cq[m][c][t] = ok ? PARRG(U, cap, m, c == 3 ? 4 : c)[j] : 0.0;
+      cal[t] = ok ? alpha[j] : 0.0;
+      cx[0][t] = ok ? x0[j] : 0.0; cx[1][t] = ok ? x1[j] : 0.0; cx[2][t] = ok ? x2[j] : 0.0;
+      cx[3][t] = (ok && x3) ? x3[j] : 0.0;
+    }
+    __syncthreads();
+    const int r = row0 + 2 * lane;
+    double pu[2][GPAK_MAX_TERMS][4], px[2][4], pal[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int i = r + h;
+      const bool ok = i < N;
+#pragma unroll
+      for (int m = 0; m < GPAK_MAX_TERMS; m++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) pu[h][m][c] = (ok && m < nterms) ? PARRG(U, cap, m, c == 3 ? 4 : c)[i] : 0.0;
+      px[h][0] = ok ? x0[i] : 0.0; px[h][1] = ok ? x1[i] : 0.0; px[h][2] = ok ? x2[i] : 0.0;
+      px[h][3] = (ok && x3) ? x3[i] : 0.0;
+      pal[h] = ok ? alpha[i] : 0.0;
+    }
+    for (int c = 0; c < GT_COLS / 4; c++) {
+      const int jl = w + 4 * c, j = col0 + jl;
+      if (j >= N) continue;
+      const double2 q2 = *reinterpret_cast<const double2 *>(Binv + r + (size_t)j * ld);
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int i = r + h;
+        if (i >= N || i < j) continue;
+        const double q = h ? q2.y : q2.x;
+        const double qw = q * xc.inv_sn2 - pal[h] * cal[jl];
+        const double wq = (i == j) ? qw : 2.0 * qw;  // every summand is symmetric in (i, j)
+        acc[0] += wq;
+        if (i == j) acc[1] += qw;
+#pragma unroll
+        for (int m = 0; m < GPAK_MAX_TERMS; m++) {
+          if (m >= nterms) break;
+          const double a = pu[h][m][0] - cq[m][0][jl], b = pu[h][m][1] - cq[m][1][jl], cc = pu[h][m][2] - cq[m][2][jl];
+          const double e4 = pu[h][m][3] - cq[m][3][jl];
+          const double d2 = a * a + b * b + cc * cc + e4 * e4;
+          if (xc.profile[m] == GPAK_PROFILE_RBF) {
+            const double we = wq * gpak_exp_nonpos(-0.5 * xc.iw[m] * d2);
+            acc[2 + m] += we;
+            acc[5 + m] = fma(we, d2, acc[5 + m]);
+          } else {
+            const double sd = gpak_sqrt_nonneg(d2);
+            const double ek = gpak_exp_nonpos(-sd);
+            const double wdk = (sd == 0.0 || i == j) ? 0.0 : wq * ek * (-0.5 / sd);
+            acc[2 + m] = fma(wq, ek, acc[2 + m]);
+            if (m == te) {
+              const double da = px[h][0] - cx[0][jl], db = px[h][1] - cx[1][jl], dc = px[h][2] - cx[2][jl];
+              const double dr = px[h][3] - cx[3][jl];
+              const double wa = wdk * da, wb = wdk * db;
+              acc[8] = fma(wa, da, acc[8]);
+              acc[9] = fma(wa, db, acc[9]);
+              acc[10] = fma(wa, dc, acc[10]);
+              acc[11] = fma(wb, db, acc[11]);
+              acc[12] = fma(wb, dc, acc[12]);
+              acc[13] = fma(wdk * dc, dc, acc[13]);
+              acc[14] = fma(wdk * dr, dr, acc[14]);
+            } else {
+              acc[5 + m] = fma(wdk, d2, acc[5 + m]);
+            }
+          }
+        }
+      }
+    }
+  }
+  // block reduction (fixed order)
+#pragma unroll
+  for (int k = 0; k < NSX; k++) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) red[w][k] = v;
+  }
+  __syncthreads();
+  if (t < NSX) part[(size_t)bid * NSX + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+}
+
+// the gradient entries from the NSX sums; pars[t] = the raw parameters of stationary term t in the reference's order
+// (ExpAns 8, Exp {hyp, Sigma}, RBF {hyp, iw, Sigma}); layout of g as gpak_grad_hyb: children in order, bias, sn2
+static void gpak_grad_exact_assemble(int nterms, const int *kinds, const double (*pars)[8], const double *red, double *g) {
+  int go = 0;
+  for (int t = 0; t < nterms; t++) {
+    const double *p = pars[t];
+    const double SWe = red[2 + t], SWd = red[5 + t];
+    if (kinds[t] == GPAK_KERN_EXPANS) {
+      // D = Delta^T A^2 Delta + (a33 Delta_4)^2, A = Rot diag(lam) Rot^T:  dD/dp = Delta^T (A A_p + A_p A) Delta
+      const double var2 = p[6] * p[6], lam[3] = {p[1], p[3], p[5]};
+      double R[3][3], D[3][3][3], A[3][3], T[3][3];
+      rot_tables(p, R, D);
+      T[0][0] = red[8]; T[0][1] = T[1][0] = red[9]; T[0][2] = T[2][0] = red[10];
+      T[1][1] = red[11]; T[1][2] = T[2][1] = red[12]; T[2][2] = red[13];
+      for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+          A[r][c] = 0.0;
+          for (int k = 0; k < 3; k++) A[r][c] += lam[k] * R[r][k] * R[c][k];
+        }
+      for (int q = 0; q < 6; q++) {
+        const int a = q / 2;
+        double Ap[3][3];
+        for (int r = 0; r < 3; r++)
+          for (int c = 0; c < 3; c++) {
+            if (q & 1) { Ap[r][c] = R[r][a] * R[c][a]; continue; }       // width lam_a: r_a r_a^T
+            Ap[r][c] = 0.0;                                              // angle a: Rot_a Lam Rot^T + Rot Lam Rot_a^T
+            for (int k = 0; k < 3; k++) Ap[r][c] += lam[k] * (D[a][r][k] * R[c][k] + R[r][k] * D[a][c][k]);
+          }
+        double s = 0.0;
+        for (int r = 0; r < 3; r++)
+          for (int c = 0; c < 3; c++) {
+            double m = 0.0;
+            for (int k = 0; k < 3; k++) m += A[r][k] * Ap[k][c] + Ap[r][k] * A[k][c];
+            s += m * T[r][c];
+          }
+        g[go + q] = 0.5 * var2 * s;
+      }
+      g[go + 6] = p[6] * SWe;
+      g[go + 7] = p[7] * var2 * red[14];   // 0 for 3-column inputs: every Delta_4 is 0
+      go += 8;
+    } else if (kinds[t] == GPAK_KERN_EXP) {   // k = Sigma^2 exp(-sqrt(d2)), d2 = |Delta|^2 / hyp^2
+      g[go] = -(p[1] * p[1] / p[0]) * SWd;
+      g[go + 1] = p[1] * SWe;
+      go += 2;
+    } else {                                  // k = Sigma^2 exp(-iw d2 / 2), d2 = |Delta|^2 / hyp^2
+      const double var2 = p[2] * p[2];
+      g[go] = var2 * p[1] / (2.0 * p[0]) * SWd;
+      g[go + 1] = -0.25 * var2 * SWd;
+      g[go + 2] = p[2] * SWe;
+      go += 3;
+    }
+  }
+  g[go++] = 0.5 * red[0];   // K gets Sigma_Bias on every entry
+  g[go] = 0.5 * red[1];     // and sn2 on the diagonal
+}
+
+int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np;
+  int need = 2, te = -1;
+  for (int t = 0; t < ctx->kp.nterms; t++) {
+    need += ctx->kinds[t] == GPAK_KERN_EXPANS ? 8 : ctx->kinds[t] == GPAK_KERN_EXP ? 2 : 3;
+    if (ctx->kinds[t] == GPAK_KERN_EXPANS) {
+      if (te >= 0) { ctx->err = "gpak_grad_exact: at most one ExpAns child"; return GPAK_ENOTIMPL; }
+      te = t;
+    }
+  }
+  if (ng != need) { ctx->err = "gpak_grad_exact: gradient vector has the wrong length"; return GPAK_EINVAL; }
+  if (ctx->kp.white != 0.0) {
+    // a context cannot tell a White child of value 0 from none, so the entry would come and go with the value
+    ctx->err = "gpak_grad_exact: compositions with a White child are not built";
+    return GPAK_ENOTIMPL;
+  }
+  int rc = grad_binv(ctx);
+  if (rc) return rc;
+  ExactConsts xc;
+  memset(&xc, 0, sizeof(xc));
+  xc.inv_sn2 = 1.0 / ctx->sn2; xc.nterms = ctx->kp.nterms; xc.te = te;
+  for (int t = 0; t < ctx->kp.nterms; t++) { xc.iw[t] = ctx->kp.term[t].iw; xc.profile[t] = ctx->kp.term[t].profile; }
+  dim3 grid(Np / GT_ROWS, Np / GT_COLS);
+  const size_t nblocks = (size_t)grid.x * grid.y;
+  rc = grad_partials(ctx, nblocks * NSX);
+  if (rc) return rc;
+  rc = gpak_ensure_U(ctx);
+  if (rc) return rc;
+  hipLaunchKernelGGL(gpak_grad_exact_pairs_f64, grid, dim3(256), 0, st, ctx->U.base, ctx->U.cap, ctx->dX, ctx->dX + Np,
+                     ctx->dX + 2 * (size_t)Np, ctx->d == 4 ? ctx->dX + 3 * (size_t)Np : (const double *)nullptr,
+                     ctx->dAlpha, ctx->dBinv, ctx->ld, N, xc, ctx->dGpart);
+  static_assert(NSX == NSUM, "gpak_grad_reduce_f64 strides the partial sums by NSUM");
+  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(NSX), dim3(256), 0, st, ctx->dGpart, (int)nblocks, ctx->dRed + 8);
+  double red[NSX];
+  GPAK_HIP(hipMemcpyAsync(red, ctx->dRed + 8, sizeof(red), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipEventRecord(ctx->ev[3], st));
+  GPAK_HIP(hipEventSynchronize(ctx->ev[3]));
+  float ms = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[3]));
+  ctx->times.grad_ms = ms;
+  gpak_grad_exact_assemble(ctx->kp.nterms, ctx->kinds, ctx->tpars, red, g);
   return GPAK_OK;
 }
 

@@ -159,6 +159,12 @@ class Gpak:
         self._check(self._lib.gpak_grad_hyb(self._h, _p(g), int(ng)))
         return g
 
+    def GradLL_exact(self, ng=10):
+        """The exact gradient of logLikelihood() (gpak_grad_exact): same layout as GradLL_hyb."""
+        g = np.zeros(int(ng))
+        self._check(self._lib.gpak_grad_exact(self._h, _p(g), int(ng)))
+        return g
+
     # -- measurement ---------------------------------------------------------------------
     def timing(self):
         t = _lib.PhaseTimes()

@@ -20,10 +20,18 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       else if (getArg() == "f32") precision = 1;
       else ErrorTermination("--precision takes f64 or f32");
     }
+    else if (isArg("--gradient", "--gradient")) {
+      incArg();
+      if (getArg() == "reference") exact_gradient = false;
+      else if (getArg() == "exact") exact_gradient = true;
+      else ErrorTermination("--gradient takes reference or exact");
+    }
     else if (isArg("-t", "--timing")) { incArg(); timing_file = getArg(); }   // "-" = stdout
     else break;
     incArg();
   }
+  if (exact_gradient && gpus > 1)
+    ErrorTermination("--gradient exact runs on one GPU only (the exact gradient is not built for multi-GPU contexts): drop --gpus or use --gradient reference");
 }
 bool Control::isArg(const std::string &s, const std::string &l) const { return getArg() == s || getArg() == l; }
 void Control::UnkFlg() const { ErrorTermination("Unknown flag: " + getArg() + " provided."); }

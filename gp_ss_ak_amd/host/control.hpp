@@ -47,6 +47,7 @@ class Control {
   bool no_prompt = false;
   int gpus = 1;                  // --gpus n: block-column-cyclic multi-GPU context (gpak_create_multi)
   int precision = 0;             // --precision f64|f32: GPAK_F64 / GPAK_F32 (fp32 prediction work)
+  bool exact_gradient = false;   // --gradient reference|exact: GradLL as the reference writes it / the derivative of nlZ
   std::string timing_file;       // --timing file|-: JSON of gpak_phase_times after the verb
   std::string mode = "gp";
   mat params, MinData, MaxData, MeanData, StData;

@@ -2,7 +2,8 @@
 //   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] train.txt [model]
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
-// (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb).
+// (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
+// (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only).
 // Same verbs, flags and files (<model>, <model>_Statistics.txt, <model>_predict.txt,
 // <model>_gnu.plt); -np/--no-prompt skips the two interactive stdin questions of `train`
 // (gp_ss_ak.cpp:235-285) and the gnuplot call of `test` (:503-505).
@@ -18,7 +19,10 @@
 
 class GP_Cntrl : public Control {
  public:
-  GP_Cntrl(int argc, char **argv) : Control(argc, argv) { GP_utils::setDeviceOptions(precision, gpus); }
+  GP_Cntrl(int argc, char **argv) : Control(argc, argv) {
+    GP_utils::setDeviceOptions(precision, gpus);
+    GP_utils::setExactGradient(exact_gradient);
+  }
   void writeTiming(const GP_utils &m) const {
     if (timing_file.empty()) return;
     const std::string j = m.timingJson();

@@ -12,6 +12,7 @@
 
 int GP_utils::default_precision = GPAK_F64;
 int GP_utils::default_gpus = 1;
+bool GP_utils::exact_gradient = false;
 
 void GP_utils::create_ctx() {
   int rc;
@@ -134,7 +135,9 @@ double GP_utils::GradLL(mat &g) const {  // GP_Utils.cpp:1171-1262
     ng += (int)c->getNPars();
   }
   std::vector<double> gd(ng);
-  if (gpak_grad_hyb(ctx, gd.data(), ng) != GPAK_OK) gpak_host_fatal("gpak_grad_hyb", ctx);
+  if (exact_gradient) {
+    if (gpak_grad_exact(ctx, gd.data(), ng) != GPAK_OK) gpak_host_fatal("gpak_grad_exact", ctx);
+  } else if (gpak_grad_hyb(ctx, gd.data(), ng) != GPAK_OK) gpak_host_fatal("gpak_grad_hyb", ctx);
   unsigned out = 0;
   int in = 0;
   for (const Kernels *c : leaves) {

@@ -50,6 +50,10 @@ class Opt_Algs {
   virtual void set_GP_Pars(mat &param) const = 0;
   virtual double Grad_Values(mat &g) const = 0;
   virtual double ObjVal() const = 0;
+  // name of parameter i (ProjectedLBFGSOptimise keeps those that begin with "Angle" linear) and whether Grad_Values
+  // returns the exact gradient of ObjVal (then Optimise runs ProjectedLBFGSOptimise)
+  virtual std::string getParName(unsigned int) const { return ""; }
+  virtual bool exactGradient() const { return false; }
   void setVerbose(int v) const { verbose = v; }
   int getVerbose() const { return verbose; }
   void setOptimiser(int v) { defaultOptimiser = v; }
@@ -63,9 +67,12 @@ class Opt_Algs {
   void LBFGSOptimise();
   // plain projected L-BFGS with backtracking (not the reference's trajectory); GPAK_OPT=simple
   void SimpleLBFGSOptimise();
+  // projected L-BFGS in log-parameters with Armijo backtracking, for an exact gradient (opt_algs.cpp)
+  void ProjectedLBFGSOptimise();
   void Optimise() {
     const char *e = getenv("GPAK_OPT");
-    if (e && std::string(e) == "simple") SimpleLBFGSOptimise();
+    if (exactGradient()) ProjectedLBFGSOptimise();
+    else if (e && std::string(e) == "simple") SimpleLBFGSOptimise();
     else LBFGSOptimise();
   }
   unsigned int numFuncEval = 0;
@@ -102,9 +109,11 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   void set_GP_Pars(mat &param) const override;
   double Grad_Values(mat &g) const override { return GradLL(g); }
   double ObjVal() const override { return logLikelihood(); }
+  std::string getParName(unsigned int i) const override { return i < KerenlW->getNPars() ? KerenlW->getParamName(i) : "likelihood"; }
+  bool exactGradient() const override { return exact_gradient; }
 
   double logLikelihood() const;   // NaN on Chol_fail (GP_Utils.cpp:1145-1158)
-  double GradLL(mat &g) const;    // g is 1 x getNumPars()
+  double GradLL(mat &g) const;    // g is 1 x getNumPars(); the exact gradient (gpak_grad_exact) when exact_gradient is set
   void OptimisePars(unsigned int iters);
   void updateKernel() const;
   std::ostream &ShowKernelPars(std::ostream &os) const;
@@ -120,6 +129,9 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   void setCompatFlags(int f) { compat = f; }
   // device-side options of every GP_utils constructed afterwards (the CLI's --precision / --gpus)
   static void setDeviceOptions(int precision, int gpus) { default_precision = precision; default_gpus = gpus; }
+  // the CLI's --gradient: false (default) = GradLL + getGradients as the reference writes them (gpak_grad_hyb),
+  // true = the derivative of logLikelihood() (gpak_grad_exact) and, through Optimise(), the driver that suits it
+  static void setExactGradient(bool v) { exact_gradient = v; }
   // gpak_phase_times of this model's context as one JSON object (the CLI's --timing)
   std::string timingJson() const;
   bool Chol_failed() const { return Chol_fail; }
@@ -136,6 +148,7 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   void sync_params() const;
   gpak_ctx *ctx = nullptr;
   static int default_precision, default_gpus;
+  static bool exact_gradient;
   void create_ctx();
   bool owns_kernel = false;
   mutable bool dirty = true;     // KUpdateStat / AlphaUpStatus (GP_Utils.h:257-279)

@@ -82,14 +82,17 @@ class QuadModel : public Opt_Algs {
   }
   double Grad_Values(mat &g) const override { double gg[6]; double f = eval(gg); for (int i = 0; i < 6; i++) g(i) = gg[i]; return f; }
   double ObjVal() const override { return eval(nullptr); }
+  // for ProjectedLBFGSOptimise: variable 2 stays linear like an angle, the others are optimised in their logarithm
+  std::string getParName(unsigned int i) const override { return i == 2 ? "AngleQ" : "q"; }
 };
 
-static int opt_only(int maxit, int variant) {
+static int opt_only(int maxit, int variant, bool projected = false) {
   QuadModel m(variant);
   m.setVerbose(1);
   m.setMaxIters(maxit);
   std::cout.precision(17);
-  m.LBFGSOptimise();
+  if (projected) m.ProjectedLBFGSOptimise();
+  else m.LBFGSOptimise();
   printf("FINAL");
   for (double v : m.x) printf(" %.17g", v);
   printf("\nNFEV %u\n", m.numFuncEval);
@@ -99,6 +102,7 @@ static int opt_only(int maxit, int variant) {
 int main(int argc, char **argv) {
   if (argc >= 3 && std::string(argv[1]) == "--logic") return logic_only(argv[2]);
   if (argc >= 3 && std::string(argv[1]) == "--opt") return opt_only(atoi(argv[2]), argc >= 4 ? atoi(argv[3]) : 0);
+  if (argc >= 3 && std::string(argv[1]) == "--opt-exact") return opt_only(atoi(argv[2]), argc >= 4 ? atoi(argv[3]) : 0, true);
   if (argc < 3) { fprintf(stderr, "usage: host_selftest train.csv test.csv\n"); return 2; }
   char *cargv[] = {argv[0], nullptr};
   Control io(1, cargv);

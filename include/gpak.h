@@ -170,6 +170,16 @@ int gpak_grad(gpak_ctx *ctx, double *g);
  * reference has no gradient for it either). */
 int gpak_grad_hyb(gpak_ctx *ctx, double *g, int ng);
 
+/* The EXACT gradient of the objective gpak_nlz returns -- what the two entry points above are not (they restate the
+ * reference's formulas as written):  d nlZ / d theta = 1/2 sum_ij W_ij dK_ij / d theta with
+ * W = (K + sn2 I)^-1 - alpha alpha^T.  Layout and length of g exactly as gpak_grad_hyb (children's blocks in order,
+ * bias, sn2; ng = 10 for ExpAns + Bias), every entry the derivative with respect to the parameter as it is passed to
+ * gpak_set_params / gpak_set_kernel (angles in radians, Sigma not squared, sn2 raw; the Exp / RBF children
+ * differentiate their OWN distance).  InversewidthR gets 0 for 3-column inputs.  Runs gram / factor / alpha if they are
+ * stale, sets grad_ms, and leaves factor, alpha and nlZ valid.  Same cost as gpak_grad: the N^3 inverse is shared.
+ * GPAK_ENOTIMPL for a composition with a White child and for a multi-GPU context (use a gpak_create context). */
+int gpak_grad_exact(gpak_ctx *ctx, double *g, int ng);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 typedef struct {
   double gram_ms;      /* fused fill of B = I + K/sn2 (lower tiles)                      */
@@ -177,7 +187,7 @@ typedef struct {
   double solve_ms;     /* two triangular solves                                          */
   double nlz_ms;       /* f = K alpha (fused Gram-matvec), lp, reductions                */
   double predict_ms;   /* last gpak_predict                                              */
-  double grad_ms;      /* last gpak_grad                                                 */
+  double grad_ms;      /* last gpak_grad / gpak_grad_hyb / gpak_grad_exact               */
   /* trailing-update kernel (the dominant, MFMA-bound launch), last factorisation,
    * measured with hipEvents on the ctx stream when GPAK_OPT_PROFILE is set: */
   double trailing_ms;        /* sum of launch durations                                  */
