@@ -11,7 +11,14 @@
  * Matrices are column-major doubles.  A rank stores a block column [J, J+W) of the N x N
  * matrix as an (Np x W) array with leading dimension ld whose column 0 is global column J;
  * Np = N rounded up to 128, padded rows/columns form an identity block.
- * Every function returns GPAK_OK or a negative HIP status.
+ * Every function returns GPAK_OK or a negative HIP status.  The functions that check their arguments -- gpak_dev_pack,
+ * gpak_dev_trsv_bwd_packed, gpak_dev_diag_inverse, gpak_dev_fill_rect, gpak_dev_solve_rows, gpak_dev_update_rect,
+ * gpak_dev_gemv_n_add, gpak_dev_transform_k (an unusable composition), gpak_dev_stream_create -- return GPAK_EINVAL for
+ * what their descriptions rule out (a width that is no multiple of 128 or above the stated limit, an odd count where
+ * 16-byte accesses need an even one) and write nothing then; the others trust the caller.  A call with nothing to do (no rows, no columns) writes nothing.  A call
+ * writes only the elements named in its description: never the rows between Np (or nrows) and the leading dimension,
+ * never a 128 x 128 tile above the diagonal where "lower tiles" is said.  tests/test_dev_ops.py holds the entry points
+ * to that one at a time, except gpak_dev_stream_create / gpak_dev_stream_destroy and the gpak_dev_grad_* family.
  */
 #ifndef GPAK_DEV_H
 #define GPAK_DEV_H
@@ -40,7 +47,9 @@ int gpak_dev_transform(void *stream, const double *x, int xs, int n, int cap, co
                        const double *mu, double *u);
 
 /* Fill the lower tiles of B = I + K/sn2 (GP_Utils.cpp:898-902) for global columns [J, J+W)
- * into blk (column 0 of blk = global column J).  u/cap/n as produced by gpak_dev_transform. */
+ * into blk (column 0 of blk = global column J).  u/cap/n as produced by gpak_dev_transform; u is read up to the PADDED
+ * row count (cap >= Np: the rows from n on may hold anything finite, they come out as the identity block).  A 128 x 128
+ * tile strictly above the diagonal is not written. */
 int gpak_dev_fill_b(void *stream, const double *u, int cap, int n, int Np, int J, int W,
                     const double *expans, double bias, double sn2, int dist_mode, double *blk, long ld);
 
@@ -57,23 +66,27 @@ int gpak_dev_factor_panel_co(void *stream, double *blk, long ld, int Np, int J, 
 
 /* Trailing update of an owned block column [Jc, Jc+Wc), Jc > J, with the factored panel of
  * [J, J+W) received from its owner.  `panel` holds rows [J+W.., Np) of that block column packed
- * with leading dimension ldp: panel[(r - prow0) + k*ldp] = L[r, J+k], prow0 = first packed row. */
+ * with leading dimension ldp: panel[(r - prow0) + k*ldp] = L[r, J+k], prow0 = first packed row.  Lower tiles only: of
+ * the block column's own Wc x Wc square, a 128 x 128 tile strictly above the diagonal is not written; nor is any row
+ * above Jc. */
 int gpak_dev_update_block(void *stream, const double *panel, long ldp, int prow0, int W, double *blk, long ld,
                           int Np, int Jc, int Wc);
 
 /* The same update for ALL block columns the rank owns from local block lb0 on, in ONE launch.
  * `local` is the rank's storage: its n_local_blocks block columns side by side (each nb columns,
- * leading dimension ld, the last one last_width wide); local block lb is global block lb*P+rank. */
+ * leading dimension ld, the last one last_width wide); local block lb is global block lb*P+rank.  Of every block
+ * column the lower tiles, as above; the local blocks before lb0 are not written; lb0 = n_local_blocks is a no-op. */
 int gpak_dev_update_cyclic(void *stream, const double *panel, long ldp, int prow0, int W, double *local, long ld,
                            int Np, int nb, int P, int rank, int lb0, int n_local_blocks, int last_width);
 
 /* Forward substitution step for block column [J, J+W):  out[J..J+W) = L_bb^-1 x[J..J+W) and
- * x[r] -= L[r, J..J+W) out  for every r >= J+W.  x, out have Np entries. */
+ * x[r] -= L[r, J..J+W) out  for every r >= J+W.  x, out have Np entries; x[J..J+W) is overwritten with intermediates,
+ * x above J and out outside [J, J+W) are not written. */
 int gpak_dev_trsv_fwd_block(void *stream, const double *blk, long ld, int Np, int J, int W, const double *inv,
                             double *x, double *out);
 /* s[0..W) = sum_{r >= J+W} L[r, J+c] x[r]   (the owner-local part of the back substitution) */
 int gpak_dev_coldot(void *stream, const double *blk, long ld, int Np, int J, int W, const double *x, double *s);
-/* out[J..J+W) = L_bb^-T x[J..J+W)  (x[J..J+W) is overwritten with intermediates) */
+/* out[J..J+W) = L_bb^-T x[J..J+W)  (x[J..J+W) is overwritten with intermediates; x outside it is not written) */
 int gpak_dev_trsv_bwd_block(void *stream, const double *blk, long ld, int J, int W, const double *inv, double *x,
                             double *out);
 /* Back substitution step for block column [J, J+W) held as a PACKED panel (element 0 of each column = global row
@@ -84,8 +97,8 @@ int gpak_dev_trsv_bwd_block(void *stream, const double *blk, long ld, int J, int
 int gpak_dev_trsv_bwd_packed(void *stream, const double *panel, long ldp, int row0, int Np, int J, int W,
                              const double *inv, const double *z, double *scratch, double *out, const double *rinv);
 /* rinv (512 x 512 doubles, leading dimension 512) <- (L_bb^-1)^T of the W x W diagonal block of a packed panel
- * (row0 = global row of element 0 of each column).  Seven small launches; meant to be queued where the stream
- * has slack (right after the panel arrives). */
+ * (row0 = global row of element 0 of each column).  Columns [0, W) of rinv are written whole, the others not at all.
+ * Seven small launches; meant to be queued where the stream has slack (right after the panel arrives). */
 int gpak_dev_diag_inverse(void *stream, const double *panel, long ldp, int row0, int J, int W, const double *inv,
                           double *rinv);
 /* out[0] = sum of log L[c,c] over the valid (c < N) columns of the block column */
@@ -100,7 +113,7 @@ int gpak_dev_nlz_terms(void *stream, int N, const double *y, const double *f, co
                        double *out);
 
 /* dst (nrows x ncols doubles, packed column-major) <- rows [row0, row0+nrows) of ncols columns of src (leading
- * dimension ld): the panel pack in front of a broadcast. */
+ * dimension ld): the panel pack in front of a broadcast.  nrows, row0 and ld must be even (16-byte copies). */
 int gpak_dev_pack(void *stream, const double *src, long ld, int row0, int nrows, int ncols, double *dst);
 
 /* ---- the reference-style gradient (GP_utils::GradLL, GP_Utils.cpp:1171-1262) distributed over P ranks that all hold
@@ -131,10 +144,12 @@ int gpak_dev_grad_consts(const double *expans, double *M36, double *m2_18);
 /* ---- pieces of the row-block x column-block layout (gpak_grid_*, include/gpak_dist.h): rectangular parts of a rank's
  * LOCAL storage; no global row addressing.  Semantics: the engine entries of the same names in gpak_dist.h.
  * gpak_dev_fill_rect: ExpAns + Bias piece of B = I + K/sn2 (the fill of HybKerns::computeK + ldB2_exact's scaling,
- *   Kernel.cpp:856-882, 362-367, GP_Utils.cpp:898-902); nrows a multiple of 128, ncols of 64.
+ *   Kernel.cpp:856-882, 362-367, GP_Utils.cpp:898-902); nrows a multiple of 128, ncols of 64; u is read up to row
+ *   row0 + nrows.  A piece with row0 != col0 is filled whole; a diagonal piece (row0 == col0) gets its lower 128-tiles.
  * gpak_dev_solve_rows: P := P Lbb^-T in 128-column steps (product with the inverted diagonal block, K = 128 update of
  *   the columns to the right), W <= 512.
- * gpak_dev_update_rect: the trailing update C -= A B^T of one block column of local blocks (MFMA GEMM).
+ * gpak_dev_update_rect: the trailing update C -= A B^T of one block column of local blocks (MFMA GEMM); mrows, ncols and
+ *   K multiples of 128.  diag_first != 0: the piece starts on the diagonal, tile (ti, tj) with ti < tj is not written.
  * gpak_dev_gemv_n_add / gpak_dev_gemv_t: the two matrix-vector products of the distributed triangular solves. */
 int gpak_dev_fill_rect(void *stream, const double *u, int cap, int n, int row0, int nrows, int col0, int ncols,
                        const double *expans, double bias, double sn2, int dist_mode, double *dst, long ld);

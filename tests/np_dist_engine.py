@@ -31,7 +31,9 @@ def _strided(ptr, rows, cols, ld):
 
 
 class NumpyDistEngine:
-    def __init__(self):
+    def __init__(self, poison_upper=True):
+        """poison_upper: a diagonal fill_rect piece gets NaN in the tiles above its diagonal, which the device leaves as
+        they were (gpak_dev.h) -- so that a schedule that READS them shows; False restates the device exactly."""
         self.np = NumpyEngine()
         self.mem = {}
         self.calls = []          # (operation, stream) in issue order, for schedule assertions
@@ -242,18 +244,20 @@ class NumpyDistEngine:
         def fill_rect(st, u, cap, n, row0, nrows, col0, ncols, expans, bias, sn2, mode, dst, ld):
             un = _arr(u, 15 * cap).reshape(15, cap)
             D = _strided(dst, nrows, ncols, ld)
+            upper = [(tj, D[:tj * TILE, tj * TILE:(tj + 1) * TILE].copy()) for tj in range(ncols // TILE)]
             D[:] = 0.0
             r1, c1 = min(n, row0 + nrows), min(n, col0 + ncols)
+            ex = [expans[i] for i in range(32 if mode & 0x20 else 8)]
             if r1 > row0 and c1 > col0:
-                D[:r1 - row0, :c1 - col0] = eng._kfun(un, slice(row0, r1), slice(col0, c1), [expans[i] for i in range(8)],
-                                                      bias, mode) / sn2
+                D[:r1 - row0, :c1 - col0] = eng._kfun(un, slice(row0, r1), slice(col0, c1), ex, bias, mode) / sn2
+            white = eng.decode_kern(ex)[1] if mode & 0x20 else 0.0     # Kern_White: Sigma_White on the diagonal
             for a in range(nrows):
                 c = row0 + a - col0
                 if 0 <= c < ncols:
-                    D[a, c] += 1.0
-            if row0 == col0:                      # a diagonal piece: only its lower 128-tiles are defined
-                for tj in range(ncols // TILE):
-                    D[:tj * TILE, tj * TILE:(tj + 1) * TILE] = np.nan
+                    D[a, c] += 1.0 + (white / sn2 if row0 + a < n else 0.0)
+            if row0 == col0:                      # a diagonal piece: only its lower 128-tiles are written
+                for tj, keep in upper:
+                    D[:tj * TILE, tj * TILE:(tj + 1) * TILE] = np.nan if poison_upper else keep
 
         def solve_rows(st, P, ld, nrows, W, Lbb, ldl, inv):
             import scipy.linalg as sl

@@ -114,6 +114,8 @@ class NumpyEngine:
     def fill_b(self, u, cap, n, Np, J, W, expans, bias, sn2, mode, blk, ld):
         un = self._un(u, cap)
         M = blk.numpy().reshape(W, ld).T  # (ld x W) column-major view
+        # gpak_dev.h: the LOWER tiles; a 128-tile strictly above the diagonal keeps what it held
+        upper = [(tj, M[:J + tj * TILE, tj * TILE:(tj + 1) * TILE].copy()) for tj in range(W // TILE)]
         M[:Np, :] = 0
         nc = max(0, min(W, n - J))
         if nc > 0:
@@ -121,6 +123,8 @@ class NumpyEngine:
         white = self.decode_kern(expans)[1] if mode & 0x20 else 0.0     # Kern_White: Sigma_White on the diagonal
         for c in range(W):
             M[J + c, c] += 1.0 + (white / sn2 if J + c < n else 0.0)
+        for tj, keep in upper:
+            M[:J + tj * TILE, tj * TILE:(tj + 1) * TILE] = keep
 
     def factor_panel(self, blk, ld, Np, J, W, inv, info):
         M = blk.numpy().reshape(W, ld).T
@@ -149,7 +153,10 @@ class NumpyEngine:
         P = panel.numpy().reshape(W, ldp).T
         C = blk.numpy().reshape(Wc, ld).T
         a = P[Jc - prow0:Np - prow0, :]
-        C[Jc:Np, :] -= a @ a[:Wc, :].T
+        upd = a @ a[:Wc, :].T
+        for tj in range(Wc // TILE):   # gpak_dev.h: lower tiles only; a tile strictly above the diagonal is not written
+            upd[:tj * TILE, tj * TILE:(tj + 1) * TILE] = 0.0
+        C[Jc:Np, :] -= upd
 
     def update_cyclic(self, panel, ldp, prow0, W, local, ld, Np, nb, P, rank, lb0, n_local, last_width):
         for lb in range(lb0, n_local):

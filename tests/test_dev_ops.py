@@ -1,0 +1,162 @@
+"""Every gpak_dev_* operation ALONE against a long-double reference (tests/dev_ops_cases.py): dispatch branches the
+workload reaches only at its own sizes (the in-place rs<4,2,false> panel product above 160 tile rows, the scalar-base
+GEMM at K >= 2048, the row splits of the packed back substitution), WHICH elements a kernel writes (tiles above the
+diagonal, tiles with art < gct of the cyclic map, skew columns, rows past nrows, read-only operands, guard bands),
+the edges of the super-tile walk, and the GPAK_EINVAL / no-op returns.
+
+CPU (-m "not gpu"): the cases on the float64 restatement (tests/np_engine.py, tests/np_dist_engine.py) -- references,
+masks and bounds agree with what the project itself says the operations do.  GPU (-m gpu): the same cases on
+libgpak_hip.so, one fresh process per group.
+
+Not covered here: gpak_dev_stream_create / gpak_dev_stream_destroy and the gpak_dev_grad_* family, whose only cover
+remains the distributed-gradient tests (tests/test_dist_cpp.py, tests/test_exact_grad_gpu.py).
+
+Worst error / bound per group on an MI355X, and the float64-vs-long-double ratios that set the substitution
+tolerances: DESIGN.md, "Device-level operations alone".
+"""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import dev_ops_cases as dc
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+NOT_COVERED = {"gpak_dev_stream_create", "gpak_dev_stream_destroy"}   # + gpak_dev_grad_*
+
+
+def _worker(engine, groups, timeout):
+    return subprocess.run([sys.executable, os.path.join(HERE, "dev_ops_worker.py"), "--engine", engine, "--group"] + list(groups),
+                          cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          timeout=timeout)
+
+
+def _records(r):
+    recs = [json.loads(l) for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    if r.returncode == 3:
+        pytest.skip(recs[-1]["skip"])
+    return recs
+
+
+def _assert_group(recs, group, r):
+    mine = [x for x in recs if x.get("group") == group]
+    expected = [n for g, n, _e, _f in dc.CASES if g == group]
+    print(f"{group}: worst error / bound = {max([0.0] + [float(x['ratio']) for x in mine]):.3g}")
+    for x in mine:
+        print(f"  {x['case']}: ratio {x['ratio']}" + "".join(f", {k} {v:.3g}" for k, v in x["info"].items()))
+        if len(x.get("ratios", {})) > 1:
+            print("      " + ", ".join(f"{k} {float(v):.3g}" for k, v in x["ratios"].items() if float(v) > 0))
+    for x in mine:
+        name = x["case"]
+        assert all(g == w for _l, g, w in x["rc"]), f"{name}: return codes (label, got, wanted) {x['rc']}"
+        assert not x["violations"], f"{name}: elements written that the operation must leave alone: {x['violations']}"
+        assert x["guards_ok"], f"{name}: a guard band was written"
+        assert float(x["ratio"]) <= 1.0, f"{name}: error / bound = {x['ratio']}"
+        assert x["deterministic"], f"{name}: two runs differ bit for bit"
+        assert x["ok"], name
+    assert [x["case"] for x in mine] == expected, (r.returncode, r.stderr.decode()[-3000:])
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def numpy_run():
+    r = _worker("numpy", dc.GROUPS, 600)        # one process: the cases share the start-up cost
+    return _records(r), r
+
+
+@pytest.mark.parametrize("group", dc.GROUPS)
+def test_cases_hold_on_the_float64_restatement(numpy_run, group):
+    recs, r = numpy_run
+    _assert_group(recs, group, r)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+
+
+def test_every_declared_entry_point_has_a_case():
+    declared = [n for n in dc.declared_entry_points() if not n.startswith("gpak_dev_grad_")]
+    covered = set(dc.covered_entry_points())
+    missing = [n for n in declared if n not in covered and n not in NOT_COVERED]
+    assert not missing, missing
+    assert covered <= set(declared), sorted(covered - set(declared))
+    assert {"gpak_dev_" + k for k in dc.SIG} >= covered
+
+
+def test_sliced_long_double_product_matches_numpy():
+    if not dc.long_double_ok():
+        pytest.skip("np.longdouble is no wider than float64 on this host")
+    rng = np.random.default_rng(5)
+    A, B = rng.standard_normal((70, 200)) * 10.0 ** rng.integers(-3, 4, (70, 1)), rng.standard_normal((45, 200))
+    plain = A.astype(np.longdouble) @ B.astype(np.longdouble).T
+    scale = (np.abs(A) @ np.abs(B).T).astype(np.longdouble)
+    assert (np.abs(dc.mm_ld(A, B) - plain) <= 200 * 2.0 ** -62 * scale).all()     # the plain product's own rounding
+    Bl = B.astype(np.longdouble) / 3
+    assert (np.abs(dc.mm_ld(A, Bl) - A.astype(np.longdouble) @ Bl.T) <= 200 * 2.0 ** -62 * scale).all()
+    L = np.tril(rng.standard_normal((40, 40))) + 6 * np.eye(40)
+    assert np.abs(dc.tri_inv_ld(L) @ L.astype(np.longdouble) - np.eye(40)).max() < 1e-17
+
+
+def test_the_checks_bite():
+    """An engine that is subtly wrong fails the case: a GEMM that forgets the skip rule writes the tiles above the
+    diagonal, one that drops a k-column is far outside the bound, a stray store in a skew row or a guard band counts."""
+    if not dc.long_double_ok():
+        pytest.skip("np.longdouble is no wider than float64 on this host")
+    cases = {n: f for _g, n, _e, f in dc.CASES}
+    good = dc.numpy_ops()
+
+    class Wrong:
+        name = "wrong"
+
+        def __init__(self, how):
+            self.how = how
+
+        def call(self, name, *a):
+            a = list(a)
+            if self.how == "no skip" and name == "update_rect":
+                a[9] = 0
+            if self.how == "short k" and name == "update_rect":
+                a[4] -= 128
+            rc = good.call(name, *a)
+            if self.how == "skew" and name == "update_rect":
+                a[5].data[a[7]] = 1.0                     # first skew row of column 0
+            if self.how == "guard" and name == "update_rect":
+                a[5].full[dc.GUARD - 1] = 1.0
+            return rc
+
+    name = "update_rect[1152,384,128,diag_first=1]"
+    ok = dc.summarise(name, cases[name](good), cases[name](good))
+    assert ok["ok"] and 0 < ok["ratio"] < 0.5
+    for how, field in (("no skip", "violations"), ("skew", "violations"), ("guard", "guards_ok")):
+        rec = dc.summarise(name, cases[name](Wrong(how)), cases[name](Wrong(how)))
+        assert not rec["ok"] and (rec[field] if field == "violations" else not rec[field]), (how, rec)
+    name = "update_rect[256,1152,512,diag_first=0]"
+    rec = dc.summarise(name, cases[name](Wrong("short k")), cases[name](Wrong("short k")))
+    assert not rec["ok"] and float(rec["ratio"]) > 1e10, rec
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------
+_DEVICE_TROUBLE = []       # set by the first worker that faulted, aborted or hung: no further GPU process is started
+
+
+def _gpu_group(group):
+    if _DEVICE_TROUBLE:
+        pytest.fail(f"not started: {_DEVICE_TROUBLE[0]}")
+    try:
+        r = _worker("hip", [group], 300)
+    except subprocess.TimeoutExpired:
+        _DEVICE_TROUBLE.append(f"the worker of group {group} did not finish in 300 s")
+        pytest.fail(_DEVICE_TROUBLE[0])
+    err = r.stderr.decode()
+    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in err or "hipError" in err:
+        _DEVICE_TROUBLE.append(f"the worker of group {group} ended with status {r.returncode}: {err[-1500:]}")
+        pytest.fail(_DEVICE_TROUBLE[0])
+    _assert_group(_records(r), group, r)
+    assert r.returncode == 0, err[-3000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group", dc.GROUPS)
+def test_device_ops_alone(group):
+    _gpu_group(group)
