@@ -35,8 +35,6 @@ int gpak_multi_timing(gpak_multi *g, gpak_phase_times *out);
 int gpak_multi_n(gpak_multi *g);
 #define GPAK_MULTI_ERR(rc_) do { int v_ = (rc_); if (v_) ctx->err = gpak_multi_error(ctx->multi); return v_; } while (0)
 int gpak_solve_chol_impl(gpak_ctx *ctx, double *X_host, int k);
-int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng);
-int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng);
 
 static std::string g_global_err;
 
@@ -125,24 +123,13 @@ int gpak_alloc_points(gpak_ctx *ctx, DevPoints &p, int cap) {
 
 // sigInv = Rot * lambda * Rot^T, Kernel.cpp:1399-1425 (host, 3x3)
 void gpak_build_siginv(const double *e, double *A) {
-  const double alpha = e[0], beta = e[2], teta = e[4];
   const double lam[3] = {e[1], e[3], e[5]};
-  double R[9];
-  const double ca = std::cos(alpha), sa = std::sin(alpha), cb = std::cos(beta), sb = std::sin(beta);
-  const double ct = std::cos(teta), st = std::sin(teta);
-  R[0 + 0 * 3] = ca * ct + sa * sb * st;
-  R[0 + 1 * 3] = -sa * ct + ca * sb * st;
-  R[0 + 2 * 3] = -cb * st;
-  R[1 + 0 * 3] = sa * cb;
-  R[1 + 1 * 3] = ca * cb;
-  R[1 + 2 * 3] = sb;
-  R[2 + 0 * 3] = ca * st - sa * sb * ct;
-  R[2 + 1 * 3] = -sa * st - ca * sb * ct;
-  R[2 + 2 * 3] = cb * ct;
+  double R[3][3];
+  gpak_rot_tables(e, R, nullptr);
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) {
       double s = 0.0;
-      for (int k = 0; k < 3; k++) s += R[r + k * 3] * lam[k] * R[c + k * 3];
+      for (int k = 0; k < 3; k++) s += R[r][k] * lam[k] * R[c][k];
       A[r + c * 3] = s;
     }
 }

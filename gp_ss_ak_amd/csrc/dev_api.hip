@@ -7,8 +7,6 @@
 #include "../../include/gpak_dev.h"
 #include "gpak_internal.h"
 
-void gpak_build_siginv(const double *e, double *A);
-
 // view of points [off, n) of a transformed set: same array stride (cap), shifted base
 static DevPoints as_points(const double *u, int cap, int n, int off = 0) {
   DevPoints p;

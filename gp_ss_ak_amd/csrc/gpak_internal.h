@@ -66,8 +66,6 @@ struct GpakKernelTuning {
   int f32_tile = 128;          // GPAK_F32_TILE      wave tile rows of the plain fp32 kernel: 128 / 64
 };
 const GpakKernelTuning &gpak_tuning();
-int gpak_build_kp(int nterms, const int *kinds, const double *pars, double bias, double white, int dist_mode,
-                  KernParams *out, double *kdiag_out);
 
 struct gpak_multi;   // multi.hip: one process driving several GPUs (gpak_create_multi)
 
@@ -212,6 +210,21 @@ __device__ __forceinline__ double gpak_exp_nonpos(double x) {
   int ni = __double2loint(t);
   ni = ni < -1022 ? -1022 : ni;
   return p * __hiloint2double((ni + 1023) << 20, 0);
+}
+// D2 (Kernel.cpp:1431-1434 / :1365-1367, or the cancellation-free equivalent)
+__device__ __forceinline__ double gpak_d2(double p0, double p1, double p2, double ps, double p3, double q0,
+                                          double q1, double q2, double qs, double q3, int mode) {
+  if (mode == GPAK_DIST_DIRECT) {
+    double a = p0 - q0, b = p1 - q1, c = p2 - q2, e = p3 - q3;
+    return a * a + b * b + c * c + e * e;  // e == 0 for 3-D inputs: the value is unchanged bit for bit
+  }
+  double dot = p0 * q0 + p1 * q1 + p2 * q2 + p3 * q3;
+  double v = ps + qs - 2.0 * dot;
+  return v < 0.0 ? 0.0 : v;
+}
+// var2 * profile(D2): Kernel.cpp:881 (ExpAns / Exp), :487 (RBF)
+__device__ __forceinline__ double gpak_profile(double d2, const KernTerm &t) {
+  return t.var2 * gpak_exp_nonpos(t.profile == GPAK_PROFILE_RBF ? -0.5 * t.iw * d2 : -gpak_sqrt_nonneg(d2));
 }
 
 // The same function with a 32-entry table of 2^(j/32) (kept in LDS by the caller: 32 doubles span the 64 banks exactly
@@ -369,7 +382,19 @@ int gpak_dist_factor_view_get(gpak_dist *h, gpak_dist_factor_view *out);
 double gpak_dist_grad_ms(const gpak_dist *h);
 int gpak_import_factor(gpak_ctx *ctx, const gpak_dist_factor_view *v);
 
+// ---- api.hip ----------------------------------------------------------------------------
+// sigInv = Rot * lambda * Rot^T of the eight ExpAns parameters (Kernel.cpp:1399-1425), column-major 3 x 3
+void gpak_build_siginv(const double *e, double *A);
+// HybKerns composition -> KernParams (mu and d are the caller's)
+int gpak_build_kp(int nterms, const int *kinds, const double *pars, double bias, double white, int dist_mode,
+                  KernParams *out, double *kdiag_out);
+
 // ---- grad.hip ---------------------------------------------------------------------------
 void gpak_grad_release(gpak_ctx *ctx);
+// gpak_grad / gpak_grad_hyb and gpak_grad_exact on a single-GPU context whose factor and alpha are current
+int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng);
+int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng);
+// Rot (Kernel.cpp:1399-1410) of the ExpAns parameters e; D (optional): D[a] = dRot / d angle_a
+void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]);
 void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *expans, int d, int N, double sn2,
                         const double *red, double *g);

@@ -1,19 +1,21 @@
-// grad.hip -- the reference-style "gradient" of the negative log marginal likelihood on gfx950.
+// grad.hip -- the gradients of the negative log marginal likelihood on gfx950.
 //
-// Replaces GP_utils::GradLL / dhyp / updateG / updateGlikelihood (GP_Utils.cpp:846-864,
+// gpak_grad / gpak_grad_hyb replace GP_utils::GradLL / dhyp / updateG / updateGlikelihood (GP_Utils.cpp:846-864,
 // 1164-1284) with Kern_ExpAnisotropic::getGradients (Kernel.cpp:886-1263) and
 // Kern_Bias::getGradients (:370-377), FORMULAS AS WRITTEN (this is not the
 // true gradient -- the optimiser trajectory of the reference depends on it as it is).
+// gpak_grad_exact is the derivative of nlZ itself; gpak_dev_grad_* (further down) is the as-written gradient
+// distributed over ranks by row blocks.
 //
 // Reference: Q = solve_chol(Lchol, diag(sW)) with N right-hand sides (2N^3 flops), ~15 N x N
 // temporaries, six N x 3 * 3 x N GEMMs.  Here, for the Gaussian likelihood (d3lp = 0, so
-// dfhat = dahat = 0, GP_Utils.cpp:414, 1210-1219):
+// dfhat = dahat = 0, GP_Utils.cpp:414, 1210-1219), all three share
 //   1. G = L^-T by blocked forward substitution on the identity, touching only the rows that
-//      can be non-zero (N^3/3 flops, MFMA);
+//      can be non-zero (N^3/3 flops, MFMA): grad_g_subst;
 //   2. B^-1 = G G^T, lower tiles, k-loop started at the row tile (N^3/3 flops, MFMA);
-//   3. ONE fused pass over the pairs i >= j that recomputes K_ij from the coordinates and
-//      accumulates the nine sums the ten gradient entries are made of.
-// gpak_grad_exact (further down) is the derivative of nlZ itself: steps 1-2 shared, a pair pass of its own.
+//   3. ONE fused pass over the pairs i >= j that recomputes what it needs of K_ij from the coordinates and
+//      accumulates NSUM sums the gradient entries are made of: gpak_grad_pairs_f64<Pass>, Pass = RefPass (as written)
+//      or ExactPass.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -25,49 +27,52 @@
 #define PB 128
 #define GT_ROWS 128
 #define GT_COLS 64
-#define NSUM 16  // 9 shared/ExpAns sums + 2 per stationary term for the Exp / RBF children + the rock-type sum
+#define NSUM 16  // sums of a pair pass (RefPass and ExactPass say what theirs are)
+#define PARRG GPAK_PARR
 
-struct GradConsts {
-  double M[6][6];   // S % S_p, symmetric 3x3 stored as {00,01,02,11,12,22}, p = 0..5
-  double m2[6][3];  // 2 * column sums of M_p : a_i^(p) = sum_k x_ik^2 m2[p][k]
-  double var2, bias, sn2;
-  int mode;
-  int te;           // index of the ExpAns term (-1: none)
-  int kinds[GPAK_MAX_TERMS];
-};
-
-__global__ void gpak_identity_f64(double *W, long ld, int n) {
+// 1 on the diagonal of L^-T, 0 elsewhere, for the rows a rank owns: local row r of the slab (leading dimension ld,
+// Np columns) is global row ((r / 128) * P + a) * 128 + r % 128; P = 1, a = 0: the whole matrix
+__global__ void gpak_identity_f64(double *W, long ld, int Np, int P, int a) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t tot = (size_t)n * ld;
+  const size_t tot = (size_t)Np * ld;
   if (i >= tot) return;
   const size_t c = i / ld, r = i - c * ld;
-  W[i] = (r == c) ? 1.0 : 0.0;
+  const size_t grow = ((r / PB) * P + a) * PB + (r % PB);
+  W[i] = (grow == c) ? 1.0 : 0.0;
 }
 
-// pair pass over the lower triangle; block partials: part[block][NSUM]
-//   [0..5] sum Rm * Di2^(p)   [6] sum QW * exp(-sqrt(D_expans))   [7] sum Q * K   [8] trace(QW)
-//   [9+2t], [10+2t]  the two sums of stationary term t when it is an Exp or RBF child; those
-//   children work on GP_utils' member D2 = the SUM of the children's D2 (Kernel.cpp:151, 491-540, 644-693)
-//   [15] sum exp(-sqrt(D_expans)) * (x4_i - x4_j)^2 for 4-column inputs (Kernel.cpp:1246-1255: the weight is
-//        KD2, not R -- RColon still holds KD2 from the Sigma block, reproduced as written)
-#define PARRG GPAK_PARR
-__global__ __launch_bounds__(256) void gpak_grad_pairs_f64(
-    const double *__restrict__ U, int cap, const double *__restrict__ x0, const double *__restrict__ x1,
-    const double *__restrict__ x2, const double *__restrict__ x3, const double *__restrict__ alpha,
-    const double *__restrict__ Binv, long ld, int N, KernParams kp, GradConsts gc, double *__restrict__ part,
-    int rowP, int rowA, int Tmax) {
+// ---------------------------------------------------------------------------------------
+// The pair pass over the lower triangle.  The skeleton owns the tiling (128 rows x 64 columns per workgroup, two
+// rows per lane in registers, the column points in LDS), where a row of B^-1 lives, the i >= j filter,
+// qw = q / sn2 - alpha_i alpha_j (dhyp, GP_Utils.cpp:1168: the W of the exact gradient) and the fixed-order
+// reduction to part[block][NSUM].  A Pass supplies
+//   Consts                what its body needs, by value;
+//   Col, stage_col        what it keeps per column point in LDS beyond the transformed coordinates and alpha;
+//   Row, stage_row        the same per row point, in registers;
+//   pair                  the body: one pair (i, j), i >= j, accumulated into acc[NSUM].
+// ---------------------------------------------------------------------------------------
+struct PairIn {
+  const double *U; int cap;          // transformed points (GPAK_PARR)
+  const double *x0, *x1, *x2, *x3;   // raw input columns; x3 = nullptr for 3-column inputs
+  const double *alpha, *Binv;
+  long ld;                           // of Binv
+  int N, nterms;
+  double inv_sn2;
   // rowP > 0 (distributed gradient): this rank holds the B^-1 ROWS of the 128-row blocks g = t*rowP + rowA as a
-  // compact (rows x Np) array whose 128-column groups are ordered by (g % rowP, g / rowP): see gpak_grad_binv_rows
-  const int row0 = (rowP ? blockIdx.x * rowP + rowA : blockIdx.x) * GT_ROWS, col0 = blockIdx.y * GT_COLS;
+  // compact (rows x Np) array whose 128-column groups are ordered by (g % rowP, g / rowP): see gpak_dev_grad_binv_rows
+  int rowP, rowA, Tmax;
+};
+
+template <class Pass>
+__global__ __launch_bounds__(256) void gpak_grad_pairs_f64(PairIn in, typename Pass::Consts pc, double *__restrict__ part) {
+  const int rowP = in.rowP, N = in.N, nterms = in.nterms;
+  const int row0 = (rowP ? blockIdx.x * rowP + in.rowA : blockIdx.x) * GT_ROWS, col0 = blockIdx.y * GT_COLS;
   const int bid = blockIdx.y * gridDim.x + blockIdx.x;
   __shared__ double cq[GPAK_MAX_TERMS][GPAK_PT][GT_COLS];  // transformed column points, per term
-  __shared__ double cx3[GT_COLS];                    // raw 4th column of the column points (0 for 3-D)
-  __shared__ double cal[GT_COLS];                    // alpha of the column points
-  __shared__ double cm[6][3][GT_COLS];               // M_p x_j
-  __shared__ double ca[6][GT_COLS];                  // a_j^(p)
+  __shared__ double cal[GT_COLS];                          // alpha of the column points
+  __shared__ typename Pass::Col cp;
   __shared__ double red[4][NSUM];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int nterms = kp.nterms, te = gc.te;
   double acc[NSUM];
 #pragma unroll
   for (int k = 0; k < NSUM; k++) acc[k] = 0.0;
@@ -77,18 +82,9 @@ __global__ __launch_bounds__(256) void gpak_grad_pairs_f64(
       const bool ok = j < N;
       for (int m = 0; m < nterms; m++)
 #pragma unroll
-        for (int c = 0; c < GPAK_PT; c++) cq[m][c][t] = ok ? PARRG(U, cap, m, c)[j] : 0.0;
-      cal[t] = ok ? alpha[j] : 0.0;
-      cx3[t] = (ok && x3) ? x3[j] : 0.0;
-      const double a = ok ? x0[j] : 0.0, b = ok ? x1[j] : 0.0, c = ok ? x2[j] : 0.0;
-#pragma unroll
-      for (int p = 0; p < 6; p++) {
-        const double *M = gc.M[p];
-        cm[p][0][t] = M[0] * a + M[1] * b + M[2] * c;
-        cm[p][1][t] = M[1] * a + M[3] * b + M[4] * c;
-        cm[p][2][t] = M[2] * a + M[4] * b + M[5] * c;
-        ca[p][t] = a * a * gc.m2[p][0] + b * b * gc.m2[p][1] + c * c * gc.m2[p][2];
-      }
+        for (int c = 0; c < GPAK_PT; c++) cq[m][c][t] = ok ? PARRG(in.U, in.cap, m, c)[j] : 0.0;
+      cal[t] = ok ? in.alpha[j] : 0.0;
+      Pass::stage_col(cp, t, ok, j, in, pc);
     }
     __syncthreads();
     const int r = row0 + 2 * lane;
@@ -97,86 +93,32 @@ __global__ __launch_bounds__(256) void gpak_grad_pairs_f64(
     long cgrp = 0;
     if (rowP) {
       const int g = col0 / PB;
-      cgrp = ((long)(g % rowP) * Tmax + g / rowP) * PB - (long)g * PB;   // added to j: the permuted column
+      cgrp = ((long)(g % rowP) * in.Tmax + g / rowP) * PB - (long)g * PB;   // added to j: the permuted column
     }
-    double pu[2][GPAK_MAX_TERMS][GPAK_PT], px[2][3], pa[2][6], pal[2], px3[2];
+    double pu[2][GPAK_MAX_TERMS][GPAK_PT], pal[2];
+    typename Pass::Row pr[2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       const int i = r + h;
       const bool ok = i < N;
-      for (int m = 0; m < nterms; m++)
 #pragma unroll
-        for (int c = 0; c < GPAK_PT; c++) pu[h][m][c] = ok ? PARRG(U, cap, m, c)[i] : 0.0;
-      px3[h] = (ok && x3) ? x3[i] : 0.0;
-      px[h][0] = ok ? x0[i] : 0.0; px[h][1] = ok ? x1[i] : 0.0; px[h][2] = ok ? x2[i] : 0.0;
-      pal[h] = ok ? alpha[i] : 0.0;
+      for (int m = 0; m < GPAK_MAX_TERMS; m++)
 #pragma unroll
-      for (int p = 0; p < 6; p++)
-        pa[h][p] = px[h][0] * px[h][0] * gc.m2[p][0] + px[h][1] * px[h][1] * gc.m2[p][1] +
-                   px[h][2] * px[h][2] * gc.m2[p][2];
+        for (int c = 0; c < GPAK_PT; c++) pu[h][m][c] = (ok && m < nterms) ? PARRG(in.U, in.cap, m, c)[i] : 0.0;
+      pal[h] = ok ? in.alpha[i] : 0.0;
+      Pass::stage_row(pr[h], ok, i, in, pc);
     }
     for (int c = 0; c < GT_COLS / 4; c++) {
       const int jl = w + 4 * c, j = col0 + jl;
       if (j >= N) continue;
-      const double2 q2 = *reinterpret_cast<const double2 *>(Binv + rloc + (size_t)(j + cgrp) * ld);
+      const double2 q2 = *reinterpret_cast<const double2 *>(in.Binv + rloc + (size_t)(j + cgrp) * in.ld);
 #pragma unroll
       for (int h = 0; h < 2; h++) {
         const int i = r + h;
         if (i >= N || i < j) continue;
         const double q = h ? q2.y : q2.x;
-        const double wgt = (i == j) ? 1.0 : 2.0;  // every summand is symmetric in (i, j)
-        double d2m[GPAK_MAX_TERMS], d2s = 0.0, kfull = gc.bias;
-#pragma unroll
-        for (int m = 0; m < GPAK_MAX_TERMS; m++) {
-          if (m >= nterms) break;
-          double d2;
-          if (gc.mode == GPAK_DIST_DIRECT) {
-            const double a = pu[h][m][0] - cq[m][0][jl], b = pu[h][m][1] - cq[m][1][jl], cc = pu[h][m][2] - cq[m][2][jl];
-            const double e4 = pu[h][m][4] - cq[m][4][jl];
-            d2 = a * a + b * b + cc * cc + e4 * e4;
-          } else {
-            const double dot = pu[h][m][0] * cq[m][0][jl] + pu[h][m][1] * cq[m][1][jl] + pu[h][m][2] * cq[m][2][jl] +
-                               pu[h][m][4] * cq[m][4][jl];
-            d2 = pu[h][m][3] + cq[m][3][jl] - 2.0 * dot;
-            d2 = d2 < 0.0 ? 0.0 : d2;
-          }
-          d2m[m] = d2;
-          d2s += d2;
-          kfull += kp.term[m].var2 * gpak_exp_nonpos(kp.term[m].profile == GPAK_PROFILE_RBF ? -0.5 * kp.term[m].iw * d2
-                                                                                            : -gpak_sqrt_nonneg(d2));
-        }
-        const double qw = q * (1.0 / gc.sn2) - pal[h] * cal[jl];   // dhyp, GP_Utils.cpp:1168
-        acc[7] = fma(wgt * q, kfull, acc[7]);                       // sum(Q % K), GP_Utils.cpp:1206
-        if (i == j) acc[8] += qw;                                   // trace(QW), Kernel.cpp:370-377
-        if (te >= 0) {
-          const double sd = gpak_sqrt_nonneg(d2m[te]);              // Kernel.cpp:1178
-          const double ek = gpak_exp_nonpos(-sd);                   // KD2, :1176
-          const double dk = (sd == 0.0 || i == j) ? 0.0 : ek * (-0.5 / sd);  // :1179-1184
-          const double rm = gc.var2 * qw * dk;                      // R = Qs % dk, :927, :1185
-#pragma unroll
-          for (int p = 0; p < 6; p++) {
-            const double xmx = px[h][0] * cm[p][0][jl] + px[h][1] * cm[p][1][jl] + px[h][2] * cm[p][2][jl];
-            const double di2 = pa[h][p] + ca[p][jl] - 4.0 * xmx;    // Di2, :1192-1194
-            acc[p] = fma(wgt * rm, di2, acc[p]);
-          }
-          acc[6] = fma(wgt * qw, ek, acc[6]);                       // :1239-1241
-          const double dx4 = px3[h] - cx3[jl];
-          acc[15] = fma(wgt * ek, dx4 * dx4, acc[15]);              // :1246-1253 (Di2_R = 2 dx4^2)
-        }
-#pragma unroll
-        for (int m = 0; m < GPAK_MAX_TERMS; m++) {
-          if (m >= nterms) break;
-          if (gc.kinds[m] == GPAK_KERN_EXP) {                       // Kernel.cpp:644-693 on the summed D2
-            const double sd = gpak_sqrt_nonneg(d2s), kd = gpak_exp_nonpos(-sd);
-            const double dk = (sd == 0.0 || i == j) ? 0.0 : kd * (-0.5 / sd);
-            acc[9 + 2 * m] = fma(wgt * qw * dk, d2s, acc[9 + 2 * m]);
-            acc[10 + 2 * m] = fma(wgt * qw * kd, kd, acc[10 + 2 * m]);
-          } else if (gc.kinds[m] == GPAK_KERN_RBF) {                // Kernel.cpp:491-540 on the summed D2
-            const double kd = gpak_exp_nonpos(-0.5 * kp.term[m].iw * d2s);
-            acc[9 + 2 * m] = fma(wgt * qw * kd, d2s, acc[9 + 2 * m]);
-            acc[10 + 2 * m] = fma(wgt * qw, kd, acc[10 + 2 * m]);
-          }
-        }
+        const double qw = q * in.inv_sn2 - pal[h] * cal[jl];
+        Pass::pair(acc, pu[h], cq, jl, pr[h], cp, q, qw, i == j, nterms, pc);
       }
     }
   }
@@ -233,36 +175,136 @@ void gpak_grad_release(gpak_ctx *ctx) {
   ctx->gpart_elems = 0;
 }
 
-// Rot (Kernel.cpp:1399-1410) and its true derivatives D[a] = dRot / d angle_a, a = 0..2 = AngleX, AngleY, AngleZ
-static void rot_tables(const double *e, double R[3][3], double D[3][3][3]) {
+// Rot (Kernel.cpp:1399-1410) and, when D is given, its true derivatives D[a] = dRot / d angle_a,
+// a = 0..2 = AngleX, AngleY, AngleZ
+void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]) {
   const double al = e[0], be = e[2], te = e[4];
   const double ca = cos(al), sa = sin(al), cb = cos(be), sb = sin(be), ct = cos(te), st = sin(te);
-  R[0][0] = ca * ct + sa * sb * st;   D[0][0][0] = -sa * ct + ca * sb * st;
-  D[1][0][0] = sa * cb * st;          D[2][0][0] = -ca * st + sa * sb * ct;
-  R[0][1] = -sa * ct + ca * sb * st;  D[0][0][1] = -ca * ct - sa * sb * st;
-  D[1][0][1] = ca * cb * st;          D[2][0][1] = sa * st + ca * sb * ct;
-  R[0][2] = -cb * st;                 D[0][0][2] = 0.0;
-  D[1][0][2] = sb * st;               D[2][0][2] = -cb * ct;
-  R[1][0] = sa * cb;                  D[0][1][0] = ca * cb;
-  D[1][1][0] = -sa * sb;              D[2][1][0] = 0.0;
-  R[1][1] = ca * cb;                  D[0][1][1] = -sa * cb;
-  D[1][1][1] = -ca * sb;              D[2][1][1] = 0.0;
-  R[1][2] = sb;                       D[0][1][2] = 0.0;
-  D[1][1][2] = cb;                    D[2][1][2] = 0.0;
-  R[2][0] = ca * st - sa * sb * ct;   D[0][2][0] = -sa * st - ca * sb * ct;
-  D[1][2][0] = -sa * cb * ct;         D[2][2][0] = ca * ct + sa * sb * st;
-  R[2][1] = -sa * st - ca * sb * ct;  D[0][2][1] = -ca * st + sa * sb * ct;
-  D[1][2][1] = -ca * cb * ct;         D[2][2][1] = -sa * ct + ca * sb * st;
-  R[2][2] = cb * ct;                  D[0][2][2] = 0.0;
-  D[1][2][2] = -sb * ct;              D[2][2][2] = -cb * st;
+  R[0][0] = ca * ct + sa * sb * st;
+  R[0][1] = -sa * ct + ca * sb * st;
+  R[0][2] = -cb * st;
+  R[1][0] = sa * cb;
+  R[1][1] = ca * cb;
+  R[1][2] = sb;
+  R[2][0] = ca * st - sa * sb * ct;
+  R[2][1] = -sa * st - ca * sb * ct;
+  R[2][2] = cb * ct;
+  if (!D) return;
+  D[0][0][0] = -sa * ct + ca * sb * st;  D[1][0][0] = sa * cb * st;    D[2][0][0] = -ca * st + sa * sb * ct;
+  D[0][0][1] = -ca * ct - sa * sb * st;  D[1][0][1] = ca * cb * st;    D[2][0][1] = sa * st + ca * sb * ct;
+  D[0][0][2] = 0.0;                      D[1][0][2] = sb * st;         D[2][0][2] = -cb * ct;
+  D[0][1][0] = ca * cb;                  D[1][1][0] = -sa * sb;        D[2][1][0] = 0.0;
+  D[0][1][1] = -sa * cb;                 D[1][1][1] = -ca * sb;        D[2][1][1] = 0.0;
+  D[0][1][2] = 0.0;                      D[1][1][2] = cb;              D[2][1][2] = 0.0;
+  D[0][2][0] = -sa * st - ca * sb * ct;  D[1][2][0] = -sa * cb * ct;   D[2][2][0] = ca * ct + sa * sb * st;
+  D[0][2][1] = -ca * st + sa * sb * ct;  D[1][2][1] = -ca * cb * ct;   D[2][2][1] = -sa * ct + ca * sb * st;
+  D[0][2][2] = 0.0;                      D[1][2][2] = -sb * ct;        D[2][2][2] = -cb * st;
 }
+
+// ---------------------------------------------------------------------------------------
+// Steps 1 and 2.
+// G = L^-T is upper triangular and its ROWS are independent right-hand sides of the blocked forward substitution on
+// the identity (the test-major scheme of predict.hip), so rank a of P computes the rows of the 128-row blocks
+// g = t*P + a into a compact slab (rows_a x Np, leading dimension lds) without communication; P = 1, a = 0 is the
+// whole matrix.  Two levels like the Cholesky: 128-column steps inside a block column of nb columns, then one K = W
+// update of the columns to the right; rows that enter the substitution later are still zero and are left out.
+// ---------------------------------------------------------------------------------------
+static int my_tiles(int Np, int P, int a) { const int T = Np / PB; return T > a ? (T - a + P - 1) / P : 0; }
+
+// block column b of L, rows from its diagonal block down (leading dimension ldp), and its inverted 128-blocks
+struct LBlockCol { const double *panel; long ldp; const double *inv; };
+
+template <class Where>   // Where: int b -> LBlockCol
+static void grad_g_subst(hipStream_t st, int Np, int nb, int P, int a, Where where, double *slab, long lds) {
+  const int Ta = my_tiles(Np, P, a);
+  if (Ta == 0) return;
+  const size_t tot = (size_t)Np * lds;
+  hipLaunchKernelGGL(gpak_identity_f64, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, slab, lds, Np, P, a);
+  auto tiles_upto = [&](int gblock) { return gblock >= a ? std::min(Ta, (gblock - a) / P + 1) : 0; };   // g <= gblock
+  for (int b = 0, J = 0; J < Np; b++, J += nb) {
+    const int W = std::min(nb, Np - J);
+    const LBlockCol L = where(b);
+    for (int j0 = J; j0 < J + W; j0 += PB) {
+      const int mt = tiles_upto(j0 / PB);   // rows below are still zero in L^-T
+      if (mt == 0) continue;
+      const double *inv = L.inv + (size_t)((j0 - J) / PB) * 2 * PB * PB;
+      double *Wj = slab + (size_t)j0 * lds;
+      gpak_launch_gemm_nt(st, mt, 1, PB, 1.0, Wj, lds, inv, PB, 0.0, Wj, lds, 0, 0, false, false);
+      const int nin = (J + W - j0 - PB) / PB;
+      if (nin > 0)
+        gpak_launch_gemm_nt(st, mt, nin, PB, -1.0, Wj, lds, L.panel + (j0 + PB - J) + (size_t)(j0 - J) * L.ldp, L.ldp, 1.0,
+                            slab + (size_t)(j0 + PB) * lds, lds, 0, 0, false, false);
+    }
+    const int nrest = (Np - J - W) / PB, mt2 = tiles_upto((J + W) / PB - 1);
+    if (nrest > 0 && mt2 > 0)
+      gpak_launch_gemm_nt(st, mt2, nrest, W, -1.0, slab + (size_t)J * lds, lds, L.panel + W, L.ldp, 1.0,
+                          slab + (size_t)(J + W) * lds, lds, 0, 0, false, false);
+  }
+}
+
+// single GPU: allocates the two N x N workspaces on first use, records ev[7] (the start of grad_ms) and leaves B^-1
+// (lower tiles) in ctx->dBinv
+static int grad_binv(gpak_ctx *ctx) {
+  hipStream_t st = ctx->stream;
+  const int Np = ctx->Np;
+  const long ld = ctx->ld;
+  if (!ctx->dG) {
+    if (hipMalloc(&ctx->dG, sizeof(double) * (size_t)ld * Np) != hipSuccess ||
+        hipMalloc(&ctx->dBinv, sizeof(double) * (size_t)ld * Np) != hipSuccess) {
+      ctx->err = "device allocation failed for the gradient workspaces (2 N x N matrices)";
+      gpak_grad_release(ctx);
+      return GPAK_ENOMEM;
+    }
+  }
+  GPAK_HIP(hipEventRecord(ctx->ev[7], st));
+  // 1. G = L^-T: block columns of 512 of the factor in dM, their inverted diagonal blocks in dInv
+  const int GNB = 512;
+  double *G = ctx->dG;
+  grad_g_subst(st, Np, GNB, 1, 0, [&](int b) {
+    const size_t J = (size_t)b * GNB;
+    return LBlockCol{ctx->dM + J + J * ld, ld, ctx->dInv + J / PB * 2 * PB * PB};
+  }, G, ld);
+  // 2. B^-1 = G G^T (lower tiles); G[i,k] = 0 for k < i, so the k-loop starts at the row tile
+  gpak_launch_gemm_nt(st, Np / PB, Np / PB, Np, 1.0, G, ld, G, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, true);
+  return GPAK_OK;
+}
+
+// per-workgroup partial sums of a pair pass: at least `elems` doubles in ctx->dGpart
+static int grad_partials(gpak_ctx *ctx, size_t elems) {
+  if (ctx->gpart_elems >= elems) return GPAK_OK;
+  if (ctx->dGpart) hipFree(ctx->dGpart);
+  ctx->dGpart = nullptr; ctx->gpart_elems = 0;
+  if (hipMalloc(&ctx->dGpart, sizeof(double) * elems) != hipSuccess) {
+    ctx->err = "device allocation failed for gradient partial sums";
+    return GPAK_ENOMEM;
+  }
+  ctx->gpart_elems = elems;
+  return GPAK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The as-written pass.  part[block][NSUM]:
+//   [0..5] sum Rm * Di2^(p)   [6] sum QW * exp(-sqrt(D_expans))   [7] sum Q * K   [8] trace(QW)
+//   [9+2t], [10+2t]  the two sums of stationary term t when it is an Exp or RBF child; those
+//   children work on GP_utils' member D2 = the SUM of the children's D2 (Kernel.cpp:151, 491-540, 644-693)
+//   [15] sum exp(-sqrt(D_expans)) * (x4_i - x4_j)^2 for 4-column inputs (Kernel.cpp:1246-1255: the weight is
+//        KD2, not R -- RColon still holds KD2 from the Sigma block, reproduced as written)
+// ---------------------------------------------------------------------------------------
+struct GradConsts {
+  double M[6][6];   // S % S_p, symmetric 3x3 stored as {00,01,02,11,12,22}, p = 0..5
+  double m2[6][3];  // 2 * column sums of M_p : a_i^(p) = sum_k x_ik^2 m2[p][k]
+  double var2, bias;
+  int mode;
+  int te;           // index of the ExpAns term (-1: none)
+  int kinds[GPAK_MAX_TERMS];
+};
 
 // S, S_alpha.. as written at Kernel.cpp:955-1166 (the (0,0) z-term of the angle derivatives lacks
 // its factor 2, :1003-1011) and M_p = S % S_p
 static void build_grad_consts(const double *e, GradConsts &gc) {
   const double iw[3] = {e[1], e[3], e[5]};
   double R[3][3], D[3][3][3];
-  rot_tables(e, R, D);
+  gpak_rot_tables(e, R, D);
   double S[3][3], Sp[6][3][3];
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) {
@@ -319,239 +361,119 @@ void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *ex
   g[go] = -1.0 * sum_dW * (2.0 / sn2) - red[NSUM];               // GP_Utils.cpp:1226
 }
 
-// steps 1 and 2, shared by the as-written and the exact gradient: allocates the two N x N workspaces on first use,
-// records ev[7] (the start of grad_ms) and leaves B^-1 (lower tiles) in ctx->dBinv
-static int grad_binv(gpak_ctx *ctx) {
-  hipStream_t st = ctx->stream;
-  const int Np = ctx->Np;
-  const long ld = ctx->ld;
-  if (!ctx->dG) {
-    if (hipMalloc(&ctx->dG, sizeof(double) * (size_t)ld * Np) != hipSuccess ||
-        hipMalloc(&ctx->dBinv, sizeof(double) * (size_t)ld * Np) != hipSuccess) {
-      ctx->err = "device allocation failed for the gradient workspaces (2 N x N matrices)";
-      gpak_grad_release(ctx);
-      return GPAK_ENOMEM;
-    }
-  }
-  GPAK_HIP(hipEventRecord(ctx->ev[7], st));
-  // 1. G = L^-T: forward substitution on the identity, rows restricted to the non-zero part
-  double *G = ctx->dG;
-  {
-    const size_t tot = (size_t)Np * ld;
-    hipLaunchKernelGGL(gpak_identity_f64, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, G, ld, Np);
-  }
-  // two levels like the Cholesky: 128-column steps inside an outer block of 512 columns, then one
-  // K = 512 update of the columns to the right; rows beyond the outer block are still zero
-  const int GNB = 512;
-  for (int J = 0; J < Np; J += GNB) {
-    const int W = (Np - J) < GNB ? (Np - J) : GNB;
-    for (int j0 = J; j0 < J + W; j0 += PB) {
-      const double *inv = ctx->dInv + (size_t)(j0 / PB) * 2 * PB * PB;
-      double *Gj = G + (size_t)j0 * ld;
-      const int mt = j0 / PB + 1;  // rows 0 .. j0+127: everything below is zero in L^-T
-      gpak_launch_gemm_nt(st, mt, 1, PB, 1.0, Gj, ld, inv, PB, 0.0, Gj, ld, 0, 0, false, false);
-      const int nin = (J + W - j0 - PB) / PB;
-      if (nin > 0)
-        gpak_launch_gemm_nt(st, mt, nin, PB, -1.0, Gj, ld, ctx->dM + (j0 + PB) + (size_t)j0 * ld, ld, 1.0,
-                            G + (size_t)(j0 + PB) * ld, ld, 0, 0, false, false);
-    }
-    const int nrest = (Np - J - W) / PB;
-    if (nrest > 0)
-      gpak_launch_gemm_nt(st, (J + W) / PB, nrest, W, -1.0, G + (size_t)J * ld, ld,
-                          ctx->dM + (J + W) + (size_t)J * ld, ld, 1.0, G + (size_t)(J + W) * ld, ld, 0, 0, false, false);
-  }
-  // 2. B^-1 = G G^T (lower tiles); G[i,k] = 0 for k < i, so the k-loop starts at the row tile
-  gpak_launch_gemm_nt(st, Np / PB, Np / PB, Np, 1.0, G, ld, G, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, true);
-  return GPAK_OK;
-}
+struct RefPass {
+  struct Consts { KernParams kp; GradConsts gc; };
+  struct Col {
+    double x3[GT_COLS];        // raw 4th column (0 for 3-D)
+    double m[6][3][GT_COLS];   // M_p x_j
+    double a[6][GT_COLS];      // a_j^(p)
+  };
+  struct Row { double x[3], a[6], x3; };
 
-// per-workgroup partial sums of a pair pass: at least `elems` doubles in ctx->dGpart
-static int grad_partials(gpak_ctx *ctx, size_t elems) {
-  if (ctx->gpart_elems >= elems) return GPAK_OK;
-  if (ctx->dGpart) hipFree(ctx->dGpart);
-  ctx->dGpart = nullptr; ctx->gpart_elems = 0;
-  if (hipMalloc(&ctx->dGpart, sizeof(double) * elems) != hipSuccess) {
-    ctx->err = "device allocation failed for gradient partial sums";
-    return GPAK_ENOMEM;
-  }
-  ctx->gpart_elems = elems;
-  return GPAK_OK;
-}
-
-// kinds of the current composition (set by gpak_set_params / gpak_set_kernel)
-int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) {
-  GPAK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int N = ctx->N, Np = ctx->Np;
-  const long ld = ctx->ld;
-  // expected length: children in order (8 / 2 / 3), bias, sn2
-  int need = 2, te = -1;
-  for (int t = 0; t < ctx->kp.nterms; t++) {
-    need += ctx->kinds[t] == GPAK_KERN_EXPANS ? 8 : ctx->kinds[t] == GPAK_KERN_EXP ? 2 : 3;
-    if (ctx->kinds[t] == GPAK_KERN_EXPANS) {
-      if (te >= 0) { ctx->err = "gpak_grad: at most one ExpAns child"; return GPAK_ENOTIMPL; }
-      te = t;
+  static __device__ __forceinline__ void stage_col(Col &s, int t, bool ok, int j, const PairIn &in, const Consts &k) {
+    s.x3[t] = (ok && in.x3) ? in.x3[j] : 0.0;
+    const double a = ok ? in.x0[j] : 0.0, b = ok ? in.x1[j] : 0.0, c = ok ? in.x2[j] : 0.0;
+#pragma unroll
+    for (int p = 0; p < 6; p++) {
+      const double *M = k.gc.M[p];
+      s.m[p][0][t] = M[0] * a + M[1] * b + M[2] * c;
+      s.m[p][1][t] = M[1] * a + M[3] * b + M[4] * c;
+      s.m[p][2][t] = M[2] * a + M[4] * b + M[5] * c;
+      s.a[p][t] = a * a * k.gc.m2[p][0] + b * b * k.gc.m2[p][1] + c * c * k.gc.m2[p][2];
     }
   }
-  if (ng != need) { ctx->err = "gpak_grad: gradient vector has the wrong length"; return GPAK_EINVAL; }
-  if (ctx->kp.white != 0.0) {
-    // Kern_White has no getGradients upstream (Kernel.h:257-283: the base method calls itself)
-    ctx->err = "gpak_grad: compositions with a White child have no gradient in the reference either";
-    return GPAK_ENOTIMPL;
+  static __device__ __forceinline__ void stage_row(Row &p, bool ok, int i, const PairIn &in, const Consts &k) {
+    p.x3 = (ok && in.x3) ? in.x3[i] : 0.0;
+    p.x[0] = ok ? in.x0[i] : 0.0; p.x[1] = ok ? in.x1[i] : 0.0; p.x[2] = ok ? in.x2[i] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+      p.a[q] = p.x[0] * p.x[0] * k.gc.m2[q][0] + p.x[1] * p.x[1] * k.gc.m2[q][1] + p.x[2] * p.x[2] * k.gc.m2[q][2];
   }
-  int rc = grad_binv(ctx);
-  if (rc) return rc;
-  // 3. fused pair pass
-  GradConsts gc;
-  memset(&gc, 0, sizeof(gc));
-  if (te >= 0) build_grad_consts(ctx->expans, gc);
-  gc.var2 = te >= 0 ? ctx->kp.term[te].var2 : 0.0;
-  gc.bias = ctx->bias; gc.sn2 = ctx->sn2; gc.mode = ctx->dist_mode; gc.te = te;
-  for (int t = 0; t < GPAK_MAX_TERMS; t++) gc.kinds[t] = t < ctx->kp.nterms ? ctx->kinds[t] : -1;
-  dim3 grid(Np / GT_ROWS, Np / GT_COLS);
-  const size_t nblocks = (size_t)grid.x * grid.y;
-  rc = grad_partials(ctx, nblocks * NSUM);
-  if (rc) return rc;
-  rc = gpak_ensure_U(ctx);
-  if (rc) return rc;
-  hipLaunchKernelGGL(gpak_grad_pairs_f64, grid, dim3(256), 0, st, ctx->U.base, ctx->U.cap, ctx->dX, ctx->dX + Np,
-                     ctx->dX + 2 * (size_t)Np, ctx->d == 4 ? ctx->dX + 3 * (size_t)Np : (const double *)nullptr,
-                     ctx->dAlpha, ctx->dBinv, ld, N, ctx->kp, gc, ctx->dGpart, 0, 0, 0);
-  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(NSUM), dim3(256), 0, st, ctx->dGpart, (int)nblocks, ctx->dRed + 8);
-  hipLaunchKernelGGL(gpak_lpdhyp_f64, dim3(1), dim3(1024), 0, st, N, ctx->dy, ctx->dF, ctx->sn2, ctx->dRed + 8 + NSUM);
-  double red[NSUM + 1];
-  GPAK_HIP(hipMemcpyAsync(red, ctx->dRed + 8, sizeof(red), hipMemcpyDeviceToHost, st));
-  GPAK_HIP(hipEventRecord(ctx->ev[3], st));
-  GPAK_HIP(hipEventSynchronize(ctx->ev[3]));
-  float ms = 0;
-  GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[3]));
-  ctx->times.grad_ms = ms;
-  gpak_grad_assemble(ctx->kp, ctx->kinds, ctx->expans, ctx->d, N, ctx->sn2, red, g);
-  return GPAK_OK;
-}
+  static __device__ __forceinline__ void pair(double (&acc)[NSUM], const double (&pu)[GPAK_MAX_TERMS][GPAK_PT],
+                                              const double (&cq)[GPAK_MAX_TERMS][GPAK_PT][GT_COLS], int jl, const Row &pr,
+                                              const Col &cp, double q, double qw, bool diag, int nterms, const Consts &k) {
+    const KernParams &kp = k.kp;
+    const GradConsts &gc = k.gc;
+    const int te = gc.te;
+    const double wgt = diag ? 1.0 : 2.0;  // every summand is symmetric in (i, j)
+    double d2m[GPAK_MAX_TERMS], d2s = 0.0, kfull = gc.bias;
+#pragma unroll
+    for (int m = 0; m < GPAK_MAX_TERMS; m++) {
+      if (m >= nterms) break;
+      const double d2 = gpak_d2(pu[m][0], pu[m][1], pu[m][2], pu[m][3], pu[m][4], cq[m][0][jl], cq[m][1][jl], cq[m][2][jl],
+                                cq[m][3][jl], cq[m][4][jl], gc.mode);
+      d2m[m] = d2;
+      d2s += d2;
+      kfull += gpak_profile(d2, kp.term[m]);
+    }
+    acc[7] = fma(wgt * q, kfull, acc[7]);                       // sum(Q % K), GP_Utils.cpp:1206
+    if (diag) acc[8] += qw;                                     // trace(QW), Kernel.cpp:370-377
+    if (te >= 0) {
+      const double sd = gpak_sqrt_nonneg(d2m[te]);              // Kernel.cpp:1178
+      const double ek = gpak_exp_nonpos(-sd);                   // KD2, :1176
+      const double dk = (sd == 0.0 || diag) ? 0.0 : ek * (-0.5 / sd);  // :1179-1184
+      const double rm = gc.var2 * qw * dk;                      // R = Qs % dk, :927, :1185
+#pragma unroll
+      for (int p = 0; p < 6; p++) {
+        const double xmx = pr.x[0] * cp.m[p][0][jl] + pr.x[1] * cp.m[p][1][jl] + pr.x[2] * cp.m[p][2][jl];
+        const double di2 = pr.a[p] + cp.a[p][jl] - 4.0 * xmx;   // Di2, :1192-1194
+        acc[p] = fma(wgt * rm, di2, acc[p]);
+      }
+      acc[6] = fma(wgt * qw, ek, acc[6]);                       // :1239-1241
+      const double dx4 = pr.x3 - cp.x3[jl];
+      acc[15] = fma(wgt * ek, dx4 * dx4, acc[15]);              // :1246-1253 (Di2_R = 2 dx4^2)
+    }
+#pragma unroll
+    for (int m = 0; m < GPAK_MAX_TERMS; m++) {
+      if (m >= nterms) break;
+      if (gc.kinds[m] == GPAK_KERN_EXP) {                       // Kernel.cpp:644-693 on the summed D2
+        const double sd = gpak_sqrt_nonneg(d2s), kd = gpak_exp_nonpos(-sd);
+        const double dk = (sd == 0.0 || diag) ? 0.0 : kd * (-0.5 / sd);
+        acc[9 + 2 * m] = fma(wgt * qw * dk, d2s, acc[9 + 2 * m]);
+        acc[10 + 2 * m] = fma(wgt * qw * kd, kd, acc[10 + 2 * m]);
+      } else if (gc.kinds[m] == GPAK_KERN_RBF) {                // Kernel.cpp:491-540 on the summed D2
+        const double kd = gpak_exp_nonpos(-0.5 * kp.term[m].iw * d2s);
+        acc[9 + 2 * m] = fma(wgt * qw * kd, d2s, acc[9 + 2 * m]);
+        acc[10 + 2 * m] = fma(wgt * qw, kd, acc[10 + 2 * m]);
+      }
+    }
+  }
+
+  // host side of gpak_grad / gpak_grad_hyb
+  static constexpr const char *entry = "gpak_grad";
+  // Kern_White has no getGradients upstream (Kernel.h:257-283: the base method calls itself)
+  static constexpr const char *white = "compositions with a White child have no gradient in the reference either";
+  static constexpr bool lp_dhyp = true;   // red[NSUM] = the lp_dhyp sum
+  static Consts consts(const KernParams &kp, const int *kinds, int te, const double *expans, double bias, int mode) {
+    Consts k;
+    memset(&k, 0, sizeof(k));
+    k.kp = kp;
+    if (te >= 0) build_grad_consts(expans, k.gc);
+    k.gc.var2 = te >= 0 ? kp.term[te].var2 : 0.0;
+    k.gc.bias = bias; k.gc.mode = mode; k.gc.te = te;
+    for (int t = 0; t < GPAK_MAX_TERMS; t++) k.gc.kinds[t] = t < kp.nterms ? kinds[t] : -1;
+    return k;
+  }
+  static Consts consts(const gpak_ctx *ctx, int te) {
+    return consts(ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode);
+  }
+  static void assemble(const gpak_ctx *ctx, const double *red, double *g) {
+    gpak_grad_assemble(ctx->kp, ctx->kinds, ctx->expans, ctx->d, ctx->N, ctx->sn2, red, g);
+  }
+};
 
 // ---------------------------------------------------------------------------------------
 // The EXACT gradient of nlZ (gpak_grad_exact): d nlZ / d theta = 1/2 sum_ij W_ij dK_ij / d theta with
-// W = (K + sn2 I)^-1 - alpha alpha^T, the `qw` of the pass above.  Steps 1-2 are shared (grad_binv); the pair pass
-// below accumulates sums that do not depend on which parameter is differentiated, and the host contracts them with
-// the 3 x 3 matrices dA / d theta (gpak_grad_exact_assemble).
-// ---------------------------------------------------------------------------------------
-#define NSX 16
-// part[block][NSX], sums over i >= j with weight 2 off the diagonal:
+// W = (K + sn2 I)^-1 - alpha alpha^T, the skeleton's `qw`.  The pass accumulates sums that do not depend on which
+// parameter is differentiated, and the host contracts them with the 3 x 3 matrices dA / d theta
+// (gpak_grad_exact_assemble).  part[block][NSUM], sums over i >= j with weight 2 off the diagonal:
 //   [0] sum W   [1] trace W   [2+t] sum W e_t   [5+t] sum W e'_t d2_t for an Exp (e' = dk) or RBF (e' = e) child, on the
 //   child's OWN d2   [8..13] sum W dk D_a D_b, (a, b) = 00 01 02 11 12 22, D = x_i - x_j on the raw columns, ExpAns term
 //   [14] sum W dk D_4^2 (raw 4th column)
 // e_t = exp(-sqrt(d2_t)) or exp(-iw d2_t / 2), dk = -e / (2 sqrt(d2)) and 0 where d2 = 0 or i == j; d2_t from the
 // transformed points by differences whatever dist_mode is (a gradient has no use for the expansion's cancellation noise)
-struct ExactConsts {
-  double inv_sn2;
-  double iw[GPAK_MAX_TERMS];
-  int profile[GPAK_MAX_TERMS];
-  int nterms;
-  int te;   // index of the ExpAns term (-1: none)
-};
-
-__global__ __launch_bounds__(256) void gpak_grad_exact_pairs_f64(
-    const double *__restrict__ U, int cap, const double *__restrict__ x0, const double *__restrict__ x1,
-    const double *__restrict__ x2, const double *__restrict__ x3, const double *__restrict__ alpha,
-    const double *__restrict__ Binv, long ld, int N, ExactConsts xc, double *__restrict__ part) {
-  const int row0 = blockIdx.x * GT_ROWS, col0 = blockIdx.y * GT_COLS;
-  const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-  __shared__ double cq[GPAK_MAX_TERMS][4][GT_COLS];  // transformed column points per term: u0, u1, u2, u3 (array 4 of U)
-  __shared__ double cx[4][GT_COLS];                  // raw columns of the column points (the 4th 0 for 3-D)
-  __shared__ double cal[GT_COLS];                    // alpha of the column points
-  __shared__ double red[4][NSX];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int nterms = xc.nterms, te = xc.te;
-  double acc[NSX];
-#pragma unroll
-  for (int k = 0; k < NSX; k++) acc[k] = 0.0;
-  if (row0 + GT_ROWS > col0) {  // tile touches the lower triangle
-    if (t < GT_COLS) {
-      const int j = col0 + t;
-      const bool ok = j < N;
-      for (int m = 0; m < nterms; m++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) cq[m][c][t] = ok ? PARRG(U, cap, m, c == 3 ? 4 : c)[j] : 0.0;
-      cal[t] = ok ? alpha[j] : 0.0;
-      cx[0][t] = ok ? x0[j] : 0.0; cx[1][t] = ok ? x1[j] : 0.0; cx[2][t] = ok ? x2[j] : 0.0;
-      cx[3][t] = (ok && x3) ? x3[j] : 0.0;
-    }
-    __syncthreads();
-    const int r = row0 + 2 * lane;
-    double pu[2][GPAK_MAX_TERMS][4], px[2][4], pal[2];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int i = r + h;
-      const bool ok = i < N;
-#pragma unroll
-      for (int m = 0; m < GPAK_MAX_TERMS; m++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) pu[h][m][c] = (ok && m < nterms) ? PARRG(U, cap, m, c == 3 ? 4 : c)[i] : 0.0;
-      px[h][0] = ok ? x0[i] : 0.0; px[h][1] = ok ? x1[i] : 0.0; px[h][2] = ok ? x2[i] : 0.0;
-      px[h][3] = (ok && x3) ? x3[i] : 0.0;
-      pal[h] = ok ? alpha[i] : 0.0;
-    }
-    for (int c = 0; c < GT_COLS / 4; c++) {
-      const int jl = w + 4 * c, j = col0 + jl;
-      if (j >= N) continue;
-      const double2 q2 = *reinterpret_cast<const double2 *>(Binv + r + (size_t)j * ld);
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int i = r + h;
-        if (i >= N || i < j) continue;
-        const double q = h ? q2.y : q2.x;
-        const double qw = q * xc.inv_sn2 - pal[h] * cal[jl];
-        const double wq = (i == j) ? qw : 2.0 * qw;  // every summand is symmetric in (i, j)
-        acc[0] += wq;
-        if (i == j) acc[1] += qw;
-#pragma unroll
-        for (int m = 0; m < GPAK_MAX_TERMS; m++) {
-          if (m >= nterms) break;
-          const double a = pu[h][m][0] - cq[m][0][jl], b = pu[h][m][1] - cq[m][1][jl], cc = pu[h][m][2] - cq[m][2][jl];
-          const double e4 = pu[h][m][3] - cq[m][3][jl];
-          const double d2 = a * a + b * b + cc * cc + e4 * e4;
-          if (xc.profile[m] == GPAK_PROFILE_RBF) {
-            const double we = wq * gpak_exp_nonpos(-0.5 * xc.iw[m] * d2);
-            acc[2 + m] += we;
-            acc[5 + m] = fma(we, d2, acc[5 + m]);
-          } else {
-            const double sd = gpak_sqrt_nonneg(d2);
-            const double ek = gpak_exp_nonpos(-sd);
-            const double wdk = (sd == 0.0 || i == j) ? 0.0 : wq * ek * (-0.5 / sd);
-            acc[2 + m] = fma(wq, ek, acc[2 + m]);
-            if (m == te) {
-              const double da = px[h][0] - cx[0][jl], db = px[h][1] - cx[1][jl], dc = px[h][2] - cx[2][jl];
-              const double dr = px[h][3] - cx[3][jl];
-              const double wa = wdk * da, wb = wdk * db;
-              acc[8] = fma(wa, da, acc[8]);
-              acc[9] = fma(wa, db, acc[9]);
-              acc[10] = fma(wa, dc, acc[10]);
-              acc[11] = fma(wb, db, acc[11]);
-              acc[12] = fma(wb, dc, acc[12]);
-              acc[13] = fma(wdk * dc, dc, acc[13]);
-              acc[14] = fma(wdk * dr, dr, acc[14]);
-            } else {
-              acc[5 + m] = fma(wdk, d2, acc[5 + m]);
-            }
-          }
-        }
-      }
-    }
-  }
-  // block reduction (fixed order)
-#pragma unroll
-  for (int k = 0; k < NSX; k++) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if (lane == 0) red[w][k] = v;
-  }
-  __syncthreads();
-  if (t < NSX) part[(size_t)bid * NSX + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
-}
-
-// the gradient entries from the NSX sums; pars[t] = the raw parameters of stationary term t in the reference's order
+// ---------------------------------------------------------------------------------------
+// the gradient entries from the NSUM sums; pars[t] = the raw parameters of stationary term t in the reference's order
 // (ExpAns 8, Exp {hyp, Sigma}, RBF {hyp, iw, Sigma}); layout of g as gpak_grad_hyb: children in order, bias, sn2
 static void gpak_grad_exact_assemble(int nterms, const int *kinds, const double (*pars)[8], const double *red, double *g) {
   int go = 0;
@@ -562,7 +484,7 @@ static void gpak_grad_exact_assemble(int nterms, const int *kinds, const double 
       // D = Delta^T A^2 Delta + (a33 Delta_4)^2, A = Rot diag(lam) Rot^T:  dD/dp = Delta^T (A A_p + A_p A) Delta
       const double var2 = p[6] * p[6], lam[3] = {p[1], p[3], p[5]};
       double R[3][3], D[3][3][3], A[3][3], T[3][3];
-      rot_tables(p, R, D);
+      gpak_rot_tables(p, R, D);
       T[0][0] = red[8]; T[0][1] = T[1][0] = red[9]; T[0][2] = T[2][0] = red[10];
       T[1][1] = red[11]; T[1][2] = T[2][1] = red[12]; T[2][2] = red[13];
       for (int r = 0; r < 3; r++)
@@ -607,103 +529,146 @@ static void gpak_grad_exact_assemble(int nterms, const int *kinds, const double 
   g[go] = 0.5 * red[1];     // and sn2 on the diagonal
 }
 
-int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng) {
+struct ExactPass {
+  struct Consts {
+    double iw[GPAK_MAX_TERMS];
+    int profile[GPAK_MAX_TERMS];
+    int te;   // index of the ExpAns term (-1: none)
+  };
+  struct Col { double x[4][GT_COLS]; };   // raw columns (the 4th 0 for 3-D)
+  struct Row { double x[4]; };
+
+  static __device__ __forceinline__ void stage_col(Col &s, int t, bool ok, int j, const PairIn &in, const Consts &) {
+    s.x[0][t] = ok ? in.x0[j] : 0.0; s.x[1][t] = ok ? in.x1[j] : 0.0; s.x[2][t] = ok ? in.x2[j] : 0.0;
+    s.x[3][t] = (ok && in.x3) ? in.x3[j] : 0.0;
+  }
+  static __device__ __forceinline__ void stage_row(Row &p, bool ok, int i, const PairIn &in, const Consts &) {
+    p.x[0] = ok ? in.x0[i] : 0.0; p.x[1] = ok ? in.x1[i] : 0.0; p.x[2] = ok ? in.x2[i] : 0.0;
+    p.x[3] = (ok && in.x3) ? in.x3[i] : 0.0;
+  }
+  static __device__ __forceinline__ void pair(double (&acc)[NSUM], const double (&pu)[GPAK_MAX_TERMS][GPAK_PT],
+                                              const double (&cq)[GPAK_MAX_TERMS][GPAK_PT][GT_COLS], int jl, const Row &pr,
+                                              const Col &cp, double, double qw, bool diag, int nterms, const Consts &xc) {
+    const int te = xc.te;
+    const double wq = diag ? qw : 2.0 * qw;  // every summand is symmetric in (i, j)
+    acc[0] += wq;
+    if (diag) acc[1] += qw;
+#pragma unroll
+    for (int m = 0; m < GPAK_MAX_TERMS; m++) {
+      if (m >= nterms) break;
+      const double a = pu[m][0] - cq[m][0][jl], b = pu[m][1] - cq[m][1][jl], cc = pu[m][2] - cq[m][2][jl];
+      const double e4 = pu[m][4] - cq[m][4][jl];
+      const double d2 = a * a + b * b + cc * cc + e4 * e4;
+      if (xc.profile[m] == GPAK_PROFILE_RBF) {
+        const double we = wq * gpak_exp_nonpos(-0.5 * xc.iw[m] * d2);
+        acc[2 + m] += we;
+        acc[5 + m] = fma(we, d2, acc[5 + m]);
+      } else {
+        const double sd = gpak_sqrt_nonneg(d2);
+        const double ek = gpak_exp_nonpos(-sd);
+        const double wdk = (sd == 0.0 || diag) ? 0.0 : wq * ek * (-0.5 / sd);
+        acc[2 + m] = fma(wq, ek, acc[2 + m]);
+        if (m == te) {
+          const double da = pr.x[0] - cp.x[0][jl], db = pr.x[1] - cp.x[1][jl], dc = pr.x[2] - cp.x[2][jl];
+          const double dr = pr.x[3] - cp.x[3][jl];
+          const double wa = wdk * da, wb = wdk * db;
+          acc[8] = fma(wa, da, acc[8]);
+          acc[9] = fma(wa, db, acc[9]);
+          acc[10] = fma(wa, dc, acc[10]);
+          acc[11] = fma(wb, db, acc[11]);
+          acc[12] = fma(wb, dc, acc[12]);
+          acc[13] = fma(wdk * dc, dc, acc[13]);
+          acc[14] = fma(wdk * dr, dr, acc[14]);
+        } else {
+          acc[5 + m] = fma(wdk, d2, acc[5 + m]);
+        }
+      }
+    }
+  }
+
+  // host side of gpak_grad_exact
+  static constexpr const char *entry = "gpak_grad_exact";
+  // a context cannot tell a White child of value 0 from none, so the entry would come and go with the value
+  static constexpr const char *white = "compositions with a White child are not built";
+  static constexpr bool lp_dhyp = false;
+  static Consts consts(const gpak_ctx *ctx, int te) {
+    Consts xc;
+    memset(&xc, 0, sizeof(xc));
+    xc.te = te;
+    for (int t = 0; t < ctx->kp.nterms; t++) { xc.iw[t] = ctx->kp.term[t].iw; xc.profile[t] = ctx->kp.term[t].profile; }
+    return xc;
+  }
+  static void assemble(const gpak_ctx *ctx, const double *red, double *g) {
+    gpak_grad_exact_assemble(ctx->kp.nterms, ctx->kinds, ctx->tpars, red, g);
+  }
+};
+
+// a pair pass on `grid` and the reduction of its block partials to out[NSUM]
+template <class Pass>
+static void grad_pairs(hipStream_t st, dim3 grid, const PairIn &in, const typename Pass::Consts &pc, double *part, double *out) {
+  hipLaunchKernelGGL(gpak_grad_pairs_f64<Pass>, grid, dim3(256), 0, st, in, pc, part);
+  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(NSUM), dim3(256), 0, st, part, (int)(grid.x * grid.y), out);
+}
+
+// the single-GPU entry points: kinds of the current composition (set by gpak_set_params / gpak_set_kernel)
+template <class Pass>
+static int grad_single(gpak_ctx *ctx, double *g, int ng) {
   GPAK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int N = ctx->N, Np = ctx->Np;
+  const std::string who = std::string(Pass::entry) + ": ";
+  // expected length: children in order (8 / 2 / 3), bias, sn2
   int need = 2, te = -1;
   for (int t = 0; t < ctx->kp.nterms; t++) {
     need += ctx->kinds[t] == GPAK_KERN_EXPANS ? 8 : ctx->kinds[t] == GPAK_KERN_EXP ? 2 : 3;
     if (ctx->kinds[t] == GPAK_KERN_EXPANS) {
-      if (te >= 0) { ctx->err = "gpak_grad_exact: at most one ExpAns child"; return GPAK_ENOTIMPL; }
+      if (te >= 0) { ctx->err = who + "at most one ExpAns child"; return GPAK_ENOTIMPL; }
       te = t;
     }
   }
-  if (ng != need) { ctx->err = "gpak_grad_exact: gradient vector has the wrong length"; return GPAK_EINVAL; }
-  if (ctx->kp.white != 0.0) {
-    // a context cannot tell a White child of value 0 from none, so the entry would come and go with the value
-    ctx->err = "gpak_grad_exact: compositions with a White child are not built";
-    return GPAK_ENOTIMPL;
-  }
+  if (ng != need) { ctx->err = who + "gradient vector has the wrong length"; return GPAK_EINVAL; }
+  if (ctx->kp.white != 0.0) { ctx->err = who + Pass::white; return GPAK_ENOTIMPL; }
   int rc = grad_binv(ctx);
   if (rc) return rc;
-  ExactConsts xc;
-  memset(&xc, 0, sizeof(xc));
-  xc.inv_sn2 = 1.0 / ctx->sn2; xc.nterms = ctx->kp.nterms; xc.te = te;
-  for (int t = 0; t < ctx->kp.nterms; t++) { xc.iw[t] = ctx->kp.term[t].iw; xc.profile[t] = ctx->kp.term[t].profile; }
+  // 3. fused pair pass
+  const typename Pass::Consts pc = Pass::consts(ctx, te);
   dim3 grid(Np / GT_ROWS, Np / GT_COLS);
-  const size_t nblocks = (size_t)grid.x * grid.y;
-  rc = grad_partials(ctx, nblocks * NSX);
+  rc = grad_partials(ctx, (size_t)grid.x * grid.y * NSUM);
   if (rc) return rc;
   rc = gpak_ensure_U(ctx);
   if (rc) return rc;
-  hipLaunchKernelGGL(gpak_grad_exact_pairs_f64, grid, dim3(256), 0, st, ctx->U.base, ctx->U.cap, ctx->dX, ctx->dX + Np,
-                     ctx->dX + 2 * (size_t)Np, ctx->d == 4 ? ctx->dX + 3 * (size_t)Np : (const double *)nullptr,
-                     ctx->dAlpha, ctx->dBinv, ctx->ld, N, xc, ctx->dGpart);
-  static_assert(NSX == NSUM, "gpak_grad_reduce_f64 strides the partial sums by NSUM");
-  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(NSX), dim3(256), 0, st, ctx->dGpart, (int)nblocks, ctx->dRed + 8);
-  double red[NSX];
-  GPAK_HIP(hipMemcpyAsync(red, ctx->dRed + 8, sizeof(red), hipMemcpyDeviceToHost, st));
+  const double *X = ctx->dX;
+  const PairIn in = {ctx->U.base, ctx->U.cap, X, X + Np, X + 2 * (size_t)Np, ctx->d == 4 ? X + 3 * (size_t)Np : nullptr,
+                     ctx->dAlpha, ctx->dBinv, ctx->ld, N, ctx->kp.nterms, 1.0 / ctx->sn2, 0, 0, 0};
+  grad_pairs<Pass>(st, grid, in, pc, ctx->dGpart, ctx->dRed + 8);
+  if (Pass::lp_dhyp)
+    hipLaunchKernelGGL(gpak_lpdhyp_f64, dim3(1), dim3(1024), 0, st, N, ctx->dy, ctx->dF, ctx->sn2, ctx->dRed + 8 + NSUM);
+  double red[NSUM + 1];
+  GPAK_HIP(hipMemcpyAsync(red, ctx->dRed + 8, sizeof(double) * (NSUM + Pass::lp_dhyp), hipMemcpyDeviceToHost, st));
   GPAK_HIP(hipEventRecord(ctx->ev[3], st));
   GPAK_HIP(hipEventSynchronize(ctx->ev[3]));
   float ms = 0;
   GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[3]));
   ctx->times.grad_ms = ms;
-  gpak_grad_exact_assemble(ctx->kp.nterms, ctx->kinds, ctx->tpars, red, g);
+  Pass::assemble(ctx, red, g);
   return GPAK_OK;
 }
+int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) { return grad_single<RefPass>(ctx, g, ng); }
+int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng) { return grad_single<ExactPass>(ctx, g, ng); }
 
 // ---------------------------------------------------------------------------------------
-// The same gradient distributed over P ranks that all hold the factor as packed panels (csrc/dist.hip).
-// G = L^-T is upper triangular and its ROWS are independent right-hand sides of the blocked forward substitution
-// (the test-major scheme of predict.hip): rank a computes the rows of the 128-row blocks g = t*P + a into a compact
-// slab (rows_a x Np, leading dimension rows_a) -- N^3/(3P) flops, no communication; the slabs are all-gathered (the
-// caller's broadcasts); B^-1 rows of the same blocks = sum_k G[I,k] G[J,k] for J <= I against every rank's slab --
+// The as-written gradient distributed over P ranks that all hold the factor as packed panels (csrc/dist.hip):
+// rank a computes its rows of G = L^-T (grad_g_subst: N^3/(3P) flops, no communication); the slabs are all-gathered
+// (the caller's broadcasts); B^-1 rows of the same blocks = sum_k G[I,k] G[J,k] for J <= I against every rank's slab --
 // N^3/(3P) flops; then the pair pass on those rows and one all-reduce of the NSUM sums.
 // ---------------------------------------------------------------------------------------
-__global__ void gpak_slab_identity_f64(double *W, int rows, int Np, int P, int a) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t tot = (size_t)rows * Np;
-  if (i >= tot) return;
-  const int c = (int)(i / rows), r = (int)(i - (size_t)c * rows);
-  const int grow = ((r / PB) * P + a) * PB + (r % PB);   // global row of local row r
-  W[i] = (grow == c) ? 1.0 : 0.0;
-}
-
-void gpak_build_siginv(const double *e, double *A);   // api.hip
-
-static int my_tiles(int Np, int P, int a) { const int T = Np / PB; return T > a ? (T - a + P - 1) / P : 0; }
+static int status() { return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP; }
 
 extern "C" int gpak_dev_grad_g_rows(void *stream, int Np, int nb, int P, int a, const double *const *panels,
                                     const double *const *invs, double *slab) {
-  hipStream_t st = (hipStream_t)stream;
-  const int Ta = my_tiles(Np, P, a);
-  if (Ta == 0) return GPAK_OK;
-  const long rows = (long)Ta * PB;
-  const size_t tot = (size_t)rows * Np;
-  hipLaunchKernelGGL(gpak_slab_identity_f64, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, slab, (int)rows, Np, P, a);
-  auto tiles_upto = [&](int gblock) { return gblock >= a ? std::min(Ta, (gblock - a) / P + 1) : 0; };   // g <= gblock
-  for (int b = 0, J = 0; J < Np; b++, J += nb) {
-    const int W = std::min(nb, Np - J);
-    const long ldp = Np - J;
-    const double *panel = panels[b];
-    for (int j0 = J; j0 < J + W; j0 += PB) {
-      const int mt = tiles_upto(j0 / PB);   // rows below are still zero in L^-T
-      if (mt == 0) continue;
-      const double *inv = invs[b] + (size_t)((j0 - J) / PB) * 2 * PB * PB;
-      double *Wj = slab + (size_t)j0 * rows;
-      gpak_launch_gemm_nt(st, mt, 1, PB, 1.0, Wj, rows, inv, PB, 0.0, Wj, rows, 0, 0, false, false);
-      const int nin = (J + W - j0 - PB) / PB;
-      if (nin > 0)
-        gpak_launch_gemm_nt(st, mt, nin, PB, -1.0, Wj, rows, panel + (j0 + PB - J) + (size_t)(j0 - J) * ldp, ldp, 1.0,
-                            slab + (size_t)(j0 + PB) * rows, rows, 0, 0, false, false);
-    }
-    const int nrest = (Np - J - W) / PB, mt2 = tiles_upto((J + W) / PB - 1);
-    if (nrest > 0 && mt2 > 0)
-      gpak_launch_gemm_nt(st, mt2, nrest, W, -1.0, slab + (size_t)J * rows, rows, panel + W, ldp, 1.0,
-                          slab + (size_t)(J + W) * rows, rows, 0, 0, false, false);
-  }
-  return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP;
+  grad_g_subst((hipStream_t)stream, Np, nb, P, a, [&](int b) { return LBlockCol{panels[b], Np - (long)b * nb, invs[b]}; },
+               slab, (long)my_tiles(Np, P, a) * PB);
+  return status();
 }
 
 // binv: rows_a x (P * Tmax * 128), leading dimension rows_a; the 128-column group of global block g = u*P + b sits at
@@ -720,7 +685,16 @@ extern "C" int gpak_dev_grad_binv_rows(void *stream, int Np, int P, int a, int b
   // skipped when t < u + (b > a ? 1 : 0)
   gpak_launch_gemm_nt_k0map(st, Ta, Tb, Np, 1.0, slab_a, rows, slab_b, (long)Tb * PB, binv + (size_t)b * Tmax * PB * rows,
                             rows, b > a ? 1 : 0, P, a);
-  return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP;
+  return status();
+}
+
+// the distributed entry points know one composition: ExpAns + Bias
+static KernParams expans_kp(const double *expans, double bias, int dist_mode) {
+  KernParams kp;
+  const int kinds[GPAK_MAX_TERMS] = {GPAK_KERN_EXPANS, 0, 0};
+  gpak_build_kp(1, kinds, expans, bias, 0.0, dist_mode & 0xF, &kp, nullptr);
+  kp.d = (dist_mode & GPAK_DIST_D4) ? 4 : 3;
+  return kp;
 }
 
 // out[0..NSUM) = this rank's share of the pair sums, out[NSUM] = sum_i ((y_i - f_i)^2 / sn2 - 1) (replicated: NOT to
@@ -731,32 +705,17 @@ extern "C" int gpak_dev_grad_pairs_rows(void *stream, const double *u, int cap, 
                                         double *out) {
   hipStream_t st = (hipStream_t)stream;
   const int Ta = my_tiles(Np, P, a), Tmax = my_tiles(Np, P, 0);
-  KernParams kp;
-  memset(&kp, 0, sizeof(kp));
-  kp.nterms = 1;
-  gpak_build_siginv(expans, kp.term[0].A);
-  kp.term[0].var2 = expans[6] * expans[6];
-  kp.term[0].profile = GPAK_PROFILE_EXPSQRT;
-  const bool d4 = (dist_mode & GPAK_DIST_D4) != 0;
-  dist_mode &= 0xF;
-  kp.term[0].a33 = expans[7];
-  kp.d = d4 ? 4 : 3; kp.bias = bias; kp.mode = dist_mode;
-  GradConsts gc;
-  memset(&gc, 0, sizeof(gc));
-  build_grad_consts(expans, gc);
-  gc.var2 = kp.term[0].var2; gc.bias = bias; gc.sn2 = sn2; gc.mode = dist_mode; gc.te = 0;
-  gc.kinds[0] = GPAK_KERN_EXPANS; gc.kinds[1] = gc.kinds[2] = -1;
+  const KernParams kp = expans_kp(expans, bias, dist_mode);
+  const int kinds[GPAK_MAX_TERMS] = {GPAK_KERN_EXPANS, 0, 0};
+  const RefPass::Consts pc = RefPass::consts(kp, kinds, 0, expans, bias, kp.mode);
   hipMemsetAsync(out, 0, sizeof(double) * (NSUM + 1), st);
   if (Ta > 0) {
-    dim3 grid(Ta, Np / GT_COLS);
-    const int nblocks = (int)(grid.x * grid.y);
-    hipLaunchKernelGGL(gpak_grad_pairs_f64, grid, dim3(256), 0, st, u, cap, x_soa, x_soa + xs, x_soa + 2 * (size_t)xs,
-                       d4 ? x_soa + 3 * (size_t)xs : (const double *)nullptr, alpha, binv, (long)Ta * PB, n, kp, gc, part, P, a,
-                       Tmax);
-    hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(NSUM), dim3(256), 0, st, part, nblocks, out);
+    const PairIn in = {u, cap, x_soa, x_soa + xs, x_soa + 2 * (size_t)xs, kp.d == 4 ? x_soa + 3 * (size_t)xs : nullptr,
+                       alpha, binv, (long)Ta * PB, n, 1, 1.0 / sn2, P, a, Tmax};
+    grad_pairs<RefPass>(st, dim3(Ta, Np / GT_COLS), in, pc, part, out);
   }
   hipLaunchKernelGGL(gpak_lpdhyp_f64, dim3(1), dim3(1024), 0, st, n, y, f, sn2, out + NSUM);
-  return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP;
+  return status();
 }
 
 // the constants of the pair pass (M_p = S % S_p as {00,01,02,11,12,22}, and 2 * its column sums): exported so that a
@@ -773,11 +732,7 @@ extern "C" int gpak_dev_grad_consts(const double *expans, double *M36, double *m
 // host side of the distributed gradient: g[10] from the all-reduced sums
 extern "C" int gpak_dev_grad_finish_d(const double *expans, double bias, double sn2, int n, int d, const double *red,
                                       double *g) {
-  KernParams kp;
-  memset(&kp, 0, sizeof(kp));
-  kp.nterms = 1;
-  kp.term[0].var2 = expans[6] * expans[6];
-  kp.bias = bias;
+  const KernParams kp = expans_kp(expans, bias, GPAK_DIST_DIRECT);
   const int kinds[GPAK_MAX_TERMS] = {GPAK_KERN_EXPANS, 0, 0};
   gpak_grad_assemble(kp, kinds, expans, d == 4 ? 4 : 3, n, sn2, red, g);
   return GPAK_OK;

@@ -42,22 +42,6 @@ void gpak_launch_transform(hipStream_t st, const double *x, int xs, int n, const
   out.n = n;
 }
 
-// D2 (Kernel.cpp:1431-1434 / :1365-1367, or the cancellation-free equivalent)
-__device__ __forceinline__ double gpak_d2(double p0, double p1, double p2, double ps, double p3, double q0,
-                                          double q1, double q2, double qs, double q3, int mode) {
-  if (mode == GPAK_DIST_DIRECT) {
-    double a = p0 - q0, b = p1 - q1, c = p2 - q2, e = p3 - q3;
-    return a * a + b * b + c * c + e * e;  // e == 0 for 3-D inputs: the value is unchanged bit for bit
-  }
-  double dot = p0 * q0 + p1 * q1 + p2 * q2 + p3 * q3;
-  double v = ps + qs - 2.0 * dot;
-  return v < 0.0 ? 0.0 : v;
-}
-// var2 * profile(D2): Kernel.cpp:881 (ExpAns / Exp), :487 (RBF)
-__device__ __forceinline__ double gpak_profile(double d2, const KernTerm &t) {
-  return t.var2 * gpak_exp_nonpos(t.profile == GPAK_PROFILE_RBF ? -0.5 * t.iw * d2 : -gpak_sqrt_nonneg(d2));
-}
-
 // ---------------------------------------------------------------------------------------
 // Tile fill.  One workgroup = 128 rows x 64 columns; a wave writes 128 consecutive rows
 // of one column per store (1 KiB, 16 B per lane).

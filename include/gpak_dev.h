@@ -13,12 +13,14 @@
  * Np = N rounded up to 128, padded rows/columns form an identity block.
  * Every function returns GPAK_OK or a negative HIP status.  The functions that check their arguments -- gpak_dev_pack,
  * gpak_dev_trsv_bwd_packed, gpak_dev_diag_inverse, gpak_dev_fill_rect, gpak_dev_solve_rows, gpak_dev_update_rect,
- * gpak_dev_gemv_n_add, gpak_dev_transform_k (an unusable composition), gpak_dev_stream_create -- return GPAK_EINVAL for
+ * gpak_dev_gemv_n_add, gpak_dev_grad_binv_rows (a rank outside 0 .. P-1), gpak_dev_transform_k (an unusable composition),
+ * gpak_dev_stream_create -- return GPAK_EINVAL for
  * what their descriptions rule out (a width that is no multiple of 128 or above the stated limit, an odd count where
  * 16-byte accesses need an even one) and write nothing then; the others trust the caller.  A call with nothing to do (no rows, no columns) writes nothing.  A call
  * writes only the elements named in its description: never the rows between Np (or nrows) and the leading dimension,
  * never a 128 x 128 tile above the diagonal where "lower tiles" is said.  tests/test_dev_ops.py holds the entry points
- * to that one at a time, except gpak_dev_stream_create / gpak_dev_stream_destroy and the gpak_dev_grad_* family.
+ * to that one at a time, except gpak_dev_stream_create / gpak_dev_stream_destroy and the pair pass of the distributed
+ * gradient (gpak_dev_grad_pairs_rows, gpak_dev_grad_consts, gpak_dev_grad_finish / _finish_d).
  */
 #ifndef GPAK_DEV_H
 #define GPAK_DEV_H

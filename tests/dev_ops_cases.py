@@ -9,7 +9,8 @@ hands back, per output buffer: what came back, a reference in np.longdouble, an 
 must come back bit-identical (everything the operation has no business writing).
 
 Every checked buffer carries a guard band of 256 doubles on either side and every leading dimension is skewed
-(ld = rows + 32, 34, 36 ...: never equal to the row count or to each other); guard bands and skew rows hold a
+(ld = rows + 32, 34, 36 ...: never equal to the row count or to each other; the `grad` group's packed panels and slabs
+have the leading dimension their interface fixes); guard bands and skew rows hold a
 sentinel bit pattern (a NaN with a payload) and belong to the bit-identical set.  Operands are dense standard_normal
 unless the case says otherwise: not kernel matrices, so a permuted fragment or a wrong tile is an O(1) error.
 
@@ -17,7 +18,7 @@ Bounds (u = 2^-53):
   * products and sums: (n + 2) u sum|terms| -- holds for ANY order of accumulation, fused or not;
   * logdiag adds 4 u sum|log L_cc| for the device's log;
   * fill / Gram mat-vec: the tolerances of test_gram_matches_oracle against the CPU oracle, scaled by 1/sn2;
-  * substitutions (trsv_*, solve_rows, diag_inverse) multiply by explicit inverses of 128 x 128 blocks, so no clean
+  * substitutions (trsv_*, solve_rows, diag_inverse, grad_g_rows) multiply by explicit inverses of 128 x 128 blocks, so no clean
     forward bound exists: 8 x the largest error of NumpyOps (the float64 restatement of the same blocked algorithm, run
     on the same inputs, the device's own factor included) against the long-double solution, elementwise relative to
     |L^-1| |b| in long double.  The 8 covers another accumulation order in an algorithm with the same first-order error.
@@ -49,7 +50,7 @@ SENTINEL = np.uint64(0x7FF8A5A5DEADBEEF)     # a quiet NaN with a payload: arith
 OK, EINVAL = 0, 2
 INT_MAX = 0x7FFFFFFF
 D4, HYB = 0x10, 0x20
-GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill")
+GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill", "grad")
 
 
 def long_double_ok():
@@ -202,14 +203,15 @@ def rng_for(name):
 # ------------------------------------------------------------------------------------------------
 # the two adaptors
 # ------------------------------------------------------------------------------------------------
-# arguments of gpak_dev_<name> after the stream: p device pointer, i int, l long, d double, h host double array
+# arguments of gpak_dev_<name> after the stream: p device pointer, i int, l long, d double, h host double array,
+# P host array of device pointers (a list here)
 SIG = {
     "transform": "piiihhp", "transform_k": "piiihihp", "fill_b": "piiiiihddipl", "fill_rect": "piiiiiihddipl",
     "factor_panel": "pliiipp", "factor_panel_co": "pliiippi", "update_block": "pliipliii", "update_cyclic": "pliipliiiiiii",
     "update_rect": "plplipliii", "solve_rows": "pliiplp", "trsv_fwd_block": "pliiippp", "coldot": "pliiipp",
     "trsv_bwd_block": "pliippp", "trsv_bwd_packed": "pliiiippppp", "diag_inverse": "pliiipp", "logdiag_block": "pliiip",
     "kmatvec": "piiiiphdipp", "nlz_terms": "ipppdp", "pack": "pliiip", "gemv_n_add": "pliipp", "gemv_t": "pliipp",
-    "vec_axpy": "idpp", "vec_scale": "ipdp", "vec_sum": "ipp",
+    "vec_axpy": "idpp", "vec_scale": "ipdp", "vec_sum": "ipp", "grad_g_rows": "iiiiPPp", "grad_binv_rows": "iiiippp",
 }
 
 
@@ -249,6 +251,9 @@ def precheck(name, a):
         return EINVAL if W > 512 else None
     if name == "gemv_t":
         return OK if a[3] <= 0 else None
+    if name == "grad_binv_rows":
+        P, ra, rb = a[1], a[2], a[3]
+        return EINVAL if ra < 0 or ra >= P or rb < 0 or rb >= P else None
     if name == "update_cyclic":
         nb, lb0, n_local, last_width = a[7], a[10], a[11], a[12]
         return OK if (n_local - 1) * (nb // TILE) + last_width // TILE - lb0 * (nb // TILE) <= 0 else None
@@ -301,6 +306,8 @@ class NumpyOps:
         for kind, v in zip(SIG[name], a):
             if kind == "p":
                 conv.append(self._ptr(v))
+            elif kind == "P":
+                conv.append((C.c_void_p * len(v))(*[self._ptr(x) for x in v]))
             elif kind == "h":
                 conv.append((C.c_double * len(v))(*[float(t) for t in v]))
             else:
@@ -312,7 +319,7 @@ class HipOps:
     """libgpak_hip.so on the device: HipEngine for the library, the device and the stream; every call uploads its
     arrays, runs, synchronises and downloads them again (guard bands included)."""
     name = "hip"
-    _ct = {"p": C.c_void_p, "i": C.c_int, "l": C.c_long, "d": C.c_double, "h": C.POINTER(C.c_double)}
+    _ct = {"p": C.c_void_p, "i": C.c_int, "l": C.c_long, "d": C.c_double, "h": C.POINTER(C.c_double), "P": C.POINTER(C.c_void_p)}
 
     def __init__(self):
         from py_schedule import HipEngine
@@ -325,15 +332,18 @@ class HipOps:
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p] + [self._ct[k] for k in SIG[name]]
         dev, conv, keep = {}, [], []
+
+        def ptr(v):
+            if id(v) not in dev:
+                dev[id(v)] = (v, self.eng.from_numpy(_buf(v)))
+            return dev[id(v)][1].data_ptr() + (8 * GUARD if isinstance(v, Mat) else 0)
+
         for kind, v in zip(SIG[name], a):
             if kind == "p":
-                if v is None:
-                    conv.append(None)
-                    continue
-                if id(v) not in dev:
-                    dev[id(v)] = (v, self.eng.from_numpy(_buf(v)))
-                t = dev[id(v)][1]
-                conv.append(t.data_ptr() + (8 * GUARD if isinstance(v, Mat) else 0))
+                conv.append(None if v is None else ptr(v))
+            elif kind == "P":
+                keep.append((C.c_void_p * len(v))(*[ptr(x) for x in v]))
+                conv.append(keep[-1])
             elif kind == "h":
                 keep.append((C.c_double * len(v))(*[float(t) for t in v]))
                 conv.append(keep[-1])
@@ -767,6 +777,133 @@ for _s in TRSV_SHAPES:
     for _N in (_s[0] - 5, _s[1] + 70, _s[1]):
         case("trsv", "logdiag_block" + _t + f"[N={_N}]", ["gpak_dev_logdiag_block"], shape=_s, N=_N)(_logdiag)
     case("trsv", "pack" + _t, ["gpak_dev_pack"], shape=_s)(_pack)
+
+
+# ---- the two linear-algebra operations of the distributed gradient ----------------------------------------
+# (gpak_dev_grad_pairs_rows / _consts / _finish stay under the distributed-gradient tests: no bound of this file's kind
+# exists for the pair sums.)  The interface fixes every leading dimension here (a packed panel has Np - J, a slab and
+# binv have rows_a), so these buffers have guard bands but no skew rows.
+def grad_tiles(Np, P, a):
+    T = Np // TILE
+    return (T - a + P - 1) // P if T > a else 0
+
+
+def grad_rows(Np, P, a):
+    """global rows of the 128-row blocks g = t P + a, in slab order"""
+    return (np.arange(grad_tiles(Np, P, a))[:, None] * P * TILE + a * TILE + np.arange(TILE)[None, :]).ravel()
+
+
+class Factor:
+    """A whole lower-triangular factor of order Np as block columns of nb: each the Panel of the trsv cases (diagonal
+    block factored by the engine under test, dense rows below), with L^-1 in long double."""
+
+    def __init__(self, ops, Np, nb):
+        self.Np, self.nb = Np, nb
+        self.cols = [Panel(ops, Np, J, min(nb, Np - J)) for J in range(0, Np, nb)]
+        self.L = np.zeros((Np, Np))
+        for p in self.cols:
+            self.L[p.J:p.J + p.W, p.J:p.J + p.W] = p.L
+            self.L[p.J + p.W:, p.J:p.J + p.W] = p.below
+        self.Li = tri_inv_ld(self.L)
+
+    def panels(self):
+        return [Mat(p.col[p.J:]) for p in self.cols]        # packed: leading dimension Np - J
+
+    def invs(self):
+        return [Mat(p.inv) for p in self.cols]
+
+
+def factor_for(ops, Np, nb):
+    return memo(("factor_full", ops.name, Np, nb), lambda: Factor(ops, Np, nb))
+
+
+def numpy_g_rows(f, P, a):
+    """csrc/grad.hip's blocked forward substitution on identity rows in float64: per block column, 128-column steps
+    W_j := W_j inv(D_j)^T, W[:, j+1..] -= W_j L[j+1.., j]^T inside it, then one update of everything to the right; a row
+    block takes part from the step of its own diagonal block on."""
+    Np, nb, Ta, rows = f.Np, f.nb, grad_tiles(f.Np, P, a), grad_rows(f.Np, P, a)
+    S = np.zeros((len(rows), Np))
+    S[np.arange(len(rows)), rows] = 1.0
+    upto = lambda g: min(Ta, (g - a) // P + 1) * TILE if g >= a else 0
+    for p in f.cols:
+        J, W = p.J, p.W
+        iv = p.inv.reshape(W // TILE, 2, TILE, TILE)
+        for j0 in range(J, J + W, TILE):
+            m, c = upto(j0 // TILE), slice(j0, j0 + TILE)
+            if m:
+                S[:m, c] = S[:m, c] @ iv[(j0 - J) // TILE, 0]
+                S[:m, j0 + TILE:J + W] -= S[:m, c] @ f.L[j0 + TILE:J + W, c].T
+        m = upto((J + W) // TILE - 1)
+        if m and J + W < Np:
+            S[:m, J + W:] -= S[:m, J:J + W] @ f.L[J + W:, J:J + W].T
+    return S
+
+
+def _grad_g_rows(ops, name, Np, nb, P, a):
+    f = factor_for(ops, Np, nb)
+    rows = grad_rows(Np, P, a)
+    panels, invs = f.panels(), f.invs()
+    slab = Mat(rng_for(name).standard_normal((max(len(rows), TILE), Np)))
+    res = Result().rc("grad_g_rows", ops.call("grad_g_rows", Np, nb, P, a, panels, invs, slab))
+    for k, (pn, iv) in enumerate(zip(panels, invs)):
+        res.add(f"panel{k}", pn).add(f"inv{k}", iv)
+    if not len(rows):
+        return res.add("slab", slab)                          # no tiles: nothing is written
+    # rows of L^-T = columns of L^-1; |L^-1| |e_i| = |L^-1|: exact zeros left of the diagonal, so the bound is 0 there
+    ref = f.Li[:, rows].T
+    bound = subst_bound(res, "slab", numpy_g_rows(f, P, a), ref, np.abs(ref).astype(np.float64))
+    return res.add("slab", slab, ref, bound, True)
+
+
+for _a in (0, 1, 2):
+    case("grad", f"grad_g_rows[Np=640,nb=256,P=3,a={_a}]", ["gpak_dev_grad_g_rows", "gpak_dev_factor_panel_co"], Np=640, nb=256,
+         P=3, a=_a)(_grad_g_rows)
+case("grad", "grad_g_rows[Np=640,nb=512,P=1,a=0]", ["gpak_dev_grad_g_rows"], Np=640, nb=512, P=1, a=0)(_grad_g_rows)
+case("grad", "grad_g_rows[Np=128,nb=128,P=2,a=1]->no-op", ["gpak_dev_grad_g_rows"], Np=128, nb=128, P=2, a=1)(_grad_g_rows)
+
+
+def grad_slab(ops, Np, nb, P, a):
+    """rank a's rows of L^-T from the engine under test (checked by the cases above)"""
+    def make():
+        f = factor_for(ops, Np, nb)
+        slab = Mat(np.zeros((grad_tiles(Np, P, a) * TILE, Np)))
+        assert ops.call("grad_g_rows", Np, nb, P, a, f.panels(), f.invs(), slab) == OK and slab.guards_ok()
+        return slab.get().copy()
+    return memo(("grad_slab", ops.name, Np, nb, P, a), make)
+
+
+def _grad_binv_rows(ops, name, a, b, want=OK, Np=640, nb=256, P=3):
+    Tmax, Ta = grad_tiles(Np, P, 0), grad_tiles(Np, P, a)
+    Sa = Mat(grad_slab(ops, Np, nb, P, a))
+    Sb = Sa if b == a else Mat(grad_slab(ops, Np, nb, P, b % P))      # the same pointer when b == a (gpak_dev.h)
+    binv = Mat(rng_for(name).standard_normal((Ta * TILE, P * Tmax * TILE)))
+    res = Result().rc("grad_binv_rows", ops.call("grad_binv_rows", Np, P, a, b, Sa, Sb, binv), want)
+    res.add("slab_a", Sa)
+    if Sb is not Sa:
+        res.add("slab_b", Sb)
+    if want != OK:
+        return res.add("binv", binv)
+    # tile (t, u) of column group b Tmax + u <- rows t of slab_a times rows u of slab_b, where u P + b <= t P + a
+    Tb = grad_tiles(Np, P, b)
+    need = np.zeros((Ta, P * Tmax), dtype=bool)
+    mine = np.zeros((Ta, P * Tmax), dtype=bool)
+    for u in range(Tb):
+        mine[:, b * Tmax + u] = True
+        need[:, b * Tmax + u] = u * P + b <= np.arange(Ta) * P + a
+    ref, bound = np.zeros(binv.get().shape, dtype=LD), np.zeros(binv.get().shape)
+    cols = slice(b * Tmax * TILE, (b * Tmax + Tb) * TILE)
+    ref[:, cols] = mm_ld(Sa.was(), Sb.was())
+    bound[:, cols] = (Np + 2) * U * (np.abs(Sa.was()) @ np.abs(Sb.was()).T)
+    # the tiles of rank b that are NOT needed come back bit-identical from the device; the float64 restatement
+    # (np_dist_engine.py) writes the whole product there, so they are free on that engine and on that engine only
+    free = tile_rows(mine & ~need) if ops.name == "numpy" else None
+    return res.add("binv", binv, ref, bound, tile_rows(need), free=free)
+
+
+for _a, _b in ((0, 0), (0, 2), (2, 0), (1, 1)):
+    case("grad", f"grad_binv_rows[Np=640,P=3,a={_a},b={_b}]", ["gpak_dev_grad_binv_rows", "gpak_dev_grad_g_rows"], a=_a,
+         b=_b)(_grad_binv_rows)
+case("grad", "grad_binv_rows[Np=640,P=3,a=1,b=3]->EINVAL", ["gpak_dev_grad_binv_rows"], a=1, b=3, want=EINVAL)(_grad_binv_rows)
 
 
 # ---- matrix-vector products and reductions ---------------------------------------------------------------
