@@ -454,9 +454,6 @@ struct RefPass {
     for (int t = 0; t < GPAK_MAX_TERMS; t++) k.gc.kinds[t] = t < kp.nterms ? kinds[t] : -1;
     return k;
   }
-  static Consts consts(const gpak_ctx *ctx, int te) {
-    return consts(ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode);
-  }
   static void assemble(const gpak_ctx *ctx, const double *red, double *g) {
     gpak_grad_assemble(ctx->kp, ctx->kinds, ctx->expans, ctx->d, ctx->N, ctx->sn2, red, g);
   }
@@ -591,11 +588,11 @@ struct ExactPass {
   // a context cannot tell a White child of value 0 from none, so the entry would come and go with the value
   static constexpr const char *white = "compositions with a White child are not built";
   static constexpr bool lp_dhyp = false;
-  static Consts consts(const gpak_ctx *ctx, int te) {
+  static Consts consts(const KernParams &kp, const int *, int te, const double *, double, int) {
     Consts xc;
     memset(&xc, 0, sizeof(xc));
     xc.te = te;
-    for (int t = 0; t < ctx->kp.nterms; t++) { xc.iw[t] = ctx->kp.term[t].iw; xc.profile[t] = ctx->kp.term[t].profile; }
+    for (int t = 0; t < kp.nterms; t++) { xc.iw[t] = kp.term[t].iw; xc.profile[t] = kp.term[t].profile; }
     return xc;
   }
   static void assemble(const gpak_ctx *ctx, const double *red, double *g) {
@@ -603,9 +600,21 @@ struct ExactPass {
   }
 };
 
-// a pair pass on `grid` and the reduction of its block partials to out[NSUM]
+// One pair pass on caller-owned buffers and the reduction of its block partials to out[NSUM]: what every entry point
+// launches.  P == 0: B^-1 is Np x Np with leading dimension ld (the single-GPU layout, rowP = 0); P >= 1: rank a's row
+// blocks as gpak_dev_grad_binv_rows leaves them (ld is then rows_a, whatever is passed); a rank without tiles launches
+// nothing.  x_soa: the raw columns with stride xs, the 4th read only when d == 4.  te: index of the ExpAns child (-1: none),
+// expans: its eight parameters.
 template <class Pass>
-static void grad_pairs(hipStream_t st, dim3 grid, const PairIn &in, const typename Pass::Consts &pc, double *part, double *out) {
+static void pair_sums(hipStream_t st, const KernParams &kp, const int *kinds, int te, const double *expans, double bias,
+                      int mode, int d, const double *u, int cap, const double *x_soa, int xs, int n, int Np,
+                      const double *alpha, const double *binv, long ld, int P, int a, double sn2, double *part, double *out) {
+  const int Ta = P ? my_tiles(Np, P, a) : Np / GT_ROWS;
+  if (Ta == 0) return;
+  const typename Pass::Consts pc = Pass::consts(kp, kinds, te, expans, bias, mode);
+  const PairIn in = {u, cap, x_soa, x_soa + xs, x_soa + 2 * (size_t)xs, d == 4 ? x_soa + 3 * (size_t)xs : nullptr,
+                     alpha, binv, P ? (long)Ta * PB : ld, n, kp.nterms, 1.0 / sn2, P, P ? a : 0, P ? my_tiles(Np, P, 0) : 0};
+  const dim3 grid(Ta, Np / GT_COLS);
   hipLaunchKernelGGL(gpak_grad_pairs_f64<Pass>, grid, dim3(256), 0, st, in, pc, part);
   hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(NSUM), dim3(256), 0, st, part, (int)(grid.x * grid.y), out);
 }
@@ -631,16 +640,12 @@ static int grad_single(gpak_ctx *ctx, double *g, int ng) {
   int rc = grad_binv(ctx);
   if (rc) return rc;
   // 3. fused pair pass
-  const typename Pass::Consts pc = Pass::consts(ctx, te);
-  dim3 grid(Np / GT_ROWS, Np / GT_COLS);
-  rc = grad_partials(ctx, (size_t)grid.x * grid.y * NSUM);
+  rc = grad_partials(ctx, (size_t)(Np / GT_ROWS) * (Np / GT_COLS) * NSUM);
   if (rc) return rc;
   rc = gpak_ensure_U(ctx);
   if (rc) return rc;
-  const double *X = ctx->dX;
-  const PairIn in = {ctx->U.base, ctx->U.cap, X, X + Np, X + 2 * (size_t)Np, ctx->d == 4 ? X + 3 * (size_t)Np : nullptr,
-                     ctx->dAlpha, ctx->dBinv, ctx->ld, N, ctx->kp.nterms, 1.0 / ctx->sn2, 0, 0, 0};
-  grad_pairs<Pass>(st, grid, in, pc, ctx->dGpart, ctx->dRed + 8);
+  pair_sums<Pass>(st, ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode, ctx->d, ctx->U.base, ctx->U.cap, ctx->dX,
+                  Np, N, Np, ctx->dAlpha, ctx->dBinv, ctx->ld, 0, 0, ctx->sn2, ctx->dGpart, ctx->dRed + 8);
   if (Pass::lp_dhyp)
     hipLaunchKernelGGL(gpak_lpdhyp_f64, dim3(1), dim3(1024), 0, st, N, ctx->dy, ctx->dF, ctx->sn2, ctx->dRed + 8 + NSUM);
   double red[NSUM + 1];
@@ -697,24 +702,54 @@ static KernParams expans_kp(const double *expans, double bias, int dist_mode) {
   return kp;
 }
 
-// out[0..NSUM) = this rank's share of the pair sums, out[NSUM] = sum_i ((y_i - f_i)^2 / sn2 - 1) (replicated: NOT to
-// be all-reduced); part: Ta * (Np / 64) * NSUM doubles of scratch
+// Either pass alone on caller-owned buffers (gpak_dev.h): out16[0..NSUM) = the sums of rank a's row blocks (P >= 1), or
+// of the whole lower triangle (P == 0); part: Ta * (Np / 64) * NSUM doubles of scratch.  `kern` as gpak_dev_transform_k.
+extern "C" int gpak_dev_grad_pair_sums(void *stream, int pass, const double *u, int cap, const double *x_soa, int xs, int n,
+                                       int Np, const double *alpha, const double *binv, long ld, int P, int a,
+                                       const double *kern, double bias, double sn2, int dist_mode, double *part,
+                                       double *out16) {
+  hipStream_t st = (hipStream_t)stream;
+  if (pass != 0 && pass != 1) return GPAK_EINVAL;
+  if (P < 0 || (P > 0 && (a < 0 || a >= P)) || (P == 0 && (ld & 1))) return GPAK_EINVAL;
+  const bool hyb = dist_mode & GPAK_DIST_HYB;
+  int kinds[GPAK_MAX_TERMS] = {GPAK_KERN_EXPANS, 0, 0};
+  for (int t = 0; hyb && t < GPAK_MAX_TERMS; t++) kinds[t] = (int)kern[1 + t];
+  KernParams kp;
+  if (gpak_build_kp(hyb ? (int)kern[0] : 1, kinds, hyb ? kern + 5 : kern, bias, hyb ? kern[4] : 0.0, dist_mode & 0xF, &kp,
+                    nullptr) != GPAK_OK)
+    return GPAK_EINVAL;
+  kp.d = (dist_mode & GPAK_DIST_D4) ? 4 : 3;
+  if (kp.white != 0.0) return GPAK_EINVAL;
+  int te = -1;
+  const double *expans = nullptr, *p = hyb ? kern + 5 : kern;
+  for (int t = 0; t < kp.nterms; t++) {
+    if (kinds[t] == GPAK_KERN_EXPANS) {
+      if (te >= 0) return GPAK_EINVAL;
+      te = t; expans = p;
+    }
+    p += kinds[t] == GPAK_KERN_EXPANS ? 8 : kinds[t] == GPAK_KERN_EXP ? 2 : 3;
+  }
+  hipMemsetAsync(out16, 0, sizeof(double) * NSUM, st);
+  if (pass == 0)
+    pair_sums<RefPass>(st, kp, kinds, te, expans, bias, kp.mode, kp.d, u, cap, x_soa, xs, n, Np, alpha, binv, ld, P, a, sn2,
+                       part, out16);
+  else
+    pair_sums<ExactPass>(st, kp, kinds, te, expans, bias, kp.mode, kp.d, u, cap, x_soa, xs, n, Np, alpha, binv, ld, P, a, sn2,
+                         part, out16);
+  return status();
+}
+
+// out[0..NSUM) = this rank's share of the as-written pair sums, out[NSUM] = sum_i ((y_i - f_i)^2 / sn2 - 1) (replicated:
+// NOT to be all-reduced); the distributed entry points know one composition: ExpAns + Bias
 extern "C" int gpak_dev_grad_pairs_rows(void *stream, const double *u, int cap, const double *x_soa, int xs, int n, int Np,
                                         const double *y, const double *f, const double *alpha, const double *binv, int P,
                                         int a, const double *expans, double bias, double sn2, int dist_mode, double *part,
                                         double *out) {
-  hipStream_t st = (hipStream_t)stream;
-  const int Ta = my_tiles(Np, P, a), Tmax = my_tiles(Np, P, 0);
-  const KernParams kp = expans_kp(expans, bias, dist_mode);
-  const int kinds[GPAK_MAX_TERMS] = {GPAK_KERN_EXPANS, 0, 0};
-  const RefPass::Consts pc = RefPass::consts(kp, kinds, 0, expans, bias, kp.mode);
-  hipMemsetAsync(out, 0, sizeof(double) * (NSUM + 1), st);
-  if (Ta > 0) {
-    const PairIn in = {u, cap, x_soa, x_soa + xs, x_soa + 2 * (size_t)xs, kp.d == 4 ? x_soa + 3 * (size_t)xs : nullptr,
-                       alpha, binv, (long)Ta * PB, n, 1, 1.0 / sn2, P, a, Tmax};
-    grad_pairs<RefPass>(st, dim3(Ta, Np / GT_COLS), in, pc, part, out);
-  }
-  hipLaunchKernelGGL(gpak_lpdhyp_f64, dim3(1), dim3(1024), 0, st, n, y, f, sn2, out + NSUM);
+  if (P < 1) return GPAK_EINVAL;
+  const int rc = gpak_dev_grad_pair_sums(stream, 0, u, cap, x_soa, xs, n, Np, alpha, binv, 0, P, a, expans, bias, sn2,
+                                         dist_mode & ~GPAK_DIST_HYB, part, out);
+  if (rc != GPAK_OK) return rc;
+  hipLaunchKernelGGL(gpak_lpdhyp_f64, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, y, f, sn2, out + NSUM);
   return status();
 }
 

@@ -13,14 +13,14 @@
  * Np = N rounded up to 128, padded rows/columns form an identity block.
  * Every function returns GPAK_OK or a negative HIP status.  The functions that check their arguments -- gpak_dev_pack,
  * gpak_dev_trsv_bwd_packed, gpak_dev_diag_inverse, gpak_dev_fill_rect, gpak_dev_solve_rows, gpak_dev_update_rect,
- * gpak_dev_gemv_n_add, gpak_dev_grad_binv_rows (a rank outside 0 .. P-1), gpak_dev_transform_k (an unusable composition),
+ * gpak_dev_gemv_n_add, gpak_dev_grad_binv_rows and gpak_dev_grad_pairs_rows (a rank outside 0 .. P-1), gpak_dev_grad_pair_sums,
+ * gpak_dev_transform_k (an unusable composition),
  * gpak_dev_stream_create -- return GPAK_EINVAL for
  * what their descriptions rule out (a width that is no multiple of 128 or above the stated limit, an odd count where
  * 16-byte accesses need an even one) and write nothing then; the others trust the caller.  A call with nothing to do (no rows, no columns) writes nothing.  A call
  * writes only the elements named in its description: never the rows between Np (or nrows) and the leading dimension,
  * never a 128 x 128 tile above the diagonal where "lower tiles" is said.  tests/test_dev_ops.py holds the entry points
- * to that one at a time, except gpak_dev_stream_create / gpak_dev_stream_destroy and the pair pass of the distributed
- * gradient (gpak_dev_grad_pairs_rows, gpak_dev_grad_consts, gpak_dev_grad_finish / _finish_d).
+ * to that one at a time, except gpak_dev_stream_create / gpak_dev_stream_destroy.
  */
 #ifndef GPAK_DEV_H
 #define GPAK_DEV_H
@@ -128,7 +128,8 @@ int gpak_dev_pack(void *stream, const double *src, long ld, int row0, int nrows,
  *   the 128-column group of global block g sits at group index (g % P) * Tmax + g / P.  One call per source rank, so a
  *   caller holds its own slab and the one passing through, never all P.
  * gpak_dev_grad_pairs_rows: out[0..16) <- this rank's share of the pair sums (to be all-reduced), out[16] <- the
- *   replicated lp_dhyp sum; part = scratch of rows_a/128 * Np/64 * 16 doubles.
+ *   replicated lp_dhyp sum; part = scratch of rows_a/128 * Np/64 * 16 doubles.  It is gpak_dev_grad_pair_sums(pass 0)
+ *   for ExpAns + Bias plus that sum.
  * gpak_dev_grad_finish (host only): g[10] = {8 ExpAns, bias, sn2} from the all-reduced sums. */
 int gpak_dev_grad_g_rows(void *stream, int Np, int nb, int P, int a, const double *const *panels,
                          const double *const *invs, double *slab);
@@ -137,6 +138,17 @@ int gpak_dev_grad_binv_rows(void *stream, int Np, int P, int a, int b, const dou
 int gpak_dev_grad_pairs_rows(void *stream, const double *u, int cap, const double *x_soa, int xs, int n, int Np,
                              const double *y, const double *f, const double *alpha, const double *binv, int P, int a,
                              const double *expans, double bias, double sn2, int dist_mode, double *part, double *out);
+/* Either pair pass ALONE on caller-owned buffers: out16[0..16) <- the 16 sums of pass 0 (as written: the layout above
+ * RefPass in csrc/grad.hip) or 1 (exact: above ExactPass) over the pairs i >= j, j < n.  P == 0: binv is the whole Np x Np
+ * B^-1 (lower part) with leading dimension ld (even), `a` is ignored; P >= 1: the row blocks of rank a as
+ * gpak_dev_grad_binv_rows leaves them, ld is ignored.  Only elements (i, j) with j <= i < n of B^-1 are used.  kern /
+ * dist_mode as gpak_dev_transform_k (u from that call); x_soa: the four raw columns, stride xs; part = scratch of
+ * (rows / 128) * (Np / 64) * 16 doubles, rows = Np or rows_a.  A rank that owns no row block gets out16 = 0 and leaves
+ * part alone.  GPAK_EINVAL, nothing written: a pass other than 0 / 1, a outside 0 .. P-1, an odd ld, a composition
+ * gpak_build_kp refuses, two ExpAns children, Sigma_White != 0 (no gradient exists for either: csrc/grad.hip). */
+int gpak_dev_grad_pair_sums(void *stream, int pass, const double *u, int cap, const double *x_soa, int xs, int n, int Np,
+                            const double *alpha, const double *binv, long ld, int P, int a, const double *kern,
+                            double bias, double sn2, int dist_mode, double *part, double *out16);
 int gpak_dev_grad_finish(const double *expans, double bias, double sn2, int n, const double *red, double *g);
 /* the same for d input columns (3 or 4): with a rock-type column g[7] is the InversewidthR slot (Kernel.cpp:1246-1255) */
 int gpak_dev_grad_finish_d(const double *expans, double bias, double sn2, int n, int d, const double *red, double *g);

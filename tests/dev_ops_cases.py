@@ -23,6 +23,48 @@ Bounds (u = 2^-53):
     on the same inputs, the device's own factor included) against the long-double solution, elementwise relative to
     |L^-1| |b| in long double.  The 8 covers another accumulation order in an algorithm with the same first-order error.
 
+The pair passes of the gradients (group `pairs`: gpak_dev_grad_pair_sums, either pass of csrc/grad.hip on caller-owned
+buffers).  Inputs: 515 drill-hole points (odd: the last row tile holds 3 valid rows and the double2 of lane 1 straddles
+the edge, the column blocks 576..639 are empty, block column 512 has 3 valid columns) transformed by the engine under
+test, Np = cap = 640, alpha standard_normal, B^-1 standard_normal on i >= j, i, j < n -- not symmetric, not a kernel
+matrix, not an inverse -- and the sentinel NaN in every other element of every buffer (i < j inside diagonal tiles, tiles
+above the diagonal, rows and columns >= n, rows >= n of u, x_soa, alpha): a read that is used shows as a NaN sum.  In
+DIRECT mode points 77 and 300 coincide (sd == 0 off the diagonal, in different tiles: dk = 0 there by definition).  The
+reference is each of the 16 sums elementwise over the pairs in np.longdouble, written from the comments above RefPass /
+ExactPass, on the u the engine produced, with M_p and m2 from gpak_dev_grad_consts (held to the oracle's independent
+S % S_p by the case `grad_consts via the oracle`).  Bound per sum, u = 2^-53:
+    (pairs + 2) u sum|t~|  +  sum (c0 + c1 s) u |t~|
+  * the first part holds for any order of accumulation (the fma of the accumulation rounds once per pair);
+  * t~ is the term with every cancelling sub-expression replaced by the sum of magnitudes: |q|/sn2 + |alpha_i alpha_j| for
+    qw, |a_i| + |a_j| + 4 |x|^T |M_p| |x| for Di2; products of differences of raw columns are products already;
+  * c0 + c1 s is the relative error of evaluating one term, from the operation count, with 1 ulp <= 2u and the documented
+    2 ulp (4u) of gpak_sqrt_nonneg / gpak_exp_nonpos (gpak_internal.h).  qw: 1/sn2, two products, one difference: 3u of
+    its magnitude.  d2 by differences: 4 differences, 4 squares, 3 additions of non-negative terms: 6u; a sum of up to
+    three of them: 8u.  sd = sqrt(d2): 3u (4u of a summed d2) + 4u.  exp(-sd): an absolute error of 7u sd (8u sd) in the
+    argument becomes a relative one of the result, + 4u: this is c1 s with s = sd.  The RBF argument iw d2 / 2 carries
+    8u + 2u, so s = iw d2 / 2 there and c1 >= 10.  dk = e (-0.5 / sd): 7u sd + 4u + 8u + 1u.  The worst slots: as written
+    0..5, var2 qw dk Di2: 3 + 13 + 2 products + Di2 (two three-term dots 6u, two additions 2u, each a_i 4u of |a_i| when its
+    three terms have one sign) = 34u + 7u sd; as written 9+2t of an Exp child, qw dk(d2s) d2s: 3 + 14 + 2 + 8 = 27u + 8u sd;
+    10+2t of an Exp child, qw kd kd, has the exponential twice: 13u + 16u sd; exact 8..13, 2 qw e (-0.5 / sd) D_a D_b:
+    3 + 4 + 8 + 2 + 2 + 2 = 21u + 7u sd.  Hence c0 = 40 and c1 = 16 for every slot (PAIR_C0, PAIR_C1);
+  * a_i = sum_k x_ik^2 m2_pk has mixed signs, so its rounding is no multiple of |a_i|: 4u sum_k x_ik^2 |m2_pk| per a is
+    charged on its own, through the term's other factors;
+  * expansion mode (as-written pass): d2 = ps + qs - 2 dot carries delta = 8u (ps + qs + 2 sum|p_c q_c|) against the true
+    |u_i - u_j|^2 that the reference uses; off the diagonal its first-order effect |dt/dd2| delta is added (|dk| delta for
+    exp(-sd), e (1 + sd) / (4 sd^3) delta for dk), and the case asserts d2 >= 1e6 delta for every such pair (the smallest
+    ratio of these inputs is 7e8); ON the diagonal the true d2 is 0 and the computed one is noise <= delta, where no first
+    order exists: 1 - exp(-sqrt(z)) <= sqrt(z), so sqrt(delta) of the term's other factors is added for the slots that
+    use exp(-sd) there (6 and 7; dk is 0 on the diagonal by definition, and x4_i - x4_i is 0).
+One dropped, doubled, misplaced or mis-weighted pair is 10^7 or more bounds (test_the_checks_bite).  A slot a pass does
+not use must be +0.0; u, x_soa, alpha, binv and every guard band come back bit-identical; `part` is scratch.  The sums of
+the ranks of a P, added in long double, are held to the P = 0 reference within the sum of the ranks' bounds.
+gpak_dev_grad_pairs_rows must give the bits of gpak_dev_grad_pair_sums on the same buffers, and out[16] within
+(n + 2) u sum((y - f)^2 / sn2 + 1).  gpak_dev_grad_finish[_d]: the formulas of gpak_grad_assemble in long double, 4u of
+each entry's magnitude (of |red_7| / sn2 + |red_16| for the sn2 entry).  The oracle case: g[10] assembled from the
+long-double sums against orc.grad_ref_q on the symmetric Q of the same lower triangle: twice the case's own bound through
+the linear assembly (the oracle is a float64 sum of the same terms in another order), the rounding of M_p itself on
+either side (derived in the case), and, for the sn2 entry, the oracle's own f = K alpha.
+
 Long-double products of float64 operands are formed from exact pieces: each operand is cut into 17-bit slices per row
 (integers times a power of two), a float64 BLAS product of two slices with K <= 2048 is exact (17 + 17 + 11 < 53 bits)
 in any order, and the slice products are summed in long double, smallest first (`mm_ld`; test_dev_ops holds it against
@@ -50,7 +92,7 @@ SENTINEL = np.uint64(0x7FF8A5A5DEADBEEF)     # a quiet NaN with a payload: arith
 OK, EINVAL = 0, 2
 INT_MAX = 0x7FFFFFFF
 D4, HYB = 0x10, 0x20
-GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill", "grad")
+GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill", "grad", "pairs")
 
 
 def long_double_ok():
@@ -203,8 +245,8 @@ def rng_for(name):
 # ------------------------------------------------------------------------------------------------
 # the two adaptors
 # ------------------------------------------------------------------------------------------------
-# arguments of gpak_dev_<name> after the stream: p device pointer, i int, l long, d double, h host double array,
-# P host array of device pointers (a list here)
+# arguments of gpak_dev_<name> after the stream: p device pointer, i int, l long, d double, h host double array (a list,
+# read only), H host double array (an array or a Mat, passed as it is), P host array of device pointers (a list here)
 SIG = {
     "transform": "piiihhp", "transform_k": "piiihihp", "fill_b": "piiiiihddipl", "fill_rect": "piiiiiihddipl",
     "factor_panel": "pliiipp", "factor_panel_co": "pliiippi", "update_block": "pliipliii", "update_cyclic": "pliipliiiiiii",
@@ -212,7 +254,10 @@ SIG = {
     "trsv_bwd_block": "pliippp", "trsv_bwd_packed": "pliiiippppp", "diag_inverse": "pliiipp", "logdiag_block": "pliiip",
     "kmatvec": "piiiiphdipp", "nlz_terms": "ipppdp", "pack": "pliiip", "gemv_n_add": "pliipp", "gemv_t": "pliipp",
     "vec_axpy": "idpp", "vec_scale": "ipdp", "vec_sum": "ipp", "grad_g_rows": "iiiiPPp", "grad_binv_rows": "iiiippp",
+    "grad_pair_sums": "ipipiiippliihddipp", "grad_pairs_rows": "pipiiippppiihddipp",
+    "grad_finish": "hddiHH", "grad_finish_d": "hddiiHH", "grad_consts": "hHH",
 }
+HOST_ONLY = ("grad_finish", "grad_finish_d", "grad_consts")       # no stream argument; H: a host array, read or written
 
 
 def precheck(name, a):
@@ -254,6 +299,17 @@ def precheck(name, a):
     if name == "grad_binv_rows":
         P, ra, rb = a[1], a[2], a[3]
         return EINVAL if ra < 0 or ra >= P or rb < 0 or rb >= P else None
+    if name == "grad_pairs_rows":
+        return EINVAL if a[10] < 1 or a[11] < 0 or a[11] >= a[10] else None
+    if name == "grad_pair_sums":
+        passno, ld, P, ra, kern, mode = a[0], a[9], a[10], a[11], a[12], a[15]
+        if passno not in (0, 1) or P < 0 or (P > 0 and (ra < 0 or ra >= P)) or (P == 0 and ld & 1):
+            return EINVAL
+        if mode & HYB:
+            nt, kinds = int(kern[0]), [int(k) for k in kern[1:4]]
+            if nt < 1 or nt > 3 or any(k not in (0, 1, 2) for k in kinds[:nt]) or kern[4] != 0.0 or kinds[:nt].count(0) > 1:
+                return EINVAL
+        return None
     if name == "update_cyclic":
         nb, lb0, n_local, last_width = a[7], a[10], a[11], a[12]
         return OK if (n_local - 1) * (nb // TILE) + last_width // TILE - lb0 * (nb // TILE) <= 0 else None
@@ -269,12 +325,14 @@ class NumpyOps:
     NumpyEngine for the two operations the C++ schedules do not use."""
     name = "numpy"
 
-    def __init__(self):
+    def __init__(self, mut=()):
+        """mut: deliberate faults of the pair pass (np_dist_engine.pair_sums), for test_the_checks_bite"""
         import torch
         from np_dist_engine import NumpyDistEngine
         self.torch = torch
         self.nde = NumpyDistEngine(poison_upper=False)
         self.eng = self.nde.np
+        self.mut = tuple(mut)
 
     @staticmethod
     def _ptr(x):
@@ -302,6 +360,27 @@ class NumpyOps:
             return OK
         if name == "factor_panel_co":
             name, a = "factor_panel", a[:-1]
+        if name == "grad_pair_sums":
+            import np_dist_engine as nd
+            pay = lambda x: x.data if isinstance(x, Mat) else x
+            passno, u, cap, xs, xst, n, Np, alpha, binv, ld, P, ra, kern, bias, sn2, mode, _part, out = a
+            nd.pair_sums(passno, pay(u), cap, pay(xs), xst, n, Np, pay(alpha), pay(binv), ld, P, ra, kern, bias, sn2, mode, pay(out),
+                         mut=self.mut)
+            if "store" in self.mut:
+                pay(binv)[0] = 1.0
+            return OK
+        if name in ("grad_finish", "grad_finish_d"):
+            E, bias, sn2, n = a[:4]
+            red, g = (x.data if isinstance(x, Mat) else x for x in a[-2:])
+            d = a[4] if name == "grad_finish_d" else 3
+            g[:6] = red[:6]
+            g[6] = 2.0 * red[6] * E[6]
+            g[7] = -4.0 * red[15] / n if d == 4 else 0.0
+            g[8] = red[8]
+            g[9] = -1.0 * (0.5 * red[7]) * (2.0 / sn2) - red[16]
+            return OK
+        if name == "grad_consts":              # host code of the library under either engine: its check is the oracle
+            return host_call(name, a)
         conv = []
         for kind, v in zip(SIG[name], a):
             if kind == "p":
@@ -315,11 +394,32 @@ class NumpyOps:
         return int(self.nde._keep[name](None, *conv))
 
 
+def host_call(name, a):
+    """a host-only entry point of libgpak_hip.so (no stream, no device)"""
+    from gp_ss_ak_amd import _lib
+    fn = getattr(_lib.load(), "gpak_dev_" + name)
+    fn.restype = C.c_int
+    fn.argtypes = [HipOps._ct[k] for k in SIG[name]]
+    conv, keep = [], []
+    for kind, v in zip(SIG[name], a):
+        if kind == "h":
+            keep.append((C.c_double * len(v))(*[float(t) for t in v]))
+            conv.append(keep[-1])
+        elif kind == "H":
+            arr = v.data if isinstance(v, Mat) else v
+            assert arr.dtype == np.float64 and arr.flags.c_contiguous
+            conv.append(arr.ctypes.data_as(C.POINTER(C.c_double)))
+        else:
+            conv.append(v)
+    return int(fn(*conv))
+
+
 class HipOps:
     """libgpak_hip.so on the device: HipEngine for the library, the device and the stream; every call uploads its
     arrays, runs, synchronises and downloads them again (guard bands included)."""
     name = "hip"
-    _ct = {"p": C.c_void_p, "i": C.c_int, "l": C.c_long, "d": C.c_double, "h": C.POINTER(C.c_double), "P": C.POINTER(C.c_void_p)}
+    _ct = {"p": C.c_void_p, "i": C.c_int, "l": C.c_long, "d": C.c_double, "h": C.POINTER(C.c_double), "P": C.POINTER(C.c_void_p),
+           "H": C.POINTER(C.c_double)}
 
     def __init__(self):
         from py_schedule import HipEngine
@@ -328,6 +428,8 @@ class HipOps:
 
     def call(self, name, *a):
         assert len(a) == len(SIG[name]), name
+        if name in HOST_ONLY:
+            return host_call(name, a)
         fn = getattr(self.lib, "gpak_dev_" + name)
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p] + [self._ct[k] for k in SIG[name]]
@@ -780,8 +882,8 @@ for _s in TRSV_SHAPES:
 
 
 # ---- the two linear-algebra operations of the distributed gradient ----------------------------------------
-# (gpak_dev_grad_pairs_rows / _consts / _finish stay under the distributed-gradient tests: no bound of this file's kind
-# exists for the pair sums.)  The interface fixes every leading dimension here (a packed panel has Np - J, a slab and
+# (the pair pass and the host ends of the chain are the group `pairs`, further down.)  The interface fixes every leading
+# dimension here (a packed panel has Np - J, a slab and
 # binv have rows_a), so these buffers have guard bands but no skew rows.
 def grad_tiles(Np, P, a):
     T = Np // TILE
@@ -1100,6 +1202,436 @@ case("fill", "fill_rect[nrows=64]->EINVAL", ["gpak_dev_fill_rect"], row0=0, nrow
      want=EINVAL)(_fill_rect)
 case("fill", "fill_rect[ncols=32]->EINVAL", ["gpak_dev_fill_rect"], row0=0, nrows=128, col0=0, ncols=32, kind="3d", mode=1,
      want=EINVAL)(_fill_rect)
+
+
+# ---- the pair passes of the gradients alone ---------------------------------------------------------------
+# gpak_dev_grad_pair_sums (either pass of csrc/grad.hip on caller-owned buffers), gpak_dev_grad_pairs_rows, and the host
+# ends of the chain (gpak_dev_grad_consts, gpak_dev_grad_finish / _finish_d).  The bound is derived in the module docstring.
+PAIR_C0, PAIR_C1 = 40.0, 16.0
+PAIR_N, PAIR_NP, PAIR_LD = 515, 640, 672
+PAIR_TWINS = (77, 300)                 # two coincident points, off the diagonal and in different tiles (DIRECT mode only)
+EXP_P, RBF_P = [0.7, 0.8], [0.5, 0.9, 0.5]
+PAIR_COMPS = {                         # name -> (terms, input columns); None = the default ExpAns parameters
+    "expans+bias": ([(0, None)], 3), "expans d4": ([(0, None)], 4), "expans+rbf": (HYB_TERMS, 3),
+    "exp+rbf": ([(1, EXP_P), (2, RBF_P)], 3), "expans+exp+rbf": ([(0, None), (1, EXP_P), (2, RBF_P)], 3),
+}
+PAIR_SLOTS = 16
+
+
+def serialise(terms, white):
+    kern = [len(terms)] + [k for k, _ in terms] + [0] * (3 - len(terms)) + [white]
+    for _k, p in terms:
+        kern += list(p)
+    return kern + [0.0] * (32 - len(kern))
+
+
+class PairData:
+    """The inputs of a pair pass: n drill-hole points (two of them coincident in DIRECT mode) transformed by the engine
+    under test, alpha and the elements i >= j of B^-1 standard_normal, the sentinel everywhere else; and, per pass, the
+    long-double sums, row by row."""
+
+    def __init__(self, ops, comp, mode, n, Np):
+        from gp_ss_ak_amd import synth
+        terms, cols = PAIR_COMPS[comp]
+        self.E = np.array(synth.DEFAULT_EXPANS, dtype=np.float64)
+        self.terms = [(k, list(self.E) if p is None else list(p)) for k, p in terms]
+        self.bias, self.sn2, self.n, self.Np, self.cap, self.d = synth.DEFAULT_BIAS, synth.DEFAULT_SN2, n, Np, Np, cols
+        self.hyb = not (len(terms) == 1 and terms[0][0] == 0)
+        self.mode = mode | (D4 if cols == 4 else 0) | (HYB if self.hyb else 0)
+        self.kern = serialise(self.terms, 0.0) if self.hyb else list(self.E)
+        rng = rng_for(f"pairs[{comp},{mode},{n}]")
+        X, _y = synth.drillholes4(n) if cols == 4 else synth.drillholes(n)
+        X = np.array(X, dtype=np.float64)
+        if mode == 1 and n > PAIR_TWINS[1]:
+            X[PAIR_TWINS[1]] = X[PAIR_TWINS[0]]
+        self.X = X
+        cap = self.cap
+        xs = np.zeros((4, cap))
+        xs[:cols, :n] = X.T
+        mu = np.zeros(4)
+        mu[:cols] = X.sum(axis=0) / n
+        call = (lambda u: ops.call("transform_k", xs.ravel(), cap, n, cap, self.kern, self.mode, mu, u)) if self.hyb else \
+               (lambda u: ops.call("transform", xs.ravel(), cap, n, cap, self.kern, mu, u))
+        u, u2 = np.zeros(15 * cap), np.zeros(15 * cap)
+        assert call(u) == OK and call(u2) == OK
+        assert np.array_equal(bits(u), bits(u2)), "two transforms of the same points differ"
+        nt = len(self.terms)
+        poison = lambda M: np.where((np.arange(cap) < n)[:, None], M, sentinel(1)[0])         # rows from n on: the sentinel
+        self.u = poison(u.reshape(15, cap).T[:, :5 * nt])                                     # cap x 5 nterms
+        self.xs = poison(xs.T)
+        self.alpha = poison(np.concatenate([rng.standard_normal(n), np.zeros(cap - n)])[:, None])
+        self.B = np.tril(rng.standard_normal((n, n)))
+        self.y, self.f = rng.standard_normal(n), rng.standard_normal(n)
+        self.un = u.reshape(15, cap)[:5 * nt, :n].reshape(nt, 5, n).copy()
+        self.te = [k for k, _ in self.terms].index(0) if 0 in [k for k, _ in self.terms] else -1
+        if self.te >= 0:
+            from np_dist_engine import grad_consts
+            self.Mp, self.m2 = grad_consts(self.terms[self.te][1])
+        self._sums = {}
+
+    def binv(self, P, a):
+        """B^-1 as rank a of P holds it (P == 0: Np x Np, leading dimension PAIR_LD): the sentinel wherever the pass has
+        no business reading"""
+        n, Np = self.n, self.Np
+        low = np.tril(np.ones((n, n), dtype=bool))
+        vals = np.where(low, self.B, sentinel(1)[0])
+        if P == 0:
+            M = sentinel(Np * Np).reshape(Np, Np)
+            M[:n, :n] = vals
+            return Mat(M, PAIR_LD if Np + 32 <= PAIR_LD else Np + 32)
+        rows, Tmax = grad_rows(Np, P, a), grad_tiles(Np, P, 0)
+        M = sentinel(max(len(rows), TILE) * P * Tmax * TILE).reshape(max(len(rows), TILE), P * Tmax * TILE)
+        cols = np.arange(n)
+        cperm = ((cols // TILE % P) * Tmax + cols // TILE // P) * TILE + cols % TILE
+        loc = np.arange(len(rows))[rows < n]
+        if len(loc):
+            M[np.ix_(loc, cperm)] = vals[rows[rows < n]]
+        return Mat(M)
+
+    def sums(self, passno):
+        """per row i and slot: the long-double sum over j <= i, sum |t~|, and the evaluation part of the bound"""
+        if passno not in self._sums:
+            self._sums[passno] = pair_reference(self, passno)
+        return self._sums[passno]
+
+    def expect(self, passno, P, a):
+        """reference and bound of the 16 sums over the rows of rank a of P"""
+        ref, tb, ev = self.sums(passno)
+        rows = grad_rows(self.Np, P, a) if P else np.arange(self.n)
+        rows = rows[rows < self.n]
+        pairs = float((rows + 1).sum())
+        return ref[:, rows].sum(axis=1), (pairs + 2) * U * tb[:, rows].sum(axis=1) + ev[:, rows].sum(axis=1)
+
+
+def pair_reference(d, passno):
+    """The 16 sums of a pass elementwise over the pairs in np.longdouble, from the formulas in the comments above RefPass
+    and ExactPass (csrc/grad.hip), with the true distance |u_i - u_j|^2 of the transformed points in either dist_mode."""
+    n, sn2, bias = d.n, LD(d.sn2), LD(d.bias)
+    ii, jj = np.arange(n)[:, None], np.arange(n)[None, :]
+    low, diag = ii >= jj, ii == jj
+    w = np.where(diag, 1.0, 2.0) * low
+    q = d.B.astype(LD)
+    al = d.alpha[:n, 0].astype(LD)
+    aa = al[:, None] * al[None, :]
+    qw, qwb = (q / sn2 - aa) * low, ((np.abs(q) / sn2 + np.abs(aa)) * low).astype(np.float64)
+    X4 = np.zeros((n, 4), dtype=LD)
+    X4[:, :d.d] = d.X
+    expansion = passno == 0 and (d.mode & 0xF) == 0
+    assert not expansion or len(d.terms) == 1, "the expansion-mode part of the bound is written for one ExpAns term"
+    d2, dd = [], []
+    for m in range(len(d.terms)):
+        c = d.un[m][[0, 1, 2, 4]].astype(LD)
+        d2.append(((c[:, :, None] - c[:, None, :]) ** 2).sum(axis=0))
+        if expansion:         # delta d2 = 8u (ps + qs + 2 sum |p_c q_c|): the rounding of |u|^2 and of the expansion itself
+            cf, ps = np.abs(d.un[m][[0, 1, 2, 4]]), d.un[m][3]
+            dd.append(8 * U * (ps[:, None] + ps[None, :] + 2 * np.einsum("ci,cj->ij", cf, cf)))
+            off = low & ~diag
+            d.cond = float((d2[m][off].astype(np.float64) / dd[m][off]).min())
+            assert d.cond >= 1e6, f"an off-diagonal pair has d2 = {d.cond:.3g} x its own cancellation noise"
+    T, TB, EV = {}, {}, {}        # slot -> term, |t~|, evaluation bound (all n x n)
+
+    def put(k, t, tbar, amp, extra=None):
+        T[k], TB[k] = t, tbar
+        EV[k] = U * (PAIR_C0 + PAIR_C1 * amp) * tbar + (0.0 if extra is None else extra)
+
+    def expsqrt(D2):
+        sd = np.sqrt(D2)
+        ek = np.exp(-sd)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dk = np.where((sd == 0) | diag, LD(0), ek * (LD(-0.5) / sd))
+        return sd, ek, dk
+
+    f = lambda a: np.asarray(a, dtype=np.float64)
+    var2 = [LD(np.float64(p[2]) * np.float64(p[2])) if k == 2 else LD(np.float64(p[6 if k == 0 else 1]) ** 2) for k, p in d.terms]
+    if passno == 0:
+        prof, amps = [], []
+        for m, (k, p) in enumerate(d.terms):
+            if k == 2:
+                arg = LD(0.5) * LD(p[1]) * d2[m]
+                prof.append(np.exp(-arg)); amps.append(f(arg))
+            else:
+                sd, ek, _dk = expsqrt(d2[m])
+                prof.append(ek); amps.append(f(sd))
+        kfull = bias + sum(v * e for v, e in zip(var2, prof))
+        kbar = f(w * np.abs(q)) * (abs(d.bias) * PAIR_C0 + sum(f(v * e) * (PAIR_C0 + PAIR_C1 * s) for v, e, s in zip(var2, prof, amps)))
+        T[7], TB[7] = w * q * kfull, f(w * np.abs(q) * (abs(bias) + sum(v * e for v, e in zip(var2, prof))))
+        EV[7] = U * kbar
+        put(8, qw * diag, qwb * diag, 0.0)
+        if d.te >= 0:
+            te = d.te
+            sd, ek, dk = expsqrt(d2[te])
+            sdf, ekf, dkf = f(sd), f(ek), np.abs(f(dk))
+            off = low & ~diag
+            x = X4[:, :3]
+            xa = np.abs(f(x))
+            dx4 = X4[:, 3][:, None] - X4[:, 3][None, :]
+            if expansion:     # first order in delta d2 off the diagonal; on it d2 is noise <= delta d2 and 1 - exp(-sqrt(z)) <= sqrt(z)
+                de = np.where(diag, np.sqrt(dd[te]), dkf * dd[te]) * low
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    ddk = np.where(off, ekf * (1.0 + sdf) / (4.0 * sdf ** 3) * dd[te], 0.0)
+                EV[7] = EV[7] + f(w * np.abs(q)) * float(var2[te]) * de
+            # what an error of e in every entry of M_p (m2 = 2 x its column sums: 6 e) does to sums 0..5, per unit of e
+            x2, x1 = (xa * xa).sum(axis=1), xa.sum(axis=1)
+            d.mp_sens = float((f(w) * float(var2[te]) * qwb * dkf * (6 * (x2[:, None] + x2[None, :]) + 4 * x1[:, None] * x1[None, :])).sum())
+            for p in range(6):
+                Mp, m2 = d.Mp[p].astype(LD), d.m2[p].astype(LD)
+                ai = (x * x) @ m2
+                di2 = ai[:, None] + ai[None, :] - 4 * (x @ Mp @ x.T)
+                di2b = np.abs(f(ai))[:, None] + np.abs(f(ai))[None, :] + 4.0 * (xa @ np.abs(d.Mp[p]) @ xa.T)
+                # a_i is itself a three-term sum with mixed signs: its rounding, 4u sum_k x_ik^2 |m2_pk|, is no multiple of
+                # |a_i| and is charged on its own
+                ab = (xa * xa) @ np.abs(d.m2[p])
+                rb = f(w) * float(var2[te]) * qwb
+                put(p, w * var2[te] * qw * dk * di2, rb * dkf * di2b, sdf,
+                    rb * dkf * 4 * U * (ab[:, None] + ab[None, :]) + (rb * di2b * ddk if expansion else 0.0))
+            put(6, w * qw * ek, f(w) * qwb * ekf, sdf, f(w) * qwb * de if expansion else None)
+            put(15, w * ek * dx4 * dx4, f(w * ek * dx4 * dx4), sdf, f(w * dx4 * dx4) * de * (~diag) if expansion else None)
+        d2s = sum(d2)
+        for m, (k, p) in enumerate(d.terms):
+            if k == 1:
+                sd, kd, dk = expsqrt(d2s)
+                put(9 + 2 * m, w * qw * dk * d2s, f(w) * qwb * np.abs(f(dk)) * f(d2s), f(sd))
+                put(10 + 2 * m, w * qw * kd * kd, f(w) * qwb * f(kd * kd), f(sd))
+            elif k == 2:
+                arg = LD(0.5) * LD(p[1]) * d2s
+                kd = np.exp(-arg)
+                put(9 + 2 * m, w * qw * kd * d2s, f(w) * qwb * f(kd * d2s), f(arg))
+                put(10 + 2 * m, w * qw * kd, f(w) * qwb * f(kd), f(arg))
+    else:
+        put(0, w * qw, f(w) * qwb, 0.0)
+        put(1, qw * diag, qwb * diag, 0.0)
+        for m, (k, p) in enumerate(d.terms):
+            if k == 2:
+                arg = LD(0.5) * LD(p[1]) * d2[m]
+                e = np.exp(-arg)
+                put(2 + m, w * qw * e, f(w) * qwb * f(e), f(arg))
+                put(5 + m, w * qw * e * d2[m], f(w) * qwb * f(e * d2[m]), f(arg))
+                continue
+            sd, ek, dk = expsqrt(d2[m])
+            put(2 + m, w * qw * ek, f(w) * qwb * f(ek), f(sd))
+            if m == d.te:
+                D = [X4[:, c][:, None] - X4[:, c][None, :] for c in range(4)]
+                for s, (ca, cb) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+                    put(8 + s, w * qw * dk * D[ca] * D[cb], f(w) * qwb * np.abs(f(dk * D[ca] * D[cb])), f(sd))
+                put(14, w * qw * dk * D[3] * D[3], f(w) * qwb * np.abs(f(dk * D[3] * D[3])), f(sd))
+            else:
+                put(5 + m, w * qw * dk * d2[m], f(w) * qwb * np.abs(f(dk)) * f(d2[m]), f(sd))
+    ref, tb, ev = np.zeros((PAIR_SLOTS, n), dtype=LD), np.zeros((PAIR_SLOTS, n)), np.zeros((PAIR_SLOTS, n))
+    for k in T:
+        ref[k], tb[k], ev[k] = T[k].sum(axis=1), np.asarray(TB[k]).sum(axis=1), np.asarray(EV[k]).sum(axis=1)
+    return ref, tb, ev
+
+
+def pair_data(ops, comp, mode, n=PAIR_N, Np=PAIR_NP):
+    return memo(("pairs", ops.name, comp, mode, n, Np), lambda: PairData(ops, comp, mode, n, Np))
+
+
+def pair_buffers(d, P, a, name):
+    Ta = grad_tiles(d.Np, P, a) if P else d.Np // TILE
+    part = Mat(rng_for(name + "part").standard_normal(max(Ta, 1) * (d.Np // 64) * PAIR_SLOTS))
+    return Mat(d.u), Mat(d.xs), Mat(d.alpha), d.binv(P, a), part
+
+
+def add_sums(res, out, ref, bound, nout=PAIR_SLOTS):
+    """one check per slot, so that each slot's ratio is printed; a slot the pass does not use (reference and bound 0) must
+    be +0.0 exactly"""
+    got = out.get()[:, 0]
+    unused = [k for k in range(PAIR_SLOTS) if ref[k] == 0 and bound[k] == 0]
+    res.rc("unused slots that are not +0.0", int(np.count_nonzero(bits(got[unused].copy()))))
+    idx = np.arange(nout)[:, None]
+    for k in range(nout):
+        res.add(f"out[{k}]", out, ref, bound, idx == k, free=idx != k)
+
+
+def _pair_sums(ops, name, passno, P, a, comp, mode, n=PAIR_N, Np=PAIR_NP):
+    d = pair_data(ops, comp, mode, n, Np)
+    u, xs, alpha, binv, part = pair_buffers(d, P, a, name)
+    out = Mat(rng_for(name + "out").standard_normal(PAIR_SLOTS))
+    res = Result().rc("grad_pair_sums", ops.call("grad_pair_sums", passno, u, d.cap, xs, d.cap, n, Np, alpha, binv, binv.ld, P, a,
+                                                 d.kern, d.bias, d.sn2, d.mode, part, out))
+    ref, bound = d.expect(passno, P, a)
+    add_sums(res, out, ref, bound)
+    if hasattr(d, "cond") and (d.mode & 0xF) == 0:
+        res.info["smallest d2 / its cancellation noise"] = d.cond
+    owns = P == 0 or grad_tiles(Np, P, a) > 0
+    res.add("part", part, free=owns)                         # a rank without tiles leaves it alone
+    return res.add("u", u).add("x_soa", xs).add("alpha", alpha).add("binv", binv)
+
+
+def _pair_rank_sum(ops, name, passno, P, comp, mode):
+    """the ranks' sums added in long double against the P = 0 reference, within the sum of the ranks' bounds"""
+    d = pair_data(ops, comp, mode)
+    res, tot, btot = Result(), np.zeros(PAIR_SLOTS, dtype=LD), np.zeros(PAIR_SLOTS)
+    for a in range(P):
+        u, xs, alpha, binv, part = pair_buffers(d, P, a, f"{name}{a}")
+        out = Mat(np.zeros(PAIR_SLOTS))
+        res.rc(f"grad_pair_sums[a={a}]", ops.call("grad_pair_sums", passno, u, d.cap, xs, d.cap, d.n, d.Np, alpha, binv, binv.ld,
+                                                  P, a, d.kern, d.bias, d.sn2, d.mode, part, out))
+        tot += out.get()[:, 0].astype(LD)
+        btot += d.expect(passno, P, a)[1]
+        res.add(f"binv{a}", binv)
+    ref = d.expect(passno, 0, 0)[0]
+    err = np.abs(tot - ref).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0.0, err / btot)
+    r[~np.isfinite(err)] = np.inf
+    res.info["ranks' sum: worst error / bound"] = float(r.max())
+    return res.rc("slots of the ranks' sum outside the bound", int(np.count_nonzero(~(r <= 1.0))))
+
+
+def _pair_refused(ops, name, what):
+    d = pair_data(ops, "expans+rbf" if what in ("two expans", "white") else "expans+bias", 1)
+    passno, P, a, kern, mode = 0, 0, 0, d.kern, d.mode
+    if what == "pass":
+        passno = 2
+    if what == "a":
+        P, a = 3, 3
+    if what == "two expans":
+        kern = serialise([(0, list(d.E)), (0, list(d.E))], 0.0)
+    if what == "white":
+        kern = serialise(d.terms, HYB_WHITE)
+    u, xs, alpha, binv, part = pair_buffers(d, P, min(a, max(P - 1, 0)), name)
+    out = Mat(rng_for(name).standard_normal(PAIR_SLOTS))
+    ld = binv.ld + 1 if what == "ld" else binv.ld
+    res = Result().rc("grad_pair_sums", ops.call("grad_pair_sums", passno, u, d.cap, xs, d.cap, d.n, d.Np, alpha, binv, ld, P, a,
+                                                 kern, d.bias, d.sn2, mode, part, out), EINVAL)
+    return res.add("out", out).add("part", part).add("u", u).add("x_soa", xs).add("alpha", alpha).add("binv", binv)
+
+
+def _pairs_rows(ops, name, comp):
+    """gpak_dev_grad_pairs_rows: the same bits as gpak_dev_grad_pair_sums on the same buffers, and the lp_dhyp sum"""
+    P, a = 3, 1
+    d = pair_data(ops, comp, 1)
+    n, cap = d.n, d.cap
+    u, xs, alpha, binv, part = pair_buffers(d, P, a, name)
+    poison = lambda v: Mat(np.concatenate([v, sentinel(cap - n)]))
+    y, f = poison(d.y), poison(d.f)
+    out, o16 = Mat(rng_for(name + "out").standard_normal(PAIR_SLOTS + 1)), Mat(np.zeros(PAIR_SLOTS))
+    res = Result().rc("grad_pairs_rows", ops.call("grad_pairs_rows", u, cap, xs, cap, n, d.Np, y, f, alpha, binv, P, a, d.kern,
+                                                  d.bias, d.sn2, d.mode, part, out))
+    res.rc("grad_pair_sums", ops.call("grad_pair_sums", 0, u, cap, xs, cap, n, d.Np, alpha, binv, 0, P, a, d.kern, d.bias, d.sn2,
+                                      d.mode, Mat(part.was()), o16))
+    res.rc("sums that differ from gpak_dev_grad_pair_sums", int(np.count_nonzero(bits(out.get()[:16, 0].copy()) != bits(o16.get()[:, 0].copy()))))
+    ref, bound = d.expect(0, P, a)
+    dl = (d.y.astype(LD) - d.f.astype(LD)) ** 2 / LD(d.sn2)
+    ref = np.concatenate([ref, [(dl - 1).sum()]])
+    bound = np.concatenate([bound, [(n + 2) * U * float((dl + 1).sum())]])
+    add_sums(res, out, ref, bound, PAIR_SLOTS + 1)
+    o2 = Mat(np.zeros(PAIR_SLOTS + 1))
+    res.rc("grad_pairs_rows[a=P]", ops.call("grad_pairs_rows", u, cap, xs, cap, n, d.Np, y, f, alpha, binv, P, P, d.kern, d.bias,
+                                            d.sn2, d.mode, part, o2), EINVAL).add("o2", o2)
+    return res.add("part", part, free=True).add("u", u).add("x_soa", xs).add("alpha", alpha).add("binv", binv).add("y", y).add("f", f)
+
+
+def finish_ld(E, bias, sn2, n, d, red):
+    """gpak_grad_assemble for ExpAns + Bias in long double: the ten entries and the magnitudes their rounding scales with"""
+    r = np.asarray(red, dtype=LD)
+    g, mag = np.zeros(10, dtype=LD), np.zeros(10)
+    g[:6] = r[:6]
+    g[6] = 2 * r[6] * LD(E[6])
+    g[7] = -4 * r[15] / LD(n) if d == 4 else 0
+    g[8] = r[8]
+    g[9] = -(LD(0.5) * r[7]) * (2 / LD(sn2)) - r[16]
+    mag[:9] = np.abs(g[:9]).astype(np.float64)
+    mag[9] = float(np.abs(r[7]) / LD(sn2) + np.abs(r[16]))
+    return g, mag
+
+
+def _finish(ops, name, d):
+    from gp_ss_ak_amd import synth
+    E, bias, sn2, n = np.array(synth.DEFAULT_EXPANS), synth.DEFAULT_BIAS, synth.DEFAULT_SN2, PAIR_N
+    red, g = Mat(rng_for(name).standard_normal(17)), Mat(rng_for(name + "g").standard_normal(10))
+    res = Result()
+    if d == 3:                 # gpak_dev_grad_finish is _finish_d(..., 3, ...)
+        g3 = Mat(g.was())
+        res.rc("grad_finish", ops.call("grad_finish", list(E), bias, sn2, n, red, g3))
+        res.rc("grad_finish_d", ops.call("grad_finish_d", list(E), bias, sn2, n, 3, red, g))
+        res.rc("entries of grad_finish that differ from grad_finish_d(3)", int(np.count_nonzero(bits(g3.data) != bits(g.data))))
+        res.rc("g[7] is not +0.0", int(bits(g.get()[7:8, 0].copy())[0] != 0))
+    else:
+        res.rc("grad_finish_d", ops.call("grad_finish_d", list(E), bias, sn2, n, d, red, g))
+    ref, mag = finish_ld(E, bias, sn2, n, d, red.was()[:, 0])
+    return res.add("g", g, ref, 4 * U * mag, True).add("red", red)
+
+
+def _consts_vs_oracle(ops, name, comp):
+    """gpak_dev_grad_consts through the oracle, which restates S % S_p on its own (expans_S_matrices): the ten gradient
+    entries from the long-double pair sums (they carry M_p and m2 of gpak_dev_grad_consts) against orc.grad_ref_q on the
+    symmetric Q of the same lower triangle."""
+    from oracle import oracle as orc
+    d = pair_data(ops, comp, 1)
+    n, E = d.n, d.E
+    M36, m2 = Mat(np.zeros(36)), Mat(np.zeros(18))
+    res = Result().rc("grad_consts", ops.call("grad_consts", list(E), M36, m2))
+    same = np.array_equal(bits(m2.data), bits(d.m2.ravel().copy())) and all(
+        np.array_equal(M36.data[6 * p:6 * p + 6], d.Mp[p][[0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2]]) for p in range(6))
+    res.rc("constants differ from those the reference sums were made with", int(not same))
+    ref16, b16 = d.expect(0, 0, 0)
+    # the oracle's lp_dhyp sum is made from its own f = K alpha: the same in long double, from the true distances
+    c = d.un[0][[0, 1, 2, 4]].astype(LD)
+    K = LD(E[6]) ** 2 * np.exp(-np.sqrt(((c[:, :, None] - c[:, None, :]) ** 2).sum(axis=0))) + LD(d.bias)
+    al = d.alpha[:n, 0].astype(LD)
+    fl = K @ al
+    dl = d.y.astype(LD) - fl
+    red = np.concatenate([ref16, [(dl * dl / LD(d.sn2) - 1).sum()]])
+    g = Mat(np.zeros(10))
+    res.rc("grad_finish_d", ops.call("grad_finish_d", list(E), d.bias, d.sn2, n, d.d, red.astype(np.float64), g))
+    Q = np.asfortranarray(d.B + np.tril(d.B, -1).T)
+    go = orc.grad_ref_q(d.X, d.y, Q, d.alpha[:n, 0].copy(), E, d.bias, d.sn2, orc.DIST_DIRECT)
+    # the oracle sums the same terms in float64 in another order: twice the case's own bound through the linear assembly
+    # (4u of it for the assembly itself); its f carries (n + 2 + c0 + c1 sd) u |K| |alpha| per entry, and the lp_dhyp sum
+    # (n + 2) u sum (d^2 / sn2 + 1) of its own
+    df = (n + 2 + PAIR_C0 + PAIR_C1 * 4.0) * U * (np.abs(K) @ np.abs(al)).astype(np.float64)
+    lp = float((2 * np.abs(dl).astype(np.float64) / d.sn2 * df).sum() + (n + 2) * U * float((dl * dl / LD(d.sn2) + 1).sum()))
+    # M_p = S % S_p itself is rounded, in the library and in the oracle: |S| <= w, |S_p| <= 2 w (w = the largest inverse
+    # width; the rows of Rot are unit vectors), S carries 8u w and S_p 16u w (three-term sums of products of rounded sines
+    # and cosines), so M_p carries (16 + 16 + 2) u w^2 on either side: 68 u w^2 between the two
+    eM = 68 * U * float(np.abs(E[[1, 3, 5]]).max()) ** 2
+    bound = np.zeros(10)
+    bound[:6] = 2 * b16[:6] + eM * d.mp_sens
+    bound[6] = 2 * abs(2 * E[6]) * b16[6]
+    bound[7] = 2 * 4 * b16[15] / n
+    bound[8] = 2 * b16[8]
+    bound[9] = 2 * b16[7] / d.sn2 + lp
+    bound += 4 * U * finish_ld(E, d.bias, d.sn2, n, d.d, red)[1]
+    return res.add("g", g, go.astype(LD), bound, True).add("M36", M36, free=True).add("m2", m2, free=True)
+
+
+_AW, _EX = "as written", "exact"
+for _mode, _mn in ((1, "direct"), (0, "expansion")):
+    case("pairs", f"pair_sums[{_AW},P=0,expans+bias,{_mn}]", ["gpak_dev_grad_pair_sums", "gpak_dev_transform"], passno=0, P=0, a=0,
+         comp="expans+bias", mode=_mode)(_pair_sums)
+for _P in (1, 2, 3):
+    for _a in range(_P):
+        case("pairs", f"pair_sums[{_AW},P={_P},a={_a},expans+bias,direct]", ["gpak_dev_grad_pair_sums"], passno=0, P=_P, a=_a,
+             comp="expans+bias", mode=1)(_pair_sums)
+    if _P > 1:
+        case("pairs", f"pair_sums[{_AW},P={_P},all ranks,expans+bias,direct]", ["gpak_dev_grad_pair_sums"], passno=0, P=_P,
+             comp="expans+bias", mode=1)(_pair_rank_sum)
+case("pairs", f"pair_sums[{_AW},P=3,a=1,expans+bias,expansion]", ["gpak_dev_grad_pair_sums"], passno=0, P=3, a=1,
+     comp="expans+bias", mode=0)(_pair_sums)
+for _c in ("expans d4", "expans+rbf", "exp+rbf", "expans+exp+rbf"):
+    case("pairs", f"pair_sums[{_AW},P=0,{_c},direct]", ["gpak_dev_grad_pair_sums", "gpak_dev_transform_k"], passno=0, P=0, a=0,
+         comp=_c, mode=1)(_pair_sums)
+for _c in PAIR_COMPS:
+    case("pairs", f"pair_sums[{_EX},P=0,{_c},direct]", ["gpak_dev_grad_pair_sums"], passno=1, P=0, a=0, comp=_c, mode=1)(_pair_sums)
+case("pairs", f"pair_sums[{_EX},P=2,a=1,expans+rbf,direct]", ["gpak_dev_grad_pair_sums"], passno=1, P=2, a=1, comp="expans+rbf",
+     mode=1)(_pair_sums)
+case("pairs", f"pair_sums[{_EX},P=2,all ranks,expans+rbf,direct]", ["gpak_dev_grad_pair_sums"], passno=1, P=2, comp="expans+rbf",
+     mode=1)(_pair_rank_sum)
+for _ps, _pn in ((0, _AW), (1, _EX)):
+    case("pairs", f"pair_sums[{_pn},P=3,a=2,n=129,Np=256]->no tile", ["gpak_dev_grad_pair_sums"], passno=_ps, P=3, a=2,
+         comp="expans+bias", mode=1, n=129, Np=256)(_pair_sums)
+    case("pairs", f"pair_sums[{_pn},P=0,n=640=Np]", ["gpak_dev_grad_pair_sums"], passno=_ps, P=0, a=0, comp="expans+bias", mode=1,
+         n=640, Np=640)(_pair_sums)
+for _w in ("pass", "a", "ld", "two expans", "white"):
+    case("pairs", f"pair_sums[bad {_w}]->EINVAL", ["gpak_dev_grad_pair_sums"], what=_w)(_pair_refused)
+for _c in ("expans+bias", "expans d4"):
+    case("pairs", f"pairs_rows[P=3,a=1,{_c}]", ["gpak_dev_grad_pairs_rows", "gpak_dev_grad_pair_sums"], comp=_c)(_pairs_rows)
+    case("pairs", f"grad_consts via the oracle[{_c}]", ["gpak_dev_grad_consts", "gpak_dev_grad_finish_d"], comp=_c)(_consts_vs_oracle)
+for _d in (3, 4):
+    case("pairs", f"grad_finish[d={_d}]", ["gpak_dev_grad_finish", "gpak_dev_grad_finish_d"] if _d == 3 else ["gpak_dev_grad_finish_d"],
+         d=_d)(_finish)
 
 
 # ------------------------------------------------------------------------------------------------

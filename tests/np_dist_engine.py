@@ -30,6 +30,148 @@ def _strided(ptr, rows, cols, ld):
     return np.lib.stride_tricks.as_strided(base, shape=(rows, cols), strides=(8, 8 * ld))
 
 
+def grad_consts(e):
+    """M_p (6 x 3 x 3) and m2 (6 x 3) of the as-written pass, from the library (host code: gpak_dev_grad_consts)"""
+    lib = gd._load()
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    M36, m2 = np.zeros(36), np.zeros(18)
+    lib.gpak_dev_grad_consts.argtypes = [gd._dp, gd._dp, gd._dp]
+    lib.gpak_dev_grad_consts(e.ctypes.data_as(gd._dp), M36.ctypes.data_as(gd._dp), m2.ctypes.data_as(gd._dp))
+    Mp = np.zeros((6, 3, 3))
+    for p in range(6):
+        v = M36[6 * p:6 * p + 6]
+        Mp[p] = [[v[0], v[1], v[2]], [v[1], v[3], v[4]], [v[2], v[4], v[5]]]
+    return Mp, m2.reshape(6, 3)
+
+
+def decode_composition(kern, mode):
+    """`kern` of a gpak_dev_* call -> (terms [(kind, params)], white): the serialisation of gpak_dev.h under
+    GPAK_DIST_HYB, the plain ExpAns list otherwise"""
+    if mode & 0x20:
+        return NumpyEngine.decode_kern(kern)
+    return [(0, [float(kern[i]) for i in range(8)])], 0.0
+
+
+def pair_rows(Np, P, a):
+    """global rows of rank a's 128-row blocks in slab order (P == 0: every row)"""
+    T = Np // TILE
+    if P == 0:
+        return np.arange(Np)
+    Ta = (T - a + P - 1) // P if T > a else 0
+    return (np.arange(Ta)[:, None] * P * TILE + a * TILE + np.arange(TILE)[None, :]).ravel().astype(int)
+
+
+def pair_sums(passno, u, cap, x_soa, xs, n, Np, alpha, binv, ld, P, a, kern, bias, sn2, mode, out, mut=()):
+    """gpak_dev_grad_pair_sums in float64 on host arrays: out[0..16) <- the sums of pass 0 (as written: the comment above
+    RefPass in csrc/grad.hip) or 1 (exact: above ExactPass) over the pairs i >= j of the rows this call owns.  `mut`:
+    deliberate faults, for tests that prove a check bites (tests/test_dev_ops.py)."""
+    terms, _white = decode_composition(kern, mode)
+    nt = len(terms)
+    d4, mode = bool(mode & 0x10), mode & 0xF
+    un = u[:5 * nt * cap].reshape(nt, 5, cap)
+    X4 = x_soa[:4 * xs].reshape(4, xs)[:, :n].T
+    al = alpha[:n]
+    rows = pair_rows(Np, P, a)
+    loc = np.arange(len(rows))[rows < n]
+    rows = rows[rows < n]
+    out[:16] = 0.0
+    if not len(rows):
+        return
+    cols = np.arange(n)
+    if P == 0:
+        Q = np.lib.stride_tricks.as_strided(binv, shape=(n, n), strides=(8, 8 * ld))
+    else:
+        Ta, Tmax = len(pair_rows(Np, P, a)), len(pair_rows(Np, P, 0)) // TILE
+        cperm = ((cols // TILE % P) * Tmax + cols // TILE // P) * TILE + cols % TILE
+        if "unpermuted" in mut:
+            cperm = cols
+        Q = binv[:Ta * P * Tmax * TILE].reshape(P * Tmax * TILE, Ta).T[loc][:, cperm]
+    low = rows[:, None] >= cols[None, :]
+    diag = rows[:, None] == cols[None, :]
+    if "last row" in mut:
+        low = low & (rows[:, None] != n - 1)
+    if "upper" in mut:
+        low = low.copy()
+        low[0, rows[0] + 1] = True                         # one element with i < j
+    wgt = np.where(diag, 2.0 if "diag2" in mut else 1.0, 2.0) * low
+    Qm = np.where(low, Q, 0.0)
+    ali = al[rows][:, None]
+    QW = np.where(low, Qm * (1.0 / sn2) - ali * (ali if "alpha row" in mut else al[None, :]), 0.0)
+    sel = [0, 1, 2, 4]                                     # the 4th transformed coordinate is 0 for 3-column inputs
+
+    def dist2(m, direct):
+        Pu, Qu = un[m][sel][:, rows].T, un[m][sel][:, :n].T
+        if direct:
+            return ((Pu[:, None, :] - Qu[None, :, :]) ** 2).sum(-1)
+        return np.maximum(un[m][3, rows][:, None] + un[m][3, :n][None, :] - 2 * Pu @ Qu.T, 0.0)
+
+    def dk_of(sd, ek):
+        zero = diag if "dk" in mut else (sd == 0) | diag
+        return np.where(zero, 0.0, ek * (-0.5 / sd))
+
+    te = [k for k, _ in terms].index(0) if 0 in [k for k, _ in terms] else -1
+    acc = np.zeros(16)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if passno == 0:
+            d2 = [dist2(m, mode == 1) for m in range(nt)]
+            d2s = sum(d2)
+            kfull = bias + sum((p[2] ** 2 * np.exp(-0.5 * p[1] * d2[m])) if k == 2 else
+                               ((p[6] if k == 0 else p[1]) ** 2 * np.exp(-np.sqrt(d2[m]))) for m, (k, p) in enumerate(terms))
+            acc[7] = (wgt * Qm * kfull).sum()
+            acc[8] = (QW * diag).sum()
+            if te >= 0:
+                e = np.asarray(terms[te][1])
+                Mp, m2 = grad_consts(e)
+                X = X4[:, :3]
+                sd = np.sqrt(d2[te])
+                ek = np.exp(-sd)
+                rm = e[6] ** 2 * QW * dk_of(sd, ek)
+                for p in range(6):
+                    pa_i, pa_j = (X[rows] ** 2) @ m2[p], (X ** 2) @ m2[p]
+                    di2 = pa_i[:, None] + pa_j[None, :] - 4.0 * (X[rows] @ Mp[p] @ X.T)
+                    acc[p] = (wgt * rm * di2).sum()
+                acc[6] = (wgt * QW * ek).sum()
+                dx = (X4[rows, 3][:, None] - X4[:, 3][None, :]) if d4 else np.zeros_like(sd)
+                acc[15] = (wgt * ek * dx * dx).sum()
+            for m, (k, p) in enumerate(terms):
+                if k == 1:       # Kern_Exponential on the summed D2
+                    sd = np.sqrt(d2s)
+                    kd = np.exp(-sd)
+                    acc[9 + 2 * m] = (wgt * QW * dk_of(sd, kd) * d2s).sum()
+                    acc[10 + 2 * m] = (wgt * QW * kd * kd).sum()
+                elif k == 2:     # Kern_RBF on the summed D2
+                    kd = np.exp(-0.5 * p[1] * d2s)
+                    acc[9 + 2 * m] = (wgt * QW * kd * d2s).sum()
+                    acc[10 + 2 * m] = (wgt * QW * kd).sum()
+        else:
+            W = wgt * QW
+            acc[0] = W.sum()
+            acc[1] = (QW * diag).sum()
+            for m, (k, p) in enumerate(terms):
+                d2 = dist2(m, True)
+                if k == 2:
+                    we = W * np.exp(-0.5 * p[1] * d2)
+                    acc[2 + m] = we.sum()
+                    acc[5 + m] = (we * d2).sum()
+                    continue
+                sd = np.sqrt(d2)
+                ek = np.exp(-sd)
+                wdk = W * dk_of(sd, ek)
+                acc[2 + m] = (W * ek).sum()
+                if m == te:
+                    D = [X4[rows, c][:, None] - X4[:, c][None, :] for c in range(4)]
+                    if not d4:
+                        D[3] = np.zeros_like(sd)
+                    for s, (ca, cb) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+                        acc[8 + s] = (wdk * D[ca] * D[cb]).sum()
+                    acc[14] = (wdk * D[3] * D[3]).sum()
+                else:
+                    acc[5 + m] = (wdk * d2).sum()
+    if "swap 9 10" in mut:
+        acc[[9, 10]] = acc[[10, 9]]
+    out[:16] = acc + 0.0                                   # -0.0 + 0.0 = +0.0: an unused slot is +0.0 as on the device
+
+
 class NumpyDistEngine:
     def __init__(self, poison_upper=True):
         """poison_upper: a diagonal fill_rect piece gets NaN in the tiles above its diagonal, which the device leaves as
@@ -185,59 +327,13 @@ class NumpyDistEngine:
                 out[:, c0:c0 + TILE] = Bi[:, u * TILE:(u + 1) * TILE]
 
         def grad_pairs_rows(st, u, cap, x_soa, xs, n, Np, y, f, alpha, binv, P, a, expans, bias, sn2, mode, part, out):
-            lib = gd._load()
-            e = np.array([expans[i] for i in range(8)])
-            M36, m2 = np.zeros(36), np.zeros(18)
-            lib.gpak_dev_grad_consts.argtypes = [gd._dp, gd._dp, gd._dp]
-            lib.gpak_dev_grad_consts(e.ctypes.data_as(gd._dp), M36.ctypes.data_as(gd._dp), m2.ctypes.data_as(gd._dp))
-            Mp = np.zeros((6, 3, 3))
-            for p in range(6):
-                v = M36[6 * p:6 * p + 6]
-                Mp[p] = [[v[0], v[1], v[2]], [v[1], v[3], v[4]], [v[2], v[4], v[5]]]
-            m2 = m2.reshape(6, 3)
-            un = _arr(u, 5 * cap).reshape(5, cap)
-            d4 = bool(mode & 0x10)
-            mode &= 0xF
-            X4 = _arr(x_soa, 4 * xs).reshape(4, xs)[:, :n].T
-            X = X4[:, :3]
-            al, yn, fn = _arr(alpha, Np)[:n], _arr(y, Np)[:n], _arr(f, Np)[:n]
-            rows, Tmax = my_rows(Np, P, a), my_tiles(Np, P, 0)
+            Ta, Tmax = my_tiles(Np, P, a), my_tiles(Np, P, 0)
             acc = np.zeros(17)
+            pair_sums(0, _arr(u, 5 * cap), cap, _arr(x_soa, 4 * xs), xs, n, Np, _arr(alpha, n),
+                      _arr(binv, max(Ta, 1) * TILE * P * Tmax * TILE), 0, P, a, [expans[i] for i in range(8)], bias, sn2,
+                      mode & ~0x20, acc[:16])
+            yn, fn = _arr(y, n), _arr(f, n)
             acc[16] = float(((yn - fn) ** 2 / sn2 - 1.0).sum())
-            rows = rows[rows < n]
-            if len(rows):
-                Bperm = _strided(binv, my_tiles(Np, P, a) * TILE, P * Tmax * TILE, my_tiles(Np, P, a) * TILE)
-                cols = np.arange(n)
-                cperm = ((cols // TILE % P) * Tmax + cols // TILE // P) * TILE + cols % TILE
-                loc = np.concatenate([np.arange(t * TILE, (t + 1) * TILE) for t in range(my_tiles(Np, P, a))])[:len(rows)]
-                Q = Bperm[loc][:, cperm]                              # (my rows) x n
-                sel = [0, 1, 2, 4] if d4 else [0, 1, 2]
-                Pu, Qu = un[sel][:, rows].T, un[sel][:, :n].T
-                if mode == 1:
-                    D2 = ((Pu[:, None, :] - Qu[None, :, :]) ** 2).sum(-1)
-                else:
-                    D2 = np.maximum(un[3, rows][:, None] + un[3, :n][None, :] - 2 * Pu @ Qu.T, 0.0)
-                low = rows[:, None] >= cols[None, :]
-                diag = rows[:, None] == cols[None, :]
-                wgt = np.where(diag, 1.0, 2.0) * low
-                sd = np.sqrt(D2)
-                ek = np.exp(-sd)
-                var2 = e[6] ** 2
-                QW = Q / sn2 - al[rows][:, None] * al[None, :]
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    dk = np.where((sd == 0) | diag, 0.0, ek * (-0.5 / sd))
-                rm = var2 * QW * dk
-                acc[7] = (wgt * Q * (bias + var2 * ek)).sum()
-                acc[8] = (QW * diag).sum()
-                acc[6] = (wgt * QW * ek).sum()
-                if d4:       # Kernel.cpp:1246-1255: weight KD2 (not R), Di2_R = 2 (x4_i - x4_j)^2; g7 = -4 acc[15] / N
-                    dx = X4[rows, 3][:, None] - X4[:, 3][None, :]
-                    acc[15] = (wgt * ek * dx * dx).sum()
-                for p in range(6):
-                    pa_i = (X[rows] ** 2) @ m2[p]
-                    pa_j = (X ** 2) @ m2[p]
-                    di2 = pa_i[:, None] + pa_j[None, :] - 4.0 * (X[rows] @ Mp[p] @ X.T)
-                    acc[p] = (wgt * rm * di2).sum()
             _arr(out, 17)[:] = acc
 
         # ---- the row-block x column-block layout (gpak_grid_*): rectangular pieces of LOCAL storage -------------

@@ -8,11 +8,11 @@ CPU (-m "not gpu"): the cases on the float64 restatement (tests/np_engine.py, te
 masks and bounds agree with what the project itself says the operations do.  GPU (-m gpu): the same cases on
 libgpak_hip.so, one fresh process per group.
 
-Not covered here: gpak_dev_stream_create / gpak_dev_stream_destroy, and the pair pass of the distributed gradient
-(gpak_dev_grad_pairs_rows, gpak_dev_grad_consts, gpak_dev_grad_finish / _finish_d: no bound of this file's kind exists
-for the pair sums), whose cover remains the distributed-gradient tests (tests/test_dist_cpp.py, tests/test_multigpu.py).
-The two linear-algebra operations of that gradient, gpak_dev_grad_g_rows and gpak_dev_grad_binv_rows, are the group
-`grad`.
+Not covered here: gpak_dev_stream_create / gpak_dev_stream_destroy.  The two linear-algebra operations of the
+distributed gradient, gpak_dev_grad_g_rows and gpak_dev_grad_binv_rows, are the group `grad`; the group `pairs` holds
+either pair pass of csrc/grad.hip alone (gpak_dev_grad_pair_sums, gpak_dev_grad_pairs_rows) to a long-double sum over
+the pairs, slot by slot, and the host ends of that chain (gpak_dev_grad_consts through the oracle, gpak_dev_grad_finish /
+_finish_d).
 
 Worst error / bound per group on an MI355X, and the float64-vs-long-double ratios that set the substitution
 tolerances: DESIGN.md, "Device-level operations alone".
@@ -29,8 +29,7 @@ import dev_ops_cases as dc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-NOT_COVERED = {"gpak_dev_stream_create", "gpak_dev_stream_destroy",
-               "gpak_dev_grad_pairs_rows", "gpak_dev_grad_consts", "gpak_dev_grad_finish", "gpak_dev_grad_finish_d"}
+NOT_COVERED = {"gpak_dev_stream_create", "gpak_dev_stream_destroy"}
 
 
 def _worker(engine, groups, timeout):
@@ -138,6 +137,30 @@ def test_the_checks_bite():
     name = "update_rect[256,1152,512,diag_first=0]"
     rec = dc.summarise(name, cases[name](Wrong("short k")), cases[name](Wrong("short k")))
     assert not rec["ok"] and float(rec["ratio"]) > 1e10, rec
+    _the_pair_checks_bite()
+
+
+def _the_pair_checks_bite():
+    """The same for the group `pairs`: wrong pair passes built on the float64 restatement (np_dist_engine.pair_sums) --
+    one pair doubled, dropped, read from above the diagonal or from the wrong column group, one operand mis-indexed, two
+    slots exchanged -- are at least 1000 bounds away, or show as NaN; the good engine is inside the bound."""
+    cases = {n: f for _g, n, _e, f in dc.CASES}
+    p0, p3, ex = ("pair_sums[as written,P=0,expans+bias,direct]", "pair_sums[as written,P=3,a=1,expans+bias,direct]",
+                  "pair_sums[exact,P=0,expans+bias,direct]")
+    good = dc.numpy_ops()
+    for name in (p0, p3, ex):
+        ok = dc.summarise(name, cases[name](good), cases[name](good))
+        assert ok["ok"] and 0 < ok["ratio"] < 1, ok
+    for how, name, want in (("diag2", p0, 1e3), ("last row", p0, 1e3), ("upper", p0, np.inf), ("unpermuted", p3, 1e3),
+                            ("alpha row", p0, 1e3), ("dk", p0, np.inf), ("swap 9 10", ex, 1e3), ("store", p0, None)):
+        wrong = dc.NumpyOps(mut=[how])
+        rec = dc.summarise(name, cases[name](wrong), cases[name](wrong))
+        print(how, rec["ratio"], rec["violations"])
+        assert not rec["ok"], (how, rec)
+        if want is None:
+            assert rec["violations"] == {"binv": 1}, (how, rec)
+        else:
+            assert float(rec["ratio"]) >= want and not rec["violations"], (how, rec)
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------
