@@ -15,7 +15,7 @@ SYMBOLS = [
     "gpak_create", "gpak_create_multi", "gpak_n_gpus", "gpak_transport", "gpak_destroy", "gpak_last_error", "gpak_global_error", "gpak_set_train",
     "gpak_set_params", "gpak_set_kernel", "gpak_set_option", "gpak_gram", "gpak_compute_k", "gpak_factor",
     "gpak_get_chol_upper", "gpak_failed_column", "gpak_solve_alpha", "gpak_solve_chol", "gpak_nlz",
-    "gpak_nlz_terms", "gpak_predict", "gpak_grad", "gpak_grad_hyb", "gpak_grad_exact", "gpak_timing", "gpak_calibrate", "gpak_reload_tuning",
+    "gpak_nlz_terms", "gpak_predict", "gpak_grad", "gpak_grad_hyb", "gpak_grad_exact", "gpak_loo", "gpak_timing", "gpak_calibrate", "gpak_reload_tuning",
 ]
 
 
@@ -26,6 +26,11 @@ class PhaseTimes(C.Structure):
                 ("trailing_launches", C.c_int), ("gram_bytes", C.c_double), ("n", C.c_int),
                 ("n_padded", C.c_int), ("trailing_bytes", C.c_double), ("kmatvec_ms", C.c_double),
                 ("accumulated_ms", C.c_double * 4), ("evaluations", C.c_int)]
+
+
+class LooSummary(C.Structure):
+    _fields_ = [("mse", C.c_double), ("mssr", C.c_double), ("log_pl", C.c_double), ("ms", C.c_double),
+                ("passes", C.c_int)]
 
 
 _lib = None
@@ -73,6 +78,7 @@ def load():
     lib.gpak_grad.argtypes = [vp, dp]
     lib.gpak_grad_hyb.argtypes = [vp, dp, C.c_int]
     lib.gpak_grad_exact.argtypes = [vp, dp, C.c_int]
+    lib.gpak_loo.argtypes = [vp, dp, dp, C.POINTER(LooSummary)]
     lib.gpak_timing.argtypes = [vp, C.POINTER(PhaseTimes)]
     lib.gpak_calibrate.argtypes = [vp, dp, dp]
     lib.gpak_reload_tuning.restype = None

@@ -369,6 +369,10 @@ int gpak_set_option(gpak_ctx *ctx, int option, long value) {
       if (value < 0 || value > 2) { ctx->err = "bwd_fused must be 0, 1 or 2"; return GPAK_EINVAL; }
       ctx->sched.bwd_fused = (int)value;
       return GPAK_OK;
+    case GPAK_OPT_LOO_ROWS:
+      if (value < 0 || value % 128) { ctx->err = "loo_rows must be 0 (the default) or a positive multiple of 128"; return GPAK_EINVAL; }
+      ctx->loo_rows = (int)std::min(value, 1L << 30);
+      return GPAK_OK;
   }
   ctx->err = "unknown option";
   return GPAK_EINVAL;
@@ -859,6 +863,23 @@ int gpak_grad_exact(gpak_ctx *ctx, double *g, int ng) {
   int rc = ensure_nlz(ctx);
   if (rc) return rc;
   return gpak_grad_exact_impl(ctx, g, ng);
+}
+
+int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary) {
+  if (!ctx) return GPAK_EINVAL;
+  if (ctx->multi) {
+    ctx->err = "gpak_loo is built for the single-GPU context (gpak_create) only";
+    return GPAK_ENOTIMPL;
+  }
+  int rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK) rc = gpak_loo_impl(ctx, mean, var, summary);
+  if (rc == GPAK_ENOTPD) {   // as gpak_nlz: GP_Utils.cpp:1145-1146
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int i = 0; mean && i < ctx->N; i++) mean[i] = nan;
+    for (int i = 0; var && i < ctx->N; i++) var[i] = nan;
+    if (summary) { summary->mse = summary->mssr = summary->log_pl = nan; summary->ms = 0.0; summary->passes = 0; }
+  }
+  return rc;
 }
 
 int gpak_timing(gpak_ctx *ctx, gpak_phase_times *out) {

@@ -145,6 +145,10 @@ struct gpak_ctx {
   double *dF = nullptr;      // Np: f = K*alpha of the last logLikelihood()
   double *dGpart = nullptr;  // per-workgroup partial sums of the pair pass
   size_t gpart_elems = 0;
+  // leave-one-out (gpak_loo): a slab of rows of L^-T of its own when the gradient has not allocated dG
+  double *dLoo = nullptr;
+  size_t loo_elems = 0;
+  int loo_rows = 0;           // GPAK_OPT_LOO_ROWS: rows of L^-T held at once (0: the default, 16384)
 
   // options
   GpakSchedule sched;         // this context's copy of the schedule set (gpak_set_option changes it)
@@ -394,6 +398,8 @@ void gpak_grad_release(gpak_ctx *ctx);
 // gpak_grad / gpak_grad_hyb and gpak_grad_exact on a single-GPU context whose factor and alpha are current
 int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng);
 int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng);
+// gpak_loo on a single-GPU context whose factor and alpha are current; mean, var, summary may each be null
+int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary);
 // Rot (Kernel.cpp:1399-1410) of the ExpAns parameters e; D (optional): D[a] = dRot / d angle_a
 void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]);
 void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *expans, int d, int N, double sn2,

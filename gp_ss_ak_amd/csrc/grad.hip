@@ -171,8 +171,9 @@ void gpak_grad_release(gpak_ctx *ctx) {
   if (ctx->dG) hipFree(ctx->dG);
   if (ctx->dBinv) hipFree(ctx->dBinv);
   if (ctx->dGpart) hipFree(ctx->dGpart);
-  ctx->dG = ctx->dBinv = ctx->dGpart = nullptr;
-  ctx->gpart_elems = 0;
+  if (ctx->dLoo) hipFree(ctx->dLoo);
+  ctx->dG = ctx->dBinv = ctx->dGpart = ctx->dLoo = nullptr;
+  ctx->gpart_elems = ctx->loo_elems = 0;
 }
 
 // Rot (Kernel.cpp:1399-1410) and, when D is given, its true derivatives D[a] = dRot / d angle_a,
@@ -660,6 +661,169 @@ static int grad_single(gpak_ctx *ctx, double *g, int ng) {
 }
 int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng) { return grad_single<RefPass>(ctx, g, ng); }
 int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng) { return grad_single<ExactPass>(ctx, g, ng); }
+
+// ---------------------------------------------------------------------------------------
+// Leave-one-out cross-validation (gpak_loo) from step 1 alone.  With Ky = K + sn2 I = sn2 B and B = L L^T,
+//   d_i = [B^-1]_ii = sum_{k >= i} G_ik^2,   var_i = sn2 / d_i,   mean_i = y_i - alpha_i var_i
+// (Rasmussen & Williams eq. 5.12).  G is formed by grad_g_subst in P passes; pass a holds the 128-row blocks
+// g = t*P + a in a compact slab, so N^2 doubles are never needed at once.  Per pass:
+//   gpak_loo_sumsq_f64    one partial per (row, 512-column chunk) of the slab;
+//   gpak_loo_rowsum_f64   d_i = the row's partials added in ascending chunk order.
+// The chunks are cut at ABSOLUTE column indices and the columns inside a chunk are dealt to the four waves by their
+// absolute index, so the order in which the squares of row i are added depends on i alone: d_i is the same number
+// whatever P, a or the leading dimension of the slab.  Then once, over the N rows: gpak_loo_finish_f64.
+// ---------------------------------------------------------------------------------------
+#define LOO_CHUNK 512   // columns per partial sum (a multiple of 128)
+#define LOO_DEFAULT_ROWS 16384
+
+// part[c * rows + r] = sum of G[r, k]^2 over the columns k >= 128 g of chunk c, for local row r of row block
+// g = (r / 128) * P + a.  Lanes run along the rows (the slab is column-major: one 16-byte load per lane, 1 KiB per
+// wave and column), wave w takes the columns k = w (mod 4).  Chunks left of the diagonal block are structural zeros:
+// neither read nor written (gpak_loo_rowsum_f64 starts at the diagonal's chunk).
+__global__ __launch_bounds__(256) void gpak_loo_sumsq_f64(const double *__restrict__ slab, long lds, int Np, int P, int a,
+                                                          long rows, double *__restrict__ part) {
+  const int t = blockIdx.x, c = blockIdx.y;
+  const int kd = (t * P + a) * PB;   // first column of the diagonal block
+  const int k1 = min(Np, (c + 1) * LOO_CHUNK);
+  if (k1 <= kd) return;
+  const int k0 = max(c * LOO_CHUNK, kd);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ double sh[4][PB];
+  const double *p = slab + (size_t)t * PB + 2 * lane + (size_t)(k0 + w) * lds;
+  const size_t step = 4 * (size_t)lds;
+  double s0 = 0.0, s1 = 0.0;
+  // k1 - k0 is a multiple of 128: 32 columns or more per wave, eight loads in flight per lane
+  for (int k = k0 + w; k < k1; k += 32) {
+    double2 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) v[u] = *reinterpret_cast<const double2 *>(p + u * step);
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      s0 = fma(v[u].x, v[u].x, s0);
+      s1 = fma(v[u].y, v[u].y, s1);
+    }
+    p += 8 * step;
+  }
+  sh[w][2 * lane] = s0;
+  sh[w][2 * lane + 1] = s1;
+  __syncthreads();
+  if (threadIdx.x < PB) {
+    const int r = threadIdx.x;
+    part[(size_t)c * rows + (size_t)t * PB + r] = ((sh[0][r] + sh[1][r]) + sh[2][r]) + sh[3][r];
+  }
+}
+
+// d[global row] = the row's partials, ascending from the chunk that holds its diagonal block
+__global__ __launch_bounds__(256) void gpak_loo_rowsum_f64(const double *__restrict__ part, long rows, int nch, int P, int a,
+                                                           double *__restrict__ d) {
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const long g = (r / PB) * P + a;
+  double s = 0.0;
+  for (int c = (int)(g * PB / LOO_CHUNK); c < nch; c++) s += part[(size_t)c * rows + r];
+  d[g * PB + r % PB] = s;
+}
+
+// var_i = sn2 / d_i, mean_i = y_i - alpha_i var_i for i < N (padding rows take no part) and, per workgroup,
+// part[block][NSUM]: [0] sum (y - mean)^2   [1] sum (y - mean)^2 / var   [2] sum log var -- reduced in fixed order by
+// gpak_grad_reduce_f64
+__global__ __launch_bounds__(256) void gpak_loo_finish_f64(int N, const double *__restrict__ d, const double *__restrict__ y,
+                                                           const double *__restrict__ alpha, double sn2,
+                                                           double *__restrict__ mean, double *__restrict__ var,
+                                                           double *__restrict__ part) {
+  __shared__ double red[4][3];
+  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double acc[3] = {0.0, 0.0, 0.0};
+  if (i < N) {
+    const double v = sn2 / d[i];
+    const double m = y[i] - alpha[i] * v;
+    var[i] = v;
+    mean[i] = m;
+    const double r = y[i] - m;
+    acc[0] = r * r;
+    acc[1] = r * r / v;
+    acc[2] = log(v);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) red[w][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3)
+    part[(size_t)blockIdx.x * NSUM + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np, T = Np / PB;
+  // where G goes: the gradient's N x N workspace once it exists (one pass), otherwise a slab of LOO's own
+  int P = 1;
+  long lds = ctx->ld;
+  double *slab = ctx->dG;
+  if (!slab) {
+    const long pad = ctx->ld - Np;   // the context's own padding of a leading dimension
+    int rt = std::min(T, (ctx->loo_rows > 0 ? ctx->loo_rows : LOO_DEFAULT_ROWS) / PB);   // row tiles held at once
+    for (;;) {
+      P = (T + rt - 1) / rt;
+      lds = (long)my_tiles(Np, P, 0) * PB + pad;
+      const size_t need = (size_t)lds * Np;
+      if (ctx->loo_elems >= need) break;
+      if (ctx->dLoo) hipFree(ctx->dLoo);
+      ctx->dLoo = nullptr; ctx->loo_elems = 0;
+      if (hipMalloc(&ctx->dLoo, sizeof(double) * need) == hipSuccess) { ctx->loo_elems = need; break; }
+      (void)hipGetLastError();
+      if (rt == 1) {
+        ctx->err = "device allocation failed for the leave-one-out workspace (128 rows of L^-T do not fit)";
+        return GPAK_ENOMEM;
+      }
+      rt = (rt + 1) / 2;   // hold fewer rows at once
+    }
+    slab = ctx->dLoo;
+  }
+  const int nch = (Np + LOO_CHUNK - 1) / LOO_CHUNK, nfin = (N + 255) / 256;
+  const long rows_max = (long)my_tiles(Np, P, 0) * PB;
+  // scratch in the gradient's partial-sum buffer: d, mean, var (Np each), the finish kernel's block sums, the chunk sums
+  int rc = grad_partials(ctx, 3 * (size_t)Np + (size_t)nfin * NSUM + (size_t)nch * rows_max);
+  if (rc) return rc;
+  double *dd = ctx->dGpart, *dmean = dd + Np, *dvar = dmean + Np, *fin = dvar + Np, *part = fin + (size_t)nfin * NSUM;
+  double *out = ctx->dRed + 32;
+  GPAK_HIP(hipEventRecord(ctx->ev[7], st));
+  const int GNB = 512;
+  for (int a = 0; a < P; a++) {
+    const int Ta = my_tiles(Np, P, a);
+    if (Ta == 0) continue;
+    const long rows = (long)Ta * PB;
+    grad_g_subst(st, Np, GNB, P, a, [&](int b) {
+      const size_t J = (size_t)b * GNB;
+      return LBlockCol{ctx->dM + J + J * ctx->ld, ctx->ld, ctx->dInv + J / PB * 2 * PB * PB};
+    }, slab, lds);
+    hipLaunchKernelGGL(gpak_loo_sumsq_f64, dim3(Ta, nch), dim3(256), 0, st, slab, lds, Np, P, a, rows, part);
+    hipLaunchKernelGGL(gpak_loo_rowsum_f64, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, part, rows, nch, P, a, dd);
+  }
+  hipLaunchKernelGGL(gpak_loo_finish_f64, dim3(nfin), dim3(256), 0, st, N, dd, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, fin);
+  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(3), dim3(256), 0, st, fin, nfin, out);
+  double red[3];
+  GPAK_HIP(hipMemcpyAsync(red, out, sizeof(red), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipEventRecord(ctx->ev[9], st));
+  if (mean) GPAK_HIP(hipMemcpyAsync(mean, dmean, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  if (var) GPAK_HIP(hipMemcpyAsync(var, dvar, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipStreamSynchronize(st));
+  GPAK_HIP(hipGetLastError());
+  float ms = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[9]));
+  if (summary) {
+    summary->mse = red[0] / N;
+    summary->mssr = red[1] / N;
+    summary->log_pl = -0.5 * (red[1] + red[2] + N * log(2.0 * M_PI));
+    summary->ms = ms;
+    summary->passes = P;
+  }
+  return GPAK_OK;
+}
 
 // ---------------------------------------------------------------------------------------
 // The as-written gradient distributed over P ranks that all hold the factor as packed panels (csrc/dist.hip):

@@ -19,6 +19,7 @@ OPT_MEMOISE, OPT_NB_OUTER, OPT_PROFILE, OPT_LOOKAHEAD = 1, 2, 3, 4
 OPT_NB_WIDE, OPT_NB_WIDE_ROWS, OPT_TAIL_ROWS, OPT_FIRST_NARROW, OPT_INV512, OPT_POTRF_CO, OPT_PRED_BATCH = 5, 6, 7, 8, 9, 10, 11
 OPT_BWD_FUSED = 12
 OPT_TAIL_MAX_NP = 13
+OPT_LOO_ROWS = 14
 KERN_EXPANS, KERN_EXP, KERN_RBF = 0, 1, 2
 
 _dp = C.POINTER(C.c_double)
@@ -164,6 +165,16 @@ class Gpak:
         g = np.zeros(int(ng))
         self._check(self._lib.gpak_grad_exact(self._h, _p(g), int(ng)))
         return g
+
+    def loo(self):
+        """Leave-one-out cross-validation from the current factor (gpak_loo): (mean, var, summary) with
+        summary = {mse, mssr, log_pl, ms, passes, status}.  On Chol_fail status is ENOTPD and every number is NaN."""
+        mean, var = np.zeros(self.N), np.zeros(self.N)
+        s = _lib.LooSummary()
+        rc = self._check(self._lib.gpak_loo(self._h, _p(mean), _p(var), C.byref(s)), allow=(ENOTPD,))
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        return mean, var, out
 
     # -- measurement ---------------------------------------------------------------------
     def timing(self):

@@ -1,9 +1,12 @@
 // gp_ss_ak.cpp -- the reference's command line (gp_ss_ak.cpp:14-557) over the HIP hot path:
 //   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] train.txt [model]
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
+//   gp_ss_ak [-v n]               [device options] cv [-np] train.txt model [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
 // (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only).
+// cv (not a reference verb): leave-one-out cross-validation of a trained model on its training set, from one
+// factorisation (gpak_loo; one GPU only), written to <model>_loo.txt.
 // Same verbs, flags and files (<model>, <model>_Statistics.txt, <model>_predict.txt,
 // <model>_gnu.plt); -np/--no-prompt skips the two interactive stdin questions of `train`
 // (gp_ss_ak.cpp:235-285) and the gnuplot call of `test` (:503-505).
@@ -32,13 +35,15 @@ class GP_Cntrl : public Control {
   }
   void train();
   void test();
+  void cv();
   void Help() const;
 };
 
 void GP_Cntrl::Help() const {
   std::cout << "\nGP_SS_AK hot path on MI355X\nCommand:\n \t ./gp_ss_ak [options] Command [Comnd-options] TrainDataFile.txt modelName\n"
             << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood.\n"
-            << "test :\n \t To estimate test data set and plot the results.\n";
+            << "test :\n \t To estimate test data set and plot the results.\n"
+            << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time.\n";
 }
 
 void GP_Cntrl::train() {
@@ -221,12 +226,73 @@ void GP_Cntrl::test() {
   exit(0);
 }
 
+void GP_Cntrl::cv() {
+  incArg();
+  setMode("cv");
+  if (gpus > 1)
+    ErrorTermination("cv runs on one GPU only (leave-one-out cross-validation is not built for multi-GPU contexts): drop --gpus");
+  bool yscale = true;
+  while (isFlgs()) {
+    if (isArgFlg()) {
+      if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
+      else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else UnkFlg();
+      incArg();
+    } else setFlgs(false);
+  }
+  if (getArgNo() + 1 >= argc) ErrorTermination("There are not enough input parameters: cv needs the training data and the model.");
+  std::string trFile = getArg(), modelName = argv[getArgNo() + 1];
+  std::string LooOut = modelName + "_loo.txt";
+  if (getArgNo() + 2 < argc) LooOut = argv[getArgNo() + 2];
+  int ds[2];
+  readDataSize(trFile, ds);
+  mat X, y;
+  readDataFile(X, y, ds, trFile);
+  prepareData(X, y, yscale, modelName);                         // the model's _Statistics.txt, as `test`
+  GP_utils *GPModel = readGpFromFile(modelName, getVerbose());  // parameters at 6 significant digits (Q5)
+  if (X.n_cols != GPModel->getInpDim()) ErrorTermination("Incorrect dimension of input data.");
+  GPModel->yTarg = y;
+  GPModel->Xinp = X;
+  GPModel->setNumData((unsigned)X.n_rows);
+  GPModel->initialize_vars();
+  GPModel->logLikelihood();
+  mat LooVals(y.n_rows, 1), LooVals_Var(y.n_rows, 1);
+  gpak_loo_summary s;
+  GPModel->LooCV(LooVals, LooVals_Var, s);
+  postData(X, LooVals, yscale, modelName);
+  postData_var(LooVals_Var, yscale, modelName);
+  postData(y, yscale, modelName);
+  double mse = 0, ym = 0, vy = 0;
+  for (size_t i = 0; i < y.n_elem; i++) { mse += (y[i] - LooVals[i]) * (y[i] - LooVals[i]); ym += y[i]; }
+  mse /= X.n_rows; ym /= y.n_elem;
+  for (size_t i = 0; i < y.n_elem; i++) vy += (y[i] - ym) * (y[i] - ym);
+  vy /= y.n_elem;
+  if (getVerbose() > 0) {
+    std::cout << "Mean Square Error of leave-one-out: " << mse << "\n" << "Var MSE Train: " << vy << "\n"
+              << "Mean standardised squared residual: " << s.mssr << "\n" << "Log pseudo-likelihood: " << s.log_pl << "\n"
+              << "LOO ms: " << s.ms << "\n";
+  } else { std::cout << mse << "\n" << vy << "\n" << s.mssr << "\n" << s.log_pl << "\n"; }
+  // rows in input order; the fourth column is what postData_var returns, as StdYh of _predict.txt
+  std::ofstream out(LooOut.c_str());
+  out << "# SampleNo, Y, Yloo, VarYloo, Inputs" << "\n";
+  for (size_t i = 0; i < y.n_elem; i++) {
+    out << (i + 1) << "\t" << y[i] << "\t" << LooVals[i] << "\t" << LooVals_Var[i] << "\t";
+    for (size_t j = 0; j < X.n_cols; j++) out << X(i, j) << "\t";
+    out << "\n";
+  }
+  out.close();
+  writeTiming(*GPModel);
+  delete GPModel;
+  exit(0);
+}
+
 int main(int argc, char **argv) {
   GP_Cntrl ctl(argc, argv);
   if (ctl.getArgNo() >= argc) { ctl.Help(); return 1; }
   std::string verb = ctl.getArg();
   if (verb == "train") ctl.train();
   else if (verb == "test") ctl.test();
+  else if (verb == "cv") ctl.cv();
   else if (verb == "-h" || verb == "--help" || verb == "-?") { ctl.Help(); return 0; }
   else ctl.ErrorTermination("Invalid command provided.");
   return 0;

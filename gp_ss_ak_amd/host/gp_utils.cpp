@@ -157,6 +157,15 @@ void GP_utils::posteriorMeanVar(mat &mu, mat &varSigma, const mat &Xin) const {
     gpak_host_fatal("gpak_predict", ctx);
 }
 
+void GP_utils::LooCV(mat &mean, mat &var, gpak_loo_summary &s) const {
+  sync_params();
+  if (mean.n_elem != Xinp.n_rows) mean.resize(Xinp.n_rows, 1);
+  if (var.n_elem != Xinp.n_rows) var.resize(Xinp.n_rows, 1);
+  int rc = gpak_loo(ctx, mean.memptr(), var.memptr(), &s);
+  Chol_fail = (rc == GPAK_ENOTPD);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_loo", ctx);
+}
+
 void GP_utils::Calc_Out(mat &yPred, mat &yVar, const mat &Xin) const { posteriorMeanVar(yPred, yVar, Xin); }
 
 void GP_utils::OptimisePars(unsigned int iters) {  // GP_Utils.cpp:1288-1301

@@ -7,9 +7,8 @@
 #include <limits>
 #include <string>
 
+#include "../../include/gpak.h"
 #include "kernels.hpp"
-
-struct gpak_ctx;
 
 class ModelInfo {
  public:
@@ -114,6 +113,9 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
 
   double logLikelihood() const;   // NaN on Chol_fail (GP_Utils.cpp:1145-1158)
   double GradLL(mat &g) const;    // g is 1 x getNumPars(); the exact gradient (gpak_grad_exact) when exact_gradient is set
+  // leave-one-out cross-validation of the training set from the current factor (gpak_loo): mean and variance (noise
+  // included) of every yTarg(i) given all the other samples, N x 1 each; NaN on Chol_fail
+  void LooCV(mat &mean, mat &var, gpak_loo_summary &s) const;
   void OptimisePars(unsigned int iters);
   void updateKernel() const;
   std::ostream &ShowKernelPars(std::ostream &os) const;

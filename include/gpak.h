@@ -118,6 +118,7 @@ int gpak_set_kernel(gpak_ctx *ctx, int nterms, const int *kinds, const double *p
 #define GPAK_OPT_BWD_FUSED   12  /* back substitution (needs INV512): 0 three launches per 512 columns, 1 the far column
                                     dots of the next block under this block's diagonal step, 2 (default) one launch  */
 #define GPAK_OPT_TAIL_MAX_NP 13  /* padded sizes above this factor without the CU-masked tail queue (0: no limit)       */
+#define GPAK_OPT_LOO_ROWS    14  /* rows of L^-T held at once (multiple of 128; 0: default)                              */
 int gpak_set_option(gpak_ctx *ctx, int option, long value);
 
 /* ---- hot path --------------------------------------------------------------------------- */
@@ -179,6 +180,25 @@ int gpak_grad_hyb(gpak_ctx *ctx, double *g, int ng);
  * stale, sets grad_ms, and leaves factor, alpha and nlZ valid.  Same cost as gpak_grad: the N^3 inverse is shared.
  * GPAK_ENOTIMPL for a composition with a White child and for a multi-GPU context (use a gpak_create context). */
 int gpak_grad_exact(gpak_ctx *ctx, double *g, int ng);
+
+/* Leave-one-out cross-validation from the one factor the context holds (no refit; Rasmussen & Williams, Gaussian
+ * Processes for Machine Learning, eq. 5.12).  With Ky = K + sn2 I = sn2 B, B = L L^T and alpha = Ky^-1 y:
+ *   d_i = [B^-1]_ii = sum_{k >= i} G_ik^2, G = L^-T;   var_i = sn2 / d_i;   mean_i = y_i - alpha_i var_i
+ * are the variance (noise included) and the mean of y_i given all the other samples.  G is formed in `passes` row
+ * slabs of at most GPAK_OPT_LOO_ROWS rows (the gradient's workspace is used instead once it exists); the result does
+ * not depend on the slab height.  Everything is fp64, also in a GPAK_F32 context.  Needs no kernel parameters: works for
+ * every composition of gpak_set_kernel, White children included.  Runs gram / factor / alpha if they are stale and leaves
+ * factor, alpha and nlZ valid.  On GPAK_ENOTPD every output passed is filled with quiet NaN.  GPAK_ENOTIMPL for a
+ * multi-GPU context. */
+typedef struct {
+  double mse;        /* mean of (y_i - mu_i)^2                                           */
+  double mssr;       /* mean of (y_i - mu_i)^2 / var_i: 1 for a calibrated model         */
+  double log_pl;     /* sum_i log N(y_i; mu_i, var_i), the LOO log pseudo-likelihood     */
+  double ms;         /* device time of this call (substitution + the two passes)         */
+  int    passes;     /* P                                                                */
+} gpak_loo_summary;
+/* mean (N), var (N), summary: each may be NULL */
+int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 typedef struct {
