@@ -882,6 +882,35 @@ int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary
   return rc;
 }
 
+static int block_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *var,
+                      int flags, double *Kbar_host) {
+  if (ctx->multi) {
+    ctx->err = std::string(name) + " is built for the single-GPU context (gpak_create) only";
+    return GPAK_ENOTIMPL;
+  }
+  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
+  if (d != ctx->d) { ctx->err = "block points must have as many columns as the training set"; return GPAK_EINVAL; }
+  int rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK) rc = gpak_predict_block_impl(ctx, Xd, M, nd, mean, var, flags, Kbar_host);
+  if (rc == GPAK_ENOTPD) {   // as gpak_loo
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (long i = 0; mean && i < M; i++) mean[i] = nan;
+    for (long i = 0; var && i < M; i++) var[i] = nan;
+    for (size_t i = 0; Kbar_host && i < (size_t)M * ctx->N; i++) Kbar_host[i] = nan;
+  }
+  return rc;
+}
+
+int gpak_block_cross(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, double *Kbar_host) {
+  if (!ctx || !Xd || !Kbar_host || M <= 0 || nd <= 0) return GPAK_EINVAL;
+  return block_call(ctx, "gpak_block_cross", Xd, M, nd, d, nullptr, nullptr, 0, Kbar_host);
+}
+
+int gpak_predict_block(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, double *mean, double *var, int flags) {
+  if (!ctx || !Xd || !mean || M <= 0 || nd <= 0) return GPAK_EINVAL;
+  return block_call(ctx, "gpak_predict_block", Xd, M, nd, d, mean, var, flags, nullptr);
+}
+
 int gpak_timing(gpak_ctx *ctx, gpak_phase_times *out) {
   if (!ctx || !out) return GPAK_EINVAL;
   if (ctx->multi) return gpak_multi_timing(ctx->multi, out);

@@ -134,6 +134,11 @@ struct gpak_ctx {
   double *dPart = nullptr;   // 64 x pred_cap partial sums
   int pred_cap = 0;
   size_t wt_elems = 0;
+  // block-support prediction (gpak_predict_block): a batch's discretisation points, raw (4 columns) and transformed
+  // point-major (gpak_transform_blocks_f64), blk_points points of blk_terms terms each
+  double *dXblk = nullptr, *dTblk = nullptr;
+  size_t blk_points = 0;
+  int blk_terms = 0;
   // fp32 prediction (ctx created with GPAK_F32): fp32 images of L and of the inverse blocks
   float *dLf = nullptr, *dInvf = nullptr;
   long ldLf = 0;             // leading dimension of dLf (Np + skew)
@@ -289,6 +294,14 @@ void gpak_launch_transform(hipStream_t st, const double *x, int xs, int n, const
 void gpak_launch_fill(hipStream_t st, const DevPoints &P, const DevPoints &Q, int rows_p, int cols_p,
                       const KernParams &kp, double scale, double diag, double pad_diag, int lower_only,
                       double *C, long ld, double *D2out, int col_off = 0);
+// Block-support prediction: the points of nb blocks of nd points each, x[k * xs + r * nd + a], transformed into out
+// point-major (point a of block r at a * cap + r, arrays nd * cap apart); the block-averaged cross-kernel of those
+// blocks against Q, rows_p x cols_p in the fill's layout; kbb[r] = the prior variance of block r's average.
+void gpak_launch_transform_blocks(hipStream_t st, const double *x, long xs, int nb, int nd, int cap,
+                                  const KernParams &kp, double *out);
+void gpak_launch_fill_blocks(hipStream_t st, const double *P, int cap, int nB, int nd, const DevPoints &Q, int rows_p,
+                             int cols_p, const KernParams &kp, double *C, long ld);
+void gpak_launch_block_self(hipStream_t st, const double *P, int cap, int nB, int nd, const KernParams &kp, double *kbb);
 // out_j = sum_i w_i K(P_i, Q_j), j < Q.n   (fused Gram-matvec; K never stored).
 // scratch holds max(splits, scratch_rows) * Q.cap doubles (scratch_rows: what the caller really has; the symmetric
 // kernel for P == Q needs one row per 512 points).
@@ -371,6 +384,9 @@ void gpak_launch_axpy(hipStream_t st, int n, double a, const double *x, double *
 
 // ---- predict.hip ------------------------------------------------------------------------
 void gpak_predict_release(gpak_ctx *ctx);
+// gpak_predict_block / gpak_block_cross on a single-GPU context whose factor and alpha are current
+int gpak_predict_block_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mean, double *var, int flags,
+                            double *Kbar_host);
 
 // ---- the distributed factor as one rank holds it (dist.hip), handed to a single-GPU context of the SAME device
 // (multi.hip: group prediction and solve_chol reuse the factor instead of factoring a replica again) ----

@@ -14,15 +14,8 @@
 // ---------------------------------------------------------------------------------------
 // u = (x - mu) A_t  (Kernel.cpp:1393-1427 / :1356-1362), s = |u|^2 ("sum(X1 % X1, 1)", :1431)
 // ---------------------------------------------------------------------------------------
-__global__ void gpak_transform_f64(const double *__restrict__ x, int xs, int n, int cap, KernParams kp,
-                                   double *__restrict__ out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cap) return;
-  double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-  if (i < n) {
-    c0 = x[i] - kp.mu[0]; c1 = x[(size_t)xs + i] - kp.mu[1]; c2 = x[2 * (size_t)xs + i] - kp.mu[2];
-    if (kp.d == 4) c3 = x[3 * (size_t)xs + i] - kp.mu[3];
-  }
+__device__ __forceinline__ void gpak_transform_store(double c0, double c1, double c2, double c3, const KernParams &kp,
+                                                     double *__restrict__ out, size_t cap, size_t i) {
   for (int t = 0; t < kp.nterms; t++) {
     const double *A = kp.term[t].A;
     const double a = c0 * A[0] + c1 * A[1] + c2 * A[2];
@@ -35,11 +28,48 @@ __global__ void gpak_transform_f64(const double *__restrict__ x, int xs, int n, 
   }
 }
 
+__global__ void gpak_transform_f64(const double *__restrict__ x, int xs, int n, int cap, KernParams kp,
+                                   double *__restrict__ out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cap) return;
+  double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+  if (i < n) {
+    c0 = x[i] - kp.mu[0]; c1 = x[(size_t)xs + i] - kp.mu[1]; c2 = x[2 * (size_t)xs + i] - kp.mu[2];
+    if (kp.d == 4) c3 = x[3 * (size_t)xs + i] - kp.mu[3];
+  }
+  gpak_transform_store(c0, c1, c2, c3, kp, out, cap, i);
+}
+
+// The discretisation points of a batch of blocks (block-support prediction).  x: column k of point a of block r at
+// x[k * xs + r * nd + a] (the caller's row order); out: POINT-MAJOR, point a of block r at index a * cap + r of each
+// array, the arrays nd * cap apart, so that a wave of the averaged fill reads 128 consecutive blocks of one point.
+// Blocks r >= nb are written as the zero point (the fill masks their rows).
+__global__ void gpak_transform_blocks_f64(const double *__restrict__ x, long xs, int nb, int nd, int cap, KernParams kp,
+                                          double *__restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, tot = (size_t)nd * cap;
+  if (i >= tot) return;
+  const int a = (int)(i / cap), r = (int)(i % cap);
+  double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+  if (r < nb) {
+    const size_t s = (size_t)r * nd + a;
+    c0 = x[s] - kp.mu[0]; c1 = x[(size_t)xs + s] - kp.mu[1]; c2 = x[2 * (size_t)xs + s] - kp.mu[2];
+    if (kp.d == 4) c3 = x[3 * (size_t)xs + s] - kp.mu[3];
+  }
+  gpak_transform_store(c0, c1, c2, c3, kp, out, tot, i);
+}
+
 void gpak_launch_transform(hipStream_t st, const double *x, int xs, int n, const KernParams &kp,
                            DevPoints &out) {
   int cap = out.cap;
   hipLaunchKernelGGL(gpak_transform_f64, dim3((cap + 255) / 256), dim3(256), 0, st, x, xs, n, cap, kp, out.base);
   out.n = n;
+}
+
+void gpak_launch_transform_blocks(hipStream_t st, const double *x, long xs, int nb, int nd, int cap,
+                                  const KernParams &kp, double *out) {
+  const size_t tot = (size_t)nd * cap;
+  hipLaunchKernelGGL(gpak_transform_blocks_f64, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, xs, nb, nd, cap,
+                     kp, out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -115,9 +145,10 @@ __global__ __launch_bounds__(256) void gpak_fill_f64(const double *__restrict__ 
 //   * a workgroup keeps both stores of a trip in flight while it computes the next trip.
 // VALU floor 0.48 ms and store floor 0.78 ms (5.5 TB/s, tools/store_bw.hip) at N=32768 instead of 0.78 + 0.78.
 // ---------------------------------------------------------------------------------------
+// exp(-sqrt(D2)) of one pair
 template <int MODE, bool D4>
-__device__ __forceinline__ double gpak_k1(double p0, double p1, double p2, double ps, double p3, double q0, double q1,
-                                          double q2, double qs, double q3, double sv, double sb, const double *tab) {
+__device__ __forceinline__ double gpak_e1(double p0, double p1, double p2, double ps, double p3, double q0, double q1,
+                                          double q2, double qs, double q3, const double *tab) {
   double d;
   if (MODE == GPAK_DIST_DIRECT) {
     const double a = p0 - q0, b = p1 - q1, c = p2 - q2;
@@ -129,7 +160,12 @@ __device__ __forceinline__ double gpak_k1(double p0, double p1, double p2, doubl
     d = ps + qs - 2.0 * dot;
     d = d < 0.0 ? 0.0 : d;
   }
-  return fma(sv, gpak_exp_neg_tab(gpak_sqrt_nonneg_fast(d), tab), sb);
+  return gpak_exp_neg_tab(gpak_sqrt_nonneg_fast(d), tab);
+}
+template <int MODE, bool D4>
+__device__ __forceinline__ double gpak_k1(double p0, double p1, double p2, double ps, double p3, double q0, double q1,
+                                          double q2, double qs, double q3, double sv, double sb, const double *tab) {
+  return fma(sv, gpak_e1<MODE, D4>(p0, p1, p2, ps, p3, q0, q1, q2, qs, q3, tab), sb);
 }
 
 template <int MODE, bool D4>
@@ -208,6 +244,171 @@ void gpak_launch_fill(hipStream_t st, const DevPoints &P, const DevPoints &Q, in
   else
     hipLaunchKernelGGL(gpak_fill_f64<0>, grid, dim3(256), 0, st, P.base, P.cap, P.n, Q.base, Q.cap, Q.n, kp, scale,
                        diag, pad_diag, lower_only, C, ld, D2out, col_off);
+}
+
+// ---------------------------------------------------------------------------------------
+// Block-averaged cross-kernel (block-support prediction): C[r, j] = (1/nd) sum_a k(x_{r,a}, q_j) for block r and
+// training sample j, in the tile shape and layout of the fills above (rows = blocks; 128 x 64 per workgroup; a wave
+// stores 128 consecutive rows of one column; padding rows and columns are zeros).  nd kernel evaluations per stored
+// element make it fp64-VALU bound from nd = 2 on, where the point fill is bound by its stores.
+// P holds the blocks' points point-major (gpak_transform_blocks_f64).  The loop over the points is OUTERMOST: a lane
+// loads its two rows of point a once (16 B per array) and adds that point's value to the accumulators of all 16 columns
+// its wave owns, so every transformed point is read once per workgroup tile; the columns' coordinates come from LDS
+// (wave-uniform addresses: broadcast reads).  Per element the nd values are added in ascending a and the sum is
+// multiplied once by var2/nd (general path: 1/nd) before the bias is added.  No white-noise term: the blocks are never
+// the training set.
+// ---------------------------------------------------------------------------------------
+#define BLK_WCOLS (FILL_COLS / 4)   // columns per wave
+template <int MODE, bool D4>
+__global__ __launch_bounds__(256) void gpak_fillblk1_f64(const double *__restrict__ P, int cap, int nB, int nd,
+                                                          const double *__restrict__ Q, int capQ, int nQ, double svn,
+                                                          double sb, double *__restrict__ C, long ld) {
+  const int row0 = blockIdx.x * FILL_ROWS, col0 = blockIdx.y * FILL_COLS;
+  __shared__ double q[GPAK_PT][FILL_COLS];
+  __shared__ double tab[GPAK_EXPTAB_N];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  if (t < FILL_COLS) {
+    const int j = col0 + t;
+    const bool ok = j < nQ;
+#pragma unroll
+    for (int c = 0; c < GPAK_PT; c++) q[c][t] = ok ? PARR(Q, capQ, 0, c)[j] : 0.0;
+  } else if (t < FILL_COLS + GPAK_EXPTAB_N) {
+    tab[t - FILL_COLS] = gpak_exp2_tab[t - FILL_COLS];
+  }
+  const int r = row0 + 2 * lane;
+  const size_t capP = (size_t)nd * cap;
+  double2 acc[BLK_WCOLS];
+#pragma unroll
+  for (int c = 0; c < BLK_WCOLS; c++) acc[c] = make_double2(0.0, 0.0);
+  __syncthreads();
+  // the next point's coordinates are loaded before this point's 32 evaluations: with the columns' coordinates held in
+  // registers across the loop (the compiler hoists the LDS reads) only one or two waves fit a SIMD
+  const double2 zero = make_double2(0.0, 0.0);
+#define GPAK_BLK_LOAD(c_, o_) (*reinterpret_cast<const double2 *>(PARR(P, capP, 0, c_) + (o_)))
+  double2 n0 = GPAK_BLK_LOAD(0, r), n1 = GPAK_BLK_LOAD(1, r), n2 = GPAK_BLK_LOAD(2, r);
+  double2 ns = MODE == GPAK_DIST_DIRECT ? zero : GPAK_BLK_LOAD(3, r);
+  double2 n3 = D4 ? GPAK_BLK_LOAD(4, r) : zero;
+  for (int a = 0; a < nd; a++) {
+    const double2 p0 = n0, p1 = n1, p2 = n2, ps = ns, p3 = n3;
+    const size_t o = (size_t)min(a + 1, nd - 1) * cap + r;
+    n0 = GPAK_BLK_LOAD(0, o); n1 = GPAK_BLK_LOAD(1, o); n2 = GPAK_BLK_LOAD(2, o);
+    if (MODE != GPAK_DIST_DIRECT) ns = GPAK_BLK_LOAD(3, o);
+    if (D4) n3 = GPAK_BLK_LOAD(4, o);
+#pragma unroll
+    for (int c = 0; c < BLK_WCOLS; c++) {
+      const int jl = w + 4 * c;
+      acc[c].x += gpak_e1<MODE, D4>(p0.x, p1.x, p2.x, ps.x, p3.x, q[0][jl], q[1][jl], q[2][jl], q[3][jl], q[4][jl], tab);
+      acc[c].y += gpak_e1<MODE, D4>(p0.y, p1.y, p2.y, ps.y, p3.y, q[0][jl], q[1][jl], q[2][jl], q[3][jl], q[4][jl], tab);
+    }
+  }
+#undef GPAK_BLK_LOAD
+#pragma unroll
+  for (int c = 0; c < BLK_WCOLS; c++) {
+    const int j = col0 + w + 4 * c;
+    const bool cj = j < nQ;
+    // svn = var2 / nd: the average of the constant is the constant
+    const double k0 = (cj && r < nB) ? fma(svn, acc[c].x, sb) : 0.0;
+    const double k1 = (cj && r + 1 < nB) ? fma(svn, acc[c].y, sb) : 0.0;
+    *reinterpret_cast<double2 *>(C + r + (size_t)j * ld) = make_double2(k0, k1);
+  }
+}
+
+// any composition: up to GPAK_MAX_TERMS terms at run time, device-libm-free exp / sqrt of gpak_profile
+__global__ __launch_bounds__(256) void gpak_fillblk_f64(const double *__restrict__ P, int cap, int nB, int nd,
+                                                         const double *__restrict__ Q, int capQ, int nQ, KernParams kp,
+                                                         double inv_nd, double *__restrict__ C, long ld) {
+  const int row0 = blockIdx.x * FILL_ROWS, col0 = blockIdx.y * FILL_COLS;
+  __shared__ double q[GPAK_MAX_TERMS][GPAK_PT][FILL_COLS];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int nterms = kp.nterms;
+  if (t < FILL_COLS) {
+    const int j = col0 + t;
+    const bool ok = j < nQ;
+    for (int m = 0; m < nterms; m++)
+#pragma unroll
+      for (int c = 0; c < GPAK_PT; c++) q[m][c][t] = ok ? PARR(Q, capQ, m, c)[j] : 0.0;
+  }
+  const int r = row0 + 2 * lane;
+  const size_t capP = (size_t)nd * cap;
+  double2 acc[BLK_WCOLS];
+#pragma unroll
+  for (int c = 0; c < BLK_WCOLS; c++) acc[c] = make_double2(0.0, 0.0);
+  __syncthreads();
+  for (int a = 0; a < nd; a++) {
+    const size_t o = (size_t)a * cap + r;
+    for (int m = 0; m < nterms; m++) {
+      double2 p[GPAK_PT];
+#pragma unroll
+      for (int c = 0; c < GPAK_PT; c++) p[c] = *reinterpret_cast<const double2 *>(PARR(P, capP, m, c) + o);
+#pragma unroll
+      for (int c = 0; c < BLK_WCOLS; c++) {
+        const int jl = w + 4 * c;
+        acc[c].x += gpak_profile(gpak_d2(p[0].x, p[1].x, p[2].x, p[3].x, p[4].x, q[m][0][jl], q[m][1][jl], q[m][2][jl],
+                                         q[m][3][jl], q[m][4][jl], kp.mode), kp.term[m]);
+        acc[c].y += gpak_profile(gpak_d2(p[0].y, p[1].y, p[2].y, p[3].y, p[4].y, q[m][0][jl], q[m][1][jl], q[m][2][jl],
+                                         q[m][3][jl], q[m][4][jl], kp.mode), kp.term[m]);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < BLK_WCOLS; c++) {
+    const int j = col0 + w + 4 * c;
+    const bool cj = j < nQ;
+    const double k0 = (cj && r < nB) ? fma(inv_nd, acc[c].x, kp.bias) : 0.0;
+    const double k1 = (cj && r + 1 < nB) ? fma(inv_nd, acc[c].y, kp.bias) : 0.0;
+    *reinterpret_cast<double2 *>(C + r + (size_t)j * ld) = make_double2(k0, k1);
+  }
+}
+
+// P: nd * cap points point-major, nB valid blocks; fills rows_p x cols_p (multiples of 128 / 64; rows_p <= cap)
+void gpak_launch_fill_blocks(hipStream_t st, const double *P, int cap, int nB, int nd, const DevPoints &Q, int rows_p,
+                             int cols_p, const KernParams &kp, double *C, long ld) {
+  dim3 grid(rows_p / FILL_ROWS, cols_p / FILL_COLS);
+  if (kp.nterms == 1 && kp.term[0].profile == GPAK_PROFILE_EXPSQRT && gpak_tuning().fill_fast) {
+    const double svn = kp.term[0].var2 / nd;
+#define GPAK_FILLB1(MODE_, D4_)                                                                                       \
+  hipLaunchKernelGGL((gpak_fillblk1_f64<MODE_, D4_>), grid, dim3(256), 0, st, P, cap, nB, nd, Q.base, Q.cap, Q.n, svn, \
+                     kp.bias, C, ld)
+    const bool d4 = kp.d == 4;
+    if (kp.mode == GPAK_DIST_DIRECT) { if (d4) GPAK_FILLB1(GPAK_DIST_DIRECT, true); else GPAK_FILLB1(GPAK_DIST_DIRECT, false); }
+    else { if (d4) GPAK_FILLB1(GPAK_DIST_EXPANSION, true); else GPAK_FILLB1(GPAK_DIST_EXPANSION, false); }
+#undef GPAK_FILLB1
+    return;
+  }
+  hipLaunchKernelGGL(gpak_fillblk_f64, grid, dim3(256), 0, st, P, cap, nB, nd, Q.base, Q.cap, Q.n, kp, 1.0 / nd, C, ld);
+}
+
+// kbb[r] = (1/nd^2) sum_{a,a'} k(x_{r,a}, x_{r,a'}) + white/nd: the prior variance of the average of block r.  One wave
+// per block; lane l takes the pairs l, l + 64, ... in ascending order and the 64 partial sums are added in lane order.
+// M nd^2 evaluations, nothing beside the fill's M N nd.
+__global__ __launch_bounds__(64) void gpak_block_self_f64(const double *__restrict__ P, int cap, int nB, int nd,
+                                                          KernParams kp, double *__restrict__ kbb) {
+  __shared__ double part[64];
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const size_t capP = (size_t)nd * cap;
+  const long npair = (long)nd * nd;
+  double s = 0.0;
+  for (long e = lane; e < npair; e += 64) {
+    const size_t oa = (size_t)(e / nd) * cap + r, ob = (size_t)(e % nd) * cap + r;
+    double k = kp.bias;
+    for (int m = 0; m < kp.nterms; m++)
+      k += gpak_profile(gpak_d2(PARR(P, capP, m, 0)[oa], PARR(P, capP, m, 1)[oa], PARR(P, capP, m, 2)[oa],
+                                PARR(P, capP, m, 3)[oa], PARR(P, capP, m, 4)[oa], PARR(P, capP, m, 0)[ob],
+                                PARR(P, capP, m, 1)[ob], PARR(P, capP, m, 2)[ob], PARR(P, capP, m, 3)[ob],
+                                PARR(P, capP, m, 4)[ob], kp.mode), kp.term[m]);
+    s += k;
+  }
+  part[lane] = s;
+  __syncthreads();
+  if (lane == 0) {
+    double tot = 0.0;
+    for (int u = 0; u < 64; u++) tot += part[u];
+    kbb[r] = tot / ((double)nd * (double)nd) + kp.white / nd;
+  }
+}
+
+void gpak_launch_block_self(hipStream_t st, const double *P, int cap, int nB, int nd, const KernParams &kp, double *kbb) {
+  hipLaunchKernelGGL(gpak_block_self_f64, dim3(nB), dim3(64), 0, st, P, cap, nB, nd, kp, kbb);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -33,7 +33,24 @@ __global__ __launch_bounds__(256) void gpak_rowsumsq_part_f64(const double *__re
   part[(size_t)blockIdx.y * part_ld + t] = s0 + s1;
 }
 
+// part[split][t] = sum over the split's columns of V[t, c] * x[c], columns in ascending order
+__global__ __launch_bounds__(256) void gpak_rowdot_part_f64(const double *__restrict__ V, long ldv, int rows, int cols,
+                                                             int cols_per_split, const double *__restrict__ x,
+                                                             double *__restrict__ part, int part_ld) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= rows) return;
+  const int c0 = blockIdx.y * cols_per_split;
+  const int c1 = min(cols, c0 + cols_per_split);
+  double s = 0.0;
+  for (int c = c0; c < c1; c++) s = fma(V[t + (size_t)c * ldv], x[c], s);
+  part[(size_t)blockIdx.y * part_ld + t] = s;
+}
+
 void gpak_predict_release(gpak_ctx *ctx) {
+  if (ctx->dXblk) hipFree(ctx->dXblk);
+  if (ctx->dTblk) hipFree(ctx->dTblk);
+  ctx->dXblk = ctx->dTblk = nullptr;
+  ctx->blk_points = 0;
   if (ctx->Upred.base) hipFree(ctx->Upred.base);
   if (ctx->Tq.base) hipFree(ctx->Tq.base);
   ctx->Upred = DevPoints(); ctx->Tq = DevPoints();
@@ -245,6 +262,106 @@ int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, do
       GPAK_HIP(hipStreamSynchronize(st));
       // varSigma = kD - sum(LKs % kX) with LKs = sW . B^-1 . sW kX   (GP_Utils.cpp:985-999)
       for (int i = 0; i < mb; i++) var[b0 + i] = kD - hsq[i] / ctx->sn2;
+    }
+  }
+  GPAK_HIP(hipEventRecord(e1, st));
+  GPAK_HIP(hipEventSynchronize(e1));
+  float ms = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, e0, e1));
+  ctx->times.predict_ms = ms;
+  return GPAK_OK;
+}
+
+// Block-support prediction (gpak_predict_block / gpak_block_cross): block b = the nd points Xd[b * nd .. b * nd + nd).
+//   kbar_b = (1/nd) sum_a k(X, x_{b,a})                       the averaged fill, test-major like the point path's batch
+//   mean_b = kbar_b . alpha                                   from the stored batch, before the substitution overwrites it
+//   var_b  = max(0, kbb_b - |L^-1 kbar_b|^2 / sn2) [+ sn2/nd]  ONE substitution per block, not one per point
+// Same batch loop, buffers, substitution and row sums as gpak_predict_impl; everything fp64 whatever the context's
+// precision.  Kbar_host (N x M, column-major) set: only the averaged fill runs and its batches are copied out.
+int gpak_predict_block_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mean, double *var, int flags,
+                            double *Kbar_host) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np, d = ctx->d;
+  KernParams kp = ctx->kp;
+  kp.d = d;
+  int batch = 16384;   // blocks per batch
+  if (ctx->sched.pred_batch > 0) batch = std::max(2 * PB, ctx->sched.pred_batch / (2 * PB) * (2 * PB));
+  while (batch > 2 * PB && (size_t)batch * Np * sizeof(double) > ((size_t)8 << 30)) batch /= 2;
+  // raw (4) and transformed (GPAK_PT per term) coordinates of the batch's points: about 1 GiB at most
+  const size_t per_block = sizeof(double) * (size_t)nd * (4 + GPAK_PT * (size_t)kp.nterms);
+  while (batch > 2 * PB && (size_t)batch * per_block > ((size_t)1 << 30)) batch /= 2;
+  batch = batch / (2 * PB) * (2 * PB);
+  const long Mp = (M + 2 * PB - 1) / (2 * PB) * (2 * PB);
+  const int cap = (int)std::min<long>(Mp, batch);
+  if ((size_t)cap * nd > ((size_t)1 << 30)) { ctx->err = "too many discretisation points per block"; return GPAK_EINVAL; }
+  int rc = ensure_predict_bufs(ctx, cap, true);
+  if (rc) return rc;
+  const size_t points = (size_t)cap * nd;
+  if (ctx->blk_points < points || ctx->blk_terms < kp.nterms) {
+    if (ctx->dXblk) hipFree(ctx->dXblk);
+    if (ctx->dTblk) hipFree(ctx->dTblk);
+    ctx->dXblk = ctx->dTblk = nullptr; ctx->blk_points = 0;
+    if (hipMalloc(&ctx->dXblk, sizeof(double) * 4 * points) != hipSuccess ||
+        hipMalloc(&ctx->dTblk, sizeof(double) * GPAK_PT * kp.nterms * points) != hipSuccess) {
+      ctx->err = "device allocation failed for the blocks' discretisation points";
+      return GPAK_ENOMEM;
+    }
+    ctx->blk_points = points; ctx->blk_terms = kp.nterms;
+  }
+  hipEvent_t e0 = ctx->ev[5], e1 = ctx->ev[6];
+  GPAK_HIP(hipEventRecord(e0, st));
+
+  // pooled mean over the training set and all M * nd points, as gpak_predict on the flattened set
+  const long Mn = M * nd;
+  double s2[4] = {0, 0, 0, 0};
+  for (int k = 0; k < d; k++)
+    for (long i = 0; i < Mn; i++) s2[k] += Xd[i + (size_t)k * Mn];
+  gpak_pooled_mean(ctx->xsum, N, s2, Mn, kp.mu);
+  gpak_launch_transform(st, ctx->dX, Np, N, kp, ctx->Upred);
+
+  const bool latent = flags & GPAK_BLOCK_LATENT;
+  const long ldw = cap + 32L * std::max(0, ctx->sched.pred_ld_skew);
+  const int vs = std::max(1, std::min(64, Np / 512));
+  const int cps = (Np + vs - 1) / vs;
+  double *dMean = ctx->dPv, *dSq = ctx->dPv + cap, *dKbb = ctx->dXte;   // dXte (4 x cap) is free on this path
+  std::vector<double> hsq, hkbb, hK;
+  for (long b0 = 0; b0 < M; b0 += cap) {
+    const int mb = (int)std::min<long>(cap, M - b0);
+    const int mbp = (mb + 2 * PB - 1) / (2 * PB) * (2 * PB);
+    const long xs = (long)mb * nd;
+    for (int k = 0; k < d; k++)
+      GPAK_HIP(hipMemcpyAsync(ctx->dXblk + (size_t)k * xs, Xd + (size_t)k * Mn + (size_t)b0 * nd, sizeof(double) * xs,
+                              hipMemcpyHostToDevice, st));
+    gpak_launch_transform_blocks(st, ctx->dXblk, xs, mb, nd, cap, kp, ctx->dTblk);
+    gpak_launch_fill_blocks(st, ctx->dTblk, cap, mb, nd, ctx->Upred, mbp, Np, kp, ctx->dWt, ldw);
+    if (Kbar_host) {
+      hK.resize((size_t)mb * N);
+      GPAK_HIP(hipMemcpy2DAsync(hK.data(), sizeof(double) * mb, ctx->dWt, sizeof(double) * ldw, sizeof(double) * mb, N,
+                                hipMemcpyDeviceToHost, st));
+      GPAK_HIP(hipStreamSynchronize(st));
+      for (int i = 0; i < mb; i++)
+        for (int j = 0; j < N; j++) Kbar_host[j + (size_t)(b0 + i) * N] = hK[i + (size_t)j * mb];
+      continue;
+    }
+    hipLaunchKernelGGL(gpak_rowdot_part_f64, dim3((mb + 255) / 256, vs), dim3(256), 0, st, ctx->dWt, ldw, mb, N, cps,
+                       ctx->dAlpha, ctx->dPart, cap);   // columns >= N are padding
+    gpak_launch_sum_splits(st, ctx->dPart, cap, vs, mb, dMean);
+    GPAK_HIP(hipMemcpyAsync(mean + b0, dMean, sizeof(double) * mb, hipMemcpyDeviceToHost, st));
+    if (var) {
+      forward_subst_batch(ctx, ctx->dWt, ldw, mbp);
+      hipLaunchKernelGGL(gpak_rowsumsq_part_f64, dim3((mbp + 255) / 256, vs), dim3(256), 0, st, ctx->dWt, ldw, mbp, Np,
+                         cps, ctx->dPart, cap);
+      gpak_launch_sum_splits(st, ctx->dPart, cap, vs, mb, dSq);
+      gpak_launch_block_self(st, ctx->dTblk, cap, mb, nd, kp, dKbb);
+      hsq.resize(mb); hkbb.resize(mb);
+      GPAK_HIP(hipMemcpyAsync(hsq.data(), dSq, sizeof(double) * mb, hipMemcpyDeviceToHost, st));
+      GPAK_HIP(hipMemcpyAsync(hkbb.data(), dKbb, sizeof(double) * mb, hipMemcpyDeviceToHost, st));
+      GPAK_HIP(hipStreamSynchronize(st));
+      for (int i = 0; i < mb; i++) {
+        const double lat = std::max(0.0, hkbb[i] - hsq[i] / ctx->sn2);
+        var[b0 + i] = latent ? lat : lat + ctx->sn2 / nd;
+      }
     }
   }
   GPAK_HIP(hipEventRecord(e1, st));

@@ -21,6 +21,7 @@ OPT_BWD_FUSED = 12
 OPT_TAIL_MAX_NP = 13
 OPT_LOO_ROWS = 14
 KERN_EXPANS, KERN_EXP, KERN_RBF = 0, 1, 2
+BLOCK_LATENT = 1
 
 _dp = C.POINTER(C.c_double)
 
@@ -37,6 +38,27 @@ def _p(a):
 
 def _f(a):
     return np.asfortranarray(a, dtype=np.float64)
+
+
+def block_points(centres, size, disc):
+    """Cell-centred discretisation of M rectangular blocks: returns (Xd, nd) for Gpak.predict_block / block_cross.
+
+    centres is M x d (d = 3 or 4), size = (dx, dy, dz) the block's edge lengths, disc = (nx, ny, nz) the points per axis.
+    Point (i, j, k) of a block sits at centre + (((i + 0.5) / nx - 0.5) dx, ((j + 0.5) / ny - 0.5) dy,
+    ((k + 0.5) / nz - 0.5) dz); row b * nd + a of Xd is point a = (i * ny + j) * nz + k of block b (x slowest, z
+    fastest).  A fourth column is copied from the centre."""
+    c = np.asarray(centres, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] not in (3, 4):
+        raise ValueError("centres must be M x 3 or M x 4")
+    n = [int(v) for v in disc]
+    if len(n) != 3 or len(size) != 3 or min(n) < 1:
+        raise ValueError("size and disc take three values, disc positive counts")
+    off = [((np.arange(n[k]) + 0.5) / n[k] - 0.5) * float(size[k]) for k in range(3)]
+    nd = n[0] * n[1] * n[2]
+    grid = np.stack(np.meshgrid(off[0], off[1], off[2], indexing="ij"), axis=-1).reshape(nd, 3)
+    Xd = np.repeat(c, nd, axis=0)
+    Xd[:, :3] = (c[:, None, :3] + grid[None, :, :]).reshape(-1, 3)
+    return np.asfortranarray(Xd), nd
 
 
 class Gpak:
@@ -175,6 +197,31 @@ class Gpak:
         out = {name: getattr(s, name) for name, _ in s._fields_}
         out["status"] = rc
         return mean, var, out
+
+    def _blocks(self, Xd, nd):
+        Xd = _f(Xd)
+        nd = int(nd)
+        if Xd.ndim != 2 or nd <= 0 or Xd.shape[0] % nd:
+            raise GpakError(EINVAL, "Xd must hold nd rows per block")
+        return Xd, Xd.shape[0] // nd, nd
+
+    def block_cross(self, Xd, nd):
+        """The block-averaged cross-kernel (gpak_block_cross): N x M, column b = the mean over block b's nd points (rows
+        b * nd .. b * nd + nd of Xd) of k(X, x)."""
+        Xd, M, nd = self._blocks(Xd, nd)
+        K = np.zeros((self.N, M), order="F")
+        self._check(self._lib.gpak_block_cross(self._h, _p(Xd), M, nd, Xd.shape[1], _p(K)))
+        return K
+
+    def predict_block(self, Xd, nd, want_var=True, latent=False):
+        """Mean and variance of the block averages (gpak_predict_block); var includes sn2 / nd unless latent.  On
+        Chol_fail both are NaN."""
+        Xd, M, nd = self._blocks(Xd, nd)
+        mean = np.zeros(M)
+        var = np.zeros(M) if want_var else None
+        self._check(self._lib.gpak_predict_block(self._h, _p(Xd), M, nd, Xd.shape[1], _p(mean), _p(var),
+                                                 BLOCK_LATENT if latent else 0), allow=(ENOTPD,))
+        return mean, var
 
     # -- measurement ---------------------------------------------------------------------
     def timing(self):

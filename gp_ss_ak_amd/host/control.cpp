@@ -2,6 +2,7 @@
 #include "control.hpp"
 
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -27,6 +28,18 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       else ErrorTermination("--gradient takes reference or exact");
     }
     else if (isArg("-t", "--timing")) { incArg(); timing_file = getArg(); }   // "-" = stdout
+    else if (isArg("--block-size", "--block-size") || isArg("--block-disc", "--block-disc")) {
+      const bool is_size = getArg() == "--block-size";
+      incArg();
+      double v[3];
+      if (sscanf(getArg().c_str(), "%lf,%lf,%lf", &v[0], &v[1], &v[2]) != 3)
+        ErrorTermination(std::string(is_size ? "--block-size takes dx,dy,dz" : "--block-disc takes nx,ny,nz"));
+      for (int k = 0; k < 3; k++) {
+        if (is_size) { if (!(v[k] >= 0.0)) ErrorTermination("--block-size takes three non-negative lengths"); block_size[k] = v[k]; }
+        else { if (!(v[k] >= 1.0) || v[k] != std::floor(v[k]) || v[k] > 64) ErrorTermination("--block-disc takes three counts between 1 and 64"); block_disc[k] = (int)v[k]; }
+      }
+    }
+    else if (isArg("--latent", "--latent")) { block_latent = true; }
     else break;
     incArg();
   }

@@ -49,6 +49,10 @@ class Control {
   int precision = 0;             // --precision f64|f32: GPAK_F64 / GPAK_F32 (fp32 prediction work)
   bool exact_gradient = false;   // --gradient reference|exact: GradLL as the reference writes it / the derivative of nlZ
   std::string timing_file;       // --timing file|-: JSON of gpak_phase_times after the verb
+  // the `block` verb: --block-size dx,dy,dz (the file's units), --block-disc nx,ny,nz, --latent (no sn2 / nd)
+  double block_size[3] = {0, 0, 0};
+  int block_disc[3] = {1, 1, 1};
+  bool block_latent = false;
   std::string mode = "gp";
   mat params, MinData, MaxData, MeanData, StData;
   double MaxTotalin = 0, MinTotalin = 0, MaxTotalo = 0, MinTotalo = 0;

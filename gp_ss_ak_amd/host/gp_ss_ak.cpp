@@ -2,11 +2,16 @@
 //   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] train.txt [model]
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
 //   gp_ss_ak [-v n]               [device options] cv [-np] train.txt model [out_file]
+//   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
 // (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only).
 // cv (not a reference verb): leave-one-out cross-validation of a trained model on its training set, from one
 // factorisation (gpak_loo; one GPU only), written to <model>_loo.txt.
+// block (not a reference verb): mean and standard deviation of the AVERAGE grade of rectangular blocks (gpak_predict_block;
+// one GPU only).  blocks.txt has the test file's format: block centres, and a last column that is read as y and carried
+// through.  Each block is discretised in the file's units into nx * ny * nz cell-centred points, which then pass through
+// the same input transform as `test`; written to <model>_block.txt in input order.
 // Same verbs, flags and files (<model>, <model>_Statistics.txt, <model>_predict.txt,
 // <model>_gnu.plt); -np/--no-prompt skips the two interactive stdin questions of `train`
 // (gp_ss_ak.cpp:235-285) and the gnuplot call of `test` (:503-505).
@@ -17,6 +22,7 @@
 #include <iostream>
 #include <numeric>
 
+#include "block_points.hpp"
 #include "control.hpp"
 #include "gp_utils.hpp"
 
@@ -36,6 +42,7 @@ class GP_Cntrl : public Control {
   void train();
   void test();
   void cv();
+  void block();
   void Help() const;
 };
 
@@ -43,7 +50,8 @@ void GP_Cntrl::Help() const {
   std::cout << "\nGP_SS_AK hot path on MI355X\nCommand:\n \t ./gp_ss_ak [options] Command [Comnd-options] TrainDataFile.txt modelName\n"
             << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood.\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
-            << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time.\n";
+            << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time.\n"
+            << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n";
 }
 
 void GP_Cntrl::train() {
@@ -286,6 +294,71 @@ void GP_Cntrl::cv() {
   exit(0);
 }
 
+void GP_Cntrl::block() {
+  incArg();
+  setMode("block");
+  if (gpus > 1)
+    ErrorTermination("gpak_predict_block is built for the single-GPU context (gpak_create) only: drop --gpus");
+  bool yscale = true;
+  while (isFlgs()) {
+    if (isArgFlg()) {
+      if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
+      else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else UnkFlg();
+      incArg();
+    } else setFlgs(false);
+  }
+  if (getArgNo() + 2 >= argc)
+    ErrorTermination("There are not enough input parameters: block needs the block centres, the model and the training data.");
+  std::string blFile = getArg(), modelName = argv[getArgNo() + 1], trFile = argv[getArgNo() + 2];
+  std::string BlockOut = modelName + "_block.txt";
+  if (getArgNo() + 3 < argc) BlockOut = argv[getArgNo() + 3];
+  int ds[2];
+  readDataSize(blFile, ds);
+  mat C, y;
+  readDataFile(C, y, ds, blFile);
+  if (C.n_cols != 3 && C.n_cols != 4) ErrorTermination("Block centres need 3 or 4 input columns.");
+  // discretise in the file's units, then standardise every point like a test point: the symmetric standardisation
+  // shares one half-range over x, y and z, so a block keeps its shape
+  std::vector<double> pts;
+  const int nd = gpak_block_points(C.memptr(), C.n_rows, C.n_cols, block_size, block_disc, pts);
+  mat Xd(C.n_rows * nd, C.n_cols), ydummy(C.n_rows * nd, 1);
+  for (size_t i = 0; i < pts.size(); i++) Xd[i] = pts[i];
+  prepareData(C, y, yscale, modelName);            // the model's _Statistics.txt, as `test`
+  prepareData(Xd, ydummy, false, modelName);
+  GP_utils *GPModel = readGpFromFile(modelName, getVerbose());  // parameters at 6 significant digits (Q5)
+  readDataSize(trFile, ds);
+  mat Xtr, ytr;
+  readDataFile(Xtr, ytr, ds, trFile);
+  prepareData(Xtr, ytr, yscale, modelName);
+  GPModel->yTarg = ytr;
+  GPModel->Xinp = Xtr;
+  GPModel->setNumData((unsigned)Xtr.n_rows);
+  GPModel->initialize_vars();
+  GPModel->logLikelihood();
+  if (C.n_cols != GPModel->getInpDim()) ErrorTermination("Incorrect dimension of input data.");
+  mat BlockVals(y.n_rows, 1), BlockVals_Var(y.n_rows, 1);
+  GPModel->BlockMeanVar(BlockVals, BlockVals_Var, Xd, nd, block_latent);
+  postData(C, BlockVals, yscale, modelName);
+  postData_var(BlockVals_Var, yscale, modelName);
+  postData(y, yscale, modelName);
+  if (getVerbose() > 0)
+    std::cout << "Blocks: " << y.n_rows << " of " << nd << " points (" << block_disc[0] << " x " << block_disc[1] << " x "
+              << block_disc[2] << ")" << (block_latent ? ", latent variance" : "") << "\n";
+  // rows in input order; the fourth column is what postData_var returns, as StdYh of _predict.txt
+  std::ofstream out(BlockOut.c_str());
+  out << "# BlockNo, Y, Yblock, StdYblock, Inputs" << "\n";
+  for (size_t i = 0; i < y.n_elem; i++) {
+    out << (i + 1) << "\t" << y[i] << "\t" << BlockVals[i] << "\t" << BlockVals_Var[i] << "\t";
+    for (size_t j = 0; j < C.n_cols; j++) out << C(i, j) << "\t";
+    out << "\n";
+  }
+  out.close();
+  writeTiming(*GPModel);
+  delete GPModel;
+  exit(0);
+}
+
 int main(int argc, char **argv) {
   GP_Cntrl ctl(argc, argv);
   if (ctl.getArgNo() >= argc) { ctl.Help(); return 1; }
@@ -293,6 +366,7 @@ int main(int argc, char **argv) {
   if (verb == "train") ctl.train();
   else if (verb == "test") ctl.test();
   else if (verb == "cv") ctl.cv();
+  else if (verb == "block") ctl.block();
   else if (verb == "-h" || verb == "--help" || verb == "-?") { ctl.Help(); return 0; }
   else ctl.ErrorTermination("Invalid command provided.");
   return 0;

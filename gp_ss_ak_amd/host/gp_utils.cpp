@@ -166,6 +166,17 @@ void GP_utils::LooCV(mat &mean, mat &var, gpak_loo_summary &s) const {
   if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_loo", ctx);
 }
 
+void GP_utils::BlockMeanVar(mat &mean, mat &var, const mat &Xd, int nd, bool latent) const {
+  sync_params();
+  const size_t M = nd > 0 ? Xd.n_rows / nd : 0;
+  if (mean.n_elem != M) mean.resize(M, 1);
+  if (var.n_elem != M) var.resize(M, 1);
+  int rc = gpak_predict_block(ctx, Xd.memptr(), (long)M, nd, (int)Xd.n_cols, mean.memptr(), var.memptr(),
+                              latent ? GPAK_BLOCK_LATENT : 0);
+  Chol_fail = (rc == GPAK_ENOTPD);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_predict_block", ctx);
+}
+
 void GP_utils::Calc_Out(mat &yPred, mat &yVar, const mat &Xin) const { posteriorMeanVar(yPred, yVar, Xin); }
 
 void GP_utils::OptimisePars(unsigned int iters) {  // GP_Utils.cpp:1288-1301

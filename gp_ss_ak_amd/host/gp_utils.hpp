@@ -116,6 +116,9 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // leave-one-out cross-validation of the training set from the current factor (gpak_loo): mean and variance (noise
   // included) of every yTarg(i) given all the other samples, N x 1 each; NaN on Chol_fail
   void LooCV(mat &mean, mat &var, gpak_loo_summary &s) const;
+  // block-support prediction (gpak_predict_block): mean and variance of the average of the field over each block, block
+  // b = rows b * nd .. b * nd + nd of Xd; the variance includes sn2 / nd unless latent; M x 1 each, NaN on Chol_fail
+  void BlockMeanVar(mat &mean, mat &var, const mat &Xd, int nd, bool latent) const;
   void OptimisePars(unsigned int iters);
   void updateKernel() const;
   std::ostream &ShowKernelPars(std::ostream &os) const;

@@ -200,13 +200,33 @@ typedef struct {
 /* mean (N), var (N), summary: each may be NULL */
 int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary);
 
+/* Block-support prediction (block kriging): mean and variance of the AVERAGE of the field over each of M blocks, block b
+ * given by nd discretisation points with uniform weights.  Xd is (M*nd) x d column-major, row b*nd + a = point a of
+ * block b.  With B = I + K/sn2 = L L^T and alpha = (K + sn2 I)^-1 y:
+ *   kbar_b[j] = (1/nd) sum_a k(x_j, x_{b,a})                          (bias included; a White child contributes nothing)
+ *   mean_b    = kbar_b . alpha                                        (= the average of the point means)
+ *   kbb_b     = (1/nd^2) sum_{a,a'} k(x_{b,a}, x_{b,a'}) + white/nd   (White: the nd diagonal pairs only)
+ *   latent_b  = max(0, kbb_b - |L^-1 kbar_b|^2 / sn2)
+ *   var_b     = latent_b + sn2/nd, the variance of the average of nd noisy point values; latent_b with GPAK_BLOCK_LATENT.
+ * One triangular substitution per block instead of one per point; at nd = 1 this is gpak_predict with compat_flags = 0.
+ * The blocks are streamed in batches of GPAK_OPT_PRED_BATCH blocks (fewer when their points would exceed about 1 GiB).
+ * The pooled mean of GPAK_DIST_EXPANSION is taken over the training set and all M*nd points.  Everything is fp64, also
+ * in a GPAK_F32 context.  Both calls run gram / factor / alpha if they are stale, only read them, and set predict_ms.
+ * GPAK_EINVAL for M <= 0, nd <= 0, d other than the training set's, a NULL Xd / mean / Kbar_host; GPAK_ENOTIMPL for a
+ * multi-GPU context; on GPAK_ENOTPD every output is filled with quiet NaN. */
+#define GPAK_BLOCK_LATENT 1   /* var = latent block variance, without + sn2/nd */
+/* the block-averaged cross-kernel alone: Kbar_host is N x M column-major, column b = kbar_b */
+int gpak_block_cross(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, double *Kbar_host);
+/* mean (M) required, var (M) may be NULL */
+int gpak_predict_block(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, double *mean, double *var, int flags);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 typedef struct {
   double gram_ms;      /* fused fill of B = I + K/sn2 (lower tiles)                      */
   double factor_ms;    /* whole blocked Cholesky                                         */
   double solve_ms;     /* two triangular solves                                          */
   double nlz_ms;       /* f = K alpha (fused Gram-matvec), lp, reductions                */
-  double predict_ms;   /* last gpak_predict                                              */
+  double predict_ms;   /* last gpak_predict / gpak_predict_block / gpak_block_cross      */
   double grad_ms;      /* last gpak_grad / gpak_grad_hyb / gpak_grad_exact               */
   /* trailing-update kernel (the dominant, MFMA-bound launch), last factorisation,
    * measured with hipEvents on the ctx stream when GPAK_OPT_PROFILE is set: */
