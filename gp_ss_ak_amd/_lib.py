@@ -15,7 +15,7 @@ SYMBOLS = [
     "gpak_create", "gpak_create_multi", "gpak_n_gpus", "gpak_transport", "gpak_destroy", "gpak_last_error", "gpak_global_error", "gpak_set_train",
     "gpak_set_params", "gpak_set_kernel", "gpak_set_option", "gpak_gram", "gpak_compute_k", "gpak_factor",
     "gpak_get_chol_upper", "gpak_failed_column", "gpak_solve_alpha", "gpak_solve_chol", "gpak_nlz",
-    "gpak_nlz_terms", "gpak_predict", "gpak_grad", "gpak_grad_hyb", "gpak_grad_exact", "gpak_loo", "gpak_block_cross", "gpak_predict_block", "gpak_timing", "gpak_calibrate", "gpak_reload_tuning",
+    "gpak_nlz_terms", "gpak_predict", "gpak_grad", "gpak_grad_hyb", "gpak_grad_exact", "gpak_loo", "gpak_block_cross", "gpak_predict_block", "gpak_predict_joint", "gpak_sample_joint", "gpak_timing", "gpak_calibrate", "gpak_reload_tuning",
 ]
 
 
@@ -81,6 +81,8 @@ def load():
     lib.gpak_loo.argtypes = [vp, dp, dp, C.POINTER(LooSummary)]
     lib.gpak_block_cross.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp]
     lib.gpak_predict_block.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]
+    lib.gpak_predict_joint.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]
+    lib.gpak_sample_joint.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, C.c_int, C.c_double, dp, dp, C.c_int]
     lib.gpak_timing.argtypes = [vp, C.POINTER(PhaseTimes)]
     lib.gpak_calibrate.argtypes = [vp, dp, dp]
     lib.gpak_reload_tuning.restype = None

@@ -911,6 +911,40 @@ int gpak_predict_block(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, d
   return block_call(ctx, "gpak_predict_block", Xd, M, nd, d, mean, var, flags, nullptr);
 }
 
+static int joint_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *cov_host,
+                      int flags, const double *Xi, int S, double nugget, double *Z) {
+  if (ctx->multi) {
+    ctx->err = std::string(name) + " is built for the single-GPU context (gpak_create) only";
+    return GPAK_ENOTIMPL;
+  }
+  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
+  if (d != ctx->d) { ctx->err = "block points must have as many columns as the training set"; return GPAK_EINVAL; }
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  int rc = ensure_nlz(ctx);
+  if (rc == GPAK_ENOTPD) {   // the training factor: as gpak_predict_block
+    ctx->err = "the training factor failed (B = I + K/sn2 is not positive definite at column " + std::to_string(ctx->failed_col) + ")";
+    for (long i = 0; mean && i < M; i++) mean[i] = nan;
+    for (size_t i = 0; cov_host && i < (size_t)M * M; i++) cov_host[i] = nan;
+    for (size_t i = 0; Z && i < (size_t)M * S; i++) Z[i] = nan;
+    return rc;
+  }
+  if (rc == GPAK_OK) rc = gpak_joint_impl(ctx, Xd, M, nd, mean, cov_host, flags, Xi, S, nugget, Z);
+  if (rc == GPAK_ENOTPD)     // C + nugget I: the mean stands
+    for (size_t i = 0; Z && i < (size_t)M * S; i++) Z[i] = nan;
+  return rc;
+}
+
+int gpak_predict_joint(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, double *mean, double *cov_host, int flags) {
+  if (!ctx || !Xd || !mean || M <= 0 || nd <= 0) return GPAK_EINVAL;
+  return joint_call(ctx, "gpak_predict_joint", Xd, M, nd, d, mean, cov_host, flags, nullptr, 0, 0.0, nullptr);
+}
+
+int gpak_sample_joint(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, const double *Xi, int S, double nugget,
+                      double *Z, double *mean, int flags) {
+  if (!ctx || !Xd || !Xi || !Z || M <= 0 || nd <= 0 || S <= 0 || !(nugget >= 0.0)) return GPAK_EINVAL;
+  return joint_call(ctx, "gpak_sample_joint", Xd, M, nd, d, mean, nullptr, flags, Xi, S, nugget, Z);
+}
+
 int gpak_timing(gpak_ctx *ctx, gpak_phase_times *out) {
   if (!ctx || !out) return GPAK_EINVAL;
   if (ctx->multi) return gpak_multi_timing(ctx->multi, out);

@@ -139,6 +139,13 @@ struct gpak_ctx {
   double *dXblk = nullptr, *dTblk = nullptr;
   size_t blk_points = 0;
   int blk_terms = 0;
+  // joint prediction / simulation (gpak_predict_joint, gpak_sample_joint): the joint_cap x joint_cap covariance and then
+  // its factor (leading dimension skewed like dWt's), that factor's inverted 128-blocks and failing column, and the
+  // normals / realisations (joint_cap x joint_s each)
+  double *dC = nullptr, *dCinv = nullptr, *dXi = nullptr, *dZ = nullptr;
+  int *dCinfo = nullptr;
+  int joint_cap = 0;
+  size_t joint_elems = 0, joint_s = 0;
   // fp32 prediction (ctx created with GPAK_F32): fp32 images of L and of the inverse blocks
   float *dLf = nullptr, *dInvf = nullptr;
   long ldLf = 0;             // leading dimension of dLf (Np + skew)
@@ -302,6 +309,10 @@ void gpak_launch_transform_blocks(hipStream_t st, const double *x, long xs, int 
 void gpak_launch_fill_blocks(hipStream_t st, const double *P, int cap, int nB, int nd, const DevPoints &Q, int rows_p,
                              int cols_p, const KernParams &kp, double *C, long ld);
 void gpak_launch_block_self(hipStream_t st, const double *P, int cap, int nB, int nd, const KernParams &kp, double *kbb);
+// Joint prediction: the prior covariance between the averages of the same blocks, lower 128 x 64 tiles of the cap x cap
+// matrix C; b == b' gets `diag` beside its average, padding rows / columns 0 off the diagonal and 1 on it.
+void gpak_launch_fill_block_pairs(hipStream_t st, const double *P, int cap, int nB, int nd, const KernParams &kp,
+                                  double diag, double *C, long ld);
 // out_j = sum_i w_i K(P_i, Q_j), j < Q.n   (fused Gram-matvec; K never stored).
 // scratch holds max(splits, scratch_rows) * Q.cap doubles (scratch_rows: what the caller really has; the symmetric
 // kernel for P == Q needs one row per 512 points).
@@ -387,6 +398,10 @@ void gpak_predict_release(gpak_ctx *ctx);
 // gpak_predict_block / gpak_block_cross on a single-GPU context whose factor and alpha are current
 int gpak_predict_block_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mean, double *var, int flags,
                             double *Kbar_host);
+// gpak_predict_joint (Xi == nullptr: mean and, when asked, cov_host) / gpak_sample_joint (Xi set: Z and the mean) on a
+// single-GPU context whose factor and alpha are current.  GPAK_ENOTPD: C + nugget I failed (mean valid, Z untouched).
+int gpak_joint_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mean, double *cov_host, int flags,
+                    const double *Xi, int S, double nugget, double *Z);
 
 // ---- the distributed factor as one rank holds it (dist.hip), handed to a single-GPU context of the SAME device
 // (multi.hip: group prediction and solve_chol reuse the factor instead of factoring a replica again) ----

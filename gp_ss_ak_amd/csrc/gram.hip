@@ -412,6 +412,105 @@ void gpak_launch_block_self(hipStream_t st, const double *P, int cap, int nB, in
 }
 
 // ---------------------------------------------------------------------------------------
+// Prior covariance between block averages (gpak_predict_joint / gpak_sample_joint):
+//   C[b, b'] = (1/nd^2) sum_{a, a'} k(x_{b,a}, x_{b',a'})  [+ diag on b == b'],
+// the lower 128 x 64 tiles of a cap x cap matrix (those that straddle the diagonal are written whole), in the store
+// pattern of the fills above.  Both operands come from the ONE point-major array gpak_transform_blocks_f64 writes.
+// nd^2 kernel evaluations per stored element: fp64-VALU bound like gpak_fillblk_f64.
+// Rows as there: a lane holds its two rows of point a, loaded once per (a, tile), all terms at once, so that an
+// evaluation is the SUM of its terms before it joins the accumulator.  The columns' points sit in LDS, PAIR_SLOTS
+// (point, term) slots of 64 columns x GPAK_PT at a time: with nd * nterms <= PAIR_SLOTS all of them are staged once
+// per tile, otherwise chunk by chunk inside every a (two barriers per chunk).  The 16 accumulator pairs of a wave stay
+// in registers over the whole a, a' loop.  Per element the nd^2 values are added in ONE order -- a ascending outside,
+// a' ascending inside, whatever the chunking -- the sum is multiplied once by 1/nd^2 and then the bias is added, so
+// an element's bytes depend on its two blocks alone, not on the tile grid or on M.
+// Padding rows / columns (>= nB): 0 off the diagonal, 1 on it (the padded matrix stays positive definite).
+// nd = 1 takes this kernel too (not gpak_launch_fill on the transformed points): one code path, one summation rule.
+// ---------------------------------------------------------------------------------------
+#define PAIR_SLOTS 12   // 12 x 5 x 64 doubles = 30 KiB of LDS: 12 / 6 / 4 points of 1 / 2 / 3 terms
+template <int NT>
+__global__ __launch_bounds__(256) void gpak_fillblk_pair_f64(const double *__restrict__ P, int cap, int nB, int nd,
+                                                              KernParams kp, double inv_nd2, double diag,
+                                                              double *__restrict__ C, long ld) {
+  const int row0 = blockIdx.x * FILL_ROWS, col0 = blockIdx.y * FILL_COLS;
+  if (row0 + FILL_ROWS <= col0) return;   // strictly above the diagonal
+  __shared__ double q[PAIR_SLOTS][GPAK_PT][FILL_COLS];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int nterms = NT ? NT : kp.nterms;
+  const int chunk = PAIR_SLOTS / max(nterms, 1);   // points of the columns held in LDS at once
+  const bool resident = nd <= chunk;
+  const int r = row0 + 2 * lane;
+  const size_t capP = (size_t)nd * cap;
+  // slot (b - b0) * nterms + m = term m of column point b; every index read is below nd * cap (col0 + 63 < cap)
+  auto stage = [&](int b0, int nb) {
+    const int tot = nb * nterms * GPAK_PT * FILL_COLS;
+    for (int e = t; e < tot; e += 256) {
+      const int col = e & (FILL_COLS - 1), pc = e / FILL_COLS, c = pc % GPAK_PT, slot = pc / GPAK_PT;
+      const int b = b0 + slot / nterms, m = slot % nterms;
+      q[slot][c][col] = PARR(P, capP, m, c)[(size_t)b * cap + col0 + col];
+    }
+  };
+  double2 acc[BLK_WCOLS];
+#pragma unroll
+  for (int c = 0; c < BLK_WCOLS; c++) acc[c] = make_double2(0.0, 0.0);
+  if (resident) { stage(0, nd); __syncthreads(); }
+  for (int a = 0; a < nd; a++) {
+    const size_t o = (size_t)a * cap + r;
+    double2 p[NT ? NT : GPAK_MAX_TERMS][GPAK_PT];
+#pragma unroll
+    for (int m = 0; m < (NT ? NT : GPAK_MAX_TERMS); m++)
+      if (m < nterms) {
+#pragma unroll
+        for (int c = 0; c < GPAK_PT; c++) p[m][c] = *reinterpret_cast<const double2 *>(PARR(P, capP, m, c) + o);
+      }
+    for (int b0 = 0; b0 < nd; b0 += chunk) {
+      const int nb = min(chunk, nd - b0);
+      if (!resident) { __syncthreads(); stage(b0, nb); __syncthreads(); }
+      for (int bb = 0; bb < nb; bb++) {
+        const int s0 = bb * nterms;
+#pragma unroll
+        for (int c = 0; c < BLK_WCOLS; c++) {
+          const int jl = w + 4 * c;
+          double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+          for (int m = 0; m < (NT ? NT : GPAK_MAX_TERMS); m++) {
+            if (m >= nterms) break;
+            const double (*qs)[FILL_COLS] = q[s0 + m];
+            v0 += gpak_profile(gpak_d2(p[m][0].x, p[m][1].x, p[m][2].x, p[m][3].x, p[m][4].x, qs[0][jl], qs[1][jl],
+                                       qs[2][jl], qs[3][jl], qs[4][jl], kp.mode), kp.term[m]);
+            v1 += gpak_profile(gpak_d2(p[m][0].y, p[m][1].y, p[m][2].y, p[m][3].y, p[m][4].y, qs[0][jl], qs[1][jl],
+                                       qs[2][jl], qs[3][jl], qs[4][jl], kp.mode), kp.term[m]);
+          }
+          acc[c].x += v0; acc[c].y += v1;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < BLK_WCOLS; c++) {
+    const int j = col0 + w + 4 * c;
+    const bool cj = j < nB;
+    double k0 = (cj && r < nB) ? fma(inv_nd2, acc[c].x, kp.bias) : 0.0;
+    double k1 = (cj && r + 1 < nB) ? fma(inv_nd2, acc[c].y, kp.bias) : 0.0;
+    if (r == j) k0 = cj ? k0 + diag : 1.0;
+    if (r + 1 == j) k1 = cj ? k1 + diag : 1.0;
+    *reinterpret_cast<double2 *>(C + r + (size_t)j * ld) = make_double2(k0, k1);
+  }
+}
+
+// P: nd * cap points point-major, nB valid blocks; fills the lower tiles of the cap x cap matrix C (cap a multiple of
+// 128); diag = what b == b' gets beside its average (white / nd, sn2 / nd, a nugget)
+void gpak_launch_fill_block_pairs(hipStream_t st, const double *P, int cap, int nB, int nd, const KernParams &kp,
+                                  double diag, double *C, long ld) {
+  dim3 grid(cap / FILL_ROWS, cap / FILL_COLS);
+  const double inv_nd2 = 1.0 / ((double)nd * (double)nd);
+  if (kp.nterms == 1)
+    hipLaunchKernelGGL(gpak_fillblk_pair_f64<1>, grid, dim3(256), 0, st, P, cap, nB, nd, kp, inv_nd2, diag, C, ld);
+  else
+    hipLaunchKernelGGL(gpak_fillblk_pair_f64<0>, grid, dim3(256), 0, st, P, cap, nB, nd, kp, inv_nd2, diag, C, ld);
+}
+
+// ---------------------------------------------------------------------------------------
 // Fused Gram-matvec: out_j = sum_i w_i k(P_i, Q_j).  Serves mvmK_exact (GP_Utils.cpp:394-397,
 // f = K*Alpha at :1147) and _postMean (:958-972) without ever storing K / kX.  The white-noise
 // diagonal is NOT part of it (callers add white * w_j where the two sets coincide).

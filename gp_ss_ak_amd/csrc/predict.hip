@@ -51,6 +51,14 @@ void gpak_predict_release(gpak_ctx *ctx) {
   if (ctx->dTblk) hipFree(ctx->dTblk);
   ctx->dXblk = ctx->dTblk = nullptr;
   ctx->blk_points = 0;
+  if (ctx->dC) hipFree(ctx->dC);
+  if (ctx->dCinv) hipFree(ctx->dCinv);
+  if (ctx->dCinfo) hipFree(ctx->dCinfo);
+  if (ctx->dXi) hipFree(ctx->dXi);
+  if (ctx->dZ) hipFree(ctx->dZ);
+  ctx->dC = ctx->dCinv = ctx->dXi = ctx->dZ = nullptr;
+  ctx->dCinfo = nullptr;
+  ctx->joint_cap = 0; ctx->joint_elems = 0; ctx->joint_s = 0;
   if (ctx->Upred.base) hipFree(ctx->Upred.base);
   if (ctx->Tq.base) hipFree(ctx->Tq.base);
   ctx->Upred = DevPoints(); ctx->Tq = DevPoints();
@@ -369,6 +377,171 @@ int gpak_predict_block_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, dou
   float ms = 0;
   GPAK_HIP(hipEventElapsedTime(&ms, e0, e1));
   ctx->times.predict_ms = ms;
+  return GPAK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Joint posterior of M blocks and conditional simulation (gpak_predict_joint / gpak_sample_joint).  The block path's
+// steps, unchanged, up to and including the means, with ALL M blocks in one batch (cap = M rounded up to 256):
+//   points -> gpak_transform_blocks_f64 -> averaged fill into dWt -> row dots with alpha = the means;
+// then W = Kbar^T L^-T by forward_subst_batch, the prior covariance between the block averages into dC
+// (gpak_fillblk_pair_f64, gram.hip), and ONE product dC -= W W^T / sn2 over the lower tiles (the padding rows of dWt are
+// zero, so the padding of dC keeps its identity).  The lower triangle is copied out and mirrored on the host:
+// cov_host is symmetric by construction.
+// Sampling: the nugget rides on the pair fill's diagonal term; dC is factored in place by the right-looking loop a
+// rank of the 1-D multi-GPU schedule runs on its columns -- gpak_factor_panel (512 columns, clipped) and a K = W update
+// of the lower tiles to its right -- with inverse blocks and an info word of its own; then Z = mean 1^T + Lc Xi by
+// gpak_joint_trmm_f64 below.  Everything is queued on the context's stream; one host synchronisation per copy-out.
+// ---------------------------------------------------------------------------------------
+#define JOINT_SCOLS 8   // realisations per thread of the triangular product
+// Z[i, s] = mean[i] + sum_{k <= i} Lc[i, k] Xi[k, s]: one thread per row (coalesced reads of a column of Lc; Xi[k, s] is
+// wave-uniform), JOINT_SCOLS realisations per thread, k ascending in one fma chain per (i, s).  M^2 S flops on the
+// vector unit: noise beside the N-proportional work of the call.
+__global__ __launch_bounds__(256) void gpak_joint_trmm_f64(const double *__restrict__ Lc, long ld, int M,
+                                                            const double *__restrict__ Xi, const double *__restrict__ mean,
+                                                            int S, double *__restrict__ Z) {
+  const int i = blockIdx.x * 256 + threadIdx.x, s0 = blockIdx.y * JOINT_SCOLS;
+  if (i >= M) return;
+  double acc[JOINT_SCOLS];
+#pragma unroll
+  for (int u = 0; u < JOINT_SCOLS; u++) acc[u] = 0.0;
+  for (int k = 0; k <= i; k++) {
+    const double l = Lc[i + (size_t)k * ld];
+#pragma unroll
+    for (int u = 0; u < JOINT_SCOLS; u++)
+      if (s0 + u < S) acc[u] = fma(l, Xi[k + (size_t)(s0 + u) * M], acc[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < JOINT_SCOLS; u++)
+    if (s0 + u < S) Z[i + (size_t)(s0 + u) * M] = mean[i] + acc[u];
+}
+
+int gpak_joint_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mean, double *cov_host, int flags,
+                    const double *Xi, int S, double nugget, double *Z) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np, d = ctx->d;
+  KernParams kp = ctx->kp;
+  kp.d = d;
+  const long Mp = (M + 2 * PB - 1) / (2 * PB) * (2 * PB);
+  // the block path's budget for the raw and transformed points of a batch, here of the one batch there is
+  const size_t per_block = sizeof(double) * (size_t)nd * (4 + GPAK_PT * (size_t)kp.nterms);
+  if (Mp > (1L << 24) || (size_t)Mp * per_block > ((size_t)1 << 30)) {
+    ctx->err = "the blocks' discretisation points exceed the 1 GiB point budget of one batch (the joint calls hold all M blocks at once)";
+    return GPAK_EINVAL;
+  }
+  const int cap = (int)Mp;
+  const bool sample = Xi != nullptr, prior = !sample && (flags & GPAK_JOINT_PRIOR);
+  const bool want_c = sample || cov_host;
+  int rc = ensure_predict_bufs(ctx, cap, true);
+  if (rc) return rc;
+  const size_t points = (size_t)cap * nd;
+  if (ctx->blk_points < points || ctx->blk_terms < kp.nterms) {
+    if (ctx->dXblk) hipFree(ctx->dXblk);
+    if (ctx->dTblk) hipFree(ctx->dTblk);
+    ctx->dXblk = ctx->dTblk = nullptr; ctx->blk_points = 0;
+    if (hipMalloc(&ctx->dXblk, sizeof(double) * 4 * points) != hipSuccess ||
+        hipMalloc(&ctx->dTblk, sizeof(double) * GPAK_PT * kp.nterms * points) != hipSuccess) {
+      ctx->err = "device allocation failed for the blocks' discretisation points";
+      return GPAK_ENOMEM;
+    }
+    ctx->blk_points = points; ctx->blk_terms = kp.nterms;
+  }
+  const long ldw = cap + 32L * std::max(0, ctx->sched.pred_ld_skew), ldc = ldw;   // the same 256-byte skew
+  if (want_c && (ctx->joint_cap < cap || ctx->joint_elems < (size_t)ldc * cap)) {
+    if (ctx->dC) hipFree(ctx->dC);
+    if (ctx->dCinv) hipFree(ctx->dCinv);
+    ctx->dC = ctx->dCinv = nullptr; ctx->joint_cap = 0; ctx->joint_elems = 0;
+    if (!ctx->dCinfo && hipMalloc(&ctx->dCinfo, sizeof(int) * 4) != hipSuccess) ctx->dCinfo = nullptr;
+    if (!ctx->dCinfo || hipMalloc(&ctx->dC, sizeof(double) * (size_t)ldc * cap) != hipSuccess ||
+        hipMalloc(&ctx->dCinv, sizeof(double) * (size_t)(cap / PB) * 2 * PB * PB) != hipSuccess) {
+      ctx->err = "device allocation failed for the joint covariance of the blocks";
+      return GPAK_ENOMEM;
+    }
+    ctx->joint_cap = cap; ctx->joint_elems = (size_t)ldc * cap;
+  }
+  if (sample && ctx->joint_s < (size_t)M * S) {
+    if (ctx->dXi) hipFree(ctx->dXi);
+    if (ctx->dZ) hipFree(ctx->dZ);
+    ctx->dXi = ctx->dZ = nullptr; ctx->joint_s = 0;
+    if (hipMalloc(&ctx->dXi, sizeof(double) * (size_t)M * S) != hipSuccess ||
+        hipMalloc(&ctx->dZ, sizeof(double) * (size_t)M * S) != hipSuccess) {
+      ctx->err = "device allocation failed for the normals and the realisations";
+      return GPAK_ENOMEM;
+    }
+    ctx->joint_s = (size_t)M * S;
+  }
+  hipEvent_t e0 = ctx->ev[5], e1 = ctx->ev[6];
+  GPAK_HIP(hipEventRecord(e0, st));
+
+  // pooled mean over the training set and all M * nd points, as gpak_predict_block
+  const long Mn = M * nd;
+  double s2[4] = {0, 0, 0, 0};
+  for (int k = 0; k < d; k++)
+    for (long i = 0; i < Mn; i++) s2[k] += Xd[i + (size_t)k * Mn];
+  gpak_pooled_mean(ctx->xsum, N, s2, Mn, kp.mu);
+  gpak_launch_transform(st, ctx->dX, Np, N, kp, ctx->Upred);
+
+  const int mb = (int)M;
+  const int vs = std::max(1, std::min(64, Np / 512));
+  const int cps = (Np + vs - 1) / vs;
+  double *dMean = ctx->dPv;
+  for (int k = 0; k < d; k++)
+    GPAK_HIP(hipMemcpyAsync(ctx->dXblk + (size_t)k * Mn, Xd + (size_t)k * Mn, sizeof(double) * Mn, hipMemcpyHostToDevice, st));
+  gpak_launch_transform_blocks(st, ctx->dXblk, Mn, mb, nd, cap, kp, ctx->dTblk);
+  gpak_launch_fill_blocks(st, ctx->dTblk, cap, mb, nd, ctx->Upred, cap, Np, kp, ctx->dWt, ldw);
+  hipLaunchKernelGGL(gpak_rowdot_part_f64, dim3((mb + 255) / 256, vs), dim3(256), 0, st, ctx->dWt, ldw, mb, N, cps,
+                     ctx->dAlpha, ctx->dPart, cap);   // columns >= N are padding
+  gpak_launch_sum_splits(st, ctx->dPart, cap, vs, mb, dMean);
+  if (mean) GPAK_HIP(hipMemcpyAsync(mean, dMean, sizeof(double) * mb, hipMemcpyDeviceToHost, st));
+
+  int info = 0;
+  const int init = 0x7fffffff;
+  if (want_c) {
+    const bool latent = flags & GPAK_JOINT_LATENT;
+    const double diag = kp.white / nd + (latent ? 0.0 : ctx->sn2 / nd) + (sample ? nugget : 0.0);
+    gpak_launch_fill_block_pairs(st, ctx->dTblk, cap, mb, nd, kp, diag, ctx->dC, ldc);
+    if (!prior) {
+      forward_subst_batch(ctx, ctx->dWt, ldw, cap);
+      // the SYRK: dC -= W W^T / sn2 on the lower 128-tiles
+      gpak_launch_gemm_nt(st, cap / PB, cap / PB, Np, -1.0 / ctx->sn2, ctx->dWt, ldw, ctx->dWt, ldw, 1.0, ctx->dC, ldc, 0, 0,
+                          true, false);
+    }
+  }
+  if (cov_host) {
+    // rows [c, M) of column c; mirrored below
+    GPAK_HIP(hipMemcpy2DAsync(cov_host, sizeof(double) * M, ctx->dC, sizeof(double) * ldc, sizeof(double) * M, M,
+                              hipMemcpyDeviceToHost, st));
+  }
+  if (sample) {
+    GPAK_HIP(hipMemcpyAsync(ctx->dCinfo, &init, sizeof(int), hipMemcpyHostToDevice, st));
+    GPAK_HIP(hipMemcpyAsync(ctx->dXi, Xi, sizeof(double) * (size_t)M * S, hipMemcpyHostToDevice, st));
+    for (int J = 0; J < cap; J += 512) {
+      const int W = std::min(512, cap - J), c0 = J + W, mt = (cap - c0) / PB;
+      gpak_factor_panel(st, ctx->dC, ldc, cap, J, W, ctx->dCinv, ctx->dCinfo, true, false, ctx->sched.potrf_co);
+      if (mt > 0) {
+        const double *P = ctx->dC + c0 + (size_t)J * ldc;
+        gpak_launch_gemm_nt(st, mt, mt, W, -1.0, P, ldc, P, ldc, 1.0, ctx->dC + c0 + (size_t)c0 * ldc, ldc, 0, 0, true, false);
+      }
+    }
+    hipLaunchKernelGGL(gpak_joint_trmm_f64, dim3((mb + 255) / 256, (S + JOINT_SCOLS - 1) / JOINT_SCOLS), dim3(256), 0, st,
+                       ctx->dC, ldc, mb, ctx->dXi, dMean, S, ctx->dZ);
+    GPAK_HIP(hipMemcpyAsync(&info, ctx->dCinfo, sizeof(int), hipMemcpyDeviceToHost, st));
+    GPAK_HIP(hipMemcpyAsync(Z, ctx->dZ, sizeof(double) * (size_t)M * S, hipMemcpyDeviceToHost, st));
+  }
+  GPAK_HIP(hipEventRecord(e1, st));
+  GPAK_HIP(hipEventSynchronize(e1));
+  float ms = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, e0, e1));
+  ctx->times.predict_ms = ms;
+  if (cov_host)
+    for (long c = 0; c < M; c++)
+      for (long r = c + 1; r < M; r++) cov_host[c + (size_t)r * M] = cov_host[r + (size_t)c * M];
+  if (sample && info != init) {
+    ctx->err = "C + nugget I of the blocks is not positive definite: its factorisation fails at column " + std::to_string(info) +
+               " (raise the nugget)";
+    return GPAK_ENOTPD;
+  }
   return GPAK_OK;
 }
 

@@ -22,6 +22,7 @@ OPT_TAIL_MAX_NP = 13
 OPT_LOO_ROWS = 14
 KERN_EXPANS, KERN_EXP, KERN_RBF = 0, 1, 2
 BLOCK_LATENT = 1
+JOINT_LATENT, JOINT_PRIOR = 1, 2
 
 _dp = C.POINTER(C.c_double)
 
@@ -222,6 +223,38 @@ class Gpak:
         self._check(self._lib.gpak_predict_block(self._h, _p(Xd), M, nd, Xd.shape[1], _p(mean), _p(var),
                                                  BLOCK_LATENT if latent else 0), allow=(ENOTPD,))
         return mean, var
+
+    def predict_joint(self, Xd, nd, want_cov=True, latent=False, prior=False):
+        """Mean (M) and full covariance (M x M, exactly symmetric) of the block averages (gpak_predict_joint); the
+        diagonal includes sn2 / nd unless latent and is not clamped.  prior: the prior covariance between the block
+        averages alone (GPAK_JOINT_PRIOR).  On Chol_fail of the training factor both are NaN."""
+        Xd, M, nd = self._blocks(Xd, nd)
+        mean = np.zeros(M)
+        cov = np.zeros((M, M), order="F") if want_cov else None
+        flags = (JOINT_LATENT if latent else 0) | (JOINT_PRIOR if prior else 0)
+        self._check(self._lib.gpak_predict_joint(self._h, _p(Xd), M, nd, Xd.shape[1], _p(mean), _p(cov), flags),
+                    allow=(ENOTPD,))
+        return mean, cov
+
+    def sample_joint(self, Xd, nd, xi, nugget=0.0, latent=False):
+        """Conditional simulation (gpak_sample_joint): Z = mean 1' + Lc xi (M x S) for the caller's standard normals xi
+        (M x S), Lc the lower Cholesky factor of the joint covariance + nugget I.  Returns (Z, mean).  Where that matrix is not
+        positive definite Z is NaN and the mean valid (last_error() names the failing column); on Chol_fail of the
+        training factor both are NaN."""
+        Xd, M, nd = self._blocks(Xd, nd)
+        xi = _f(xi)
+        if xi.ndim == 1:
+            xi = xi.reshape(-1, 1, order="F")
+        if xi.ndim != 2 or xi.shape[0] != M:
+            raise GpakError(EINVAL, "xi must hold one row per block")
+        S = xi.shape[1]
+        Z, mean = np.zeros((M, S), order="F"), np.zeros(M)
+        self._check(self._lib.gpak_sample_joint(self._h, _p(Xd), M, nd, Xd.shape[1], _p(xi), S, float(nugget), _p(Z),
+                                                _p(mean), JOINT_LATENT if latent else 0), allow=(ENOTPD,))
+        return Z, mean
+
+    def last_error(self):
+        return self._lib.gpak_last_error(self._h).decode()
 
     # -- measurement ---------------------------------------------------------------------
     def timing(self):

@@ -30,6 +30,7 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
     else if (isArg("-t", "--timing")) { incArg(); timing_file = getArg(); }   // "-" = stdout
     else if (isArg("--block-size", "--block-size") || isArg("--block-disc", "--block-disc")) {
       const bool is_size = getArg() == "--block-size";
+      (is_size ? block_size_set : block_disc_set) = true;
       incArg();
       double v[3];
       if (sscanf(getArg().c_str(), "%lf,%lf,%lf", &v[0], &v[1], &v[2]) != 3)
@@ -40,6 +41,15 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       }
     }
     else if (isArg("--latent", "--latent")) { block_latent = true; }
+    else if (isArg("--realisations", "--realizations")) { incArg(); sim_realisations = getIntArg(); sim_realisations_set = true; }
+    else if (isArg("--seed", "--seed")) { incArg(); sim_seed = strtoull(getArg().c_str(), nullptr, 10); sim_seed_set = true; }
+    else if (isArg("--xi", "--xi")) { incArg(); sim_xi_file = getArg(); }
+    else if (isArg("--nugget", "--nugget")) {
+      incArg();
+      char *end = nullptr;
+      sim_nugget = strtod(getArg().c_str(), &end);
+      if (end == getArg().c_str() || !(sim_nugget >= 0.0)) ErrorTermination("--nugget takes a non-negative value");
+    }
     else break;
     incArg();
   }

@@ -53,6 +53,13 @@ class Control {
   double block_size[3] = {0, 0, 0};
   int block_disc[3] = {1, 1, 1};
   bool block_latent = false;
+  bool block_size_set = false, block_disc_set = false;
+  // the `sim` verb: --realisations S, --seed n | --xi file (M x S normals), --nugget v (added to the covariance's diagonal)
+  int sim_realisations = 0;
+  bool sim_realisations_set = false, sim_seed_set = false;
+  unsigned long long sim_seed = 0;
+  std::string sim_xi_file;
+  double sim_nugget = 0.0;
   std::string mode = "gp";
   mat params, MinData, MaxData, MeanData, StData;
   double MaxTotalin = 0, MinTotalin = 0, MaxTotalo = 0, MinTotalo = 0;

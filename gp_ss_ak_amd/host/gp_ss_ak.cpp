@@ -3,6 +3,8 @@
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
 //   gp_ss_ak [-v n]               [device options] cv [-np] train.txt model [out_file]
 //   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
+//   gp_ss_ak [-v n] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] [--nugget v] --realisations S (--seed n | --xi file)
+//            sim nodes.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
 // (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only).
@@ -12,6 +14,10 @@
 // one GPU only).  blocks.txt has the test file's format: block centres, and a last column that is read as y and carried
 // through.  Each block is discretised in the file's units into nx * ny * nz cell-centred points, which then pass through
 // the same input transform as `test`; written to <model>_block.txt in input order.
+// sim (not a reference verb): S realisations of the grade at the nodes given the training data (conditional simulation,
+// gpak_sample_joint; one GPU only).  nodes.txt is read as block reads its centres; without --block-size / --block-disc the
+// nodes are points.  The normals come from --xi (an M x S text matrix) or from --seed (std::mt19937_64 + Box-Muller,
+// sim_normals.hpp).  Written to <model>_sim.txt in input order: the conditional mean and the S realisations.
 // Same verbs, flags and files (<model>, <model>_Statistics.txt, <model>_predict.txt,
 // <model>_gnu.plt); -np/--no-prompt skips the two interactive stdin questions of `train`
 // (gp_ss_ak.cpp:235-285) and the gnuplot call of `test` (:503-505).
@@ -21,10 +27,13 @@
 #include <fstream>
 #include <iostream>
 #include <numeric>
+#include <sstream>
+#include <string>
 
 #include "block_points.hpp"
 #include "control.hpp"
 #include "gp_utils.hpp"
+#include "sim_normals.hpp"
 
 class GP_Cntrl : public Control {
  public:
@@ -43,6 +52,7 @@ class GP_Cntrl : public Control {
   void test();
   void cv();
   void block();
+  void sim();
   void Help() const;
 };
 
@@ -51,7 +61,8 @@ void GP_Cntrl::Help() const {
             << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood.\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time.\n"
-            << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n";
+            << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
+            << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]).\n";
 }
 
 void GP_Cntrl::train() {
@@ -359,6 +370,109 @@ void GP_Cntrl::block() {
   exit(0);
 }
 
+void GP_Cntrl::sim() {
+  incArg();
+  setMode("sim");
+  if (gpus > 1)
+    ErrorTermination("gpak_sample_joint is built for the single-GPU context (gpak_create) only: drop --gpus");
+  bool yscale = true;
+  while (isFlgs()) {
+    if (isArgFlg()) {
+      if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
+      else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else UnkFlg();
+      incArg();
+    } else setFlgs(false);
+  }
+  if (getArgNo() + 2 >= argc)
+    ErrorTermination("There are not enough input parameters: sim needs the nodes, the model and the training data.");
+  if (!sim_realisations_set || sim_realisations <= 0) ErrorTermination("sim needs --realisations S with S > 0");
+  if (sim_seed_set == !sim_xi_file.empty()) ErrorTermination("sim needs exactly one of --seed n and --xi file");
+  if (block_size_set != block_disc_set)
+    ErrorTermination("sim takes --block-size and --block-disc together (neither: the nodes are points)");
+  std::string ndFile = getArg(), modelName = argv[getArgNo() + 1], trFile = argv[getArgNo() + 2];
+  std::string SimOut = modelName + "_sim.txt";
+  if (getArgNo() + 3 < argc) SimOut = argv[getArgNo() + 3];
+  int ds[2];
+  readDataSize(ndFile, ds);
+  mat C, y;
+  readDataFile(C, y, ds, ndFile);
+  if (C.n_cols != 3 && C.n_cols != 4) ErrorTermination("Nodes need 3 or 4 input columns.");
+  const size_t M = C.n_rows, S = (size_t)sim_realisations;
+  // the normals, M x S column-major: realisation s is column s
+  mat Xi(M, S);
+  if (!sim_xi_file.empty()) {
+    std::ifstream in(sim_xi_file.c_str());
+    if (!in.is_open()) ErrorTermination("File is " + sim_xi_file + " not readable");
+    std::vector<double> vals;
+    size_t rows = 0;
+    bool shape_ok = true;
+    std::string line;
+    while (std::getline(in, line)) {
+      if (line.empty() || line[0] == '#') continue;
+      std::istringstream ls(line);
+      size_t n = 0;
+      double v;
+      while (ls >> v) { vals.push_back(v); n++; }
+      if (n == 0) continue;
+      if (n != S) shape_ok = false;
+      rows++;
+    }
+    if (!shape_ok || rows != M)
+      ErrorTermination("--xi needs an M x S matrix: one row per node (" + std::to_string(M) + ") of " + std::to_string(S) + " normals");
+    for (size_t i = 0; i < M; i++)
+      for (size_t s = 0; s < S; s++) Xi(i, s) = vals[i * S + s];
+  } else {
+    std::vector<double> z;
+    gpak_sim_normals(sim_seed, M * S, z);
+    for (size_t i = 0; i < M * S; i++) Xi[i] = z[i];
+  }
+  // as block: discretise in the file's units, then standardise every point like a test point
+  const double point_size[3] = {0, 0, 0};
+  const int point_disc[3] = {1, 1, 1};
+  std::vector<double> pts;
+  const int nd = gpak_block_points(C.memptr(), C.n_rows, C.n_cols, block_size_set ? block_size : point_size,
+                                   block_disc_set ? block_disc : point_disc, pts);
+  mat Xd(C.n_rows * nd, C.n_cols), ydummy(C.n_rows * nd, 1);
+  for (size_t i = 0; i < pts.size(); i++) Xd[i] = pts[i];
+  prepareData(C, y, yscale, modelName);            // the model's _Statistics.txt, as `test`
+  prepareData(Xd, ydummy, false, modelName);
+  GP_utils *GPModel = readGpFromFile(modelName, getVerbose());  // parameters at 6 significant digits (Q5)
+  readDataSize(trFile, ds);
+  mat Xtr, ytr;
+  readDataFile(Xtr, ytr, ds, trFile);
+  prepareData(Xtr, ytr, yscale, modelName);
+  GPModel->yTarg = ytr;
+  GPModel->Xinp = Xtr;
+  GPModel->setNumData((unsigned)Xtr.n_rows);
+  GPModel->initialize_vars();
+  GPModel->logLikelihood();
+  if (C.n_cols != GPModel->getInpDim()) ErrorTermination("Incorrect dimension of input data.");
+  mat MeanVals(M, 1), SimVals(M, S);
+  if (!GPModel->JointSample(SimVals, MeanVals, Xd, nd, Xi, sim_nugget, block_latent))
+    std::cerr << "The joint covariance of the nodes is not positive definite: the realisations are NaN (try --nugget)" << std::endl;
+  postData(C, MeanVals, yscale, modelName);
+  postData(SimVals, yscale, modelName);
+  postData(y, yscale, modelName);
+  if (getVerbose() > 0)
+    std::cout << "Nodes: " << M << " of " << nd << " points, " << S << " realisations"
+              << (block_latent ? ", latent" : "") << ", nugget " << sim_nugget << "\n";
+  std::ofstream out(SimOut.c_str());
+  out << "# NodeNo, Y, Ymean";
+  for (size_t s = 0; s < S; s++) out << ", Sim" << (s + 1);
+  out << ", Inputs" << "\n";
+  for (size_t i = 0; i < M; i++) {
+    out << (i + 1) << "\t" << y[i] << "\t" << MeanVals[i] << "\t";
+    for (size_t s = 0; s < S; s++) out << SimVals(i, s) << "\t";
+    for (size_t j = 0; j < C.n_cols; j++) out << C(i, j) << "\t";
+    out << "\n";
+  }
+  out.close();
+  writeTiming(*GPModel);
+  delete GPModel;
+  exit(0);
+}
+
 int main(int argc, char **argv) {
   GP_Cntrl ctl(argc, argv);
   if (ctl.getArgNo() >= argc) { ctl.Help(); return 1; }
@@ -367,6 +481,7 @@ int main(int argc, char **argv) {
   else if (verb == "test") ctl.test();
   else if (verb == "cv") ctl.cv();
   else if (verb == "block") ctl.block();
+  else if (verb == "sim") ctl.sim();
   else if (verb == "-h" || verb == "--help" || verb == "-?") { ctl.Help(); return 0; }
   else ctl.ErrorTermination("Invalid command provided.");
   return 0;

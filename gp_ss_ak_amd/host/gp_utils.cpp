@@ -177,6 +177,29 @@ void GP_utils::BlockMeanVar(mat &mean, mat &var, const mat &Xd, int nd, bool lat
   if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_predict_block", ctx);
 }
 
+void GP_utils::JointMeanCov(mat &mean, mat &cov, const mat &Xd, int nd, bool latent) const {
+  sync_params();
+  const size_t M = nd > 0 ? Xd.n_rows / nd : 0;
+  if (mean.n_elem != M) mean.resize(M, 1);
+  if (cov.n_rows != M || cov.n_cols != M) cov.resize(M, M);
+  int rc = gpak_predict_joint(ctx, Xd.memptr(), (long)M, nd, (int)Xd.n_cols, mean.memptr(), cov.memptr(),
+                              latent ? GPAK_JOINT_LATENT : 0);
+  Chol_fail = (rc == GPAK_ENOTPD);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_predict_joint", ctx);
+}
+
+bool GP_utils::JointSample(mat &Z, mat &mean, const mat &Xd, int nd, const mat &Xi, double nugget, bool latent) const {
+  sync_params();
+  const size_t M = nd > 0 ? Xd.n_rows / nd : 0, S = Xi.n_cols;
+  if (mean.n_elem != M) mean.resize(M, 1);
+  if (Z.n_rows != M || Z.n_cols != S) Z.resize(M, S);
+  int rc = gpak_sample_joint(ctx, Xd.memptr(), (long)M, nd, (int)Xd.n_cols, Xi.memptr(), (int)S, nugget, Z.memptr(),
+                             mean.memptr(), latent ? GPAK_JOINT_LATENT : 0);
+  Chol_fail = (rc == GPAK_ENOTPD && std::isnan(mean[0]));   // the training factor; otherwise the blocks' covariance
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_sample_joint", ctx);
+  return rc == GPAK_OK;
+}
+
 void GP_utils::Calc_Out(mat &yPred, mat &yVar, const mat &Xin) const { posteriorMeanVar(yPred, yVar, Xin); }
 
 void GP_utils::OptimisePars(unsigned int iters) {  // GP_Utils.cpp:1288-1301

@@ -119,6 +119,13 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // block-support prediction (gpak_predict_block): mean and variance of the average of the field over each block, block
   // b = rows b * nd .. b * nd + nd of Xd; the variance includes sn2 / nd unless latent; M x 1 each, NaN on Chol_fail
   void BlockMeanVar(mat &mean, mat &var, const mat &Xd, int nd, bool latent) const;
+  // joint posterior of the blocks (gpak_predict_joint): mean M x 1 and the full M x M covariance (exactly symmetric;
+  // the diagonal includes sn2 / nd unless latent and is not clamped); NaN on Chol_fail
+  void JointMeanCov(mat &mean, mat &cov, const mat &Xd, int nd, bool latent) const;
+  // conditional simulation (gpak_sample_joint): Z (M x S) = mean 1' + Lc Xi for the caller's normals Xi (M x S), Lc the
+  // factor of the covariance + nugget I.  Returns false when that matrix is not positive definite (Z NaN, mean valid);
+  // everything NaN on Chol_fail
+  bool JointSample(mat &Z, mat &mean, const mat &Xd, int nd, const mat &Xi, double nugget, bool latent) const;
   void OptimisePars(unsigned int iters);
   void updateKernel() const;
   std::ostream &ShowKernelPars(std::ostream &os) const;

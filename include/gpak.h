@@ -220,13 +220,39 @@ int gpak_block_cross(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, dou
 /* mean (M) required, var (M) may be NULL */
 int gpak_predict_block(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, double *mean, double *var, int flags);
 
+/* Joint posterior of M blocks (full covariance) and conditional simulation from it.  Xd, M, nd, d as for
+ * gpak_predict_block; at nd = 1 the blocks are points.  With kbar_b, alpha, L, sn2 as above and w_b = L^-1 kbar_b:
+ *   mean_b  = kbar_b . alpha
+ *   Kbb_bb' = (1/nd^2) sum_{a,a'} k(x_{b,a}, x_{b',a'})          the prior covariance between two block averages
+ *   C_bb'   = Kbb_bb' - w_b . w_b' / sn2  [+ (sn2/nd) delta_bb' unless GPAK_JOINT_LATENT]
+ * A White child adds white/nd to Kbb_bb only (the nd coincident pairs of a block with itself; nothing between different
+ * blocks, even where two blocks share a point).  The diagonal is NOT clamped at 0: where gpak_predict_block does not
+ * clamp, the two agree to rounding.  The variance of any weighted sum of the blocks is w^T C w.
+ * gpak_sample_joint returns Z = mean 1^T + Lc Xi with Lc the lower Cholesky factor of C + nugget I and Xi the CALLER'S
+ * standard normals (M x S): the call is a deterministic function of its inputs.
+ * The M blocks are held at once in one batch (M rounded up to 256 rows by N padded, plus an M x M matrix);
+ * GPAK_OPT_PRED_BATCH does not apply.  Everything is fp64, also in a GPAK_F32 context.  Both calls run gram / factor /
+ * alpha if they are stale, only read them, and set predict_ms.
+ * GPAK_EINVAL for M <= 0, nd <= 0, S <= 0, nugget < 0, d other than the training set's, a NULL Xd / mean (joint) / Xi / Z,
+ * and for blocks whose points exceed the block path's 1 GiB point budget; GPAK_ENOTIMPL for a multi-GPU context;
+ * GPAK_ENOMEM when the batch does not fit.  GPAK_ENOTPD in two cases that gpak_last_error tells apart: the training
+ * factor fails (every output is filled with quiet NaN), or C + nugget I is not positive definite (Z is quiet NaN, the
+ * mean is valid, the text names the failing column). */
+#define GPAK_JOINT_LATENT 1   /* as GPAK_BLOCK_LATENT: without + sn2/nd on the diagonal */
+#define GPAK_JOINT_PRIOR  2   /* cov_host = Kbb (+ the diagonal terms) alone: no substitution, no w . w' / sn2 */
+/* mean (M) required; cov_host (M x M column-major, FULL and exactly symmetric) may be NULL */
+int gpak_predict_joint(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, double *mean, double *cov_host, int flags);
+/* Z (M x S column-major); Xi (M x S column-major); mean (M) may be NULL */
+int gpak_sample_joint(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, const double *Xi, int S, double nugget,
+                      double *Z, double *mean, int flags);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 typedef struct {
   double gram_ms;      /* fused fill of B = I + K/sn2 (lower tiles)                      */
   double factor_ms;    /* whole blocked Cholesky                                         */
   double solve_ms;     /* two triangular solves                                          */
   double nlz_ms;       /* f = K alpha (fused Gram-matvec), lp, reductions                */
-  double predict_ms;   /* last gpak_predict / gpak_predict_block / gpak_block_cross      */
+  double predict_ms;   /* last gpak_predict / gpak_predict_block / gpak_block_cross / gpak_*_joint */
   double grad_ms;      /* last gpak_grad / gpak_grad_hyb / gpak_grad_exact               */
   /* trailing-update kernel (the dominant, MFMA-bound launch), last factorisation,
    * measured with hipEvents on the ctx stream when GPAK_OPT_PROFILE is set: */
