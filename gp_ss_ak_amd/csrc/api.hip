@@ -439,8 +439,11 @@ int gpak_set_params(gpak_ctx *ctx, const double *expans, double bias, double sn2
   if (!ctx || !expans) return GPAK_EINVAL;
   if (dist_mode != GPAK_DIST_EXPANSION && dist_mode != GPAK_DIST_DIRECT) { ctx->err = "bad dist_mode"; return GPAK_EINVAL; }
   if (ctx->multi) { ctx->sn2 = sn2; GPAK_MULTI_ERR(gpak_multi_set_params(ctx->multi, expans, bias, sn2, dist_mode)); }
-  bool same = ctx->have_params && memcmp(expans, ctx->expans, sizeof(double) * 8) == 0 && bias == ctx->bias &&
-              sn2 == ctx->sn2 && dist_mode == ctx->dist_mode;
+  // "same" compares with what gpak_set_kernel stores too: the stored kernel must be the one this call builds (one ExpAns
+  // term, no White), or a composition's factor and alpha would pass for this kernel's
+  bool same = ctx->have_params && ctx->expans_only && ctx->kp.white == 0.0 &&
+              memcmp(expans, ctx->expans, sizeof(double) * 8) == 0 && bias == ctx->bias && sn2 == ctx->sn2 &&
+              dist_mode == ctx->dist_mode;
   memcpy(ctx->expans, expans, sizeof(double) * 8);
   memcpy(ctx->tpars[0], expans, sizeof(double) * 8);
   ctx->bias = bias; ctx->sn2 = sn2; ctx->dist_mode = dist_mode;
@@ -812,6 +815,7 @@ int gpak_predict(gpak_ctx *ctx, const double *Xte, long M, int d, double *mean, 
     rc = gpak_multi_predict(ctx->multi, Xte, M, d, mean, var);
     if (rc) { ctx->err = gpak_multi_error(ctx->multi); return rc; }
   } else {
+    if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
     if (d != ctx->d) { ctx->err = "test points must have as many columns as the training set"; return GPAK_EINVAL; }
     // _postVar calls logLikelihood() (GP_Utils.cpp:980); _postMean calls updateAlpha() (:961)
     rc = ensure_nlz(ctx);

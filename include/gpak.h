@@ -87,8 +87,9 @@ int gpak_set_train(gpak_ctx *ctx, const double *X, const double *y, int N, int d
  * {AngleX, inverseWidthx, AngleY, inverseWidthy, AngleZ, inverseWidthz, Sigma, InversewidthR}
  * (Kernel.cpp:737-761), Kern_Bias Sigma_Bias (Kernel.cpp:317-320), hyperlf(0)=sn2 used raw
  * (GP_Utils.cpp:405-406).  Like the reference, every call invalidates K, L and alpha
- * (GP_Utils.cpp:132-133) -- unless `memoise` was enabled with gpak_set_option and the
- * values are bit-identical to the previous call. */
+ * (GP_Utils.cpp:132-133) -- unless `memoise` was enabled with gpak_set_option, the kernel in
+ * force is ExpAns(+Bias) alone (not a gpak_set_kernel composition with further children or a
+ * White child, whatever its ExpAns child holds) and its values are bit-identical to these. */
 int gpak_set_params(gpak_ctx *ctx, const double *expans, double bias, double sn2, int dist_mode);
 
 /* General additive composition (HybKerns of other children, Kernel.cpp:140-154): up to 3 stationary
@@ -117,6 +118,10 @@ int gpak_set_kernel(gpak_ctx *ctx, int nterms, const int *kinds, const double *p
 #define GPAK_OPT_PRED_BATCH  11  /* test points per prediction batch (0: 16384 fp64, 65536 fp32)                    */
 #define GPAK_OPT_BWD_FUSED   12  /* back substitution (needs INV512): 0 three launches per 512 columns, 1 the far column
                                     dots of the next block under this block's diagonal step, 2 (default) one launch  */
+/* GPAK_OPT_INV512 and GPAK_OPT_BWD_FUSED take effect at the NEXT factorisation (the inverses and stacks they ask for are
+ * built beside it): until gpak_set_params / gpak_set_kernel / gpak_set_train / gpak_gram makes the factor stale, gpak_solve_alpha
+ * and gpak_solve_chol keep the back substitution the current factor was made for -- the same solution, summed in the order of
+ * the options that were in force when the context factored. */
 #define GPAK_OPT_TAIL_MAX_NP 13  /* padded sizes above this factor without the CU-masked tail queue (0: no limit)       */
 #define GPAK_OPT_LOO_ROWS    14  /* rows of L^-T held at once (multiple of 128; 0: default)                              */
 int gpak_set_option(gpak_ctx *ctx, int option, long value);

@@ -1,0 +1,591 @@
+"""What a context of include/gpak.h must answer, whatever it was asked before.  TEST INFRASTRUCTURE.
+
+ModelGpak has the method names of gp_ss_ak_amd.gpak.Gpak and no memory beyond the last training set, the last kernel call
+and the options: every answer is computed from those alone, on the CPU, from the references the suite already holds the
+single features to (the CPU checker in oracle/, exact_grad_ref, loo_ref, block_ref, joint_ref).  Results are cached by
+(training set, kernel, operation), so a long sequence costs each distinct state once.  It restates the statuses the header
+promises (GPAK_ESTATE before a training set or parameters, GPAK_ENOTIMPL, GPAK_EINVAL, GPAK_ENOTPD with quiet NaN).
+
+CachingModel is the opposite: a Python restatement of the VALIDITY LOGIC of csrc/api.hip -- which call marks what as
+built, which call drops it -- that answers every question from the state its flags point at.  Unmutated it equals
+ModelGpak step for step.  Each name in MUTATIONS drops one invalidation; tests/test_ctx_sequences.py proves on the CPU
+that every one of them is caught by a named sequence, i.e. that the sequences would notice the corresponding slip in
+api.hip.
+"""
+import hashlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import block_ref  # noqa: E402
+import exact_grad_ref as xref  # noqa: E402
+import joint_ref  # noqa: E402
+import loo_ref  # noqa: E402
+
+OK, ENOTPD, EINVAL, ESTATE, ENOMEM, ENOTIMPL = 0, 1, 2, 3, 4, 5
+F64, F32 = 0, 1
+DIST_EXPANSION, DIST_DIRECT = 0, 1
+OPT_MEMOISE, OPT_NB_OUTER, OPT_NB_WIDE, OPT_POTRF_CO, OPT_TAIL_MAX_NP, OPT_BWD_FUSED, OPT_LOO_ROWS = 1, 2, 5, 10, 13, 12, 14
+NPARS = {xref.EXPANS: 8, xref.EXP: 2, xref.RBF: 3}
+SIGMA_AT = {xref.EXPANS: 6, xref.EXP: 1, xref.RBF: 2}
+
+MUTATIONS = ("memo ignores composition", "gram keeps factor", "set_train keeps alpha", "set_kernel keeps U",
+             "failed factor keeps alpha", "solve_chol keeps z", "predict leaks pooled mean", "f32 image kept",
+             "recovery keeps failed_column")
+
+
+class ModelError(RuntimeError):
+    def __init__(self, status, msg=""):
+        super().__init__(f"model status {status}: {msg}")
+        self.status = status
+
+
+def _orc():
+    from oracle import oracle
+    oracle.lib()
+    return oracle
+
+
+def _digest(*arrays):
+    h = hashlib.sha1()
+    for a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        h.update(str(a.shape).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()[:16]
+
+
+class ModelGpak:
+    def __init__(self, precision=F64, cache=None):
+        self.precision = precision
+        self.cache = {} if cache is None else cache
+        self.opts = {}
+        self.X = self.y = self.tkey = None
+        self.kern = self.kkey = None
+        self.N = self.d = 0
+
+    def close(self):
+        pass
+
+    # -- state ---------------------------------------------------------------------------------------------------
+    def set_option(self, opt, value):
+        value = int(value)
+        bad = {OPT_NB_OUTER: value < 128 or value % 128, OPT_NB_WIDE: value < 0 or value % 128,
+               OPT_POTRF_CO: not 0 <= value <= 2, OPT_TAIL_MAX_NP: value < 0, OPT_BWD_FUSED: not 0 <= value <= 2,
+               OPT_LOO_ROWS: value < 0 or value % 128}
+        if not 1 <= opt <= 14 or bad.get(opt, False):
+            raise ModelError(EINVAL, "option")
+        self.opts[opt] = value
+
+    def set_train(self, X, y):
+        X = np.asfortranarray(X, dtype=np.float64)
+        if X.shape[1] not in (3, 4):
+            raise ModelError(ENOTIMPL, "inputs must have 3 or 4 columns")
+        self.X, self.y = X, np.ascontiguousarray(y, dtype=np.float64).ravel()
+        self.N, self.d = X.shape
+        self.tkey = _digest(self.X, self.y)
+
+    def set_params(self, expans, bias, sn2, dist_mode=DIST_DIRECT):
+        ModelGpak.set_kernel(self, [(xref.EXPANS, expans)], bias, 0.0, sn2, dist_mode)
+
+    def set_kernel(self, terms, bias, white, sn2, dist_mode=DIST_DIRECT):
+        if dist_mode not in (DIST_EXPANSION, DIST_DIRECT) or not 1 <= len(terms) <= 3:
+            raise ModelError(EINVAL, "kernel")
+        terms = tuple((int(k), tuple(float(v) for v in p)) for k, p in terms)
+        self.kern = dict(terms=terms, bias=float(bias), white=float(white), sn2=float(sn2), mode=int(dist_mode))
+        self.kkey = (terms, float(bias), float(white), float(sn2), int(dist_mode))
+
+    # -- what the answers are computed from ---------------------------------------------------------------------
+    def _cached(self, op, fn):
+        key = (self.tkey, self.kkey, op)
+        if key not in self.cache:
+            self.cache[key] = fn()
+        return self.cache[key]
+
+    def _need(self, train=True, params=True):
+        if train and self.X is None:
+            raise ModelError(ESTATE, "no training set")
+        if params and self.kern is None:
+            raise ModelError(ESTATE, "no parameters")
+
+    @property
+    def expans_only(self):
+        k = self.kern
+        return k is None or (len(k["terms"]) == 1 and k["terms"][0][0] == xref.EXPANS and k["white"] == 0.0)
+
+    def prior_variance(self):
+        k = self.kern
+        return k["bias"] + k["white"] + sum(p[SIGMA_AT[kind]] ** 2 for kind, p in k["terms"])
+
+    def _gram(self, X1, X2, white, want_d2=False):
+        k, orc = self.kern, _orc()
+        if self.expans_only:
+            return orc.gram(X1, X2, np.array(k["terms"][0][1]), k["bias"], k["mode"], want_d2=want_d2)
+        return orc.gram_hyb(X1, X2, [(kd, list(p)) for kd, p in k["terms"]], k["bias"], white, k["mode"], want_d2=want_d2)
+
+    def _fit(self):
+        """{K (White on the diagonal), col (failing column, 0: none), info, alpha, L}"""
+        def build():
+            orc, k = _orc(), self.kern
+            K = self._gram(self.X, self.X, k["white"])
+            _, col = orc.potrf_lower(np.eye(self.N) + K / k["sn2"])
+            if col:
+                return dict(K=K, col=int(col))
+            info, alpha, L = orc.nlz_lean(K, self.y, k["sn2"])
+            return dict(K=K, col=0, info=info, alpha=alpha, L=L)
+        self._need()
+        return self._cached("fit", build)
+
+    def _fit_ok(self):
+        f = self._fit()
+        if f["col"]:
+            raise ModelError(ENOTPD, "B = I + K/sn2 is not positive definite")
+        return f
+
+    def _terms(self):
+        return [(kd, list(p)) for kd, p in self.kern["terms"]]
+
+    # -- hot path -------------------------------------------------------------------------------------------------
+    def gram(self, want_d2=False):
+        self._need()
+        K, D2 = self._cached("gram", lambda: self._gram(self.X, self.X, self.kern["white"], want_d2=True))
+        return (K, D2) if want_d2 else K
+
+    def compute_k(self, X1, X2, want_d2=False):
+        X1, X2 = np.asfortranarray(X1, dtype=float), np.asfortranarray(X2, dtype=float)
+        if X1.shape[1] not in (3, 4):
+            raise ModelError(ENOTIMPL, "inputs must have 3 or 4 columns")
+        self._need(train=False)
+        key = (None, self.kkey, ("compute_k", _digest(X1), _digest(X2)))
+        if key not in self.cache:
+            self.cache[key] = self._gram(X1, X2, self.kern["white"], want_d2=True)
+        K, D2 = self.cache[key]
+        return (K, D2) if want_d2 else K
+
+    def factor(self):
+        return self._fit()["col"] == 0
+
+    def failed_column(self):
+        """Of the factorisation of the current state: the sequences ask right after a call that factors."""
+        if self.X is None or self.kern is None:
+            return 0
+        return self._fit()["col"]
+
+    def chol_upper(self):
+        return np.asfortranarray(self._fit_ok()["L"].T)
+
+    def solve_alpha(self):
+        return self._fit_ok()["alpha"].copy()
+
+    def solve_chol(self, X):
+        L = self._fit_ok()["L"]
+        return _orc().solve_chol(L, np.asarray(X, dtype=float))
+
+    def logLikelihood(self):
+        f = self._fit()
+        return float("nan") if f["col"] else f["info"].nlz
+
+    def nlz_terms(self):
+        i = self._fit_ok()["info"]
+        return i.quad, i.sumlp, i.logdet
+
+    def posteriorMeanVar(self, Xte, want_var=True, compat=0):
+        Xte = np.asfortranarray(Xte, dtype=float)
+        if self.X is None:
+            raise ModelError(ESTATE, "no training set")
+        if Xte.shape[1] != self.d:
+            raise ModelError(EINVAL, "test points must have as many columns as the training set")
+        f = self._fit_ok()
+
+        def build():
+            import scipy.linalg as sl
+            k, orc = self.kern, _orc()
+            if self.expans_only:
+                return orc.predict(self.X, Xte, np.array(k["terms"][0][1]), k["bias"], k["sn2"], f["alpha"], f["L"], k["mode"],
+                                   compat, True)
+            assert compat == 0
+            kX = self._gram(self.X, Xte, k["white"])                     # the checker leaves White out of a cross block
+            V = sl.solve_triangular(f["L"], kX, lower=True)
+            var = np.maximum(self.prior_variance() - np.sum(V * V, axis=0) / k["sn2"], 0.0) + k["sn2"]
+            return kX.T @ f["alpha"], var
+        mean, var = self._cached(("predict", _digest(Xte), compat), build)
+        return mean.copy(), (var.copy() if want_var else None)
+
+    def _ng(self):
+        return sum(NPARS[kd] for kd, _ in self.kern["terms"]) + 2
+
+    def _grad_checks(self, ng):
+        if sum(kd == xref.EXPANS for kd, _ in self.kern["terms"]) > 1:
+            raise ModelError(ENOTIMPL, "at most one ExpAns child")
+        if int(ng) != self._ng():
+            raise ModelError(EINVAL, "gradient vector has the wrong length")
+        if self.kern["white"] != 0.0:
+            raise ModelError(ENOTIMPL, "no gradient for a White child")
+
+    def GradLL(self):
+        if not self.expans_only:
+            raise ModelError(ENOTIMPL, "gpak_grad handles the ExpAns(+Bias) composition only")
+        f, k = self._fit_ok(), self.kern
+        return self._cached("grad", lambda: _orc().grad_ref(self.X, self.y, f["K"], f["L"], f["alpha"], np.array(k["terms"][0][1]),
+                                                            k["bias"], k["sn2"], k["mode"])).copy()
+
+    def GradLL_hyb(self, ng):
+        f, k = self._fit_ok(), self.kern
+        self._grad_checks(ng)
+        return self._cached("grad_hyb", lambda: _orc().grad_hyb(self.X, self.y, f["K"], f["L"], f["alpha"], self._terms(), True,
+                                                                k["sn2"], k["mode"])).copy()
+
+    def GradLL_exact(self, ng=10):
+        self._fit_ok()
+        self._grad_checks(ng)
+        k = self.kern
+        return self._cached("grad_exact", lambda: xref.grad_exact(self.X, self.y, self._terms(), k["bias"], k["sn2"])).copy()
+
+    def loo(self):
+        f = self._fit()
+        nan = float("nan")
+        if f["col"]:
+            return np.full(self.N, nan), np.full(self.N, nan), dict(mse=nan, mssr=nan, log_pl=nan, ms=0.0, passes=0, status=ENOTPD)
+
+        def build():
+            m, v = loo_ref.loo(f["K"], self.y, self.kern["sn2"])
+            return m, v, loo_ref.summary(self.y, m, v)
+        m, v, s = self._cached("loo", build)
+        return m.copy(), v.copy(), dict(s, status=OK)
+
+    def _block_pre(self, Xd, nd):
+        Xd = np.asfortranarray(Xd, dtype=float)
+        if self.X is None:
+            raise ModelError(ESTATE, "no training set")
+        if Xd.shape[1] != self.d:
+            raise ModelError(EINVAL, "block points must have as many columns as the training set")
+        self._need()
+        return Xd, Xd.shape[0] // int(nd), int(nd)
+
+    def _block(self, Xd, nd):
+        k = self.kern
+        return self._cached(("block", _digest(Xd), nd), lambda: block_ref.block_predict(self.X, self.y, Xd, nd, self._terms(), k["bias"],
+                                                                                        k["white"], k["sn2"]))
+
+    def block_cross(self, Xd, nd):
+        Xd, M, nd = self._block_pre(Xd, nd)
+        self._fit_ok()        # the C call fills Kbar with NaN and returns GPAK_ENOTPD; Gpak.block_cross raises it
+        return self._cached(("cross", _digest(Xd), nd), lambda: block_ref.block_cross(self.X, Xd, nd, self._terms(), self.kern["bias"]))
+
+    def predict_block(self, Xd, nd, want_var=True, latent=False):
+        Xd, M, nd = self._block_pre(Xd, nd)
+        if self._fit()["col"]:
+            return np.full(M, np.nan), (np.full(M, np.nan) if want_var else None)
+        r = self._block(Xd, nd)
+        return r["mean"].copy(), ((r["latent"] if latent else r["var"]).copy() if want_var else None)
+
+    def _joint(self, Xd, nd):
+        k = self.kern
+        method = "points" if self.N + Xd.shape[0] <= 2400 else "blocks"
+        return self._cached(("joint", _digest(Xd), nd), lambda: joint_ref.joint(self.X, self.y, Xd, nd, self._terms(), k["bias"], k["white"],
+                                                                                k["sn2"], want_prior=False, method=method))
+
+    def predict_joint(self, Xd, nd, want_cov=True, latent=False, prior=False):
+        Xd, M, nd = self._block_pre(Xd, nd)
+        assert not prior
+        if self._fit()["col"]:
+            return np.full(M, np.nan), (np.full((M, M), np.nan) if want_cov else None)
+        r = self._joint(Xd, nd)
+        cov = r["latent"] + (0.0 if latent else self.kern["sn2"] / nd) * np.eye(M)
+        return r["mean"].copy(), (cov if want_cov else None)
+
+    def sample_joint(self, Xd, nd, xi, nugget=0.0, latent=False):
+        Xd, M, nd = self._block_pre(Xd, nd)
+        xi = np.asarray(xi, dtype=float).reshape(M, -1)
+        if self._fit()["col"]:
+            return np.full(xi.shape, np.nan), np.full(M, np.nan)
+        mean, cov = self.predict_joint(Xd, nd, latent=latent)
+        Lc = np.linalg.cholesky(cov + nugget * np.eye(M))
+        return mean[:, None] + Lc @ xi, mean
+
+    def timing(self):
+        return None      # how often a context factored is not a function of its state: CachingModel counts
+
+
+# -------------------------------------------------------------------------------------------------------------------------
+def _spoil(out):
+    """What a kernel reading the wrong buffer returns: not the right numbers."""
+    if isinstance(out, tuple):
+        return tuple(_spoil(o) for o in out)
+    if isinstance(out, dict):
+        return {k: (v if k in ("status", "passes", "ms") else _spoil(v)) for k, v in out.items()}
+    if out is None or isinstance(out, (bool, np.bool_)):
+        return out
+    return np.asarray(out, dtype=float) * (1.0 + 1e-3) if isinstance(out, np.ndarray) else out * (1.0 + 1e-3)
+
+
+class CachingModel(ModelGpak):
+    """The flags of gpak_ctx (csrc/gpak_internal.h) as csrc/api.hip sets and clears them.  A `snapshot` names the state
+    (training set, kernel) a cached quantity was built from: uS the transformed points U, fS the factor in dM, aS alpha,
+    nS the nlZ terms, lfS the fp32 image of the factor.  Answers come from ModelGpak AT that snapshot; `taint` holds the
+    buffers whose contents are not what their flag says."""
+
+    def __init__(self, precision=F64, cache=None, mut=()):
+        super().__init__(precision, cache)
+        unknown = [m for m in mut if m not in MUTATIONS]
+        assert not unknown, unknown
+        self.mut = set(mut)
+        self.states = {}
+        self.uS = self.fS = self.aS = self.nS = self.lfS = None
+        self.bufA = self.bufN = None          # what dAlpha / the nlZ terms physically hold
+        self.z_ok = self.z_clobbered = False
+        self.taint = set()
+        self.failed_col = 0
+        self.failS = None
+        self.evals = 0
+        self.memoise = False
+        self.have_params = False
+        self.stored = None                    # expans, bias, sn2, dist_mode as gpak_ctx keeps them
+        self.stored_expans = None
+        self.was_expans_only, self.was_white = True, 0.0
+        self.dropped = []                     # (mutation, what it kept) each time a mutation changed the outcome
+
+    # -- snapshots ----------------------------------------------------------------------------------------------
+    def _cur(self):
+        key = (self.tkey, self.kkey)
+        self.states[key] = (self.X, self.y, self.kern)
+        return key
+
+    def _at(self, S):
+        X, y, kern = self.states[S]
+        m = ModelGpak(self.precision, self.cache)
+        if X is not None:
+            m.set_train(X, y)
+        if kern is not None:
+            m.set_kernel(kern["terms"], kern["bias"], kern["white"], kern["sn2"], kern["mode"])
+        m.opts = dict(self.opts)
+        return m
+
+    def _invalidate(self):
+        self.fS = self.aS = self.nS = None
+
+    # -- state --------------------------------------------------------------------------------------------------
+    def set_option(self, opt, value):
+        super().set_option(opt, value)
+        if opt == OPT_MEMOISE:
+            self.memoise = int(value) != 0
+
+    def set_train(self, X, y):
+        super().set_train(X, y)
+        self.fS = self.lfS = self.uS = None               # release_train
+        if "set_train keeps alpha" in self.mut and self.aS is not None:
+            self.dropped.append(("set_train keeps alpha", self.aS))
+        else:
+            self.aS = self.nS = None
+        self.evals = 0
+        self.taint.discard("U")
+
+    def set_params(self, expans, bias, sn2, dist_mode=DIST_DIRECT):
+        e = tuple(float(v) for v in expans)
+        new = (e, float(bias), float(sn2), int(dist_mode))
+        same = self.have_params and self.stored == new
+        if "memo ignores composition" not in self.mut:
+            same = same and self.was_expans_only and self.was_white == 0.0
+        elif same and self.memoise and not (self.was_expans_only and self.was_white == 0.0):
+            self.dropped.append(("memo ignores composition", self.fS))
+        super().set_params(expans, bias, sn2, dist_mode)
+        self.stored, self.have_params = new, True
+        self.was_expans_only, self.was_white = True, 0.0
+        if not (same and self.memoise):
+            self._invalidate()
+            self.uS = None
+
+    def set_kernel(self, terms, bias, white, sn2, dist_mode=DIST_DIRECT):
+        super().set_kernel(terms, bias, white, sn2, dist_mode)
+        e = self.stored[0] if self.stored else (0.0,) * 8
+        for kd, p in self.kern["terms"]:
+            if kd == xref.EXPANS:
+                e = p
+        self.stored, self.have_params = (e, float(bias), float(sn2), int(dist_mode)), True
+        self.was_expans_only, self.was_white = self.expans_only, float(white)
+        self._invalidate()
+        if "set_kernel keeps U" in self.mut and self.uS is not None:
+            self.dropped.append(("set_kernel keeps U", self.uS))
+        else:
+            self.uS = None
+
+    # -- the ensure_* chain of api.hip -----------------------------------------------------------------------------
+    def _ensure_U(self):
+        if self.X is None or self.kern is None:
+            return ESTATE
+        if self.uS is None or self.uS[0] != self.tkey:          # U.n == N
+            self.uS = self._cur()
+            self.taint.discard("U")
+        return OK
+
+    def _factor_changed(self):
+        self.z_ok = self.z_clobbered = False
+        if "f32 image kept" in self.mut and self.lfS is not None:
+            self.dropped.append(("f32 image kept", self.lfS))
+        else:
+            self.lfS = None
+
+    def _ensure_factor(self):
+        if self.fS is not None:
+            return OK
+        rc = self._ensure_U()
+        if rc:
+            return rc
+        self._factor_changed()
+        self.evals += 1
+        col = self._at(self.uS)._fit()["col"]
+        self.taint.discard("factor")
+        if col:
+            self.failed_col = col
+            self.failS = self.uS
+            return ENOTPD
+        if "recovery keeps failed_column" in self.mut and self.failed_col:
+            self.dropped.append(("recovery keeps failed_column", self.failed_col))
+        else:
+            self.failed_col = 0
+        self.fS = self.uS
+        if "U" in self.taint:
+            self.taint.add("factor")
+        self.z_ok = True                                  # the forward substitution of y / sn2 rides along
+        return OK
+
+    def _ensure_alpha(self):
+        rc = self._ensure_factor()
+        if rc == ENOTPD and "failed factor keeps alpha" in self.mut and self.bufA is not None:
+            self.dropped.append(("failed factor keeps alpha", self.bufA))
+            self.aS, self.nS = self.bufA, self.bufN
+            return OK
+        if rc:
+            return rc
+        if self.aS is not None:
+            return OK
+        self.taint.discard("alpha")
+        if "factor" in self.taint or (self.z_ok and self.z_clobbered):
+            self.taint.add("alpha")
+        self.z_ok = self.z_clobbered = False              # the back substitution consumes L^-1 y / sn2
+        self.aS = self.bufA = self.fS
+        return OK
+
+    def _ensure_nlz(self):
+        rc = self._ensure_alpha()
+        if rc:
+            return rc
+        if self.nS is None:
+            self.nS = self.bufN = self.aS
+            self.taint.discard("nlz")
+            if "alpha" in self.taint:
+                self.taint.add("nlz")
+        return OK
+
+    def _answer(self, name, need, snaps, taints, *a, rc=None, **k):
+        if rc is None:
+            rc = {"U": self._ensure_U, "factor": self._ensure_factor, "alpha": self._ensure_alpha, "nlz": self._ensure_nlz}[need]()
+        cur = self._cur()
+        if rc == ENOTPD:
+            S = self.failS
+        elif rc:
+            S = cur
+        else:
+            S = next((s for s in (getattr(self, n) for n in snaps) if s is not None and s != cur), cur)
+        out = getattr(ModelGpak, name)(self._at(S), *a, **k)
+        return _spoil(out) if rc == OK and self.taint & set(taints) else out
+
+    # -- hot path ---------------------------------------------------------------------------------------------------
+    def gram(self, want_d2=False):
+        if self.X is not None and self.kern is not None:
+            if "gram keeps factor" in self.mut and self.fS is not None:
+                self.dropped.append(("gram keeps factor", self.fS))
+                self.taint.add("factor")                  # dM holds K where the flag says L
+            else:
+                self._ensure_U()
+                self._invalidate()
+        return self._answer("gram", "U", ("uS",), ("U",), want_d2)
+
+    def factor(self):
+        rc = self._ensure_factor()
+        if rc == ESTATE:
+            return ModelGpak.factor(self)                 # raises it
+        return rc == OK
+
+    def failed_column(self):
+        return self.failed_col
+
+    def chol_upper(self):
+        return self._answer("chol_upper", "factor", ("fS",), ("factor",))
+
+    def solve_alpha(self):
+        return self._answer("solve_alpha", "alpha", ("aS",), ("alpha",))
+
+    def solve_chol(self, X):
+        out = self._answer("solve_chol", "factor", ("fS",), ("factor",), X)
+        if self.fS is not None:
+            if "solve_chol keeps z" in self.mut and self.z_ok:
+                self.dropped.append(("solve_chol keeps z", self.fS))
+                self.z_clobbered = True
+            else:
+                self.z_ok = False
+        return out
+
+    def logLikelihood(self):
+        return self._answer("logLikelihood", "nlz", ("nS",), ("nlz",))
+
+    def nlz_terms(self):
+        return self._answer("nlz_terms", "nlz", ("nS",), ("nlz",))
+
+    def posteriorMeanVar(self, Xte, want_var=True, compat=0):
+        snaps, rc = ["aS", "fS"], None
+        if np.asarray(Xte).shape[1] == self.d:
+            rc = self._ensure_nlz()
+        if rc == OK:
+            if self.precision == F32 and want_var:
+                if self.lfS is None:
+                    self.lfS = self.fS
+                snaps.append("lfS")
+            if self.kern["mode"] == DIST_EXPANSION and "predict leaks pooled mean" in self.mut and self.uS is not None:
+                self.dropped.append(("predict leaks pooled mean", self.uS))
+                self.taint.add("U")                       # U re-centred on the train + test mean
+        if rc is None:
+            return ModelGpak.posteriorMeanVar(self, Xte, want_var, compat)     # refused before anything is brought up to date
+        return self._answer("posteriorMeanVar", "nlz", snaps, ("alpha", "factor"), Xte, want_var, compat, rc=rc)
+
+    def GradLL(self):
+        if not self.expans_only:
+            return ModelGpak.GradLL(self)                 # refused before anything is brought up to date
+        return self._answer("GradLL", "nlz", ("aS", "fS"), ("alpha", "factor"))
+
+    def GradLL_hyb(self, ng):
+        return self._answer("GradLL_hyb", "nlz", ("aS", "fS"), ("alpha", "factor"), ng)
+
+    def GradLL_exact(self, ng=10):
+        return self._answer("GradLL_exact", "nlz", ("aS", "fS"), ("alpha", "factor"), ng)
+
+    def loo(self):
+        return self._answer("loo", "nlz", ("aS", "fS"), ("alpha", "factor"))
+
+    def _blocks_ok(self, Xd):
+        return self.X is not None and np.asarray(Xd).shape[1] == self.d
+
+    def block_cross(self, Xd, nd):
+        if not self._blocks_ok(Xd):
+            return ModelGpak.block_cross(self, Xd, nd)
+        return self._answer("block_cross", "nlz", (), (), Xd, nd)
+
+    def predict_block(self, Xd, nd, want_var=True, latent=False):
+        if not self._blocks_ok(Xd):
+            return ModelGpak.predict_block(self, Xd, nd, want_var, latent)
+        return self._answer("predict_block", "nlz", ("aS", "fS"), ("alpha", "factor"), Xd, nd, want_var, latent)
+
+    def predict_joint(self, Xd, nd, want_cov=True, latent=False, prior=False):
+        if not self._blocks_ok(Xd):
+            return ModelGpak.predict_joint(self, Xd, nd, want_cov, latent, prior)
+        return self._answer("predict_joint", "nlz", ("aS", "fS"), ("alpha", "factor"), Xd, nd, want_cov, latent, prior)
+
+    def sample_joint(self, Xd, nd, xi, nugget=0.0, latent=False):
+        if not self._blocks_ok(Xd):
+            return ModelGpak.sample_joint(self, Xd, nd, xi, nugget, latent)
+        return self._answer("sample_joint", "nlz", ("aS", "fS"), ("alpha", "factor"), Xd, nd, xi, nugget, latent)
+
+    def timing(self):
+        return {"evaluations": self.evals}

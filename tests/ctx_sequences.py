@@ -1,0 +1,617 @@
+"""Call sequences on one long-lived context (include/gpak.h) and how a step's answer is judged.  TEST INFRASTRUCTURE.
+
+A step is (context index, method of gp_ss_ak_amd.gpak.Gpak, arguments BY KEY); the keys name the small fixed data
+below.  The same steps run on tests/ctx_model.py (CPU) and, through tests/ctx_seq_worker.py, on libgpak_hip.so, where
+every step that returns numbers is compared
+
+  (a) bit for bit with a FRESH context of the same precision that received only the current options, set_train, the
+      current kernel call and that one method, and
+  (b) with ModelGpak, under the bound the method's own GPU test uses (model_errors below names the test).
+
+Training sets (synth.drillholes / drillholes4), N chosen to cross what the state depends on and no larger:
+  129 -> Np 256 (the second tile almost all padding), 300 -> 384, 700 -> 768 (a second, partial 512-column block of the
+  back substitution), 1100 -> 1152 (Np >= 1024: leading-dimension pad 32, two column splits of the row-sum kernels).
+
+Seeded random sequences: RANDOM_COUNT = 4 sequences of RANDOM_LENGTH = 36 steps, seed RANDOM_SEED + k, drawn from the
+same vocabulary at N in {129, 300}; the generator keeps the preconditions (a gradient length matching the composition, no
+gradient with a White child, points with the training set's columns).
+"""
+import functools
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ctx_model as cm  # noqa: E402
+from gp_ss_ak_amd import synth  # noqa: E402
+
+OK, ENOTPD, EINVAL, ESTATE, ENOTIMPL = cm.OK, cm.ENOTPD, cm.EINVAL, cm.ESTATE, cm.ENOTIMPL
+F64, F32 = cm.F64, cm.F32
+EXPANSION, DIRECT = cm.DIST_EXPANSION, cm.DIST_DIRECT
+COMPAT_VARCLAMP, COMPAT_SN2SKIP = 1, 2
+OPTS = {"MEMOISE": 1, "INV512": 9, "PRED_BATCH": 11, "BWD_FUSED": 12, "LOO_ROWS": 14}
+EXPANS, EXP, RBF = 0, 1, 2
+U = 2.0 ** -53
+FILL_TOL = {DIRECT: 1e-13, EXPANSION: 2e-7}      # tests/dev_ops_cases.py FILL_TOL = test_gram_matches_oracle
+
+# ---- the data the keys name -------------------------------------------------------------------------------------------
+TRAIN = {"T129": (129, 3), "T300": (300, 3), "T700": (700, 3), "T1100": (1100, 3), "T1100d4": (1100, 4)}
+E = list(synth.DEFAULT_EXPANS)
+E13 = list(E)
+E13[1] *= 1.3
+THETA2 = [0.3, 1.7, -0.4, 1.1, 0.8, 0.6, 1.2, 0.9]
+# name -> (terms, bias, white, sn2)
+KERN = {
+    "E": ([(EXPANS, E)], synth.DEFAULT_BIAS, 0.0, synth.DEFAULT_SN2),
+    "E13": ([(EXPANS, E13)], synth.DEFAULT_BIAS, 0.0, synth.DEFAULT_SN2),
+    "Esn": ([(EXPANS, E)], synth.DEFAULT_BIAS, 0.0, 0.05),
+    "T2": ([(EXPANS, THETA2)], 0.35, 0.0, 0.05),
+    "ER": ([(EXPANS, E), (RBF, [0.5, 0.9, 0.5])], synth.DEFAULT_BIAS, 0.0, synth.DEFAULT_SN2),
+    "EXR": ([(EXPANS, E), (EXP, [0.5, 0.9]), (RBF, [0.5, 0.9, 0.5])], synth.DEFAULT_BIAS, 0.0, synth.DEFAULT_SN2),
+    "EW": ([(EXPANS, E)], synth.DEFAULT_BIAS, 0.05, synth.DEFAULT_SN2),
+    "BAD": ([(EXPANS, E)], synth.DEFAULT_BIAS, 0.0, -0.5),          # B = I + K / sn2 is indefinite
+}
+NG = {name: sum(cm.NPARS[k] for k, _ in v[0]) + 2 for name, v in KERN.items()}
+POINTS = {"P5": (5, 3), "P300": (300, 3), "P700": (700, 3), "Q5": (5, 4), "Q300": (300, 4)}
+BLOCKS = {"B12x8": (12, 8, 3), "B40x8": (40, 8, 3), "B40x1": (40, 1, 3), "B300x1": (300, 1, 3), "C12x8": (12, 8, 4), "C40x1": (40, 1, 4)}
+DISC = {1: (1, 1, 1), 8: (2, 2, 2)}
+
+
+@functools.lru_cache(maxsize=None)
+def train(key):
+    n, d = TRAIN[key]
+    X, y = synth.drillholes4(n) if d == 4 else synth.drillholes(n)
+    X.setflags(write=False)
+    y.setflags(write=False)
+    return X, y
+
+
+@functools.lru_cache(maxsize=None)
+def points(key):
+    if key.startswith("X:"):
+        return train(key[2:])[0]
+    m, d = POINTS[key]
+    P = synth.test_points4(m) if d == 4 else synth.test_points(m)
+    P.setflags(write=False)
+    return P
+
+
+@functools.lru_cache(maxsize=None)
+def blocks(key):
+    from gp_ss_ak_amd import gpak
+    m, nd, d = BLOCKS[key]
+    rng = np.random.default_rng(7000 + 100 * m + 10 * nd + d)
+    c = rng.uniform(-0.9, 0.9, (m, d))
+    if d == 4:
+        c[:, 3] = rng.integers(0, 4, m) * (2.0 / 3.0) - 1.0
+    Xd, n = gpak.block_points(c, (0.1, 0.1, 0.05), DISC[nd])
+    assert n == nd
+    Xd.setflags(write=False)
+    return Xd, nd
+
+
+@functools.lru_cache(maxsize=None)
+def rhs(n, k):
+    return np.asfortranarray(np.random.default_rng(31 * n + k).standard_normal((n, k)))
+
+
+# ---- steps ------------------------------------------------------------------------------------------------------------
+class Track:
+    """What a fresh context must be given to stand where context c stands: options, training set, kernel call."""
+
+    def __init__(self, precision):
+        self.precision, self.opts, self.train, self.kern = precision, {}, None, None
+
+    def note(self, method, kw):
+        if method == "set_option":
+            self.opts[kw["opt"]] = kw["value"]
+        elif method == "set_train":
+            self.train = kw["train"]
+        elif method in ("set_params", "set_kernel"):
+            self.kern = (method, kw["kern"], kw.get("mode", DIRECT))
+
+    def key(self):
+        return (self.precision, tuple(sorted(self.opts.items())), self.train, self.kern)
+
+    def state(self):
+        """The state in the sense of the separation condition: training set and kernel VALUES (not the distance form,
+        not the options: they change how an answer is computed, not what it is)."""
+        k = self.kern
+        return (self.train, None if k is None else kern_values(k[0], k[1]))
+
+
+def kern_values(method, name):
+    terms, bias, white, sn2 = KERN[name]
+    if method == "set_params":            # gpak_set_params takes the ExpAns child alone and has no White
+        terms, white = [t for t in terms if t[0] == EXPANS][:1], 0.0
+    return (tuple((k, tuple(p)) for k, p in terms), bias, white, sn2)
+
+
+SETTERS = ("set_option", "set_train", "set_params", "set_kernel")
+API_STATUSES = (ENOTPD, EINVAL, ESTATE, ENOTIMPL)    # what the header promises as answers to a question
+DEVICE_ERROR = []         # set by the first call that failed in any other way: contexts are then left unclosed ...
+LEAKED = []               # ... and kept referenced here, so that no destructor calls into the library either
+
+
+def invoke(obj, method, kw, n_train):
+    """Call obj.method with the data the keys name; returns (status, [arrays or None])."""
+    try:
+        if method == "set_option":
+            out = obj.set_option(OPTS[kw["opt"]], kw["value"])
+        elif method == "set_train":
+            out = obj.set_train(*train(kw["train"]))
+        elif method == "set_params":
+            terms, bias, white, sn2 = kern_values("set_params", kw["kern"])
+            out = obj.set_params(np.array(terms[0][1]), bias, sn2, kw.get("mode", DIRECT))
+        elif method == "set_kernel":
+            terms, bias, white, sn2 = KERN[kw["kern"]]
+            out = obj.set_kernel(terms, bias, white, sn2, kw.get("mode", DIRECT))
+        elif method == "gram":
+            out = obj.gram(want_d2=kw.get("want_d2", False))
+        elif method == "compute_k":
+            out = obj.compute_k(points(kw["X1"]), points(kw["X2"]), want_d2=kw.get("want_d2", False))
+        elif method == "solve_chol":
+            out = obj.solve_chol(rhs(n_train, kw["k"]))
+        elif method == "posteriorMeanVar":
+            out = obj.posteriorMeanVar(points(kw["X"]), want_var=kw.get("want_var", True), compat=kw.get("compat", 0))
+        elif method in ("GradLL_hyb", "GradLL_exact"):
+            out = getattr(obj, method)(kw["ng"])
+        elif method == "block_cross":
+            out = obj.block_cross(*blocks(kw["blocks"]))
+        elif method == "predict_block":
+            out = obj.predict_block(*blocks(kw["blocks"]), want_var=kw.get("want_var", True), latent=kw.get("latent", False))
+        elif method == "predict_joint":
+            out = obj.predict_joint(*blocks(kw["blocks"]), want_cov=kw.get("want_cov", True), latent=kw.get("latent", False))
+        elif method == "sample_joint":
+            Xd, nd = blocks(kw["blocks"])
+            out = obj.sample_joint(Xd, nd, np.eye(Xd.shape[0] // nd), nugget=kw.get("nugget", 0.0), latent=kw.get("latent", False))
+        elif method == "timing":
+            t = obj.timing()
+            out = None if t is None else np.array([t["evaluations"]])
+        else:
+            out = getattr(obj, method)()
+    except Exception as e:    # GpakError and ModelError both carry the status of include/gpak.h
+        if getattr(e, "status", None) not in API_STATUSES:
+            # GPAK_EHIP (a HIP failure: the device may have faulted), GPAK_ENOMEM, anything else: not an answer.  The run
+            # ends here with the library's message, and nothing more is asked of the device, not even to close a context.
+            DEVICE_ERROR.append(f"{method} {kw}: {e}")
+            raise
+        return int(e.status), []
+    status = OK
+    if method == "loo":
+        status = int(out[2]["status"])
+        out = (out[0], out[1], np.array([out[2][k] for k in ("mse", "mssr", "log_pl")]))
+    if not isinstance(out, tuple):
+        out = (out,)
+    return status, [None if o is None else np.atleast_1d(np.asarray(o, dtype=float)) for o in out]
+
+
+def same_bits(a, b):
+    """Status and every array equal bit for bit, NaN equal to NaN."""
+    if a[0] != b[0] or len(a[1]) != len(b[1]):
+        return False
+    for x, y in zip(a[1], b[1]):
+        if (x is None) != (y is None):
+            return False
+        if x is not None and not (x.shape == y.shape and np.array_equal(x, y, equal_nan=True)):
+            return False
+    return True
+
+
+def fresh_answer(make, track, method, kw, n_train):
+    """The same question to a context that has done nothing else.  failed_column reports the last factorisation: the fresh
+    context factors first."""
+    g = make(track.precision)
+    try:
+        for opt, value in track.opts.items():
+            must(invoke(g, "set_option", dict(opt=opt, value=value), n_train), "set_option", opt)
+        if track.train:
+            must(invoke(g, "set_train", dict(train=track.train), n_train), "set_train", track.train)
+        if track.kern:
+            must(invoke(g, track.kern[0], dict(kern=track.kern[1], mode=track.kern[2]), n_train), *track.kern)
+        if method == "failed_column":
+            invoke(g, "factor", {}, n_train)
+        return invoke(g, method, kw, n_train)
+    finally:
+        if DEVICE_ERROR:
+            LEAKED.append(g)
+        else:
+            g.close()
+
+
+def must(res, *what):
+    """A setter of the sequences' own vocabulary answers GPAK_OK."""
+    if res[0] != OK:
+        DEVICE_ERROR.append(f"{what}: status {res[0]}")
+        raise RuntimeError(f"{what}: status {res[0]} where GPAK_OK was due")
+    return res
+
+
+def arg_key(kw):
+    return tuple(sorted(kw.items()))
+
+
+def run(seq, make, fresh_make=None, fresh_cache=None):
+    """Drive the sequence; yields one record per step: index, ctx, method, kw, track key, state, result, fresh result
+    (None without fresh_make, and for the setters and timing)."""
+    ctxs, tracks = {}, {}
+    try:
+        for i, (c, method, kw) in enumerate(seq["steps"]):
+            if c not in ctxs:
+                ctxs[c] = make(seq["precision"])
+                tracks[c] = Track(seq["precision"])
+            tr = tracks[c]
+            n_train = TRAIN[tr.train][0] if tr.train else 0
+            res = invoke(ctxs[c], method, kw, n_train)
+            if method in SETTERS:
+                must(res, seq["name"], i, method, kw)
+                tr.note(method, kw)
+            fr = None
+            if fresh_make is not None and method not in SETTERS and method != "timing":
+                fk = (tr.key(), method, arg_key(kw))
+                if fresh_cache is None or fk not in fresh_cache:
+                    ans = fresh_answer(fresh_make, tr, method, kw, n_train)
+                    if fresh_cache is None:
+                        fr = ans
+                    else:
+                        fresh_cache[fk] = ans
+                if fresh_cache is not None:
+                    fr = fresh_cache[fk]
+            yield dict(i=i, ctx=c, method=method, kw=kw, track=tr.key(), state=tr.state(), mode=tr.kern[2] if tr.kern else DIRECT,
+                       train=tr.train, kern=tr.kern, res=res, fresh=fr)
+    finally:
+        if DEVICE_ERROR:
+            LEAKED.extend(ctxs.values())
+        else:
+            for g in ctxs.values():
+                g.close()
+
+
+def model_at(rec, cache, precision=F64):
+    """ModelGpak standing where the record's context stood."""
+    m = cm.ModelGpak(precision, cache)
+    if rec["train"]:
+        m.set_train(*train(rec["train"]))
+    if rec["kern"]:
+        invoke(m, rec["kern"][0], dict(kern=rec["kern"][1], mode=rec["kern"][2]), 0)
+    return m
+
+
+# ---- (b): the bound each method's own GPU test uses -----------------------------------------------------------------
+def rel(a, b):
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(np.asarray(b)).max(), 1e-300))
+
+
+def model_errors(method, kw, got, want, m, precision=F64):
+    """[(label, error, bound)] of a result against the model's, both as invoke returns them.  m: the ModelGpak of the state
+    (scales: max|y|, the prior variance).  An empty list: nothing numeric to compare (statuses are compared apart).
+    Shapes that differ count as an infinite error."""
+    if got[0] != want[0]:
+        return [("status", float("inf"), 1.0)]
+    g, w = got[1], want[1]
+    if len(g) != len(w) or any((x is None) != (y is None) or (x is not None and x.shape != y.shape) for x, y in zip(g, w)):
+        return [("shape", float("inf"), 1.0)]
+    if not g or all(x is None for x in g):
+        return []
+    if any(np.isnan(y).any() for y in w if y is not None):      # quiet NaN where the header promises it: NaN for NaN
+        ok = all(np.array_equal(np.isnan(x), np.isnan(y)) for x, y in zip(g, w) if y is not None)
+        return [("nan", 0.0 if ok else float("inf"), 1.0)]
+    mode = m.kern["mode"] if m.kern else DIRECT
+    direct = mode == DIRECT
+    # 1e-8 DIRECT / 1e-5 EXPANSION: test_predict_matches_oracle, test_reference_style_gradient_matches_oracle.  The tests of
+    # loo, predict_block, predict_joint, sample_joint and GradLL_exact named below hold those methods to 1e-8 in the DIRECT form
+    # and run nothing downstream of the factor in the EXPANSION form, and their references (loo_ref, block_ref, joint_ref,
+    # exact_grad_ref) are direct-form: in the EXPANSION form these methods BORROW the prediction's 1e-5 (they inherit the same
+    # cancellation noise of the Gram matrix through alpha and the factor); no existing test sets a bound of their own there.
+    t8 = 1e-8 if direct else 1e-5
+    plain = m.expans_only and m.d == 3
+    if method in ("gram", "compute_k"):               # test_gram_matches_oracle; 1e-12 on D2: test_other_kernel_compositions, test_four_column_inputs
+        out = [("K", rel(g[0], w[0]), 1e-13 if direct else 2e-7)]
+        if len(g) > 1 and g[1] is not None:
+            out.append(("D2", float(np.abs(g[1] - w[1]).max()), (1e-14 if direct else 1e-13) if plain else 1e-12))
+        return out
+    if method == "factor":
+        return [("factor", float(g[0][0] != w[0][0]), 0.5)]
+    if method == "failed_column":                     # test_not_positive_definite_reports_chol_fail: >= 1 on failure, 0 otherwise
+        return [("failed_column", float((g[0][0] >= 1) != (w[0][0] >= 1)), 0.5)]
+    if method == "chol_upper":                        # test_factor_alpha_nlz_match_oracle (direct form)
+        assert direct
+        return [("R", rel(g[0], w[0]), 1e-11)]
+    if method in ("solve_alpha", "solve_chol"):       # test_factor_alpha_nlz_match_oracle, test_other_kernel_compositions
+        return [("x", rel(g[0], w[0]), t8)]
+    if method == "logLikelihood":                     # 1e-9 direct, 1e-6 expansion: test_other_kernel_compositions
+        return [("nlz", abs(g[0][0] - w[0][0]) / abs(w[0][0]), 1e-9 if direct else 1e-6)]
+    if method == "nlz_terms":                         # test_factor_alpha_nlz_match_oracle
+        b = [1e-9, 1e-9, 1e-11] if direct else [1e-6] * 3
+        return [(n, abs(g[k][0] - w[k][0]) / abs(w[k][0]), b[k]) for k, n in enumerate(("quad", "sumlp", "logdet"))]
+    if method == "posteriorMeanVar":                  # test_predict_matches_oracle; fp32: test_fp32_prediction_context
+        out = [("mean", rel(g[0], w[0]), 1e-8 if precision == F32 else t8)]
+        if g[1] is not None:
+            out.append(("var", rel(g[1], w[1]), 2e-4 if precision == F32 else t8))
+        return out
+    if method in ("GradLL", "GradLL_hyb"):
+        return [("g", float(np.abs(g[0] - w[0]).max() / np.abs(w[0]).max()), t8)]
+    if method == "GradLL_exact":                      # test_exact_gradient_matches_numpy_restatement: per group
+        nk = len(w[0]) - 2
+        return [("kernel block", float(np.abs(g[0][:nk] - w[0][:nk]).max() / np.abs(w[0][:nk]).max()), t8),
+                ("bias", abs(g[0][nk] - w[0][nk]) / abs(w[0][nk]), t8), ("sn2", abs(g[0][nk + 1] - w[0][nk + 1]) / abs(w[0][nk + 1]), t8)]
+    ymax, pv = float(np.abs(m.y).max()), m.prior_variance()
+    if method == "loo":                               # test_loo_matches_numpy_restatement (DIRECT; EXPANSION: borrowed, see t8)
+        return [("mean", float(np.abs(g[0] - w[0]).max() / ymax), t8), ("var", float((np.abs(g[1] - w[1]) / w[1]).max()), t8),
+                ("summary", float((np.abs(g[2] - w[2]) / np.abs(w[2])).max()), t8)]
+    if method == "block_cross":                       # test_block_cross_against_long_double / _in_the_expansion_form
+        nd = BLOCKS[kw["blocks"]][1]
+        wl = np.abs(w[0])
+        bound = FILL_TOL[mode] * float(wl.max()) + (nd + 2) * U * wl
+        return [("kbar", float((np.abs(g[0] - w[0]) / bound).max()), 1.0)]
+    if method == "predict_block":                     # test_predict_block_matches_numpy_reference (DIRECT; EXPANSION: borrowed, see t8)
+        out = [("mean", float(np.abs(g[0] - w[0]).max() / ymax), t8)]
+        if g[1] is not None:
+            out.append(("var", float(np.abs(g[1] - w[1]).max() / pv), t8))
+        return out
+    if method == "predict_joint":                     # test_predict_joint_matches_numpy_reference (DIRECT; EXPANSION: borrowed, see t8)
+        out = [("mean", float(np.abs(g[0] - w[0]).max() / ymax), t8)]
+        if g[1] is not None:
+            out.append(("cov", float(np.abs(g[1] - w[1]).max() / pv), t8))
+        return out
+    if method == "sample_joint":
+        # The normals are the identity, so Z - mean 1' is the factor Lc itself (test_identity_normals_return_the_factor).
+        # Lc Lc' against the MODEL's covariance + nugget I: the covariance's own bound t8 * prior variance
+        # (test_predict_joint_matches_numpy_reference) plus the backward error of the factorisation, 8 (M + 1) u max diag
+        # (test_identity_normals_return_the_factor), plus the rounding of Z = mean + Lc taken away again:
+        # |d_ij| <= u (|mean_i| + |Lc_ij|), which moves (Lc Lc')_ij by at most 2 u (max|mean| + sqrt(max diag)) sqrt(M max diag)
+        # (Cauchy-Schwarz on a row of Lc).  A factor's conditioning does not enter: the product is compared, not Lc.
+        Xd, nd = blocks(kw["blocks"])
+        M = Xd.shape[0] // nd
+        _, cov = m.predict_joint(Xd, nd, latent=kw.get("latent", False))
+        A = cov + kw.get("nugget", 0.0) * np.eye(M)
+        Lc = g[0].astype(np.longdouble) - g[1].astype(np.longdouble)[:, None]
+        dmax = float(np.diag(A).max())
+        bound = t8 * pv + 8 * (M + 1) * U * dmax + 2 * U * (float(np.abs(g[1]).max()) + dmax ** 0.5) * (M * dmax) ** 0.5
+        return [("mean", float(np.abs(g[1] - w[1]).max() / ymax), t8),
+                ("Lc Lc'", float(np.abs((Lc @ Lc.T).astype(float) - A).max()), bound),
+                ("above the diagonal", float(np.abs(np.triu(Lc.astype(float), 1)).max()), 4 * U * float(np.abs(g[1]).max()) + 1e-300)]
+    raise AssertionError(method)
+
+
+def worst(errs):
+    return max([0.0] + [e / b for _, e, b in errs])
+
+
+# ---- the named sequences -------------------------------------------------------------------------------------------------
+def S(method, ctx=0, **kw):
+    return (ctx, method, kw)
+
+
+def opt(name, value, ctx=0):
+    return S("set_option", ctx, opt=name, value=value)
+
+
+def everything(pts, b8, b1, ng=10, hyb=False, ctx=0):
+    """predict with variance, predict_block, predict_joint, sample_joint, loo and the gradients of the composition"""
+    out = [S("posteriorMeanVar", ctx, X=pts), S("predict_block", ctx, blocks=b8), S("predict_joint", ctx, blocks=b1),
+           S("sample_joint", ctx, blocks=b1), S("loo", ctx)]
+    out += [S("GradLL_hyb", ctx, ng=ng)] if hyb else [S("GradLL", ctx)]
+    return out + [S("GradLL_exact", ctx, ng=ng)]
+
+
+def seq_memo():
+    """GPAK_OPT_MEMOISE: gpak_set_params after a composition whose ExpAns child, bias, sn2 and distance form are the
+    values it is given (an extra child; a White child), and the reverse; identical values rebuild nothing (the count of
+    factorisations stands still); the distance form alone, sn2 alone rebuild."""
+    s = [opt("MEMOISE", 1), S("set_train", train="T300")]
+    for comp in ("ER", "EW"):
+        s += [S("set_kernel", kern=comp), S("logLikelihood"), S("timing"),
+              S("set_params", kern="E"), S("logLikelihood"), S("timing"), S("solve_alpha"), S("posteriorMeanVar", X="P5"), S("loo"),
+              S("GradLL"), S("nlz_terms"),
+              S("set_params", kern="E"), S("logLikelihood"), S("timing"), S("solve_alpha")]          # identical: nothing rebuilt
+    s += [S("set_kernel", kern="ER"), S("logLikelihood"), S("timing"), S("set_kernel", kern="EW"), S("logLikelihood"), S("loo"),
+          S("set_kernel", kern="EW"), S("logLikelihood"), S("timing"),                                 # set_kernel always rebuilds
+          S("set_params", kern="E"), S("logLikelihood"), S("timing"),
+          S("set_params", kern="E", mode=EXPANSION), S("logLikelihood"), S("timing"), S("nlz_terms"),
+          S("set_params", kern="E", mode=EXPANSION), S("logLikelihood"), S("timing"),
+          S("set_params", kern="Esn", mode=EXPANSION), S("logLikelihood"), S("timing"), S("nlz_terms"),
+          opt("MEMOISE", 0), S("set_params", kern="Esn", mode=EXPANSION), S("logLikelihood"), S("timing")]
+    return s
+
+
+def seq_gram_between(mode):
+    """gpak_gram reuses the matrix buffer: whatever factor it held is gone, alpha and nlZ with it.  In the expansion form
+    a prediction centres ITS copy of the training points on the train + test mean: the Gram matrices after it must still
+    be centred on the training mean."""
+    s = [S("set_train", train="T300"), S("set_params", kern="T2", mode=mode), S("logLikelihood"),
+         S("set_params", kern="E", mode=mode), S("logLikelihood"), S("gram", want_d2=True), S("solve_alpha"),
+         S("posteriorMeanVar", X="P300"), S("loo"), S("compute_k", X1="X:T300", X2="P5", want_d2=True), S("gram"),
+         S("posteriorMeanVar", X="P5", compat=COMPAT_VARCLAMP | COMPAT_SN2SKIP), S("predict_block", blocks="B12x8"), S("gram"),
+         S("logLikelihood"), S("nlz_terms")]
+    if mode == DIRECT:
+        s += [S("gram"), S("chol_upper")]
+    return s
+
+
+def seq_size_walk():
+    """N 300 -> 1100 -> 129 -> 1100 with 3 -> 4 -> 3 -> 3 input columns: buffers grown at the large size are used at the
+    small one and the other way round; the kernel is set once per column count and survives gpak_set_train."""
+    s = [S("set_train", train="T300"), S("set_params", kern="E")] + everything("P300", "B12x8", "B40x1")
+    s += [S("set_train", train="T1100d4"), S("set_params", kern="T2")] + everything("Q300", "C12x8", "C40x1")
+    s += [S("set_train", train="T129")] + everything("P300", "B12x8", "B40x1")
+    s += [S("set_train", train="T1100")] + everything("P300", "B12x8", "B40x1")
+    return s
+
+
+def seq_prediction_buffers(mode, ctx=0):
+    """dWt / dPart / dPv / dXte / Upred / Tq are shared by the point, block and joint paths, dXblk / dTblk / dC by the
+    block and joint ones; M = 700 under GPAK_OPT_PRED_BATCH = 256 is three batches with a ragged last one."""
+    c = dict(ctx=ctx)
+    return [S("set_train", train="T700", **c), S("set_params", kern="E", mode=mode, **c), opt("PRED_BATCH", 256, ctx),
+            S("posteriorMeanVar", X="P700", **c), S("predict_block", blocks="B40x8", **c), S("predict_joint", blocks="B300x1", **c),
+            S("sample_joint", blocks="B300x1", **c), opt("PRED_BATCH", 0, ctx), S("posteriorMeanVar", X="P5", **c),
+            S("block_cross", blocks="B40x8", **c), opt("PRED_BATCH", 256, ctx), S("posteriorMeanVar", X="P700", want_var=False, **c),
+            S("set_params", kern="T2", mode=mode, **c), S("posteriorMeanVar", X="P700", **c), S("predict_block", blocks="B40x8", latent=True, **c),
+            S("predict_joint", blocks="B40x8", latent=True, **c), opt("PRED_BATCH", 0, ctx), S("posteriorMeanVar", X="P300", **c),
+            S("gram", **c), S("logLikelihood", **c)]
+
+
+def seq_solve_scratch():
+    """dWork: L^-1 y / sn2 from the factorisation, the right-hand sides of gpak_solve_chol, the back substitution's
+    scratch.  GPAK_OPT_INV512 / GPAK_OPT_BWD_FUSED change between calls without a gpak_set_params, then with one."""
+    return [S("set_train", train="T700"), S("set_params", kern="E"), S("factor"), S("solve_chol", k=3), S("solve_alpha"),
+            S("logLikelihood"), S("solve_chol", k=1), S("GradLL"), S("solve_alpha"), S("chol_upper"),
+            opt("INV512", 0), S("solve_chol", k=3), S("solve_alpha"), opt("BWD_FUSED", 0), opt("INV512", 1), S("solve_chol", k=1),
+            S("logLikelihood"),
+            S("set_params", kern="E13"), S("solve_chol", k=3), S("solve_alpha"), S("logLikelihood"),
+            opt("BWD_FUSED", 1), S("set_params", kern="E"), S("solve_alpha"), S("solve_chol", k=1),
+            opt("INV512", 0), S("set_params", kern="E13"), S("solve_chol", k=3), S("solve_alpha"), S("nlz_terms"),
+            opt("INV512", 1), opt("BWD_FUSED", 2), S("set_params", kern="E"), S("solve_alpha"), S("chol_upper")]
+
+
+def seq_fail_and_recover():
+    """sn2 = -0.5: the factorisation fails.  NaN / GPAK_ENOTPD where the header promises them, the same failing values
+    again under memoisation still fail, and good parameters afterwards answer as a fresh context does."""
+    al = [S("logLikelihood"), S("failed_column"), S("solve_alpha")] + everything("P5", "B12x8", "B40x1")
+    bad = [S("logLikelihood"), S("failed_column"), S("loo"), S("predict_block", blocks="B12x8"), S("predict_joint", blocks="B40x1"),
+           S("sample_joint", blocks="B40x1"), S("block_cross", blocks="B12x8"), S("GradLL"), S("GradLL_exact", ng=10),
+           S("posteriorMeanVar", X="P5"), S("solve_alpha"), S("nlz_terms"), S("factor"), S("failed_column")]
+    return ([S("set_train", train="T300"), S("set_params", kern="E")] + al + [S("set_params", kern="BAD")] + bad +
+            [opt("MEMOISE", 1), S("set_params", kern="BAD"), S("logLikelihood"), S("timing"), S("failed_column"), S("loo"),
+             S("set_params", kern="E13")] + al + [S("chol_upper"), S("timing")])
+
+
+def seq_gradients(ctx=0):
+    """dG / dGpart are shared by the three gradients and gpak_loo; a refused gradient leaves the context as it was."""
+    c = dict(ctx=ctx)
+    return [S("set_train", train="T300", **c), S("set_params", kern="E", **c), S("GradLL", **c), S("loo", **c), S("GradLL_exact", ng=10, **c),
+            S("set_params", kern="E13", **c), S("loo", **c), S("GradLL", **c),
+            S("set_kernel", kern="ER", **c), S("GradLL_hyb", ng=13, **c), S("GradLL_exact", ng=13, **c), S("GradLL", **c),
+            S("logLikelihood", **c), S("solve_alpha", **c), S("GradLL_exact", ng=10, **c),
+            S("set_kernel", kern="EXR", **c), S("GradLL_hyb", ng=15, **c), S("loo", **c), S("GradLL_exact", ng=15, **c),
+            S("set_kernel", kern="EW", **c), S("GradLL_exact", ng=10, **c), S("loo", **c), S("logLikelihood", **c),
+            S("set_params", kern="T2", **c), S("GradLL_exact", ng=10, **c), S("GradLL", **c)]
+
+
+def seq_f32():
+    """GPAK_F32: the fp32 image of the factor follows new parameters and a new training set; loo, predict_block and
+    predict_joint in between are fp64 per the header."""
+    return [S("set_train", train="T300"), S("set_params", kern="E"), S("posteriorMeanVar", X="P300"), S("loo"),
+            S("set_params", kern="T2"), S("posteriorMeanVar", X="P300"), S("predict_block", blocks="B12x8"),
+            S("set_train", train="T1100"), S("posteriorMeanVar", X="P300"), S("predict_joint", blocks="B40x1"),
+            S("set_params", kern="E"), S("loo"), S("posteriorMeanVar", X="P300"), S("posteriorMeanVar", X="P5", want_var=False),
+            S("set_train", train="T129"), S("posteriorMeanVar", X="P300")]
+
+
+def seq_two_contexts():
+    """Two live contexts of different N advanced alternately, step by step."""
+    a, b = seq_prediction_buffers(DIRECT, 0), seq_gradients(1)
+    out = []
+    for k in range(max(len(a), len(b))):
+        out += a[k:k + 1] + b[k:k + 1]
+    return out
+
+
+def seq_out_of_order():
+    """Calls before gpak_set_train and before any parameters return GPAK_ESTATE and leave the context usable;
+    gpak_set_params before gpak_set_train; gpak_set_train twice."""
+    early = ["logLikelihood", "nlz_terms", "solve_alpha", "gram", "factor", "loo", "GradLL"]
+    s = [S(m) for m in early] + [S("GradLL_exact", ng=10), S("posteriorMeanVar", X="P5"), S("predict_block", blocks="B12x8"),
+                                 S("predict_joint", blocks="B40x1"), S("sample_joint", blocks="B40x1"), S("failed_column")]
+    s += [S("set_params", kern="E")] + [S(m) for m in early] + [S("posteriorMeanVar", X="P5"), S("predict_block", blocks="B12x8"),
+                                                                 S("compute_k", X1="P300", X2="P5")]
+    s += [S("set_train", train="T129"), S("logLikelihood"), S("solve_alpha"), S("posteriorMeanVar", X="P5")]
+    s += [S("set_train", ctx=1, train="T129")] + [S(m, ctx=1) for m in early] + [S("predict_block", ctx=1, blocks="B12x8"),
+                                                                                  S("posteriorMeanVar", ctx=1, X="P5"),
+                                                                                  S("posteriorMeanVar", ctx=1, X="Q5")]
+    s += [S("set_params", ctx=1, kern="E13"), S("logLikelihood", ctx=1), S("loo", ctx=1)]
+    s += [S("set_train", train="T300"), S("set_train", train="T129"), S("logLikelihood"), S("solve_alpha"), S("loo"),
+          S("posteriorMeanVar", X="Q5"), S("logLikelihood")]
+    return s
+
+
+RANDOM_SEED, RANDOM_COUNT, RANDOM_LENGTH = 20171027, 4, 36
+
+
+def seq_random(k):
+    rng = np.random.default_rng(RANDOM_SEED + k)
+    pick = lambda a: a[int(rng.integers(len(a)))]   # noqa: E731
+    cur = dict(train=None, kern=None)
+
+    def set_train():
+        cur["train"] = pick(["T129", "T300"])
+        return S("set_train", train=cur["train"])
+
+    def set_kern():
+        cur["kern"] = pick(["E", "E13", "T2", "Esn", "ER", "EXR", "EW"])
+        if cur["kern"] in ("ER", "EXR", "EW"):
+            return S("set_kernel", kern=cur["kern"])
+        return S("set_params", kern=cur["kern"])
+
+    steps = [set_train(), set_kern()]
+    plain = lambda: cur["kern"] in ("E", "E13", "T2", "Esn")   # noqa: E731
+    while len(steps) < RANDOM_LENGTH:
+        r = rng.random()
+        if r < 0.08:
+            steps.append(set_train())
+        elif r < 0.25:
+            steps.append(set_kern())
+        elif r < 0.33:
+            steps.append(opt(*pick([("PRED_BATCH", 256), ("PRED_BATCH", 0), ("LOO_ROWS", 128), ("LOO_ROWS", 0), ("MEMOISE", 1), ("MEMOISE", 0)])))
+        else:
+            m = pick(["gram", "factor", "solve_alpha", "solve_chol", "logLikelihood", "nlz_terms", "posteriorMeanVar", "grad", "exact", "loo",
+                      "block_cross", "predict_block", "predict_joint", "sample_joint", "compute_k", "chol_upper"])
+            ng = NG[cur["kern"]]
+            if m == "grad":
+                if cur["kern"] == "EW":
+                    continue
+                steps.append(S("GradLL") if plain() else S("GradLL_hyb", ng=ng))
+            elif m == "exact":
+                if cur["kern"] == "EW":
+                    continue
+                steps.append(S("GradLL_exact", ng=ng))
+            elif m == "solve_chol":
+                steps.append(S("solve_chol", k=int(rng.integers(1, 4))))
+            elif m == "posteriorMeanVar":
+                steps.append(S("posteriorMeanVar", X=pick(["P5", "P300"]), want_var=bool(rng.integers(2))))
+            elif m == "compute_k":
+                steps.append(S("compute_k", X1="P300", X2="P5"))
+            elif m in ("block_cross", "predict_block"):
+                steps.append(S(m, blocks=pick(["B12x8", "B40x1"])))
+            elif m in ("predict_joint", "sample_joint"):
+                steps.append(S(m, blocks=pick(["B12x8", "B40x1"])))
+            else:
+                steps.append(S(m))
+    return steps
+
+
+def _seq(name, group, steps, precision=F64, doc=""):
+    return dict(name=name, group=group, steps=steps, precision=precision, doc=doc)
+
+
+SEQUENCES = [
+    _seq("memo", "memo", seq_memo()),
+    _seq("gram between [direct]", "gram", seq_gram_between(DIRECT)),
+    _seq("gram between [expansion]", "gram", seq_gram_between(EXPANSION)),
+    _seq("size walk", "walk", seq_size_walk()),
+    _seq("prediction buffers [direct]", "pred", seq_prediction_buffers(DIRECT)),
+    _seq("prediction buffers [expansion]", "pred", seq_prediction_buffers(EXPANSION)),
+    _seq("solve scratch", "solve", seq_solve_scratch()),
+    _seq("fail and recover", "fail", seq_fail_and_recover()),
+    _seq("gradients", "grad", seq_gradients()),
+    _seq("f32", "f32", seq_f32(), F32),
+    _seq("two contexts", "two", seq_two_contexts()),
+    _seq("out of order", "order", seq_out_of_order()),
+] + [_seq(f"random {k}", "random", seq_random(k)) for k in range(RANDOM_COUNT)]
+GROUPS = []
+for _s in SEQUENCES:
+    if _s["group"] not in GROUPS:
+        GROUPS.append(_s["group"])
+BY_NAME = {s["name"]: s for s in SEQUENCES}
+
+# which function of include/gpak.h a step reaches (gpak_create / gpak_destroy / gpak_last_error: every context made, closed,
+# every status turned into GpakError)
+ENTRY = {"set_option": "gpak_set_option", "set_train": "gpak_set_train", "set_params": "gpak_set_params", "set_kernel": "gpak_set_kernel",
+         "gram": "gpak_gram", "compute_k": "gpak_compute_k", "factor": "gpak_factor", "failed_column": "gpak_failed_column",
+         "chol_upper": "gpak_get_chol_upper", "solve_alpha": "gpak_solve_alpha", "solve_chol": "gpak_solve_chol", "logLikelihood": "gpak_nlz",
+         "nlz_terms": "gpak_nlz_terms", "posteriorMeanVar": "gpak_predict", "GradLL": "gpak_grad", "GradLL_hyb": "gpak_grad_hyb",
+         "GradLL_exact": "gpak_grad_exact", "loo": "gpak_loo", "block_cross": "gpak_block_cross", "predict_block": "gpak_predict_block",
+         "predict_joint": "gpak_predict_joint", "sample_joint": "gpak_sample_joint", "timing": "gpak_timing"}
+ALWAYS = {"gpak_create", "gpak_destroy", "gpak_last_error"}
