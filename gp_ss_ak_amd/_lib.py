@@ -17,6 +17,8 @@ SYMBOLS = [
     "gpak_get_chol_upper", "gpak_failed_column", "gpak_solve_alpha", "gpak_solve_chol", "gpak_nlz",
     "gpak_nlz_terms", "gpak_predict", "gpak_grad", "gpak_grad_hyb", "gpak_grad_exact", "gpak_loo", "gpak_block_cross", "gpak_predict_block", "gpak_predict_joint", "gpak_sample_joint", "gpak_timing", "gpak_calibrate", "gpak_reload_tuning",
 ]
+# every symbol include/gpak_loo_grad.h declares (tests/test_loo_grad.py checks the header and this list agree)
+LOO_GRAD_SYMBOLS = ["gpak_loo_grad"]
 
 
 class PhaseTimes(C.Structure):
@@ -46,9 +48,9 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). gp_ss_ak_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS if not hasattr(lib, s)]
     if missing:
-        raise RuntimeError(f"libgpak_hip.so lacks symbols declared in include/gpak.h: {missing}")
+        raise RuntimeError(f"libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -79,6 +81,7 @@ def load():
     lib.gpak_grad_hyb.argtypes = [vp, dp, C.c_int]
     lib.gpak_grad_exact.argtypes = [vp, dp, C.c_int]
     lib.gpak_loo.argtypes = [vp, dp, dp, C.POINTER(LooSummary)]
+    lib.gpak_loo_grad.argtypes = [vp, dp, C.c_int, C.POINTER(LooSummary)]
     lib.gpak_block_cross.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp]
     lib.gpak_predict_block.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.gpak_predict_joint.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]

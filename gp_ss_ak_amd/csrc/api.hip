@@ -886,6 +886,27 @@ int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary
   return rc;
 }
 
+int gpak_loo_grad(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary) {
+  if (!ctx || !g) return GPAK_EINVAL;
+  if (ctx->multi) {
+    ctx->err = "gpak_loo_grad is built for the single-GPU context (gpak_create) only";
+    return GPAK_ENOTIMPL;
+  }
+  // what the call refuses is refused before anything is factored
+  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
+  if (!ctx->have_params) { ctx->err = "no parameters (gpak_set_params)"; return GPAK_ESTATE; }
+  int rc = gpak_loo_grad_layout(ctx, ng);
+  if (rc) return rc;
+  rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK) rc = gpak_loo_grad_impl(ctx, g, ng, summary);
+  if (rc == GPAK_ENOTPD) {   // as gpak_loo
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int i = 0; i < ng; i++) g[i] = nan;
+    if (summary) { summary->mse = summary->mssr = summary->log_pl = nan; summary->ms = 0.0; summary->passes = 0; }
+  }
+  return rc;
+}
+
 static int block_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *var,
                       int flags, double *Kbar_host) {
   if (ctx->multi) {

@@ -431,6 +431,10 @@ int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng);
 int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng);
 // gpak_loo on a single-GPU context whose factor and alpha are current; mean, var, summary may each be null
 int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary);
+// gpak_loo_grad on a single-GPU context whose factor and alpha are current; summary may be null
+int gpak_loo_grad_impl(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary);
+// its refusals, from the composition alone: GPAK_EINVAL for a wrong ng, GPAK_ENOTIMPL for a White child or a second ExpAns child
+int gpak_loo_grad_layout(gpak_ctx *ctx, int ng);
 // Rot (Kernel.cpp:1399-1410) of the ExpAns parameters e; D (optional): D[a] = dRot / d angle_a
 void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]);
 void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *expans, int d, int N, double sn2,

@@ -4,8 +4,9 @@
 // 1164-1284) with Kern_ExpAnisotropic::getGradients (Kernel.cpp:886-1263) and
 // Kern_Bias::getGradients (:370-377), FORMULAS AS WRITTEN (this is not the
 // true gradient -- the optimiser trajectory of the reference depends on it as it is).
-// gpak_grad_exact is the derivative of nlZ itself; gpak_dev_grad_* (further down) is the as-written gradient
-// distributed over ranks by row blocks.
+// gpak_grad_exact is the derivative of nlZ itself; gpak_loo (leave-one-out cross-validation) is step 1 below alone and
+// gpak_loo_grad the gradient of its pseudo-likelihood: the exact pass with another weight matrix; gpak_dev_grad_*
+// (further down) is the as-written gradient distributed over ranks by row blocks.
 //
 // Reference: Q = solve_chol(Lchol, diag(sW)) with N right-hand sides (2N^3 flops), ~15 N x N
 // temporaries, six N x 3 * 3 x N GEMMs.  Here, for the Gaussian likelihood (d3lp = 0, so
@@ -620,25 +621,34 @@ static void pair_sums(hipStream_t st, const KernParams &kp, const int *kinds, in
   hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(NSUM), dim3(256), 0, st, part, (int)(grid.x * grid.y), out);
 }
 
+// what every single-GPU gradient checks first: ng against the composition's layout (children in order, 8 / 2 / 3
+// entries, then bias and sn2), at most one ExpAns child (*te: its index, -1: none), no White child
+static int grad_layout(gpak_ctx *ctx, const char *entry, const char *white, int ng, int *te) {
+  const std::string who = std::string(entry) + ": ";
+  int need = 2;
+  *te = -1;
+  for (int t = 0; t < ctx->kp.nterms; t++) {
+    need += ctx->kinds[t] == GPAK_KERN_EXPANS ? 8 : ctx->kinds[t] == GPAK_KERN_EXP ? 2 : 3;
+    if (ctx->kinds[t] == GPAK_KERN_EXPANS) {
+      if (*te >= 0) { ctx->err = who + "at most one ExpAns child"; return GPAK_ENOTIMPL; }
+      *te = t;
+    }
+  }
+  if (ng != need) { ctx->err = who + "gradient vector has the wrong length"; return GPAK_EINVAL; }
+  if (ctx->kp.white != 0.0) { ctx->err = who + white; return GPAK_ENOTIMPL; }
+  return GPAK_OK;
+}
+
 // the single-GPU entry points: kinds of the current composition (set by gpak_set_params / gpak_set_kernel)
 template <class Pass>
 static int grad_single(gpak_ctx *ctx, double *g, int ng) {
   GPAK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int N = ctx->N, Np = ctx->Np;
-  const std::string who = std::string(Pass::entry) + ": ";
-  // expected length: children in order (8 / 2 / 3), bias, sn2
-  int need = 2, te = -1;
-  for (int t = 0; t < ctx->kp.nterms; t++) {
-    need += ctx->kinds[t] == GPAK_KERN_EXPANS ? 8 : ctx->kinds[t] == GPAK_KERN_EXP ? 2 : 3;
-    if (ctx->kinds[t] == GPAK_KERN_EXPANS) {
-      if (te >= 0) { ctx->err = who + "at most one ExpAns child"; return GPAK_ENOTIMPL; }
-      te = t;
-    }
-  }
-  if (ng != need) { ctx->err = who + "gradient vector has the wrong length"; return GPAK_EINVAL; }
-  if (ctx->kp.white != 0.0) { ctx->err = who + Pass::white; return GPAK_ENOTIMPL; }
-  int rc = grad_binv(ctx);
+  int te = -1;
+  int rc = grad_layout(ctx, Pass::entry, Pass::white, ng, &te);
+  if (rc) return rc;
+  rc = grad_binv(ctx);
   if (rc) return rc;
   // 3. fused pair pass
   rc = grad_partials(ctx, (size_t)(Np / GT_ROWS) * (Np / GT_COLS) * NSUM);
@@ -756,6 +766,16 @@ __global__ __launch_bounds__(256) void gpak_loo_finish_f64(int N, const double *
     part[(size_t)blockIdx.x * NSUM + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
+// the summary from the three sums of gpak_loo_finish_f64 (gpak_loo and gpak_loo_grad: the same expressions, so the same bytes)
+static void loo_fill_summary(gpak_loo_summary *summary, const double *red, int N, double ms, int P) {
+  if (!summary) return;
+  summary->mse = red[0] / N;
+  summary->mssr = red[1] / N;
+  summary->log_pl = -0.5 * (red[1] + red[2] + N * log(2.0 * M_PI));
+  summary->ms = ms;
+  summary->passes = P;
+}
+
 int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary) {
   GPAK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -815,13 +835,183 @@ int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *su
   GPAK_HIP(hipGetLastError());
   float ms = 0;
   GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[9]));
-  if (summary) {
-    summary->mse = red[0] / N;
-    summary->mssr = red[1] / N;
-    summary->log_pl = -0.5 * (red[1] + red[2] + N * log(2.0 * M_PI));
-    summary->ms = ms;
-    summary->passes = P;
+  loo_fill_summary(summary, red, N, ms, P);
+  return GPAK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The gradient of the leave-one-out pseudo-likelihood (gpak_loo_grad): F = -log_pl of gpak_loo (Rasmussen & Williams
+// eq. 5.10-5.13).  With Kinv = (K + sn2 I)^-1 = B^-1 / sn2, alpha = Kinv y and kappa_i = Kinv_ii = d_i / sn2,
+//   F = sum_i [ -1/2 log kappa_i + alpha_i^2 / (2 kappa_i) ] + N/2 log 2 pi,    dF / d theta = 1/2 sum_ij W_ij dK_ij / d theta,
+//   c_i = (1 / kappa_i + alpha_i^2 / kappa_i^2) / 2,   b_i = alpha_i / kappa_i,   v = Kinv b,
+//   W = 2 M - v alpha^T - alpha v^T,   M = Kinv diag(c) Kinv = H H^T,   H = Kinv diag(sqrt c).
+// W is symmetric and every sum of ExactPass is linear in the weight, so the pass and its host assembly serve as they
+// are: handed sn2 = 1 and a zero alpha, the skeleton's qw is the stored entry itself.  Memory: the gradient's two
+// N x N workspaces and nothing else -- G then H in dG, B^-1 then W (lower tiles) in dBinv.
+// ---------------------------------------------------------------------------------------
+#define LM_T 64   // tile of the mirror and rank-2 kernels; 128 / LM_T tiles per GEMM tile side
+
+// s_i = sqrt(c_i) / sn2 (column scale of H = B^-1 diag(s)) and r_i = b_i / sn2 (right-hand side of v = B^-1 r) for
+// i < N; 0 on the padding
+__global__ __launch_bounds__(256) void gpak_loo_vectors_f64(int N, int Np, const double *__restrict__ d,
+                                                            const double *__restrict__ alpha, double sn2,
+                                                            double *__restrict__ s, double *__restrict__ r) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Np) return;
+  double sv = 0.0, rv = 0.0;
+  if (i < N) {
+    const double ik = sn2 / d[i];          // 1 / kappa_i: the LOO variance
+    const double b = alpha[i] * ik;        // y_i - mu_i
+    const double c = 0.5 * (ik + b * b);
+    sv = sqrt(c) / sn2;
+    rv = b / sn2;
   }
+  s[i] = sv;
+  r[i] = rv;
+}
+
+// H[i, k] = s_k B^-1[max(i, k), min(i, k)] for i, k < N and 0 elsewhere: the FULL Np x Np matrix from the stored lower
+// tiles of B^-1.  One workgroup per 64 x 64 tile (bi >= bj) of the lower triangle: it writes the tile itself from
+// registers and its transpose through LDS, so that the reads and both writes run along columns, 16 bytes per lane.
+// A lane holds the row pair (2l, 2l + 1); in LDS both indices are permuted, x -> x / 2 + 32 (x & 1), and the pitch is
+// 65: the stores of a half-wave then go to consecutive doubles and its transposed loads to doubles 65 apart, both free
+// of bank conflicts.  A tile on the diagonal holds both halves of its own output: every entry is taken from the lower
+// half, so that H diag(1/s) is symmetric bit for bit.  Np^2 / 2 reads, Np^2 writes.
+#define LM_PERM(x) (((x) >> 1) + 32 * ((x) & 1))
+__global__ __launch_bounds__(256) void gpak_loo_mirror_scale_f64(int N, const double *__restrict__ Binv, long ldb,
+                                                                 const double *__restrict__ s, double *__restrict__ H, long ldh) {
+  const int bi = blockIdx.x, bj = blockIdx.y;
+  if (bi < bj) return;
+  __shared__ double tile[LM_T][LM_T + 1];   // tile[LM_PERM(k)][LM_PERM(i)] = B^-1[i0 + i, k0 + k]
+  const int i0 = bi * LM_T, k0 = bj * LM_T;
+  const int l = threadIdx.x & 31, r = 2 * l, c8 = threadIdx.x >> 5;
+  const bool diag = bi == bj;
+  // rows i0 + r, i0 + r + 1 of the stored tile, eight of its columns
+#pragma unroll
+  for (int u = 0; u < 8; u++) {
+    const int c = c8 + 8 * u;
+    const double2 q = *reinterpret_cast<const double2 *>(Binv + (size_t)(i0 + r) + (size_t)(k0 + c) * ldb);
+    tile[LM_PERM(c)][l] = q.x;
+    tile[LM_PERM(c)][l + 32] = q.y;
+    if (!diag) {
+      const double sk = s[k0 + c];   // 0 for k >= N
+      double2 o;
+      o.x = i0 + r < N ? sk * q.x : 0.0;
+      o.y = i0 + r + 1 < N ? sk * q.y : 0.0;
+      *reinterpret_cast<double2 *>(H + (size_t)(i0 + r) + (size_t)(k0 + c) * ldh) = o;
+    }
+  }
+  __syncthreads();
+  if (diag) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      const int c = c8 + 8 * u, pc = LM_PERM(c);
+      const double sk = s[k0 + c];
+      double2 o;
+      o.x = i0 + r < N ? sk * (r >= c ? tile[pc][l] : tile[l][pc]) : 0.0;
+      o.y = i0 + r + 1 < N ? sk * (r + 1 >= c ? tile[pc][l + 32] : tile[l + 32][pc]) : 0.0;
+      *reinterpret_cast<double2 *>(H + (size_t)(i0 + r) + (size_t)(k0 + c) * ldh) = o;
+    }
+    return;
+  }
+  // the transpose: rows k0 + r, k0 + r + 1 and eight of the columns i0 + c of H
+#pragma unroll
+  for (int u = 0; u < 8; u++) {
+    const int c = c8 + 8 * u, pc = LM_PERM(c);
+    const double si = s[i0 + c];     // 0 for i >= N
+    double2 o;
+    o.x = k0 + r < N ? si * tile[l][pc] : 0.0;
+    o.y = k0 + r + 1 < N ? si * tile[l + 32][pc] : 0.0;
+    *reinterpret_cast<double2 *>(H + (size_t)(k0 + r) + (size_t)(i0 + c) * ldh) = o;
+  }
+}
+
+// W[i, j] -= v_i alpha_j + alpha_i v_j on the 64 x 64 tiles bi >= bj of the lower triangle, in place (v and alpha are 0 on
+// the padding)
+__global__ __launch_bounds__(256) void gpak_loo_rank2_f64(double *__restrict__ W, long ld, const double *__restrict__ v,
+                                                          const double *__restrict__ alpha) {
+  const int bi = blockIdx.x, bj = blockIdx.y;
+  if (bi < bj) return;
+  const int i = bi * LM_T + 2 * (threadIdx.x & 31), c8 = threadIdx.x >> 5;
+  const double2 vi = *reinterpret_cast<const double2 *>(v + i), ai = *reinterpret_cast<const double2 *>(alpha + i);
+#pragma unroll
+  for (int u = 0; u < 8; u++) {
+    const int j = bj * LM_T + c8 + 8 * u;
+    const double vj = v[j], aj = alpha[j];
+    double2 *p = reinterpret_cast<double2 *>(W + (size_t)i + (size_t)j * ld);
+    double2 w = *p;
+    w.x -= fma(vi.x, aj, ai.x * vj);
+    w.y -= fma(vi.y, aj, ai.y * vj);
+    *p = w;
+  }
+}
+
+// gpak_loo_grad on a single-GPU context whose factor and alpha are current.  Everything goes to the context's stream
+// and the host waits once, at the end.  Afterwards dG holds H and dBinv holds W: no claim is left behind, because
+// gpak_grad / gpak_grad_hyb / gpak_grad_exact run grad_binv (G and B^-1 anew) and gpak_loo runs grad_g_subst (G anew)
+// on EVERY call -- the context keeps no validity flag for either workspace.  dAlpha, the factor, nlZ and the first two
+// vectors of dWork (z_ok) are only read.
+int gpak_loo_grad_layout(gpak_ctx *ctx, int ng) {
+  int te;
+  return grad_layout(ctx, "gpak_loo_grad", ExactPass::white, ng, &te);
+}
+
+int gpak_loo_grad_impl(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np, T = Np / PB;
+  const long ld = ctx->ld;
+  int te = -1;
+  int rc = grad_layout(ctx, "gpak_loo_grad", ExactPass::white, ng, &te);
+  if (rc) return rc;
+  // scratch in the gradient's partial-sum buffer: gpak_loo's layout (d, mean, var, the finish kernel's block sums, the
+  // chunk sums), reused by the pair pass once d has been consumed
+  const int nch = (Np + LOO_CHUNK - 1) / LOO_CHUNK, nfin = (N + 255) / 256;
+  rc = grad_partials(ctx, std::max(3 * (size_t)Np + (size_t)nfin * NSUM + (size_t)nch * Np,
+                                   (size_t)(Np / GT_ROWS) * (Np / GT_COLS) * NSUM));
+  if (rc) return rc;
+  rc = gpak_ensure_U(ctx);
+  if (rc) return rc;
+  double *dd = ctx->dGpart, *dmean = dd + Np, *dvar = dmean + Np, *fin = dvar + Np, *part = fin + (size_t)nfin * NSUM;
+  // five vectors of dWork behind the back substitution's scratch (which starts at 2 Np: api.hip sizes dWork as 70 Np +
+  // that scratch), in what is otherwise the Gram mat-vec's transient room
+  const int bw = ctx->bwd_bw;
+  double *bs_scratch = ctx->dWork + 2 * (size_t)Np;
+  double *vs = bs_scratch + (size_t)std::max(8 + bw / 32, 34) * bw, *vr = vs + Np, *vz = vr + Np, *vv = vz + Np, *zero = vv + Np;
+  // 1. G = L^-T in dG, B^-1 in dBinv (records ev[7])
+  rc = grad_binv(ctx);
+  if (rc) return rc;
+  // 2. the LOO diagonal and summary: what gpak_loo launches on dG (P = 1)
+  hipLaunchKernelGGL(gpak_loo_sumsq_f64, dim3(T, nch), dim3(256), 0, st, ctx->dG, ld, Np, 1, 0, (long)Np, part);
+  hipLaunchKernelGGL(gpak_loo_rowsum_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, part, (long)Np, nch, 1, 0, dd);
+  hipLaunchKernelGGL(gpak_loo_finish_f64, dim3(nfin), dim3(256), 0, st, N, dd, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, fin);
+  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(3), dim3(256), 0, st, fin, nfin, ctx->dRed + 32);
+  // 3. s, r and v = B^-1 r by two substitutions on scratch vectors
+  hipLaunchKernelGGL(gpak_loo_vectors_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, dd, ctx->dAlpha, ctx->sn2, vs, vr);
+  gpak_launch_trsv_fwd(st, Np, ctx->dM, ld, ctx->dInv, vr, vz);
+  gpak_backsolve(ctx, st, vz, vv, bs_scratch);
+  // 4. H into dG (G has been consumed)
+  const dim3 lt(Np / LM_T, Np / LM_T);
+  hipLaunchKernelGGL(gpak_loo_mirror_scale_f64, lt, dim3(256), 0, st, N, ctx->dBinv, ld, vs, ctx->dG, ld);
+  // 5. 2 M = 2 H H^T, lower tiles, into dBinv; H is full: the k-loop runs over all of Np
+  gpak_launch_gemm_nt(st, T, T, Np, 2.0, ctx->dG, ld, ctx->dG, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, false);
+  // 6. W = 2 M - v alpha^T - alpha v^T
+  hipLaunchKernelGGL(gpak_loo_rank2_f64, lt, dim3(256), 0, st, ctx->dBinv, ld, vv, ctx->dAlpha);
+  // 7. the exact pass with W for its weight
+  GPAK_HIP(hipMemsetAsync(zero, 0, sizeof(double) * Np, st));
+  pair_sums<ExactPass>(st, ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode, ctx->d, ctx->U.base, ctx->U.cap,
+                       ctx->dX, Np, N, Np, zero, ctx->dBinv, ld, 0, 0, 1.0, ctx->dGpart, ctx->dRed + 8);
+  double red[NSUM], lred[3];
+  GPAK_HIP(hipMemcpyAsync(red, ctx->dRed + 8, sizeof(red), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipMemcpyAsync(lred, ctx->dRed + 32, sizeof(lred), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipEventRecord(ctx->ev[3], st));
+  GPAK_HIP(hipEventSynchronize(ctx->ev[3]));
+  GPAK_HIP(hipGetLastError());
+  float ms = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[3]));
+  ctx->times.grad_ms = ms;
+  ExactPass::assemble(ctx, red, g);
+  loo_fill_summary(summary, lred, N, ms, 1);
   return GPAK_OK;
 }
 

@@ -199,6 +199,16 @@ class Gpak:
         out["status"] = rc
         return mean, var, out
 
+    def loo_grad(self, ng=10):
+        """The gradient of -log_pl of loo() (gpak_loo_grad): (g, summary), g in GradLL_exact's layout and summary as
+        loo()'s.  On Chol_fail status is ENOTPD and every number is NaN."""
+        g = np.zeros(int(ng))
+        s = _lib.LooSummary()
+        rc = self._check(self._lib.gpak_loo_grad(self._h, _p(g), int(ng), C.byref(s)), allow=(ENOTPD,))
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        return g, out
+
     def _blocks(self, Xd, nd):
         Xd = _f(Xd)
         nd = int(nd)

@@ -23,9 +23,16 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
     }
     else if (isArg("--gradient", "--gradient")) {
       incArg();
+      gradient_set = true;
       if (getArg() == "reference") exact_gradient = false;
       else if (getArg() == "exact") exact_gradient = true;
       else ErrorTermination("--gradient takes reference or exact");
+    }
+    else if (isArg("--objective", "--objective")) {
+      incArg();
+      if (getArg() == "nlz") loo_objective = false;
+      else if (getArg() == "loo") loo_objective = true;
+      else ErrorTermination("--objective takes nlz or loo");
     }
     else if (isArg("-t", "--timing")) { incArg(); timing_file = getArg(); }   // "-" = stdout
     else if (isArg("--block-size", "--block-size") || isArg("--block-disc", "--block-disc")) {
@@ -53,6 +60,10 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
     else break;
     incArg();
   }
+  if (loo_objective && gradient_set && !exact_gradient)
+    ErrorTermination("--objective loo has an exact gradient only (gpak_loo_grad) and implies its driver: drop --gradient reference");
+  if (loo_objective && gpus > 1)
+    ErrorTermination("--objective loo runs on one GPU only (the leave-one-out gradient is not built for multi-GPU contexts): drop --gpus");
   if (exact_gradient && gpus > 1)
     ErrorTermination("--gradient exact runs on one GPU only (the exact gradient is not built for multi-GPU contexts): drop --gpus or use --gradient reference");
 }

@@ -7,7 +7,9 @@
 //            sim nodes.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
-// (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only).
+// (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only),
+// --objective nlz|loo (loo: `train` minimises -log_pl of the leave-one-out predictions, what `cv` reports, with its exact
+// gradient gpak_loo_grad and the exact gradient's driver; the objective column of the trace holds -log_pl; one GPU only).
 // cv (not a reference verb): leave-one-out cross-validation of a trained model on its training set, from one
 // factorisation (gpak_loo; one GPU only), written to <model>_loo.txt.
 // block (not a reference verb): mean and standard deviation of the AVERAGE grade of rectangular blocks (gpak_predict_block;
@@ -40,6 +42,7 @@ class GP_Cntrl : public Control {
   GP_Cntrl(int argc, char **argv) : Control(argc, argv) {
     GP_utils::setDeviceOptions(precision, gpus);
     GP_utils::setExactGradient(exact_gradient);
+    GP_utils::setLooObjective(loo_objective);
   }
   void writeTiming(const GP_utils &m) const {
     if (timing_file.empty()) return;
@@ -58,7 +61,7 @@ class GP_Cntrl : public Control {
 
 void GP_Cntrl::Help() const {
   std::cout << "\nGP_SS_AK hot path on MI355X\nCommand:\n \t ./gp_ss_ak [options] Command [Comnd-options] TrainDataFile.txt modelName\n"
-            << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood.\n"
+            << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood).\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time.\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"

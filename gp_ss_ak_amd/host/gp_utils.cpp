@@ -13,6 +13,7 @@
 int GP_utils::default_precision = GPAK_F64;
 int GP_utils::default_gpus = 1;
 bool GP_utils::exact_gradient = false;
+bool GP_utils::loo_objective = false;
 
 void GP_utils::create_ctx() {
   int rc;
@@ -113,9 +114,21 @@ double GP_utils::logLikelihood() const {
   return nlz;
 }
 
+double GP_utils::LooObjective() const {
+  sync_params();
+  gpak_loo_summary s;
+  int rc = gpak_loo(ctx, nullptr, nullptr, &s);
+  Chol_fail = (rc == GPAK_ENOTPD);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_loo", ctx);
+  return -s.log_pl;   // NaN on Chol_fail
+}
+
 double GP_utils::GradLL(mat &g) const {  // GP_Utils.cpp:1171-1262
-  double nlz = logLikelihood();
-  if (Chol_fail) return std::numeric_limits<double>::quiet_NaN();
+  double nlz = std::numeric_limits<double>::quiet_NaN();
+  if (!loo_objective) {
+    nlz = logLikelihood();
+    if (Chol_fail) return std::numeric_limits<double>::quiet_NaN();
+  }
   // one device call evaluates GradLL + every child's getGradients; the result comes back as the
   // stationary children's blocks in order, then the Bias entry, then the likelihood entry
   std::vector<const Kernels *> leaves;
@@ -135,7 +148,15 @@ double GP_utils::GradLL(mat &g) const {  // GP_Utils.cpp:1171-1262
     ng += (int)c->getNPars();
   }
   std::vector<double> gd(ng);
-  if (exact_gradient) {
+  if (loo_objective) {
+    sync_params();
+    gpak_loo_summary s;
+    int rc = gpak_loo_grad(ctx, gd.data(), ng, &s);
+    Chol_fail = (rc == GPAK_ENOTPD);
+    if (Chol_fail) return std::numeric_limits<double>::quiet_NaN();
+    if (rc != GPAK_OK) gpak_host_fatal("gpak_loo_grad", ctx);
+    nlz = -s.log_pl;
+  } else if (exact_gradient) {
     if (gpak_grad_exact(ctx, gd.data(), ng) != GPAK_OK) gpak_host_fatal("gpak_grad_exact", ctx);
   } else if (gpak_grad_hyb(ctx, gd.data(), ng) != GPAK_OK) gpak_host_fatal("gpak_grad_hyb", ctx);
   unsigned out = 0;

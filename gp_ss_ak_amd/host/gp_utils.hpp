@@ -107,12 +107,15 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   void get_GP_Pars(mat &param) const override;
   void set_GP_Pars(mat &param) const override;
   double Grad_Values(mat &g) const override { return GradLL(g); }
-  double ObjVal() const override { return logLikelihood(); }
+  double ObjVal() const override { return loo_objective ? LooObjective() : logLikelihood(); }
   std::string getParName(unsigned int i) const override { return i < KerenlW->getNPars() ? KerenlW->getParamName(i) : "likelihood"; }
-  bool exactGradient() const override { return exact_gradient; }
+  bool exactGradient() const override { return exact_gradient || loo_objective; }
 
   double logLikelihood() const;   // NaN on Chol_fail (GP_Utils.cpp:1145-1158)
-  double GradLL(mat &g) const;    // g is 1 x getNumPars(); the exact gradient (gpak_grad_exact) when exact_gradient is set
+  // g is 1 x getNumPars(); the exact gradient (gpak_grad_exact) when exact_gradient is set; with loo_objective the
+  // gradient of LooObjective() (gpak_loo_grad), which is then the value returned
+  double GradLL(mat &g) const;
+  double LooObjective() const;    // -log_pl of gpak_loo at the current parameters; NaN on Chol_fail
   // leave-one-out cross-validation of the training set from the current factor (gpak_loo): mean and variance (noise
   // included) of every yTarg(i) given all the other samples, N x 1 each; NaN on Chol_fail
   void LooCV(mat &mean, mat &var, gpak_loo_summary &s) const;
@@ -144,6 +147,9 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // the CLI's --gradient: false (default) = GradLL + getGradients as the reference writes them (gpak_grad_hyb),
   // true = the derivative of logLikelihood() (gpak_grad_exact) and, through Optimise(), the driver that suits it
   static void setExactGradient(bool v) { exact_gradient = v; }
+  // the CLI's --objective: false (default) = Optimise() minimises logLikelihood(); true = it minimises LooObjective()
+  // with its exact gradient, through the exact gradient's driver
+  static void setLooObjective(bool v) { loo_objective = v; }
   // gpak_phase_times of this model's context as one JSON object (the CLI's --timing)
   std::string timingJson() const;
   bool Chol_failed() const { return Chol_fail; }
@@ -160,7 +166,7 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   void sync_params() const;
   gpak_ctx *ctx = nullptr;
   static int default_precision, default_gpus;
-  static bool exact_gradient;
+  static bool exact_gradient, loo_objective;
   void create_ctx();
   bool owns_kernel = false;
   mutable bool dirty = true;     // KUpdateStat / AlphaUpStatus (GP_Utils.h:257-279)

@@ -205,6 +205,8 @@ typedef struct {
 /* mean (N), var (N), summary: each may be NULL */
 int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary);
 
+/* The gradient of the pseudo-likelihood log_pl, for training on it: gpak_loo_grad.h, included at the end of this file. */
+
 /* Block-support prediction (block kriging): mean and variance of the AVERAGE of the field over each of M blocks, block b
  * given by nd discretisation points with uniform weights.  Xd is (M*nd) x d column-major, row b*nd + a = point a of
  * block b.  With B = I + K/sn2 = L L^T and alpha = (K + sn2 I)^-1 y:
@@ -258,7 +260,7 @@ typedef struct {
   double solve_ms;     /* two triangular solves                                          */
   double nlz_ms;       /* f = K alpha (fused Gram-matvec), lp, reductions                */
   double predict_ms;   /* last gpak_predict / gpak_predict_block / gpak_block_cross / gpak_*_joint */
-  double grad_ms;      /* last gpak_grad / gpak_grad_hyb / gpak_grad_exact               */
+  double grad_ms;      /* last gpak_grad / gpak_grad_hyb / gpak_grad_exact / gpak_loo_grad */
   /* trailing-update kernel (the dominant, MFMA-bound launch), last factorisation,
    * measured with hipEvents on the ctx stream when GPAK_OPT_PROFILE is set: */
   double trailing_ms;        /* sum of launch durations                                  */
@@ -288,4 +290,5 @@ int gpak_calibrate(gpak_ctx *ctx, double *mfma_f64_tflops, double *hbm_write_gbs
 #ifdef __cplusplus
 }
 #endif
+#include "gpak_loo_grad.h"
 #endif /* GPAK_H */
