@@ -380,7 +380,12 @@ int gpak_set_option(gpak_ctx *ctx, int option, long value) {
 
 int gpak_set_train(gpak_ctx *ctx, const double *X, const double *y, int N, int d) {
   if (!ctx || !X || !y || N <= 0) return GPAK_EINVAL;
-  if (ctx->multi) { ctx->N = N; ctx->d = d; GPAK_MULTI_ERR(gpak_multi_set_train(ctx->multi, X, y, N, d)); }
+  if (ctx->multi) {   // N and d change only once the group has accepted the set: a refused call leaves the context as it was
+    int v = gpak_multi_set_train(ctx->multi, X, y, N, d);
+    if (v) { ctx->err = gpak_multi_error(ctx->multi); return v; }
+    ctx->N = N; ctx->d = d;
+    return GPAK_OK;
+  }
   // d = 3: x, y, z; d = 4: + rock-type column with its own inverse width (Kernel.cpp:1411-1424)
   if (d != 3 && d != 4) { ctx->err = "inputs must have 3 or 4 columns"; return GPAK_ENOTIMPL; }
   GPAK_HIP(hipSetDevice(ctx->device));
@@ -475,11 +480,11 @@ int gpak_set_kernel(gpak_ctx *ctx, int nterms, const int *kinds, const double *p
                     double sn2, int dist_mode) {
   if (!ctx || !kinds || !pars || nterms < 1 || nterms > GPAK_MAX_TERMS) return GPAK_EINVAL;
   if (dist_mode != GPAK_DIST_EXPANSION && dist_mode != GPAK_DIST_DIRECT) { ctx->err = "bad dist_mode"; return GPAK_EINVAL; }
-  if (ctx->multi) { ctx->sn2 = sn2; GPAK_MULTI_ERR(gpak_multi_set_kernel(ctx->multi, nterms, kinds, pars, bias, white, sn2, dist_mode)); }
   KernParams kp;
   double kdiag = 0.0;
   int rc = gpak_build_kp(nterms, kinds, pars, bias, white, dist_mode, &kp, &kdiag);
-  if (rc) { ctx->err = "unknown kernel kind"; return rc; }
+  if (rc) { ctx->err = "unknown kernel kind"; return rc; }   // before a group stores anything: a refused call changes nothing
+  if (ctx->multi) { ctx->sn2 = sn2; GPAK_MULTI_ERR(gpak_multi_set_kernel(ctx->multi, nterms, kinds, pars, bias, white, sn2, dist_mode)); }
   {
     const double *p = pars;
     for (int t = 0; t < nterms; t++) {

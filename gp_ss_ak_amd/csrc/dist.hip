@@ -758,11 +758,12 @@ int gpak_dist_set_kernel(gpak_dist *h, int nterms, const int *kinds, const doubl
   if (!h || !kinds || !pars || nterms < 1 || nterms > GPAK_MAX_TERMS) return GPAK_EINVAL;
   if (dist_mode != GPAK_DIST_EXPANSION && dist_mode != GPAK_DIST_DIRECT) { h->err = "bad dist_mode"; return GPAK_EINVAL; }
   if (!h->E.transform_k || !h->E.vec_axpy) { h->err = "the engine has no transform_k / vec_axpy entry"; return GPAK_ENOTIMPL; }
+  for (int t = 0; t < nterms; t++)   // refused before the stored composition is touched
+    if (kinds[t] != GPAK_KERN_EXPANS && kinds[t] != GPAK_KERN_EXP && kinds[t] != GPAK_KERN_RBF) { h->err = "unknown kernel kind"; return GPAK_EINVAL; }
   memset(h->kern, 0, sizeof(h->kern));
   h->kern[0] = nterms; h->kern[4] = white;
   int np = 0;
   for (int t = 0; t < nterms; t++) {
-    if (kinds[t] != GPAK_KERN_EXPANS && kinds[t] != GPAK_KERN_EXP && kinds[t] != GPAK_KERN_RBF) { h->err = "unknown kernel kind"; return GPAK_EINVAL; }
     h->kern[1 + t] = kinds[t];
     const int k = kinds[t] == GPAK_KERN_EXPANS ? 8 : kinds[t] == GPAK_KERN_EXP ? 2 : 3;
     if (kinds[t] == GPAK_KERN_EXPANS) memcpy(h->expans, pars + np, sizeof(double) * 8);

@@ -232,6 +232,7 @@ struct gpak_multi {
 
 static int ensure_replica(gpak_multi *g, int r) {
   if (!g->test_engines.empty()) return g->fail(r, GPAK_ENOTIMPL, "a group over caller-supplied engines has no device replicas");
+  if (!g->N) return g->fail(r, GPAK_ESTATE, "no training set (gpak_set_train)");   // not GPAK_EINVAL from a replica handed an empty set
   if (!g->replicas[r]) {
     int rc = gpak_create(&g->replicas[r], g->devices[r], g->precision);
     if (rc) return g->fail(r, rc, std::string("replica context: ") + gpak_global_error());
@@ -391,6 +392,7 @@ int gpak_multi_set_train(gpak_multi *g, const double *X, const double *y, int N,
   g->acc_ms[0] = g->acc_ms[1] = g->acc_ms[2] = g->acc_ms[3] = 0;
   g->evaluations = 0;
   g->failed_col = 0;
+  g->factor_current = false;   // the ranks dropped their result with the old set: the next evaluation is a new one and counts
   return g->run([&](int r) {
     int v = gpak_dist_set_train(g->ranks[r], g->X.data(), g->y.data(), N, d, g->nb);
     return v ? g->fail(r, v, gpak_dist_last_error(g->ranks[r])) : (int)GPAK_OK;
@@ -445,7 +447,9 @@ int gpak_multi_nlz(gpak_multi *g, double *nlz, double *quad, double *sumlp, doub
   });
   if (nlz) *nlz = v[0];
   g->failed_col = gpak_dist_failed_column(g->ranks[0]);   // min-reduced inside factor(): the same on every rank
-  if (fresh) {   // a new evaluation (not a cached result): rank 0's phase times join the accumulated totals
+  // a new evaluation (not a cached result): rank 0's phase times join the accumulated totals.  A failed factorisation is
+  // one; a call refused before anything was factored (GPAK_ESTATE: no parameters yet) is not
+  if (fresh && (rc == GPAK_OK || rc == GPAK_ENOTPD)) {
     gpak_dist_stats st;
     if (gpak_dist_get_stats(g->ranks[0], &st) == GPAK_OK) {
       g->acc_ms[0] += st.fill_ms; g->acc_ms[1] += st.factor_ms;
@@ -541,6 +545,7 @@ int gpak_multi_on_replica0(gpak_multi *g, const std::function<int(gpak_ctx *)> &
 // replica's factor from the packed panels it already holds (device-to-device copies, N^2/2 doubles) and predicts a
 // contiguous slice with the pooled mean of ALL test points.
 int gpak_multi_predict(gpak_multi *g, const double *Xte, long M, int d, double *mean, double *var) {
+  if (!g->N) { g->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }   // as gpak_predict on one GPU: before the columns
   if (d != g->d) { g->err = "test points must have as many columns as the training set"; return GPAK_EINVAL; }
   double nlz;
   int rc = gpak_multi_nlz(g, &nlz, nullptr, nullptr, nullptr);

@@ -99,8 +99,9 @@ class Gpak:
     def set_train(self, X, y):
         X = _f(X)
         y = np.ascontiguousarray(y, dtype=np.float64).ravel()
-        self.N, self.d = X.shape
-        self._check(self._lib.gpak_set_train(self._h, _p(X), _p(y), self.N, self.d))
+        N, d = X.shape
+        self._check(self._lib.gpak_set_train(self._h, _p(X), _p(y), N, d))
+        self.N, self.d = N, d      # only once the library accepted the set: the outputs below are sized by them
 
     def set_params(self, expans, bias, sn2, dist_mode=DIST_DIRECT):
         e = np.ascontiguousarray(expans, dtype=np.float64)
@@ -273,6 +274,9 @@ class Gpak:
         out = {name: getattr(t, name) for name, _ in t._fields_}
         out["accumulated_ms"] = list(t.accumulated_ms)
         return out
+
+    def n_gpus(self):
+        return self._lib.gpak_n_gpus(self._h)
 
     def transport(self):
         return self._lib.gpak_transport(self._h).decode()

@@ -11,6 +11,10 @@ built, which call drops it -- that answers every question from the state its fla
 ModelGpak step for step.  Each name in MUTATIONS drops one invalidation; tests/test_ctx_sequences.py proves on the CPU
 that every one of them is caught by a named sequence, i.e. that the sequences would notice the corresponding slip in
 api.hip.
+
+GroupCaching does the same for a group (gpak_create_multi): the flags of csrc/multi.hip, RankCore::have_result of
+csrc/dist.hip and the replica contexts' flags, with GROUP_MUTATIONS; it also counts the evaluations gpak_timing reports.
+ModelGpak(ranks > 1) is the stateless model of a group: the calls built for one GPU alone are refused.
 """
 import hashlib
 import os
@@ -58,8 +62,9 @@ def _digest(*arrays):
 
 
 class ModelGpak:
-    def __init__(self, precision=F64, cache=None):
+    def __init__(self, precision=F64, cache=None, ranks=1):
         self.precision = precision
+        self.ranks = int(ranks)               # > 1: a group (gpak_create_multi): the calls built for one GPU alone are refused
         self.cache = {} if cache is None else cache
         self.opts = {}
         self.X = self.y = self.tkey = None
@@ -94,6 +99,8 @@ class ModelGpak:
         if dist_mode not in (DIST_EXPANSION, DIST_DIRECT) or not 1 <= len(terms) <= 3:
             raise ModelError(EINVAL, "kernel")
         terms = tuple((int(k), tuple(float(v) for v in p)) for k, p in terms)
+        if any(k not in NPARS for k, _ in terms):
+            raise ModelError(EINVAL, "unknown kernel kind")
         self.kern = dict(terms=terms, bias=float(bias), white=float(white), sn2=float(sn2), mode=int(dist_mode))
         self.kkey = (terms, float(bias), float(white), float(sn2), int(dist_mode))
 
@@ -237,13 +244,29 @@ class ModelGpak:
         return self._cached("grad_hyb", lambda: _orc().grad_hyb(self.X, self.y, f["K"], f["L"], f["alpha"], self._terms(), True,
                                                                 k["sn2"], k["mode"])).copy()
 
+    def _single_only(self, name):
+        if self.ranks > 1:
+            raise ModelError(ENOTIMPL, f"{name} is built for the single-GPU context only")
+
+    def n_gpus(self):
+        return self.ranks
+
+    def transport(self):
+        return "none" if self.ranks == 1 else "in-process peer copies"       # every rank of a test's group sits on device 0
+
+    def loo_grad(self, ng=10):
+        self._single_only("gpak_loo_grad")
+        raise AssertionError("the sequences ask gpak_loo_grad of groups only (tests/test_loo_grad_gpu.py holds it to its reference)")
+
     def GradLL_exact(self, ng=10):
+        self._single_only("gpak_grad_exact")
         self._fit_ok()
         self._grad_checks(ng)
         k = self.kern
         return self._cached("grad_exact", lambda: xref.grad_exact(self.X, self.y, self._terms(), k["bias"], k["sn2"])).copy()
 
     def loo(self):
+        self._single_only("gpak_loo")
         f = self._fit()
         nan = float("nan")
         if f["col"]:
@@ -256,6 +279,7 @@ class ModelGpak:
         return m.copy(), v.copy(), dict(s, status=OK)
 
     def _block_pre(self, Xd, nd):
+        self._single_only("the block and joint calls")
         Xd = np.asfortranarray(Xd, dtype=float)
         if self.X is None:
             raise ModelError(ESTATE, "no training set")
@@ -586,6 +610,249 @@ class CachingModel(ModelGpak):
         if not self._blocks_ok(Xd):
             return ModelGpak.sample_joint(self, Xd, nd, xi, nugget, latent)
         return self._answer("sample_joint", "nlz", ("aS", "fS"), ("alpha", "factor"), Xd, nd, xi, nugget, latent)
+
+    def timing(self):
+        return {"evaluations": self.evals}
+
+
+# -------------------------------------------------------------------------------------------------------------------------
+# Each name drops ONE invalidation or reset of the group's three layers (csrc/multi.hip, RankCore::have_result of
+# csrc/dist.hip, the replica contexts).  GROUP_MUTATIONS change an answer, a status or the count of evaluations;
+# GROUP_REDUNDANT name resets that another reset covers (replica_train_ok = 0 makes ensure_replica clear replica_params_ok,
+# and that clears replica_factor_ok), so dropping one of them alone changes nothing that can be observed.
+GROUP_MUTATIONS = ("set_train keeps factor_current", "set_train keeps count", "set_params keeps factor_current",
+                   "set_params keeps have_result", "set_train keeps replica train", "set_params keeps replica params",
+                   "gram keeps replica factor", "set_params keeps general_kernel", "recovery keeps failed_column",
+                   "import keeps f32 image")
+GROUP_REDUNDANT = ("set_train keeps replica factor", "set_params keeps replica factor")
+
+
+class _Replica:
+    """What multi.hip knows about the gpak_ctx of one rank (train_ok, params_ok, factor_ok) and what that context holds:
+    the training set and kernel it was last given (tS, kS: keys), the state its matrix buffer's factor was built from (fS;
+    None: no factor), the state of its fp32 image (lfS), and whether the matrix buffer holds K where the group believes L."""
+
+    def __init__(self):
+        self.train_ok = self.params_ok = self.factor_ok = False
+        self.tS = self.kS = self.fS = self.lfS = None
+        self.N = 0
+        self.holds_K = False
+
+
+class GroupCaching(ModelGpak):
+    """The validity logic of a group: gpak_multi (factor_current, failed_col, evaluations, general_kernel), the ranks'
+    have_result / have_params, and per rank the replica flags with the replica's own factor state.  Answers come from
+    ModelGpak at the snapshot the flags point at; a replica that holds something else than the flags say spoils them."""
+
+    def __init__(self, precision=F64, cache=None, ranks=2, mut=()):
+        super().__init__(precision, cache, ranks)
+        unknown = [m for m in mut if m not in GROUP_MUTATIONS + GROUP_REDUNDANT]
+        assert not unknown and ranks >= 2, (unknown, ranks)
+        self.mut = set(mut)
+        self.states = {}
+        self.rep = [_Replica() for _ in range(ranks)]
+        self.rS = None                        # RankCore::have_result, as the state the ranks' result was built from
+        self.rank_failed = 0                  # RankCore::failed_col
+        self.failS = None
+        self.factor_current = False
+        self.general = False
+        self.have_params = False
+        self.failed_col = 0
+        self.evals = 0
+        self.dropped = []
+
+    _cur, _at = CachingModel._cur, CachingModel._at
+
+    def _keeps(self, name, what=True):
+        if name in self.mut and what:
+            self.dropped.append((name, what))
+            return True
+        return False
+
+    # -- state --------------------------------------------------------------------------------------------------------
+    def set_option(self, opt, value):
+        pass                                  # gpak_set_option on a group: nothing to set, GPAK_OK
+
+    def set_train(self, X, y):
+        super().set_train(X, y)               # refused (columns) before anything is stored
+        for r in self.rep:
+            if not self._keeps("set_train keeps replica train", r.train_ok):
+                r.train_ok = False
+            if not self._keeps("set_train keeps replica factor", r.factor_ok):
+                r.factor_ok = False
+        if not self._keeps("set_train keeps count", self.evals):
+            self.evals = 0
+        self.failed_col = 0
+        if not self._keeps("set_train keeps factor_current", self.factor_current):
+            self.factor_current = False
+        self.rS = None                        # release_problem: the ranks' buffers are gone
+
+    def _new_kernel(self, general):
+        if not (self.general and not general and self._keeps("set_params keeps general_kernel")):
+            self.general = general
+        self.have_params = True
+        for r in self.rep:
+            if not self._keeps("set_params keeps replica params", r.params_ok):
+                r.params_ok = False
+            if not self._keeps("set_params keeps replica factor", r.factor_ok):
+                r.factor_ok = False
+        if not self._keeps("set_params keeps factor_current", self.factor_current):
+            self.factor_current = False
+        if not self._keeps("set_params keeps have_result", self.rS):
+            self.rS = None
+
+    def set_params(self, expans, bias, sn2, dist_mode=DIST_DIRECT):
+        super().set_params(expans, bias, sn2, dist_mode)
+        self._new_kernel(False)
+
+    def set_kernel(self, terms, bias, white, sn2, dist_mode=DIST_DIRECT):
+        super().set_kernel(terms, bias, white, sn2, dist_mode)
+        self._new_kernel(True)
+
+    # -- gpak_multi_nlz ---------------------------------------------------------------------------------------------------
+    def _nlz(self):
+        if self.X is None or self.kern is None:
+            return ESTATE                     # the group / every rank refuses: nothing is factored, nothing counted
+        fresh = not self.factor_current
+        rc = OK
+        if self.rS is None:
+            S = self._cur()
+            self.rank_failed = self._at(S)._fit()["col"]
+            if self.rank_failed:
+                self.failS, rc = S, ENOTPD
+            else:
+                self.rS = S
+        if not (rc == OK and self._keeps("recovery keeps failed_column", self.failed_col)):
+            self.failed_col = self.rank_failed
+        if fresh:
+            self.evals += 1                   # a failed factorisation is an evaluation too
+        if rc == OK:
+            self.factor_current = True
+        return rc
+
+    def _ask(self, name, rc, S, *a, spoil=False, **k):
+        if rc == ENOTPD:
+            S = self.failS
+        elif rc:
+            S = self._cur()                   # ModelGpak raises the same status there
+        out = getattr(ModelGpak, name)(self._at(S), *a, **k)
+        return _spoil(out) if spoil and rc == OK else out
+
+    # -- the replicas (ensure_replica / replica_with_factor of multi.hip) -------------------------------------------------
+    def _ensure_replica(self, r):
+        p = self.rep[r]
+        if not p.train_ok:
+            p.tS, p.N, p.fS, p.lfS, p.holds_K = self.tkey, self.N, None, None, False     # gpak_set_train on the replica
+            p.train_ok, p.params_ok = True, False
+        if not p.params_ok:
+            if not self.have_params:
+                raise ModelError(ESTATE, "no parameters")
+            p.kS, p.fS = self.kkey, None
+            p.params_ok, p.factor_ok = True, False
+
+    def _with_factor(self, r, factors_itself=False):
+        """Bring replica r up to the ranks' factor as multi.hip does; returns whether the replica then holds what the group
+        believes it holds.  factors_itself: the call goes through the replica's own ensure_factor (solve_chol, the factor
+        copy, the gradient), which factors from what the replica holds when its matrix buffer has no factor; the sharded
+        prediction reads the buffer as it is."""
+        self._ensure_replica(r)
+        p = self.rep[r]
+        if not p.factor_ok:
+            if p.N != self.N:
+                raise ModelError(ESTATE, "gpak_import_factor: the context does not hold the group's training set")
+            p.fS, p.holds_K, p.factor_ok = self.rS, False, True
+            if not self._keeps("import keeps f32 image", p.lfS):
+                p.lfS = None
+        if factors_itself and p.fS is None:
+            p.fS, p.holds_K = "own", False
+        held = (p.tS, p.kS) == self.rS
+        return held and p.fS in (self.rS, "own") and not p.holds_K
+
+    def _on_replica0(self, name, wants_factor, *a, **k):
+        if wants_factor:
+            rc = self._nlz()
+            if rc:
+                return self._ask(name, rc, None, *a, **k)
+            return self._ask(name, OK, self.rS, *a, spoil=not self._with_factor(0, True), **k)
+        if self.X is None:
+            raise ModelError(ESTATE, "no training set")
+        self._ensure_replica(0)
+        p = self.rep[0]
+        return self._ask(name, OK, self._cur(), *a, spoil=(p.tS, p.kS) != (self.tkey, self.kkey), **k)
+
+
+    # -- hot path ------------------------------------------------------------------------------------------------------------
+    def gram(self, want_d2=False):
+        out = self._on_replica0("gram", False, want_d2)
+        p = self.rep[0]
+        p.fS = None                           # gpak_gram on the replica: its matrix buffer holds K
+        if self._keeps("gram keeps replica factor", p.factor_ok):
+            p.holds_K = True
+        else:
+            p.factor_ok = False
+        return out
+
+    def compute_k(self, X1, X2, want_d2=False):
+        out = self._on_replica0("compute_k", False, X1, X2, want_d2)
+        self.rep[0].factor_ok = False         # not needed (the call leaves the matrix alone): costs one import
+        return out
+
+    def factor(self):
+        rc = self._nlz()
+        if rc == ESTATE:
+            return ModelGpak.factor(self)
+        return rc == OK
+
+    def failed_column(self):
+        return self.failed_col
+
+    def chol_upper(self):
+        return self._on_replica0("chol_upper", True)
+
+    def solve_chol(self, X):
+        return self._on_replica0("solve_chol", True, X)
+
+    def solve_alpha(self):
+        return self._ask("solve_alpha", self._nlz(), self.rS)
+
+    def logLikelihood(self):
+        return self._ask("logLikelihood", self._nlz(), self.rS)
+
+    def nlz_terms(self):
+        return self._ask("nlz_terms", self._nlz(), self.rS)
+
+    def posteriorMeanVar(self, Xte, want_var=True, compat=0):
+        Xte = np.asarray(Xte)
+        if self.X is None or Xte.shape[1] != self.d:
+            return ModelGpak.posteriorMeanVar(self, Xte, want_var, compat)      # GPAK_ESTATE, then GPAK_EINVAL
+        rc = self._nlz()
+        if rc:
+            return self._ask("posteriorMeanVar", rc, None, Xte, want_var, compat)
+        M = Xte.shape[0]
+        per = -(-(-(-M // self.ranks)) // 256) * 256          # ceil(M / P) rounded up to 256: the slices of gpak_multi_predict
+        good = True
+        for r in range(self.ranks):
+            if min(M, r * per) >= min(M, (r + 1) * per):
+                continue                      # no slice: the replica is not even built
+            good &= self._with_factor(r)
+            p = self.rep[r]
+            if self.precision == F32 and want_var:
+                if p.lfS is None:
+                    p.lfS = p.fS
+                good &= p.lfS == self.rS
+        return self._ask("posteriorMeanVar", OK, self.rS, Xte, want_var, compat, spoil=not good)
+
+    def GradLL(self):
+        if self.general:
+            raise ModelError(ENOTIMPL, "gpak_grad handles the ExpAns(+Bias) composition only")
+        return self._ask("GradLL", self._nlz(), self.rS)
+
+    def GradLL_hyb(self, ng):
+        if not self.general:
+            if int(ng) != 10:
+                raise ModelError(EINVAL, "the ExpAns(+Bias) composition has 10 gradient entries")
+            return self._ask("GradLL_hyb", self._nlz(), self.rS, ng)
+        return self._on_replica0("GradLL_hyb", True, ng)
 
     def timing(self):
         return {"evaluations": self.evals}

@@ -15,6 +15,13 @@ Training sets (synth.drillholes / drillholes4), N chosen to cross what the state
 Seeded random sequences: RANDOM_COUNT = 4 sequences of RANDOM_LENGTH = 36 steps, seed RANDOM_SEED + k, drawn from the
 same vocabulary at N in {129, 300}; the generator keeps the preconditions (a gradient length matching the composition, no
 gradient with a White child, points with the training set's columns).
+
+A setter a sequence means to be REFUSED is a step made with no(...): run() requires exactly that status (refused, beside
+must) and Track does not hear of it, so every later answer is compared with a context that never saw the call.
+
+GROUP_SEQUENCES (further down) are the sequences on a multi-GPU context: `ranks` per context, make(precision, ranks), a
+fresh answer from a fresh group of the same rank count; engine_sequence cuts them down to what a group over caller-supplied
+engines answers, for the run of the group's host code on the CPU.
 """
 import functools
 import os
@@ -56,10 +63,20 @@ NG = {name: sum(cm.NPARS[k] for k, _ in v[0]) + 2 for name, v in KERN.items()}
 POINTS = {"P5": (5, 3), "P300": (300, 3), "P700": (700, 3), "Q5": (5, 4), "Q300": (300, 4)}
 BLOCKS = {"B12x8": (12, 8, 3), "B40x8": (40, 8, 3), "B40x1": (40, 1, 3), "B300x1": (300, 1, 3), "C12x8": (12, 8, 4), "C40x1": (40, 1, 4)}
 DISC = {1: (1, 1, 1), 8: (2, 2, 2)}
+# what a setter must REFUSE (cs.refused): a training set of five columns, a composition with a kind that does not exist; the
+# third is gpak_set_params with BAD_MODE as its distance form
+BAD_TRAIN = {"T129x5": (129, 5)}
+BAD_KERN = {"UNK": ([(EXPANS, E), (9, [0.5, 0.9, 0.5])], synth.DEFAULT_BIAS, 0.0, synth.DEFAULT_SN2)}
+BAD_MODE = 7
+TRANSPORTS = ("none", "in-process peer copies", "rccl")      # gpak_transport, as the number the sequences compare
 
 
 @functools.lru_cache(maxsize=None)
 def train(key):
+    if key in BAD_TRAIN:
+        n, d = BAD_TRAIN[key]
+        X, y = synth.drillholes4(n)
+        return np.asfortranarray(np.hstack([X, X[:, :d - 4]])), y
     n, d = TRAIN[key]
     X, y = synth.drillholes4(n) if d == 4 else synth.drillholes(n)
     X.setflags(write=False)
@@ -100,8 +117,8 @@ def rhs(n, k):
 class Track:
     """What a fresh context must be given to stand where context c stands: options, training set, kernel call."""
 
-    def __init__(self, precision):
-        self.precision, self.opts, self.train, self.kern = precision, {}, None, None
+    def __init__(self, precision, ranks=1):
+        self.precision, self.ranks, self.opts, self.train, self.kern = precision, ranks, {}, None, None
 
     def note(self, method, kw):
         if method == "set_option":
@@ -112,7 +129,7 @@ class Track:
             self.kern = (method, kw["kern"], kw.get("mode", DIRECT))
 
     def key(self):
-        return (self.precision, tuple(sorted(self.opts.items())), self.train, self.kern)
+        return (self.precision, tuple(sorted(self.opts.items())), self.train, self.kern) + ((self.ranks,) if self.ranks > 1 else ())
 
     def state(self):
         """The state in the sense of the separation condition: training set and kernel VALUES (not the distance form,
@@ -145,7 +162,7 @@ def invoke(obj, method, kw, n_train):
             terms, bias, white, sn2 = kern_values("set_params", kw["kern"])
             out = obj.set_params(np.array(terms[0][1]), bias, sn2, kw.get("mode", DIRECT))
         elif method == "set_kernel":
-            terms, bias, white, sn2 = KERN[kw["kern"]]
+            terms, bias, white, sn2 = (BAD_KERN if kw["kern"] in BAD_KERN else KERN)[kw["kern"]]
             out = obj.set_kernel(terms, bias, white, sn2, kw.get("mode", DIRECT))
         elif method == "gram":
             out = obj.gram(want_d2=kw.get("want_d2", False))
@@ -157,6 +174,12 @@ def invoke(obj, method, kw, n_train):
             out = obj.posteriorMeanVar(points(kw["X"]), want_var=kw.get("want_var", True), compat=kw.get("compat", 0))
         elif method in ("GradLL_hyb", "GradLL_exact"):
             out = getattr(obj, method)(kw["ng"])
+        elif method == "loo_grad":
+            g, s = obj.loo_grad(kw["ng"])
+            out = (g, np.array([s[k] for k in ("mse", "mssr", "log_pl")]))
+        elif method == "transport":
+            name = obj.transport()
+            out = np.array([[name.startswith(t) for t in TRANSPORTS].index(True)])
         elif method == "block_cross":
             out = obj.block_cross(*blocks(kw["blocks"]))
         elif method == "predict_block":
@@ -199,10 +222,15 @@ def same_bits(a, b):
     return True
 
 
+def make_one(make, precision, ranks):
+    """make(precision) for a single context, make(precision, ranks) for a group of `ranks` ranks."""
+    return make(precision) if ranks == 1 else make(precision, ranks)
+
+
 def fresh_answer(make, track, method, kw, n_train):
-    """The same question to a context that has done nothing else.  failed_column reports the last factorisation: the fresh
-    context factors first."""
-    g = make(track.precision)
+    """The same question to a context (a group of the same rank count) that has done nothing else.  failed_column reports
+    the last factorisation: the fresh context factors first."""
+    g = make_one(make, track.precision, track.ranks)
     try:
         for opt, value in track.opts.items():
             must(invoke(g, "set_option", dict(opt=opt, value=value), n_train), "set_option", opt)
@@ -228,6 +256,20 @@ def must(res, *what):
     return res
 
 
+def refused(res, status, *what):
+    """A setter the sequence means to be REFUSED answers exactly that status; the context must then stand where it stood
+    (every later step is compared with a fresh context that never saw the call)."""
+    if res[0] != status:
+        DEVICE_ERROR.append(f"{what}: status {res[0]} where {status} was due")
+        raise RuntimeError(f"{what}: status {res[0]} where the refusal {status} was due")
+    return res
+
+
+def ranks_of(seq, c):
+    r = seq.get("ranks", 1)
+    return r[c] if isinstance(r, (tuple, list)) else r
+
+
 def arg_key(kw):
     return tuple(sorted(kw.items()))
 
@@ -239,12 +281,16 @@ def run(seq, make, fresh_make=None, fresh_cache=None):
     try:
         for i, (c, method, kw) in enumerate(seq["steps"]):
             if c not in ctxs:
-                ctxs[c] = make(seq["precision"])
-                tracks[c] = Track(seq["precision"])
+                ctxs[c] = make_one(make, seq["precision"], ranks_of(seq, c))
+                tracks[c] = Track(seq["precision"], ranks_of(seq, c))
             tr = tracks[c]
             n_train = TRAIN[tr.train][0] if tr.train else 0
+            kw = dict(kw)
+            refuse = kw.pop("refuse", None)
             res = invoke(ctxs[c], method, kw, n_train)
-            if method in SETTERS:
+            if method in SETTERS and refuse is not None:
+                refused(res, refuse, seq["name"], i, method, kw)           # Track.note does not hear of it
+            elif method in SETTERS:
                 must(res, seq["name"], i, method, kw)
                 tr.note(method, kw)
             fr = None
@@ -259,7 +305,7 @@ def run(seq, make, fresh_make=None, fresh_cache=None):
                 if fresh_cache is not None:
                     fr = fresh_cache[fk]
             yield dict(i=i, ctx=c, method=method, kw=kw, track=tr.key(), state=tr.state(), mode=tr.kern[2] if tr.kern else DIRECT,
-                       train=tr.train, kern=tr.kern, res=res, fresh=fr)
+                       train=tr.train, kern=tr.kern, ranks=tr.ranks, tracker=tr, n_train=n_train, res=res, fresh=fr)
     finally:
         if DEVICE_ERROR:
             LEAKED.extend(ctxs.values())
@@ -270,7 +316,7 @@ def run(seq, make, fresh_make=None, fresh_cache=None):
 
 def model_at(rec, cache, precision=F64):
     """ModelGpak standing where the record's context stood."""
-    m = cm.ModelGpak(precision, cache)
+    m = cm.ModelGpak(precision, cache, rec.get("ranks", 1))
     if rec["train"]:
         m.set_train(*train(rec["train"]))
     if rec["kern"]:
@@ -311,8 +357,8 @@ def model_errors(method, kw, got, want, m, precision=F64):
         if len(g) > 1 and g[1] is not None:
             out.append(("D2", float(np.abs(g[1] - w[1]).max()), (1e-14 if direct else 1e-13) if plain else 1e-12))
         return out
-    if method == "factor":
-        return [("factor", float(g[0][0] != w[0][0]), 0.5)]
+    if method in ("factor", "n_gpus", "transport"):   # yes / no, a count, a name: equal or not
+        return [(method, float(g[0][0] != w[0][0]), 0.5)]
     if method == "failed_column":                     # test_not_positive_definite_reports_chol_fail: >= 1 on failure, 0 otherwise
         return [("failed_column", float((g[0][0] >= 1) != (w[0][0] >= 1)), 0.5)]
     if method == "chol_upper":                        # test_factor_alpha_nlz_match_oracle (direct form)
@@ -615,3 +661,259 @@ ENTRY = {"set_option": "gpak_set_option", "set_train": "gpak_set_train", "set_pa
          "GradLL_exact": "gpak_grad_exact", "loo": "gpak_loo", "block_cross": "gpak_block_cross", "predict_block": "gpak_predict_block",
          "predict_joint": "gpak_predict_joint", "sample_joint": "gpak_sample_joint", "timing": "gpak_timing"}
 ALWAYS = {"gpak_create", "gpak_destroy", "gpak_last_error"}
+
+
+# ---- refused setters: the context stands where it stood -------------------------------------------------------------------
+def no(method, status, ctx=0, **kw):
+    """A setter call that must be refused with `status` (run: cs.refused)."""
+    return (ctx, method, dict(kw, refuse=status))
+
+
+def seq_refused_setters():
+    """A refused gpak_set_train (five columns), gpak_set_params (a distance form that does not exist) and gpak_set_kernel (an
+    unknown kind) change nothing: the sizes the binding allocates by, the parameters, the composition and what is cached."""
+    return [S("set_train", train="T300"), S("set_params", kern="E"), S("logLikelihood"),
+            no("set_train", ENOTIMPL, train="T129x5"), S("solve_alpha"), S("logLikelihood"), S("posteriorMeanVar", X="P5"), S("timing"),
+            no("set_params", EINVAL, kern="E13", mode=BAD_MODE), S("logLikelihood"), S("GradLL"), S("timing"),
+            no("set_kernel", EINVAL, kern="UNK"), S("logLikelihood"), S("GradLL"), S("timing"),
+            S("set_params", kern="T2"), S("logLikelihood"), no("set_train", ENOTIMPL, train="T129x5"), S("solve_alpha"), S("loo"),
+            S("set_train", train="T129"), no("set_kernel", EINVAL, kern="UNK"), S("solve_alpha"), S("gram"), S("timing")]
+
+
+SEQUENCES.append(_seq("refused setters", "refused", seq_refused_setters()))
+GROUPS.append("refused")
+BY_NAME["refused setters"] = SEQUENCES[-1]
+ENTRY.update(n_gpus="gpak_n_gpus", transport="gpak_transport", loo_grad="gpak_loo_grad")
+
+
+# ---- sequences on a group (gpak_create_multi): DESIGN.md section 8, "Call sequences on a multi-GPU context" -----------------
+# The group's block width is 512.  T129: Np 256, one block column (P = 2: rank 1 owns nothing).  T700: Np 768, columns
+# 512 + 256 (P = 2: one each; P = 3: rank 2 owns nothing).  T1100 / T1100d4: Np 1152, 512 + 512 + 128, leading-dimension pad 32
+# (P = 2: rank 0 owns two; P = 3: one each).  Prediction is sharded in slices of ceil(M / P) rounded up to 256: P5 -> rank 0
+# alone (the other replicas are not even built); P300 at P = 2 -> 256 + 44; P700 -> 512 + 188 (P = 2), 256 + 256 + 188 (P = 3).
+REFUSED_ON_A_GROUP = ("GradLL_exact", "loo", "loo_grad", "predict_block", "block_cross", "predict_joint", "sample_joint")
+
+
+def g_all(pts, ctx=0, hyb=None):
+    """what a group answers from one factorisation: sharded prediction, the calls on replica 0, the distributed ones"""
+    c = dict(ctx=ctx)
+    return [S("posteriorMeanVar", X=pts, **c), S("solve_chol", k=2, **c), S("logLikelihood", **c), S("nlz_terms", **c), S("solve_alpha", **c),
+            S("GradLL_hyb", ng=hyb, **c) if hyb else S("GradLL", **c), S("timing", **c)]
+
+
+def seq_g_count():
+    """gpak_set_train while the parameters stay: evaluations and the accumulated times restart at the new set's FIRST
+    factorisation; gpak_set_params before gpak_set_train; gpak_set_train twice; the same values set again factor again."""
+    return [S("set_params", kern="E"), S("set_train", train="T300"), S("logLikelihood"), S("timing"), S("logLikelihood"), S("timing"),
+            S("set_train", train="T129"), S("logLikelihood"), S("timing"), S("solve_alpha"), S("timing"),
+            S("set_params", kern="E13"), S("GradLL"), S("timing"), S("nlz_terms"), S("timing"),
+            S("set_train", train="T300"), S("set_train", train="T129"), S("timing"), S("factor"), S("timing"),
+            S("set_params", kern="E13"), S("logLikelihood"), S("timing"), S("posteriorMeanVar", X="P5"), S("timing"),
+            S("set_params", kern="E"), S("solve_alpha"), S("timing")]
+
+
+def seq_g_late(ctx=0):
+    """A replica first used late: P5 is rank 0's alone, then new parameters, then P700 builds replicas 1 .. P-1, which must
+    take the CURRENT training set, kernel and factor; then a new training set and P300."""
+    c = dict(ctx=ctx)
+    return [S("set_train", train="T700", **c), S("set_params", kern="E", **c), S("posteriorMeanVar", X="P5", **c),
+            S("set_params", kern="T2", **c), S("posteriorMeanVar", X="P700", **c), S("timing", **c),
+            S("set_train", train="T1100", **c), S("posteriorMeanVar", X="P300", **c), S("solve_chol", k=2, **c), S("timing", **c),
+            S("set_params", kern="E13", **c), S("posteriorMeanVar", X="P700", want_var=False, **c), S("posteriorMeanVar", X="P5", **c),
+            S("timing", **c)]
+
+
+def seq_g_gram(mode, ctx=0):
+    """gpak_gram / gpak_compute_k run on replica 0 and overwrite its matrix: the prediction, solve_chol and the factor copy
+    after them import the ranks' factor again, and nothing is factored again (evaluations stand still).  In the EXPANSION
+    form the sharded prediction centres on the pooled mean of ALL test points."""
+    c = dict(ctx=ctx)
+    s = [S("set_train", train="T300", **c), S("set_params", kern="T2", mode=mode, **c), S("logLikelihood", **c),
+         S("set_params", kern="E", mode=mode, **c), S("logLikelihood", **c), S("timing", **c), S("gram", want_d2=True, **c),
+         S("posteriorMeanVar", X="P300", **c), S("compute_k", X1="X:T300", X2="P5", want_d2=True, **c), S("solve_chol", k=3, **c),
+         S("gram", **c), S("solve_chol", k=1, **c), S("solve_alpha", **c), S("gram", **c), S("posteriorMeanVar", X="P700", **c),
+         S("timing", **c)]
+    if mode == DIRECT:
+        s += [S("gram", **c), S("chol_upper", **c)]
+    return s + [S("nlz_terms", **c), S("timing", **c)]
+
+
+def seq_g_compositions():
+    """gpak_set_kernel <-> gpak_set_params: gpak_grad on a composition is refused and leaves the group usable; gpak_grad_hyb
+    with the composition's length runs on replica 0 from the distributed factor; a wrong length is GPAK_EINVAL; a White child."""
+    return [S("set_train", train="T300"), S("set_kernel", kern="ER"), S("GradLL"), S("logLikelihood"), S("GradLL_hyb", ng=13),
+            S("posteriorMeanVar", X="P300"), S("timing"),
+            S("set_params", kern="E"), S("GradLL"), S("GradLL_hyb", ng=13), S("GradLL_hyb", ng=10), S("posteriorMeanVar", X="P300"),
+            S("set_kernel", kern="EW"), S("logLikelihood"), S("GradLL_hyb", ng=10), S("GradLL"), S("posteriorMeanVar", X="P5"),
+            S("solve_chol", k=1),
+            S("set_kernel", kern="EXR"), S("GradLL_hyb", ng=15), S("GradLL_hyb", ng=13), S("solve_alpha"),
+            S("set_params", kern="T2"), S("GradLL"), S("timing")]
+
+
+def seq_g_fail():
+    """sn2 = -0.5: NaN and GPAK_ENOTPD as the header promises, every ask of failing values factors (and counts) again, the
+    calls on the replicas import nothing; good parameters afterwards answer as a fresh group does."""
+    bad = [S("logLikelihood"), S("failed_column"), S("timing"), S("logLikelihood"), S("timing"), S("factor"), S("solve_alpha"),
+           S("nlz_terms"), S("GradLL"), S("posteriorMeanVar", X="P5"), S("solve_chol", k=1), S("chol_upper"), S("timing")]
+    return ([S("set_train", train="T300"), S("set_params", kern="E"), S("logLikelihood"), S("failed_column"),
+             S("set_params", kern="BAD")] + bad + [S("set_params", kern="BAD"), S("logLikelihood"), S("failed_column"), S("timing"),
+                                                   S("set_params", kern="E13"), S("logLikelihood"), S("failed_column"),
+                                                   S("posteriorMeanVar", X="P5"), S("solve_chol", k=1), S("chol_upper"), S("timing")])
+
+
+def seq_g_walk():
+    """N 300 -> 1100 (four columns) -> 129 -> 1100: one, three, one, three block columns; the ranks' and the replicas' buffers
+    follow; points with the wrong number of columns are refused and change nothing."""
+    return ([S("set_train", train="T300"), S("set_params", kern="E")] + g_all("P300") + [S("posteriorMeanVar", X="Q5")] +
+            [S("set_train", train="T1100d4"), S("set_params", kern="T2")] + g_all("Q300") + [S("posteriorMeanVar", X="P5")] +
+            [S("set_train", train="T129")] + g_all("P300") + [S("set_train", train="T1100")] + g_all("P700"))
+
+
+def seq_g_f32():
+    """GPAK_F32 group: the replicas' fp32 image of the IMPORTED factor follows new parameters and a new training set."""
+    return [S("set_train", train="T300"), S("set_params", kern="E"), S("posteriorMeanVar", X="P300"),
+            S("set_params", kern="T2"), S("posteriorMeanVar", X="P300"),
+            S("set_train", train="T1100"), S("posteriorMeanVar", X="P700"),
+            S("set_params", kern="E"), S("posteriorMeanVar", X="P300"), S("posteriorMeanVar", X="P5", want_var=False),
+            S("set_train", train="T129"), S("posteriorMeanVar", X="P300")]
+
+
+def refusals(ctx=0):
+    c = dict(ctx=ctx)
+    return [S("GradLL_exact", ng=10, **c), S("loo", **c), S("loo_grad", ng=10, **c), S("predict_block", blocks="B12x8", **c),
+            S("block_cross", blocks="B12x8", **c), S("predict_joint", blocks="B40x1", **c), S("sample_joint", blocks="B40x1", **c)]
+
+
+def seq_g_refusals():
+    """The seven calls a group refuses (GPAK_ENOTIMPL), between questions: nothing changes, nothing is factored again."""
+    return ([S("n_gpus"), S("transport"), S("set_train", train="T300"), S("set_params", kern="E"), S("logLikelihood"), S("timing")] +
+            refusals() + [S("logLikelihood"), S("timing"), S("posteriorMeanVar", X="P5")] + refusals()[:3] +
+            [S("solve_alpha"), S("solve_chol", k=1), S("timing"), S("n_gpus"), S("transport")])
+
+
+def alternate(a, b):
+    out = []
+    for k in range(max(len(a), len(b))):
+        out += a[k:k + 1] + b[k:k + 1]
+    return out
+
+
+def seq_g_order():
+    """Questions before gpak_set_train and before any parameters: GPAK_ESTATE, nothing counted, the group usable afterwards."""
+    def early(ctx, factor_reads):
+        c = dict(ctx=ctx)
+        s = [S("logLikelihood", **c), S("nlz_terms", **c), S("solve_alpha", **c), S("factor", **c), S("GradLL", **c),
+             S("GradLL_hyb", ng=10, **c), S("gram", **c), S("posteriorMeanVar", X="P5", **c), S("failed_column", **c)]
+        return s + ([S("solve_chol", k=1, **c), S("chol_upper", **c)] if factor_reads else []) + [S("n_gpus", **c), S("transport", **c)]
+    s = early(0, False) + [S("set_params", kern="E")] + early(0, False)
+    s += [S("set_train", train="T129"), S("logLikelihood"), S("solve_alpha"), S("posteriorMeanVar", X="P5"), S("timing")]
+    s += [S("set_train", ctx=1, train="T129")] + early(1, True) + [S("posteriorMeanVar", ctx=1, X="Q5"), S("timing", ctx=1)]
+    s += [S("set_params", ctx=1, kern="E13"), S("logLikelihood", ctx=1), S("timing", ctx=1)]
+    s += [S("set_train", train="T300"), S("set_train", train="T129"), S("logLikelihood"), S("solve_alpha"),
+          S("posteriorMeanVar", X="Q5"), S("logLikelihood"), S("timing")]
+    return s
+
+
+def seq_g_refused_setters():
+    """seq_refused_setters on a group: the group's copy of the set, its composition flag and the ranks' stored composition too."""
+    return [S("set_train", train="T300"), S("set_params", kern="E"), S("logLikelihood"),
+            no("set_train", ENOTIMPL, train="T129x5"), S("solve_alpha"), S("posteriorMeanVar", X="P5"), S("timing"),
+            no("set_params", EINVAL, kern="E13", mode=BAD_MODE), S("logLikelihood"), S("GradLL"), S("timing"),
+            no("set_kernel", EINVAL, kern="UNK"), S("logLikelihood"), S("GradLL"), S("solve_chol", k=1), S("timing"),
+            S("set_kernel", kern="ER"), S("logLikelihood"), no("set_kernel", EINVAL, kern="UNK"), S("logLikelihood"), S("GradLL_hyb", ng=13),
+            S("solve_alpha"), no("set_train", ENOTIMPL, train="T129x5"), S("posteriorMeanVar", X="P300"), S("timing")]
+
+
+GROUP_RANDOM = ((129, 2), (300, 3))        # (N, P) of the seeded random sequences
+GROUP_RANDOM_LENGTH = 24
+
+
+def seq_g_random(k):
+    n, _ = GROUP_RANDOM[k]
+    rng = np.random.default_rng(RANDOM_SEED + 100 + k)
+    pick = lambda a: a[int(rng.integers(len(a)))]   # noqa: E731
+    cur = dict(kern=None)
+
+    def set_kern():
+        cur["kern"] = pick(["E", "E13", "T2", "Esn", "ER", "EXR", "EW"])
+        return S("set_kernel" if cur["kern"] in ("ER", "EXR", "EW") else "set_params", kern=cur["kern"])
+
+    steps = [S("set_train", train=f"T{n}"), set_kern()]
+    while len(steps) < GROUP_RANDOM_LENGTH:
+        r = rng.random()
+        if r < 0.08:
+            steps.append(S("set_train", train=f"T{n}"))
+        elif r < 0.25:
+            steps.append(set_kern())
+        else:
+            m = pick(["gram", "factor", "solve_alpha", "solve_chol", "logLikelihood", "nlz_terms", "posteriorMeanVar", "grad", "compute_k",
+                      "chol_upper", "timing", "failed_column", "refused", "n_gpus", "transport"])
+            if m == "grad":
+                if cur["kern"] == "EW":
+                    continue
+                plain = cur["kern"] in ("E", "E13", "T2", "Esn")
+                steps.append(S("GradLL") if plain else S("GradLL_hyb", ng=NG[cur["kern"]]))
+            elif m == "solve_chol":
+                steps.append(S("solve_chol", k=int(rng.integers(1, 4))))
+            elif m == "posteriorMeanVar":
+                steps.append(S("posteriorMeanVar", X=pick(["P5", "P300", "P700"]), want_var=bool(rng.integers(2))))
+            elif m == "compute_k":
+                steps.append(S("compute_k", X1="P300", X2="P5"))
+            elif m == "refused":
+                steps.append(pick(refusals()))
+            else:
+                steps.append(S(m))
+    return steps
+
+
+def _gseq(name, wgroup, steps, ranks, precision=F64):
+    return dict(name=name, group=wgroup, steps=steps, ranks=ranks, precision=precision)
+
+
+# `group`: the worker process the sequence runs in on the device (tests/ctx_seq_worker.py --group NAME --ranks P, P the
+# largest rank count of its sequences); split so that each stays near ten seconds (DESIGN.md has the measured figures)
+GROUP_SEQUENCES = [
+    _gseq("group count", "g-count", seq_g_count(), 2),
+    _gseq("refusals (group)", "g-count", seq_g_refusals(), 2),
+    _gseq("late replicas [P=2]", "g-late2", seq_g_late(), 2),
+    _gseq("late replicas [P=3]", "g-late3", seq_g_late(), 3),
+    _gseq("gram between (group) [direct]", "g-gram2", seq_g_gram(DIRECT), 2),
+    _gseq("gram between (group) [expansion]", "g-gram3", seq_g_gram(EXPANSION), 3),
+    _gseq("compositions (group)", "g-comp", seq_g_compositions(), 2),
+    _gseq("fail and recover (group)", "g-fail", seq_g_fail(), 3),
+    _gseq("size walk (group) [P=2]", "g-walk2", seq_g_walk(), 2),
+    _gseq("size walk (group) [P=3]", "g-walk3", seq_g_walk(), 3),
+    _gseq("f32 (group)", "g-f32", seq_g_f32(), 2, F32),
+    _gseq("two groups", "g-two", alternate(seq_g_late(0), seq_g_gram(DIRECT, 1)), (2, 3)),
+    _gseq("a group and a single context", "g-single", alternate(seq_g_gram(DIRECT, 0), seq_gradients(1)), (2, 1)),
+    _gseq("out of order (group)", "g-order", seq_g_order(), (2, 2)),
+    _gseq("refused setters (group)", "g-order", seq_g_refused_setters(), 2),
+] + [_gseq(f"random (group) {k}", f"g-random{k}", seq_g_random(k), GROUP_RANDOM[k][1]) for k in range(len(GROUP_RANDOM))]
+GROUP_BY_NAME = {s["name"]: s for s in GROUP_SEQUENCES}
+WORKER_GROUPS = {}                         # worker group -> --ranks
+for _s in GROUP_SEQUENCES:
+    _r = _s["ranks"]
+    WORKER_GROUPS[_s["group"]] = max(WORKER_GROUPS.get(_s["group"], 0), max(_r) if isinstance(_r, tuple) else _r)
+
+# What a group over caller-supplied engines (gpak_create_multi_with_engines: the group's real host code on the CPU) answers
+# without device replicas
+ENGINE_VOCABULARY = SETTERS + ("logLikelihood", "nlz_terms", "solve_alpha", "GradLL", "GradLL_hyb", "factor", "failed_column", "timing",
+                               "n_gpus", "transport") + REFUSED_ON_A_GROUP
+
+
+def engine_sequence(seq, ranks):
+    """The steps of a group sequence that an engine group answers (GradLL_hyb: while the kernel in force is ExpAns(+Bias),
+    i.e. while the call is distributed), every group with `ranks` ranks; contexts that are no groups are left out; None
+    where nothing is left to ask."""
+    general, steps = {}, []
+    for c, method, kw in seq["steps"]:
+        if ranks_of(seq, c) == 1 or method not in ENGINE_VOCABULARY or seq["precision"] != F64:
+            continue
+        if method in ("set_params", "set_kernel") and "refuse" not in kw:
+            general[c] = method == "set_kernel"
+        if method == "GradLL_hyb" and general.get(c, False):
+            continue
+        steps.append((c, method, kw))
+    if not any(m not in SETTERS + ("timing",) for _c, m, _kw in steps):
+        return None
+    return dict(seq, steps=steps, ranks=ranks)
