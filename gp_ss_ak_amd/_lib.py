@@ -19,6 +19,8 @@ SYMBOLS = [
 ]
 # every symbol include/gpak_loo_grad.h declares (tests/test_loo_grad.py checks the header and this list agree)
 LOO_GRAD_SYMBOLS = ["gpak_loo_grad"]
+# every symbol include/gpak_cv_groups.h declares (tests/test_cv_groups.py checks the header and this list agree)
+CV_GROUPS_SYMBOLS = ["gpak_cv_groups"]
 
 
 class PhaseTimes(C.Structure):
@@ -35,6 +37,11 @@ class LooSummary(C.Structure):
                 ("passes", C.c_int)]
 
 
+class CvGroupsSummary(C.Structure):
+    _fields_ = [("mse", C.c_double), ("mssr", C.c_double), ("msmd", C.c_double), ("log_pl", C.c_double),
+                ("ms", C.c_double), ("groups", C.c_int), ("max_size", C.c_int)]
+
+
 _lib = None
 
 
@@ -48,9 +55,10 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). gp_ss_ak_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS if not hasattr(lib, s)]
     if missing:
-        raise RuntimeError(f"libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h: {missing}")
+        raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
+                           f"gpak_cv_groups.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -82,6 +90,7 @@ def load():
     lib.gpak_grad_exact.argtypes = [vp, dp, C.c_int]
     lib.gpak_loo.argtypes = [vp, dp, dp, C.POINTER(LooSummary)]
     lib.gpak_loo_grad.argtypes = [vp, dp, C.c_int, C.POINTER(LooSummary)]
+    lib.gpak_cv_groups.argtypes = [vp, C.POINTER(C.c_int), C.c_int, dp, dp, dp, C.POINTER(CvGroupsSummary)]
     lib.gpak_block_cross.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp]
     lib.gpak_predict_block.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.gpak_predict_joint.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]

@@ -912,6 +912,60 @@ int gpak_loo_grad(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary) {
   return rc;
 }
 
+int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,
+                   gpak_cv_groups_summary *summary) {
+  if (!ctx) return GPAK_EINVAL;
+  if (ctx->multi) {
+    ctx->err = "gpak_cv_groups is built for the single-GPU context (gpak_create) only";
+    return GPAK_ENOTIMPL;
+  }
+  // what the call refuses is refused before anything is factored
+  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
+  if (!ctx->have_params) { ctx->err = "no parameters (gpak_set_params)"; return GPAK_ESTATE; }
+  const int N = ctx->N;
+  const std::string who = "gpak_cv_groups: ";
+  if (!group) { ctx->err = who + "group is NULL"; return GPAK_EINVAL; }
+  if (n_groups < 1 || n_groups > N) {
+    ctx->err = who + "n_groups = " + std::to_string(n_groups) + " is outside [1, N = " + std::to_string(N) + "]";
+    return GPAK_EINVAL;
+  }
+  // the samples sorted by (group, sample): a counting sort
+  std::vector<int> offs((size_t)n_groups + 1, 0), perm((size_t)N);
+  for (int i = 0; i < N; i++) {
+    if (group[i] < 0 || group[i] >= n_groups) {
+      ctx->err = who + "sample " + std::to_string(i) + " has label " + std::to_string(group[i]) + ", outside [0, " +
+                 std::to_string(n_groups) + ")";
+      return GPAK_EINVAL;
+    }
+    if (++offs[(size_t)group[i] + 1] == GPAK_CV_GROUP_MAX + 1) {
+      ctx->err = who + "group " + std::to_string(group[i]) + " has more than " + std::to_string(GPAK_CV_GROUP_MAX) +
+                 " samples (sample " + std::to_string(i) + " is one too many)";
+      return GPAK_EINVAL;
+    }
+  }
+  for (int g = 0; g < n_groups; g++) {
+    if (offs[(size_t)g + 1] == 0) { ctx->err = who + "label " + std::to_string(g) + " is not used"; return GPAK_EINVAL; }
+    offs[(size_t)g + 1] += offs[g];
+  }
+  {
+    std::vector<int> at(offs.begin(), offs.end() - 1);
+    for (int i = 0; i < N; i++) perm[(size_t)at[group[i]]++] = i;
+  }
+  int rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK) return gpak_cv_groups_impl(ctx, perm.data(), offs.data(), n_groups, mean, var, group_logp, summary);
+  if (rc == GPAK_ENOTPD) {   // the training factor: as gpak_loo
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int i = 0; mean && i < N; i++) mean[i] = nan;
+    for (int i = 0; var && i < N; i++) var[i] = nan;
+    for (int g = 0; group_logp && g < n_groups; g++) group_logp[g] = nan;
+    if (summary) {
+      summary->mse = summary->mssr = summary->msmd = summary->log_pl = nan;
+      summary->ms = 0.0; summary->groups = n_groups; summary->max_size = 0;
+    }
+  }
+  return rc;
+}
+
 static int block_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *var,
                       int flags, double *Kbar_host) {
   if (ctx->multi) {

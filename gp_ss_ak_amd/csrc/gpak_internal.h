@@ -161,6 +161,9 @@ struct gpak_ctx {
   double *dLoo = nullptr;
   size_t loo_elems = 0;
   int loo_rows = 0;           // GPAK_OPT_LOO_ROWS: rows of L^-T held at once (0: the default, 16384)
+  // leave-group-out (gpak_cv_groups) holds all of L^-T: in dG when the gradient has allocated it, otherwise in dLoo grown
+  // to Np x ld.  The substitution, the Gram pass and the solve pass of the last call, in ms:
+  double cvg_ms[3] = {0, 0, 0};
 
   // options
   GpakSchedule sched;         // this context's copy of the schedule set (gpak_set_option changes it)
@@ -439,3 +442,13 @@ int gpak_loo_grad_layout(gpak_ctx *ctx, int ng);
 void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]);
 void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *expans, int d, int N, double sn2,
                         const double *red, double *g);
+// at least `elems` doubles in ctx->dGpart (contents are not kept); G = L^-T of the current factor as one Np x Np matrix
+// (leading dimension ldg) on the context's stream
+int gpak_grad_scratch(gpak_ctx *ctx, size_t elems);
+void gpak_grad_g_full(gpak_ctx *ctx, double *G, long ldg);
+
+// ---- cv_groups.hip ----------------------------------------------------------------------
+// gpak_cv_groups on a single-GPU context whose factor and alpha are current and whose labels api.hip has checked: perm =
+// the samples sorted by (group, sample), offs = where each group starts in it (n_groups + 1 entries)
+int gpak_cv_groups_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *mean, double *var,
+                        double *group_logp, gpak_cv_groups_summary *summary);

@@ -284,6 +284,19 @@ static int grad_partials(gpak_ctx *ctx, size_t elems) {
   return GPAK_OK;
 }
 
+// what gpak_cv_groups (cv_groups.hip) shares with the passes of this file: the scratch buffer, and G = L^-T of the
+// context's factor as ONE Np x Np matrix (P = 1) in a buffer of the caller's
+int gpak_grad_scratch(gpak_ctx *ctx, size_t elems) { return grad_partials(ctx, elems); }
+
+void gpak_grad_g_full(gpak_ctx *ctx, double *G, long ldg) {
+  const int GNB = 512;
+  const long ld = ctx->ld;
+  grad_g_subst(ctx->stream, ctx->Np, GNB, 1, 0, [&](int b) {
+    const size_t J = (size_t)b * GNB;
+    return LBlockCol{ctx->dM + J + J * ld, ld, ctx->dInv + J / PB * 2 * PB * PB};
+  }, G, ldg);
+}
+
 // ---------------------------------------------------------------------------------------
 // The as-written pass.  part[block][NSUM]:
 //   [0..5] sum Rm * Di2^(p)   [6] sum QW * exp(-sqrt(D_expans))   [7] sum Q * K   [8] trace(QW)

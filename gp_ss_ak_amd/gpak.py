@@ -62,6 +62,19 @@ def block_points(centres, size, disc):
     return np.asfortranarray(Xd), nd
 
 
+def group_labels(labels, n=None):
+    """Any integer labels -> (group, values): group[i] in 0 .. G - 1 is the rank of labels[i] among the sorted unique
+    values (int32, what gpak_cv_groups takes), values those G sorted labels.  Raises ValueError for labels that are not
+    a one-dimensional integer array (of length n when n is given)."""
+    a = np.asarray(labels)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu":
+        raise ValueError("labels must be a one-dimensional array of integers")
+    if n is not None and a.size != int(n):
+        raise ValueError(f"labels must hold one entry per training sample: {a.size} for {int(n)}")
+    values, group = np.unique(a, return_inverse=True)
+    return np.ascontiguousarray(group.reshape(-1), dtype=np.int32), values
+
+
 class Gpak:
     """One context = one GPU. Mirrors the slice of GP_utils that sits on the hot path."""
 
@@ -209,6 +222,22 @@ class Gpak:
         out = {name: getattr(s, name) for name, _ in s._fields_}
         out["status"] = rc
         return g, out
+
+    def cv_groups(self, labels):
+        """Leave-group-out cross-validation from the current factor (gpak_cv_groups): (mean, var, logp, summary).
+        labels: one integer per training sample, any values; the groups are numbered by sorted unique label and logp
+        (one joint log predictive density per group) follows that order.  summary = {mse, mssr, msmd, log_pl, ms,
+        groups, max_size, status, labels}, labels the sorted unique values.  On Chol_fail status is ENOTPD and every
+        number is NaN."""
+        group, values = group_labels(labels, self.N)
+        mean, var, logp = np.zeros(self.N), np.zeros(self.N), np.zeros(values.size)
+        s = _lib.CvGroupsSummary()
+        rc = self._check(self._lib.gpak_cv_groups(self._h, group.ctypes.data_as(C.POINTER(C.c_int)), int(values.size),
+                                                  _p(mean), _p(var), _p(logp), C.byref(s)), allow=(ENOTPD,))
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        out["labels"] = values
+        return mean, var, logp, out
 
     def _blocks(self, Xd, nd):
         Xd = _f(Xd)

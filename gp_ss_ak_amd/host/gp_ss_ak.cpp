@@ -1,7 +1,7 @@
 // gp_ss_ak.cpp -- the reference's command line (gp_ss_ak.cpp:14-557) over the HIP hot path:
 //   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] train.txt [model]
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
-//   gp_ss_ak [-v n]               [device options] cv [-np] train.txt model [out_file]
+//   gp_ss_ak [-v n]               [device options] cv [-np] [--groups labels.txt] train.txt model [out_file]
 //   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
 //   gp_ss_ak [-v n] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] [--nugget v] --realisations S (--seed n | --xi file)
 //            sim nodes.txt model train.txt [out_file]
@@ -11,7 +11,9 @@
 // --objective nlz|loo (loo: `train` minimises -log_pl of the leave-one-out predictions, what `cv` reports, with its exact
 // gradient gpak_loo_grad and the exact gradient's driver; the objective column of the trace holds -log_pl; one GPU only).
 // cv (not a reference verb): leave-one-out cross-validation of a trained model on its training set, from one
-// factorisation (gpak_loo; one GPU only), written to <model>_loo.txt.
+// factorisation (gpak_loo; one GPU only), written to <model>_loo.txt.  With --groups FILE (one integer label per training
+// sample, in input order; `#` lines are skipped) it leaves out whole groups instead -- a drill hole, a fold -- of at most
+// 128 samples each (gpak_cv_groups) and writes <model>_lgo.txt.
 // block (not a reference verb): mean and standard deviation of the AVERAGE grade of rectangular blocks (gpak_predict_block;
 // one GPU only).  blocks.txt has the test file's format: block centres, and a last column that is read as y and carried
 // through.  Each block is discretised in the file's units into nx * ny * nz cell-centred points, which then pass through
@@ -24,6 +26,7 @@
 // <model>_gnu.plt); -np/--no-prompt skips the two interactive stdin questions of `train`
 // (gp_ss_ak.cpp:235-285) and the gnuplot call of `test` (:503-505).
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdlib>
 #include <fstream>
@@ -54,6 +57,7 @@ class GP_Cntrl : public Control {
   void train();
   void test();
   void cv();
+  void readGroupLabels(const std::string &file, std::vector<long long> &labels) const;
   void block();
   void sim();
   void Help() const;
@@ -63,7 +67,7 @@ void GP_Cntrl::Help() const {
   std::cout << "\nGP_SS_AK hot path on MI355X\nCommand:\n \t ./gp_ss_ak [options] Command [Comnd-options] TrainDataFile.txt modelName\n"
             << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood).\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
-            << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time.\n"
+            << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
             << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]).\n";
 }
@@ -248,26 +252,73 @@ void GP_Cntrl::test() {
   exit(0);
 }
 
+// one integer label per line (or several, separated by blanks, tabs or commas); `#` lines are skipped
+void GP_Cntrl::readGroupLabels(const std::string &file, std::vector<long long> &labels) const {
+  std::ifstream in(file.c_str());
+  if (!in.is_open()) ErrorTermination("File is " + file + " not readable");
+  std::string line;
+  while (std::getline(in, line)) {
+    if (!line.empty() && line[0] == '#') continue;
+    for (char &ch : line) if (ch == '\t' || ch == ',' || ch == '\r') ch = ' ';
+    std::istringstream ss(line);
+    std::string tok;
+    while (ss >> tok) {
+      char *end = nullptr;
+      errno = 0;
+      const long long v = strtoll(tok.c_str(), &end, 10);
+      if (end == tok.c_str() || *end != '\0' || errno == ERANGE)
+        ErrorTermination("--groups: '" + tok + "' in " + file + " is not an integer label");
+      labels.push_back(v);
+    }
+  }
+}
+
 void GP_Cntrl::cv() {
   incArg();
   setMode("cv");
   if (gpus > 1)
     ErrorTermination("cv runs on one GPU only (leave-one-out cross-validation is not built for multi-GPU contexts): drop --gpus");
   bool yscale = true;
+  std::string groupsFile;
   while (isFlgs()) {
     if (isArgFlg()) {
       if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
       else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else if (isArg("--groups", "--groups")) {
+        incArg();
+        if (getArgNo() >= argc) ErrorTermination("--groups takes a file of labels");
+        groupsFile = getArg();
+      }
       else UnkFlg();
       incArg();
     } else setFlgs(false);
   }
   if (getArgNo() + 1 >= argc) ErrorTermination("There are not enough input parameters: cv needs the training data and the model.");
   std::string trFile = getArg(), modelName = argv[getArgNo() + 1];
-  std::string LooOut = modelName + "_loo.txt";
+  const bool grouped = !groupsFile.empty();
+  std::string LooOut = modelName + (grouped ? "_lgo.txt" : "_loo.txt");
   if (getArgNo() + 2 < argc) LooOut = argv[getArgNo() + 2];
   int ds[2];
   readDataSize(trFile, ds);
+  std::vector<long long> labels, values;   // as read; the sorted unique labels
+  std::vector<int> group;                  // rank of each sample's label among them
+  if (grouped) {                           // everything that can be refused is refused before a context exists
+    readGroupLabels(groupsFile, labels);
+    if ((int)labels.size() != ds[0])
+      ErrorTermination("--groups: " + groupsFile + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(ds[0]) +
+                       " training samples");
+    values = labels;
+    std::sort(values.begin(), values.end());
+    values.erase(std::unique(values.begin(), values.end()), values.end());
+    std::vector<int> count(values.size(), 0);
+    group.resize(labels.size());
+    for (size_t i = 0; i < labels.size(); i++) {
+      group[i] = (int)(std::lower_bound(values.begin(), values.end(), labels[i]) - values.begin());
+      if (++count[group[i]] == GPAK_CV_GROUP_MAX + 1)
+        ErrorTermination("--groups: group " + std::to_string(labels[i]) + " has more than " + std::to_string(GPAK_CV_GROUP_MAX) +
+                         " samples (leave-group-out holds a group in one workgroup's memory)");
+    }
+  }
   mat X, y;
   readDataFile(X, y, ds, trFile);
   prepareData(X, y, yscale, modelName);                         // the model's _Statistics.txt, as `test`
@@ -279,6 +330,37 @@ void GP_Cntrl::cv() {
   GPModel->initialize_vars();
   GPModel->logLikelihood();
   mat LooVals(y.n_rows, 1), LooVals_Var(y.n_rows, 1);
+  if (grouped) {
+    mat logp(values.size(), 1);
+    gpak_cv_groups_summary gs;
+    GPModel->GroupCV(group, (int)values.size(), LooVals, LooVals_Var, logp, gs);
+    postData(X, LooVals, yscale, modelName);
+    postData_var(LooVals_Var, yscale, modelName);
+    postData(y, yscale, modelName);
+    double mse = 0, ym = 0, vy = 0;
+    for (size_t i = 0; i < y.n_elem; i++) { mse += (y[i] - LooVals[i]) * (y[i] - LooVals[i]); ym += y[i]; }
+    mse /= X.n_rows; ym /= y.n_elem;
+    for (size_t i = 0; i < y.n_elem; i++) vy += (y[i] - ym) * (y[i] - ym);
+    vy /= y.n_elem;
+    if (getVerbose() > 0) {
+      std::cout << "Mean Square Error of leave-group-out: " << mse << "\n" << "Var MSE Train: " << vy << "\n"
+                << "Mean standardised squared residual: " << gs.mssr << "\n" << "Mean squared Mahalanobis residual: " << gs.msmd << "\n"
+                << "Log predictive density of the groups: " << gs.log_pl << "\n" << "Groups: " << gs.groups << "\n"
+                << "LGO ms: " << gs.ms << "\n";
+    } else { std::cout << mse << "\n" << vy << "\n" << gs.mssr << "\n" << gs.msmd << "\n" << gs.log_pl << "\n"; }
+    // rows in input order; the fifth column is what postData_var returns, as StdYh of _predict.txt
+    std::ofstream out(LooOut.c_str());
+    out << "# SampleNo, Group, Y, Ylgo, StdYlgo, Inputs" << "\n";
+    for (size_t i = 0; i < y.n_elem; i++) {
+      out << (i + 1) << "\t" << labels[i] << "\t" << y[i] << "\t" << LooVals[i] << "\t" << LooVals_Var[i] << "\t";
+      for (size_t j = 0; j < X.n_cols; j++) out << X(i, j) << "\t";
+      out << "\n";
+    }
+    out.close();
+    writeTiming(*GPModel);
+    delete GPModel;
+    exit(0);
+  }
   gpak_loo_summary s;
   GPModel->LooCV(LooVals, LooVals_Var, s);
   postData(X, LooVals, yscale, modelName);

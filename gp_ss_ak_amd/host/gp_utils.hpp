@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <limits>
 #include <string>
+#include <vector>
 
 #include "../../include/gpak.h"
 #include "kernels.hpp"
@@ -119,6 +120,10 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // leave-one-out cross-validation of the training set from the current factor (gpak_loo): mean and variance (noise
   // included) of every yTarg(i) given all the other samples, N x 1 each; NaN on Chol_fail
   void LooCV(mat &mean, mat &var, gpak_loo_summary &s) const;
+  // leave-group-out cross-validation (gpak_cv_groups): group[i] in [0, n_groups) for every training sample; mean and
+  // marginal variance (noise included) of every yTarg(i) given all the samples outside its group, N x 1 each, and the
+  // joint log predictive density of each group (n_groups x 1); NaN on Chol_fail
+  void GroupCV(const std::vector<int> &group, int n_groups, mat &mean, mat &var, mat &logp, gpak_cv_groups_summary &s) const;
   // block-support prediction (gpak_predict_block): mean and variance of the average of the field over each block, block
   // b = rows b * nd .. b * nd + nd of Xd; the variance includes sn2 / nd unless latent; M x 1 each, NaN on Chol_fail
   void BlockMeanVar(mat &mean, mat &var, const mat &Xd, int nd, bool latent) const;

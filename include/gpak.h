@@ -205,7 +205,8 @@ typedef struct {
 /* mean (N), var (N), summary: each may be NULL */
 int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary);
 
-/* The gradient of the pseudo-likelihood log_pl, for training on it: gpak_loo_grad.h, included at the end of this file. */
+/* The gradient of the pseudo-likelihood log_pl, for training on it: gpak_loo_grad.h, included at the end of this file.
+ * Leaving out whole groups of samples (a drill hole, a fold) instead of one: gpak_cv_groups.h, included there too. */
 
 /* Block-support prediction (block kriging): mean and variance of the AVERAGE of the field over each of M blocks, block b
  * given by nd discretisation points with uniform weights.  Xd is (M*nd) x d column-major, row b*nd + a = point a of
@@ -291,4 +292,5 @@ int gpak_calibrate(gpak_ctx *ctx, double *mfma_f64_tflops, double *hbm_write_gbs
 }
 #endif
 #include "gpak_loo_grad.h"
+#include "gpak_cv_groups.h"
 #endif /* GPAK_H */
