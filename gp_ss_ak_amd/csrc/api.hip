@@ -6,35 +6,9 @@
 #include <cstring>
 #include <limits>
 
-#include "../../include/gpak_dist.h"
-#include "gpak_internal.h"
+#include "multi.h"
 
-int gpak_calibrate_impl(gpak_ctx *ctx, double *scratch, size_t scratch_bytes, double *tflops, double *gbs);
-int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, double *var, const double *pool_sum,
-                      long pool_M);
-// multi.hip
-#include <functional>
-int gpak_multi_create(gpak_multi **out, int n, const int *devices, int precision, std::string &err,
-                      const gpak_dist_engine *const *engines);
-void gpak_multi_destroy(gpak_multi *g);
-const char *gpak_multi_error(gpak_multi *g);
-int gpak_multi_set_train(gpak_multi *g, const double *X, const double *y, int N, int d);
-int gpak_multi_set_params(gpak_multi *g, const double *expans, double bias, double sn2, int dist_mode);
-int gpak_multi_nlz(gpak_multi *g, double *nlz, double *quad, double *sumlp, double *logdet);
-int gpak_multi_alpha(gpak_multi *g, double *alpha_host);
-int gpak_multi_on_replica0(gpak_multi *g, const std::function<int(gpak_ctx *)> &f, bool wants_factor);
-int gpak_multi_failed_column(gpak_multi *g);
-int gpak_multi_set_kernel(gpak_multi *g, int nterms, const int *kinds, const double *pars, double bias, double white,
-                          double sn2, int dist_mode);
-int gpak_multi_grad_hyb(gpak_multi *g, double *grad, int ng);
-const char *gpak_multi_transport(gpak_multi *g);
-int gpak_multi_stats(gpak_multi *g, int r, gpak_dist_stats *out);
-int gpak_multi_predict(gpak_multi *g, const double *Xte, long M, int d, double *mean, double *var);
-int gpak_multi_grad(gpak_multi *g, double *grad10);
-int gpak_multi_timing(gpak_multi *g, gpak_phase_times *out);
-int gpak_multi_n(gpak_multi *g);
 #define GPAK_MULTI_ERR(rc_) do { int v_ = (rc_); if (v_) ctx->err = gpak_multi_error(ctx->multi); return v_; } while (0)
-int gpak_solve_chol_impl(gpak_ctx *ctx, double *X_host, int k);
 
 static std::string g_global_err;
 
@@ -104,21 +78,10 @@ extern "C" void gpak_reload_tuning(void) { tuning_storage() = read_tuning_env();
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-static void free_points(DevPoints &p) {
-  if (p.base) hipFree(p.base);
-  p = DevPoints();
-}
-int gpak_alloc_points(gpak_ctx *ctx, DevPoints &p, int cap) {
-  if (p.cap >= cap) return GPAK_OK;
-  free_points(p);
-  double *base = nullptr;
-  if (hipMalloc(&base, sizeof(double) * GPAK_PT * GPAK_MAX_TERMS * (size_t)cap) != hipSuccess) {
-    ctx->err = "hipMalloc(points) failed";
-    return GPAK_ENOMEM;
-  }
-  p.base = base;
-  p.cap = cap;
-  return GPAK_OK;
+int gpak_alloc_points(gpak_ctx *ctx, DevPointsBuf &p, int cap) {
+  if (p.reserve(cap)) return GPAK_OK;
+  ctx->err = "hipMalloc(points) failed";
+  return GPAK_ENOMEM;
 }
 
 // sigInv = Rot * lambda * Rot^T, Kernel.cpp:1399-1425 (host, 3x3)
@@ -180,26 +143,25 @@ void gpak_pooled_mean(const double *s1, long n, const double *s2, long m, double
   }
 }
 
+// The buffers that go with a training set: sized by N, and meaningless under another one.  The prediction buffers, the
+// reduction scratch and the ticket ring are kept: they only grow.
 static void release_train(gpak_ctx *ctx) {
-  if (ctx->dX) hipFree(ctx->dX);
-  if (ctx->dy) hipFree(ctx->dy);
-  if (ctx->dM) hipFree(ctx->dM);
-  if (ctx->dInv) hipFree(ctx->dInv);
-  if (ctx->dInv512) hipFree(ctx->dInv512);
-  if (ctx->dT512) hipFree(ctx->dT512);
-  if (ctx->dAlpha) hipFree(ctx->dAlpha);
-  if (ctx->dWork) hipFree(ctx->dWork);
-  if (ctx->dF) hipFree(ctx->dF);
-  gpak_grad_release(ctx);
-  ctx->dX = ctx->dy = ctx->dM = ctx->dInv = ctx->dInv512 = ctx->dT512 = ctx->dAlpha = ctx->dWork = ctx->dF = nullptr;
-  free_points(ctx->U);
-  if (ctx->dLf) hipFree(ctx->dLf);
-  if (ctx->dInvf) hipFree(ctx->dInvf);
-  ctx->dLf = ctx->dInvf = nullptr;
-  ctx->lf_ok = false;
+  for (DevBuf<double> *b : {&ctx->dX, &ctx->dy, &ctx->dM, &ctx->dInv, &ctx->dInv512, &ctx->dT512, &ctx->dAlpha, &ctx->dWork, &ctx->dF,
+                            &ctx->dG, &ctx->dBinv, &ctx->dGpart, &ctx->dLoo})
+    b->release();
+  ctx->U.release();
+  ctx->dLf.release();
+  ctx->dInvf.release();
   ctx->N = ctx->Np = 0;
-  ctx->mstate = gpak_ctx::M_NONE;
-  ctx->alpha_ok = ctx->nlz_ok = false;
+  ctx->state.new_training_set();
+}
+
+// events and streams, after the buffers of the context have freed themselves.  A group's context has none of either.
+gpak_queues::~gpak_queues() {
+  for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+  for (auto e : ev_pool) hipEventDestroy(e);
+  for (auto e : ev_sync) hipEventDestroy(e);
+  for (hipStream_t s : {stream_hi, stream_fs, stream_x, stream_tail, stream_bulk, stream}) if (s) hipStreamDestroy(s);
 }
 
 extern "C" {
@@ -274,8 +236,9 @@ int gpak_create(gpak_ctx **out, int device, int precision) {
     g_global_err = hipGetErrorString(e); delete ctx; return GPAK_EHIP;
   }
   for (int i = 0; i < 10; i++) hipEventCreate(&ctx->ev[i]);
-  hipMalloc(&ctx->dRed, sizeof(double) * 64);
-  hipMalloc(&ctx->dInfo, sizeof(int) * 4);
+  if (!ctx->dRed.reserve(64) || !ctx->dInfo.reserve(4)) {
+    g_global_err = "device allocation failed for the context's reduction scratch"; delete ctx; return GPAK_ENOMEM;
+  }
   *out = ctx;
   return GPAK_OK;
 }
@@ -318,20 +281,7 @@ void gpak_destroy(gpak_ctx *ctx) {
   if (ctx->multi) { gpak_multi_destroy(ctx->multi); delete ctx; return; }
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
-  release_train(ctx);
-  gpak_predict_release(ctx);
-  if (ctx->dRed) hipFree(ctx->dRed);
-  if (ctx->dInfo) hipFree(ctx->dInfo);
-  if (ctx->dTickets) hipFree(ctx->dTickets);
-  for (int i = 0; i < 10; i++) hipEventDestroy(ctx->ev[i]);
-  for (auto e : ctx->ev_pool) hipEventDestroy(e);
-  for (auto e : ctx->ev_sync) hipEventDestroy(e);
-  hipStreamDestroy(ctx->stream_hi);
-  hipStreamDestroy(ctx->stream_fs);
-  hipStreamDestroy(ctx->stream_x);
-  if (ctx->stream_tail) hipStreamDestroy(ctx->stream_tail);
-  if (ctx->stream_bulk) hipStreamDestroy(ctx->stream_bulk);
-  hipStreamDestroy(ctx->stream);
+  release_train(ctx);   // first, as ever; the other buffers go with the context, and its streams after them
   delete ctx;
 }
 
@@ -341,7 +291,7 @@ int gpak_set_option(gpak_ctx *ctx, int option, long value) {
   if (!ctx) return GPAK_EINVAL;
   if (ctx->multi) return GPAK_OK;   // schedule options of the single-GPU factorisation: nothing to set on a group
   switch (option) {
-    case GPAK_OPT_MEMOISE: ctx->memoise = value != 0; return GPAK_OK;
+    case GPAK_OPT_MEMOISE: ctx->state.set_memoise(value != 0); return GPAK_OK;
     case GPAK_OPT_NB_OUTER:
       if (value < 128 || value % 128) { ctx->err = "nb_outer must be a positive multiple of 128"; return GPAK_EINVAL; }
       ctx->sched.nb_outer = (int)value;
@@ -389,41 +339,28 @@ int gpak_set_train(gpak_ctx *ctx, const double *X, const double *y, int N, int d
   // d = 3: x, y, z; d = 4: + rock-type column with its own inverse width (Kernel.cpp:1411-1424)
   if (d != 3 && d != 4) { ctx->err = "inputs must have 3 or 4 columns"; return GPAK_ENOTIMPL; }
   GPAK_HIP(hipSetDevice(ctx->device));
-  release_train(ctx);
+  release_train(ctx);   // from here to the last line the context holds no training set: a failure leaves it that way
   const int Np = round_up(N, GPAK_TILE);
   long pad = Np >= 1024 ? 32 : 0;
   if (ctx->sched.ld_pad >= 0) pad = ctx->sched.ld_pad;
   const long ld = Np + pad;
-  ctx->N = N; ctx->Np = Np; ctx->ld = (int)ld; ctx->d = d;
-  ctx->hX.assign(X, X + (size_t)N * d);
-  ctx->xsum[3] = 0.0;
-  for (int k = 0; k < d; k++) {
-    double s = 0.0;
-    for (int i = 0; i < N; i++) s += X[i + (size_t)k * N];
-    ctx->xsum[k] = s;
-  }
   const int T = Np / GPAK_TILE;
   // width of the back substitution's explicit diagonal-block inverses (fixed per training set: it sizes dInv512)
   int bw = ctx->sched.bwd_block;
   if (bw != 512 && bw != 1024 && bw != 2048) bw = 512;
-  ctx->bwd_bw = bw;
-  if (hipMalloc(&ctx->dX, sizeof(double) * 4 * (size_t)Np) != hipSuccess ||
-      hipMalloc(&ctx->dy, sizeof(double) * (size_t)Np) != hipSuccess ||
-      hipMalloc(&ctx->dM, sizeof(double) * (size_t)ld * Np) != hipSuccess ||
-      hipMalloc(&ctx->dInv, sizeof(double) * (size_t)T * 2 * GPAK_TILE * GPAK_TILE) != hipSuccess ||
-      hipMalloc(&ctx->dInv512, sizeof(double) * (size_t)((Np + bw - 1) / bw) * bw * bw) != hipSuccess ||
-      hipMalloc(&ctx->dT512, sizeof(double) * (size_t)(2 * ((Np + bw - 1) / bw)) * bw * bw) != hipSuccess ||
-      hipMalloc(&ctx->dAlpha, sizeof(double) * (size_t)Np) != hipSuccess ||
-      hipMalloc(&ctx->dF, sizeof(double) * (size_t)Np) != hipSuccess ||
+  const size_t nbw = (size_t)((Np + bw - 1) / bw);
+  if (!ctx->dX.reserve(4 * (size_t)Np) || !ctx->dy.reserve(Np) || !ctx->dM.reserve((size_t)ld * Np) ||
+      !ctx->dInv.reserve((size_t)T * 2 * GPAK_TILE * GPAK_TILE) || !ctx->dInv512.reserve(nbw * bw * bw) ||
+      !ctx->dT512.reserve(2 * nbw * bw * bw) || !ctx->dAlpha.reserve(Np) || !ctx->dF.reserve(Np) ||
       // 70 Np doubles of vectors + the back substitution's scratch for the widest block ((8 + bw / 32) * bw for the
       // three-launch step, 34 * bw for the fused one: solve.hip)
-      hipMalloc(&ctx->dWork, sizeof(double) * (70 * (size_t)Np + (size_t)std::max(8 + bw / 32, 34) * bw)) != hipSuccess) {
+      !ctx->dWork.reserve(70 * (size_t)Np + (size_t)std::max(8 + bw / 32, 34) * bw)) {
     ctx->err = "device allocation failed for the training set";
     release_train(ctx);
     return GPAK_ENOMEM;
   }
   int rc = gpak_alloc_points(ctx, ctx->U, Np);
-  if (rc) return rc;
+  if (rc) { release_train(ctx); return rc; }
   GPAK_HIP(hipMemsetAsync(ctx->dX, 0, sizeof(double) * 4 * (size_t)Np, ctx->stream));
   GPAK_HIP(hipMemsetAsync(ctx->dy, 0, sizeof(double) * (size_t)Np, ctx->stream));
   // the inverse blocks are triangular: zero once, potrf128 only writes inside the triangles
@@ -434,9 +371,18 @@ int gpak_set_train(gpak_ctx *ctx, const double *X, const double *y, int N, int d
                             hipMemcpyHostToDevice, ctx->stream));
   GPAK_HIP(hipMemcpyAsync(ctx->dy, y, sizeof(double) * N, hipMemcpyHostToDevice, ctx->stream));
   GPAK_HIP(hipStreamSynchronize(ctx->stream));
+  // everything is in place: the context now holds the set
+  ctx->N = N; ctx->Np = Np; ctx->ld = (int)ld; ctx->d = d;
+  ctx->bwd_bw = bw;
+  ctx->hX.assign(X, X + (size_t)N * d);
+  ctx->xsum[3] = 0.0;
+  for (int k = 0; k < d; k++) {
+    double s = 0.0;
+    for (int i = 0; i < N; i++) s += X[i + (size_t)k * N];
+    ctx->xsum[k] = s;
+  }
   memset(&ctx->times, 0, sizeof(ctx->times));
   ctx->times.n = N; ctx->times.n_padded = Np;
-  ctx->U.n = 0;  // transformed points are rebuilt on the next use
   return GPAK_OK;
 }
 
@@ -446,32 +392,16 @@ int gpak_set_params(gpak_ctx *ctx, const double *expans, double bias, double sn2
   if (ctx->multi) { ctx->sn2 = sn2; GPAK_MULTI_ERR(gpak_multi_set_params(ctx->multi, expans, bias, sn2, dist_mode)); }
   // "same" compares with what gpak_set_kernel stores too: the stored kernel must be the one this call builds (one ExpAns
   // term, no White), or a composition's factor and alpha would pass for this kernel's
-  bool same = ctx->have_params && ctx->expans_only && ctx->kp.white == 0.0 &&
-              memcmp(expans, ctx->expans, sizeof(double) * 8) == 0 && bias == ctx->bias && sn2 == ctx->sn2 &&
-              dist_mode == ctx->dist_mode;
-  memcpy(ctx->expans, expans, sizeof(double) * 8);
-  memcpy(ctx->tpars[0], expans, sizeof(double) * 8);
-  ctx->bias = bias; ctx->sn2 = sn2; ctx->dist_mode = dist_mode;
-  ctx->have_params = true;
-  ctx->expans_only = true;
-  ctx->kinds[0] = GPAK_KERN_EXPANS;
-  ctx->kp.nterms = 1;
-  gpak_build_siginv(expans, ctx->kp.term[0].A);
-  ctx->kp.term[0].a33 = expans[7];  // InversewidthR: lambda(3,3) for a 4th input column (Kernel.cpp:1421-1424)
-  ctx->kp.term[0].var2 = expans[6] * expans[6];
-  ctx->kp.term[0].iw = 0.0;
-  ctx->kp.term[0].profile = GPAK_PROFILE_EXPSQRT;
-  ctx->kp.bias = bias;
-  ctx->kp.white = 0.0;
-  ctx->kp.mode = dist_mode;
-  ctx->kdiag = expans[6] * expans[6] + bias;
-  if (!(same && ctx->memoise)) {
-    // GP_Utils.cpp:132-133: setKUpdateStat(false) -> K, alpha and the likelihood are stale
-    ctx->mstate = gpak_ctx::M_NONE;
-    ctx->alpha_ok = ctx->nlz_ok = false;
-    ctx->U.n = 0;
-  }
-  return GPAK_OK;
+  const bool same = ctx->have_params && ctx->expans_only && ctx->kp.white == 0.0 &&
+                    memcmp(expans, ctx->expans, sizeof(double) * 8) == 0 && bias == ctx->bias && sn2 == ctx->sn2 &&
+                    dist_mode == ctx->dist_mode;
+  // Memoised: nothing is stored, every value being identical by the definition of "same" -- and kp.mu / kp.d, which
+  // gpak_build_kp zeroes and gpak_ensure_U refills only when it rebuilds U, must stand with the U that is kept.
+  if (same && ctx->state.memoise) { ctx->state.same_kernel(); return GPAK_OK; }
+  // The one-ExpAns composition without White.  kdiag comes out as (bias + 0.0) + var2 where this function used to compute
+  // var2 + bias: the same bits (x + 0.0 == x but for x = -0.0, and -0.0 + var2 == +0.0 + var2 for every var2 >= +0.0).
+  const int kind = GPAK_KERN_EXPANS;
+  return gpak_set_kernel(ctx, 1, &kind, expans, bias, 0.0, sn2, dist_mode);
 }
 
 // general composition: kinds[t] in {GPAK_KERN_EXPANS, GPAK_KERN_EXP, GPAK_KERN_RBF}, pars = the children's
@@ -500,9 +430,7 @@ int gpak_set_kernel(gpak_ctx *ctx, int nterms, const int *kinds, const double *p
   ctx->expans_only = (nterms == 1 && kinds[0] == GPAK_KERN_EXPANS && white == 0.0);
   ctx->bias = bias; ctx->sn2 = sn2; ctx->dist_mode = dist_mode;
   ctx->have_params = true;
-  ctx->mstate = gpak_ctx::M_NONE;
-  ctx->alpha_ok = ctx->nlz_ok = false;
-  ctx->U.n = 0;
+  ctx->state.new_kernel();
   return GPAK_OK;
 }
 
@@ -512,22 +440,16 @@ int gpak_set_kernel(gpak_ctx *ctx, int nterms, const int *kinds, const double *p
 int gpak_ensure_U(gpak_ctx *ctx) {
   if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
   if (!ctx->have_params) { ctx->err = "no parameters (gpak_set_params)"; return GPAK_ESTATE; }
-  if (ctx->U.n == ctx->N) return GPAK_OK;
+  if (ctx->state.points) return GPAK_OK;
   gpak_pooled_mean(ctx->xsum, ctx->N, ctx->xsum, ctx->N, ctx->kp.mu);
   ctx->kp.d = ctx->d;
   gpak_launch_transform(ctx->stream, ctx->dX, ctx->Np, ctx->N, ctx->kp, ctx->U);
+  ctx->state.points_built();
   return GPAK_OK;
 }
 
-// dM is about to hold another factor: nothing that was derived from the old one is valid any more
-static void factor_changed(gpak_ctx *ctx) {
-  ctx->z_ok = false;                          // dWork does not hold L^-1 (y/sn2)
-  ctx->backsolve = gpak_ctx::BS_BLOCKS128;    // no explicit inverses of wider diagonal blocks
-  ctx->lf_ok = false;                         // the fp32 image (GPAK_F32 prediction) is rebuilt on first use
-}
-
 static int ensure_factor(gpak_ctx *ctx) {
-  if (ctx->mstate == gpak_ctx::M_L) return GPAK_OK;
+  if (ctx->state.has(CtxState::FACTOR)) return GPAK_OK;
   int rc = gpak_ensure_U(ctx);
   if (rc) return rc;
   GPAK_HIP(hipSetDevice(ctx->device));
@@ -536,8 +458,7 @@ static int ensure_factor(gpak_ctx *ctx) {
   // B = I + (sW sW') % K  with W = 1/sn2  (GP_Utils.cpp:898-902); lower tiles only
   gpak_launch_fill(st, ctx->U, ctx->U, ctx->Np, ctx->Np, ctx->kp, 1.0 / ctx->sn2, 1.0, 1.0, 1, ctx->dM,
                    ctx->ld, nullptr);
-  ctx->mstate = gpak_ctx::M_B;
-  factor_changed(ctx);
+  ctx->state.factorisation_started();   // dM is about to hold another factor: nothing derived from the old one stands
   if (ctx->sched.fwd_in_factor) gpak_launch_scale(st, ctx->Np, ctx->dy, 1.0 / ctx->sn2, ctx->dWork);  // rhs = y/sn2
   GPAK_HIP(hipEventRecord(ctx->ev[1], st));
   rc = gpak_potrf_blocked(ctx);
@@ -550,38 +471,27 @@ static int ensure_factor(gpak_ctx *ctx) {
   ctx->times.factor_ms = ms;
   ctx->times.accumulated_ms[0] += ctx->times.gram_ms;
   ctx->times.accumulated_ms[1] += ctx->times.factor_ms;
-  ctx->times.evaluations++;
   ctx->times.gram_bytes = 8.0 * ((double)ctx->Np * (ctx->Np + GPAK_TILE) / 2.0);
-  if (rc == GPAK_ENOTPD) {
-    ctx->mstate = gpak_ctx::M_NONE;
-    ctx->err = "B = I + K/sn2 is not positive definite";
-    return rc;
-  }
+  if (rc == GPAK_ENOTPD) ctx->err = "B = I + K/sn2 is not positive definite";   // gpak_potrf_blocked has told ctx->state
   if (rc) return rc;
-  ctx->mstate = gpak_ctx::M_L;
-  const GpakSchedule &sc = ctx->sched;
-  ctx->z_ok = sc.fwd_in_factor;
-  // the explicit inverses are built beside the forward substitution only (gpak_potrf_plan)
-  ctx->backsolve = !(sc.fwd_in_factor && sc.inv512) ? gpak_ctx::BS_BLOCKS128
-                   : sc.bwd_fused == 2              ? gpak_ctx::BS_RT
-                   : sc.bwd_fused == 1              ? gpak_ctx::BS_INV_FAR
-                                                    : gpak_ctx::BS_INV_STEP;
+  // how a context substitutes backwards is settled here, by the options it factored under
+  ctx->state.factorisation_succeeded(ctx->sched.fwd_in_factor, ctx->sched.inv512, ctx->sched.bwd_fused);
   return GPAK_OK;
 }
 
 static int ensure_alpha(gpak_ctx *ctx) {
   int rc = ensure_factor(ctx);
   if (rc) return rc;
-  if (ctx->alpha_ok) return GPAK_OK;
+  if (ctx->state.has(CtxState::ALPHA)) return GPAK_OK;
   hipStream_t st = ctx->stream;
   double *w0 = ctx->dWork, *w1 = ctx->dWork + ctx->Np;
   GPAK_HIP(hipEventRecord(ctx->ev[3], st));
   // alpha = (K + sn2 I)^-1 y = B^-1 (y / sn2)
-  if (!ctx->z_ok) {
+  if (!ctx->state.z) {
     gpak_launch_scale(st, ctx->Np, ctx->dy, 1.0 / ctx->sn2, w0);
     gpak_launch_trsv_fwd(st, ctx->Np, ctx->dM, ctx->ld, ctx->dInv, w0, w1);
   }
-  ctx->z_ok = false;  // the back substitution consumes w1
+  ctx->state.work_vectors_overwritten();  // the back substitution consumes w1
   gpak_backsolve(ctx, st, w1, ctx->dAlpha, ctx->dWork + 2 * (size_t)ctx->Np);
   GPAK_HIP(hipEventRecord(ctx->ev[4], st));
   GPAK_HIP(hipEventSynchronize(ctx->ev[4]));
@@ -589,14 +499,14 @@ static int ensure_alpha(gpak_ctx *ctx) {
   GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
   ctx->times.solve_ms = ms;
   ctx->times.accumulated_ms[2] += ms;
-  ctx->alpha_ok = true;
+  ctx->state.alpha_built();
   return GPAK_OK;
 }
 
 static int ensure_nlz(gpak_ctx *ctx) {
   int rc = ensure_alpha(ctx);
   if (rc) return rc;
-  if (ctx->nlz_ok) return GPAK_OK;
+  if (ctx->state.has(CtxState::NLZ)) return GPAK_OK;
   hipStream_t st = ctx->stream;
   double *f = ctx->dF;
   double *scratch = ctx->dWork + 4 * (size_t)ctx->Np;  // 64 * Np doubles available
@@ -619,7 +529,7 @@ static int ensure_nlz(gpak_ctx *ctx) {
   ctx->times.kmatvec_ms = ms;
   ctx->logdet = red[0]; ctx->quad = red[1]; ctx->sumlp = red[2];
   ctx->nlz = ctx->quad - ctx->sumlp + ctx->logdet;  // GP_Utils.cpp:1159
-  ctx->nlz_ok = true;
+  ctx->state.nlz_built();
   return GPAK_OK;
 }
 
@@ -647,10 +557,7 @@ int gpak_import_factor(gpak_ctx *ctx, const gpak_dist_factor_view *v) {
   GPAK_HIP(hipMemcpyAsync(ctx->dAlpha, v->alpha, sizeof(double) * Np, hipMemcpyDeviceToDevice, st));
   GPAK_HIP(hipMemcpyAsync(ctx->dF, v->f, sizeof(double) * Np, hipMemcpyDeviceToDevice, st));
   GPAK_HIP(hipStreamSynchronize(st));
-  ctx->mstate = gpak_ctx::M_L;
-  factor_changed(ctx);       // in particular the 512-block inverses were not imported: back substitutions use the 128-blocks
-  ctx->alpha_ok = true; ctx->nlz_ok = true;
-  ctx->failed_col = 0;
+  ctx->state.factor_imported();   // in particular the 512-block inverses were not imported: back substitutions use the 128-blocks
   ctx->quad = v->quad; ctx->sumlp = v->sumlp; ctx->logdet = v->logdet; ctx->nlz = v->nlz;
   return GPAK_OK;
 }
@@ -663,6 +570,35 @@ static int copy_out(gpak_ctx *ctx, const double *dsrc, long ld, int n, int m, do
   return GPAK_OK;
 }
 
+static int ensure(gpak_ctx *ctx, CtxState::Rung rung) {
+  return rung == CtxState::NLZ ? ensure_nlz(ctx) : rung == CtxState::ALPHA ? ensure_alpha(ctx) : rung == CtxState::FACTOR ? ensure_factor(ctx) : GPAK_OK;
+}
+
+// The prologue of a call built for the single-GPU context, in the order every such call has had it: a group is refused;
+// then a training set, parameters, and (cols set: "test points" / "block points") d columns like the training set's, each
+// where the call requires it; then the context is brought up to `rung` (NONE: the caller has more to refuse first).
+static int single_gpu_call(gpak_ctx *ctx, const char *name, bool train, bool params, CtxState::Rung rung, int d = 0,
+                           const char *cols = nullptr) {
+  if (ctx->multi) {
+    ctx->err = std::string(name) + " is built for the single-GPU context (gpak_create) only";
+    return GPAK_ENOTIMPL;
+  }
+  if (train && !ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
+  if (params && !ctx->have_params) { ctx->err = "no parameters (gpak_set_params)"; return GPAK_ESTATE; }
+  if (cols && d != ctx->d) { ctx->err = std::string(cols) + " must have as many columns as the training set"; return GPAK_EINVAL; }
+  return ensure(ctx, rung);
+}
+
+// what a call answers when the training factor failed (as gpak_nlz: GP_Utils.cpp:1145-1146); p may be null
+static void fill_nan(double *p, size_t n) {
+  for (size_t i = 0; p && i < n; i++) p[i] = std::numeric_limits<double>::quiet_NaN();
+}
+static void nan_summary(gpak_loo_summary *s) {
+  if (!s) return;
+  s->mse = s->mssr = s->log_pl = std::numeric_limits<double>::quiet_NaN();
+  s->ms = 0.0; s->passes = 0;
+}
+
 extern "C" {
 
 int gpak_gram(gpak_ctx *ctx, double *K_host, double *D2_host) {
@@ -671,21 +607,19 @@ int gpak_gram(gpak_ctx *ctx, double *K_host, double *D2_host) {
   GPAK_HIP(hipSetDevice(ctx->device));
   int rc = gpak_ensure_U(ctx);
   if (rc) return rc;
-  double *dD2 = nullptr;
-  if (D2_host && hipMalloc(&dD2, sizeof(double) * (size_t)ctx->ld * ctx->Np) != hipSuccess) {
+  DevBuf<double> dD2;
+  if (D2_host && !dD2.reserve((size_t)ctx->ld * ctx->Np)) {
     ctx->err = "device allocation failed for D2";
     return GPAK_ENOMEM;
   }
   // the matrix buffer is reused: whatever factor it held is gone
-  ctx->mstate = gpak_ctx::M_NONE;
-  ctx->alpha_ok = ctx->nlz_ok = false;
+  ctx->state.matrix_overwritten();
   gpak_launch_fill(ctx->stream, ctx->U, ctx->U, ctx->Np, ctx->Np, ctx->kp, 1.0, 0.0, 0.0, 0, ctx->dM, ctx->ld,
                    dD2);
   rc = GPAK_OK;
   if (K_host) rc = copy_out(ctx, ctx->dM, ctx->ld, ctx->N, ctx->N, K_host);
   if (!rc && D2_host) rc = copy_out(ctx, dD2, ctx->ld, ctx->N, ctx->N, D2_host);
   GPAK_HIP(hipStreamSynchronize(ctx->stream));
-  if (dD2) hipFree(dD2);
   return rc;
 }
 
@@ -707,13 +641,11 @@ int gpak_compute_k(gpak_ctx *ctx, const double *X1, int n, const double *X2, int
   kp.d = d;
   gpak_pooled_mean(s1, n, s2, m, kp.mu);
   if (!(X1[0] == X2[0] && n == m)) kp.white = 0.0;  // Kern_White::computeK, Kernel.cpp:260-262
-  DevPoints P, Q;
-  double *dx = nullptr, *dK = nullptr, *dD2 = nullptr;
+  DevBuf<double> dD2, dK, dx;   // freed last-declared first: P, Q, dx, dK, dD2 as ever
+  DevPointsBuf Q, P;
   int rc = gpak_alloc_points(ctx, P, np);
   if (!rc) rc = gpak_alloc_points(ctx, Q, mp);
-  if (!rc && (hipMalloc(&dx, sizeof(double) * 4 * (size_t)(np + mp)) != hipSuccess ||
-              hipMalloc(&dK, sizeof(double) * (size_t)np * mp) != hipSuccess ||
-              (D2_host && hipMalloc(&dD2, sizeof(double) * (size_t)np * mp) != hipSuccess))) {
+  if (!rc && (!dx.reserve(4 * (size_t)(np + mp)) || !dK.reserve((size_t)np * mp) || (D2_host && !dD2.reserve((size_t)np * mp)))) {
     ctx->err = "device allocation failed in gpak_compute_k";
     rc = GPAK_ENOMEM;
   }
@@ -732,10 +664,6 @@ int gpak_compute_k(gpak_ctx *ctx, const double *X1, int n, const double *X2, int
     if (!rc && D2_host) rc = copy_out(ctx, dD2, np, n, m, D2_host);
     hipStreamSynchronize(st);
   }
-  free_points(P); free_points(Q);
-  if (dx) hipFree(dx);
-  if (dK) hipFree(dK);
-  if (dD2) hipFree(dD2);
   return rc;
 }
 
@@ -747,7 +675,7 @@ int gpak_factor(gpak_ctx *ctx) {
 
 int gpak_failed_column(const gpak_ctx *ctx) {
   if (!ctx) return 0;
-  return ctx->multi ? gpak_multi_failed_column(ctx->multi) : ctx->failed_col;
+  return ctx->multi ? gpak_multi_failed_column(ctx->multi) : ctx->state.failed_col;
 }
 int gpak_n_gpus(const gpak_ctx *ctx) { return !ctx ? 0 : (ctx->multi ? gpak_multi_n(ctx->multi) : 1); }
 const char *gpak_transport(const gpak_ctx *ctx) { return !ctx ? "" : (ctx->multi ? gpak_multi_transport(ctx->multi) : "none"); }
@@ -820,10 +748,8 @@ int gpak_predict(gpak_ctx *ctx, const double *Xte, long M, int d, double *mean, 
     rc = gpak_multi_predict(ctx->multi, Xte, M, d, mean, var);
     if (rc) { ctx->err = gpak_multi_error(ctx->multi); return rc; }
   } else {
-    if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
-    if (d != ctx->d) { ctx->err = "test points must have as many columns as the training set"; return GPAK_EINVAL; }
     // _postVar calls logLikelihood() (GP_Utils.cpp:980); _postMean calls updateAlpha() (:961)
-    rc = ensure_nlz(ctx);
+    rc = single_gpu_call(ctx, "gpak_predict", true, false, CtxState::NLZ, d, "test points");
     if (rc) return rc;
     rc = gpak_predict_impl(ctx, Xte, M, mean, var, nullptr, 0);
     if (rc) return rc;
@@ -865,49 +791,35 @@ int gpak_grad_hyb(gpak_ctx *ctx, double *g, int ng) {
 
 int gpak_grad_exact(gpak_ctx *ctx, double *g, int ng) {
   if (!ctx || !g) return GPAK_EINVAL;
-  if (ctx->multi) {
-    ctx->err = "gpak_grad_exact is built for the single-GPU context (gpak_create) only; a multi-GPU context has gpak_grad / gpak_grad_hyb";
-    return GPAK_ENOTIMPL;
-  }
-  int rc = ensure_nlz(ctx);
+  int rc = single_gpu_call(ctx, "gpak_grad_exact", false, false, CtxState::NLZ);
+  if (ctx->multi) ctx->err += "; a multi-GPU context has gpak_grad / gpak_grad_hyb";
   if (rc) return rc;
   return gpak_grad_exact_impl(ctx, g, ng);
 }
 
 int gpak_loo(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *summary) {
   if (!ctx) return GPAK_EINVAL;
-  if (ctx->multi) {
-    ctx->err = "gpak_loo is built for the single-GPU context (gpak_create) only";
-    return GPAK_ENOTIMPL;
-  }
-  int rc = ensure_nlz(ctx);
+  int rc = single_gpu_call(ctx, "gpak_loo", false, false, CtxState::NLZ);
   if (rc == GPAK_OK) rc = gpak_loo_impl(ctx, mean, var, summary);
-  if (rc == GPAK_ENOTPD) {   // as gpak_nlz: GP_Utils.cpp:1145-1146
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; mean && i < ctx->N; i++) mean[i] = nan;
-    for (int i = 0; var && i < ctx->N; i++) var[i] = nan;
-    if (summary) { summary->mse = summary->mssr = summary->log_pl = nan; summary->ms = 0.0; summary->passes = 0; }
+  if (rc == GPAK_ENOTPD) {
+    fill_nan(mean, ctx->N);
+    fill_nan(var, ctx->N);
+    nan_summary(summary);
   }
   return rc;
 }
 
 int gpak_loo_grad(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary) {
   if (!ctx || !g) return GPAK_EINVAL;
-  if (ctx->multi) {
-    ctx->err = "gpak_loo_grad is built for the single-GPU context (gpak_create) only";
-    return GPAK_ENOTIMPL;
-  }
   // what the call refuses is refused before anything is factored
-  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
-  if (!ctx->have_params) { ctx->err = "no parameters (gpak_set_params)"; return GPAK_ESTATE; }
-  int rc = gpak_loo_grad_layout(ctx, ng);
+  int rc = single_gpu_call(ctx, "gpak_loo_grad", true, true, CtxState::NONE);
+  if (rc == GPAK_OK) rc = gpak_loo_grad_layout(ctx, ng);
   if (rc) return rc;
   rc = ensure_nlz(ctx);
   if (rc == GPAK_OK) rc = gpak_loo_grad_impl(ctx, g, ng, summary);
-  if (rc == GPAK_ENOTPD) {   // as gpak_loo
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < ng; i++) g[i] = nan;
-    if (summary) { summary->mse = summary->mssr = summary->log_pl = nan; summary->ms = 0.0; summary->passes = 0; }
+  if (rc == GPAK_ENOTPD) {
+    fill_nan(g, ng);
+    nan_summary(summary);
   }
   return rc;
 }
@@ -915,13 +827,9 @@ int gpak_loo_grad(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary) {
 int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,
                    gpak_cv_groups_summary *summary) {
   if (!ctx) return GPAK_EINVAL;
-  if (ctx->multi) {
-    ctx->err = "gpak_cv_groups is built for the single-GPU context (gpak_create) only";
-    return GPAK_ENOTIMPL;
-  }
   // what the call refuses is refused before anything is factored
-  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
-  if (!ctx->have_params) { ctx->err = "no parameters (gpak_set_params)"; return GPAK_ESTATE; }
+  int rc = single_gpu_call(ctx, "gpak_cv_groups", true, true, CtxState::NONE);
+  if (rc) return rc;
   const int N = ctx->N;
   const std::string who = "gpak_cv_groups: ";
   if (!group) { ctx->err = who + "group is NULL"; return GPAK_EINVAL; }
@@ -951,15 +859,14 @@ int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, 
     std::vector<int> at(offs.begin(), offs.end() - 1);
     for (int i = 0; i < N; i++) perm[(size_t)at[group[i]]++] = i;
   }
-  int rc = ensure_nlz(ctx);
+  rc = ensure_nlz(ctx);
   if (rc == GPAK_OK) return gpak_cv_groups_impl(ctx, perm.data(), offs.data(), n_groups, mean, var, group_logp, summary);
-  if (rc == GPAK_ENOTPD) {   // the training factor: as gpak_loo
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; mean && i < N; i++) mean[i] = nan;
-    for (int i = 0; var && i < N; i++) var[i] = nan;
-    for (int g = 0; group_logp && g < n_groups; g++) group_logp[g] = nan;
-    if (summary) {
-      summary->mse = summary->mssr = summary->msmd = summary->log_pl = nan;
+  if (rc == GPAK_ENOTPD) {   // the training factor
+    fill_nan(mean, N);
+    fill_nan(var, N);
+    fill_nan(group_logp, n_groups);
+    if (summary) {   // its own summary type: written out
+      summary->mse = summary->mssr = summary->msmd = summary->log_pl = std::numeric_limits<double>::quiet_NaN();
       summary->ms = 0.0; summary->groups = n_groups; summary->max_size = 0;
     }
   }
@@ -968,19 +875,12 @@ int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, 
 
 static int block_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *var,
                       int flags, double *Kbar_host) {
-  if (ctx->multi) {
-    ctx->err = std::string(name) + " is built for the single-GPU context (gpak_create) only";
-    return GPAK_ENOTIMPL;
-  }
-  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
-  if (d != ctx->d) { ctx->err = "block points must have as many columns as the training set"; return GPAK_EINVAL; }
-  int rc = ensure_nlz(ctx);
+  int rc = single_gpu_call(ctx, name, true, false, CtxState::NLZ, d, "block points");
   if (rc == GPAK_OK) rc = gpak_predict_block_impl(ctx, Xd, M, nd, mean, var, flags, Kbar_host);
-  if (rc == GPAK_ENOTPD) {   // as gpak_loo
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (long i = 0; mean && i < M; i++) mean[i] = nan;
-    for (long i = 0; var && i < M; i++) var[i] = nan;
-    for (size_t i = 0; Kbar_host && i < (size_t)M * ctx->N; i++) Kbar_host[i] = nan;
+  if (rc == GPAK_ENOTPD) {
+    fill_nan(mean, M);
+    fill_nan(var, M);
+    fill_nan(Kbar_host, (size_t)M * ctx->N);
   }
   return rc;
 }
@@ -997,24 +897,16 @@ int gpak_predict_block(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, d
 
 static int joint_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *cov_host,
                       int flags, const double *Xi, int S, double nugget, double *Z) {
-  if (ctx->multi) {
-    ctx->err = std::string(name) + " is built for the single-GPU context (gpak_create) only";
-    return GPAK_ENOTIMPL;
-  }
-  if (!ctx->N) { ctx->err = "no training set (gpak_set_train)"; return GPAK_ESTATE; }
-  if (d != ctx->d) { ctx->err = "block points must have as many columns as the training set"; return GPAK_EINVAL; }
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  int rc = ensure_nlz(ctx);
+  int rc = single_gpu_call(ctx, name, true, false, CtxState::NLZ, d, "block points");
   if (rc == GPAK_ENOTPD) {   // the training factor: as gpak_predict_block
-    ctx->err = "the training factor failed (B = I + K/sn2 is not positive definite at column " + std::to_string(ctx->failed_col) + ")";
-    for (long i = 0; mean && i < M; i++) mean[i] = nan;
-    for (size_t i = 0; cov_host && i < (size_t)M * M; i++) cov_host[i] = nan;
-    for (size_t i = 0; Z && i < (size_t)M * S; i++) Z[i] = nan;
+    ctx->err = "the training factor failed (B = I + K/sn2 is not positive definite at column " + std::to_string(ctx->state.failed_col) + ")";
+    fill_nan(mean, M);
+    fill_nan(cov_host, (size_t)M * M);
+    fill_nan(Z, (size_t)M * S);
     return rc;
   }
   if (rc == GPAK_OK) rc = gpak_joint_impl(ctx, Xd, M, nd, mean, cov_host, flags, Xi, S, nugget, Z);
-  if (rc == GPAK_ENOTPD)     // C + nugget I: the mean stands
-    for (size_t i = 0; Z && i < (size_t)M * S; i++) Z[i] = nan;
+  if (rc == GPAK_ENOTPD) fill_nan(Z, (size_t)M * S);   // C + nugget I: the mean stands
   return rc;
 }
 
@@ -1033,6 +925,7 @@ int gpak_timing(gpak_ctx *ctx, gpak_phase_times *out) {
   if (!ctx || !out) return GPAK_EINVAL;
   if (ctx->multi) return gpak_multi_timing(ctx->multi, out);
   *out = ctx->times;
+  out->evaluations = ctx->state.factorisations;
   return GPAK_OK;
 }
 
@@ -1042,11 +935,9 @@ int gpak_calibrate(gpak_ctx *ctx, double *mfma_f64_tflops, double *hbm_write_gbs
     GPAK_MULTI_ERR(gpak_multi_on_replica0(ctx->multi, [&](gpak_ctx *c) { return gpak_calibrate(c, mfma_f64_tflops, hbm_write_gbs); }, false));
   GPAK_HIP(hipSetDevice(ctx->device));
   const size_t bytes = (size_t)4 << 30;
-  double *scratch = nullptr;
-  if (hipMalloc(&scratch, bytes) != hipSuccess) { ctx->err = "calibration scratch allocation failed"; return GPAK_ENOMEM; }
-  int rc = gpak_calibrate_impl(ctx, scratch, bytes, mfma_f64_tflops, hbm_write_gbs);
-  hipFree(scratch);
-  return rc;
+  DevBuf<double> scratch;
+  if (!scratch.reserve(bytes / sizeof(double))) { ctx->err = "calibration scratch allocation failed"; return GPAK_ENOMEM; }
+  return gpak_calibrate_impl(ctx, scratch, bytes, mfma_f64_tflops, hbm_write_gbs);
 }
 
 }  // extern "C"

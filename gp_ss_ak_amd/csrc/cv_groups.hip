@@ -234,16 +234,9 @@ int gpak_cv_groups_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_g
   // (dG is never allocated alone: grad_binv takes dG != NULL to mean that dBinv exists too.)
   double *G = ctx->dG;
   if (!G) {
-    const size_t need = (size_t)ld * Np;
-    if (ctx->loo_elems < need) {
-      if (ctx->dLoo) hipFree(ctx->dLoo);
-      ctx->dLoo = nullptr; ctx->loo_elems = 0;
-      if (hipMalloc(&ctx->dLoo, sizeof(double) * need) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->err = "device allocation failed for the leave-group-out workspace (L^-T as one N x N matrix)";
-        return GPAK_ENOMEM;
-      }
-      ctx->loo_elems = need;
+    if (!gpak_loo_workspace(ctx, (size_t)ld * Np)) {
+      ctx->err = "device allocation failed for the leave-group-out workspace (L^-T as one N x N matrix)";
+      return GPAK_ENOMEM;
     }
     G = ctx->dLoo;
   }

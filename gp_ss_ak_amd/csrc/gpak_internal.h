@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/gpak.h"
+#include "ctx_state.h"   // CtxState: what of a context's device contents is current (HIP-free)
 #include "potrf_plan.h"  // GPAK_TILE, GpakSchedule and the factorisation's schedule (HIP-free)
 
 // The covariance function as the device sees it: a SUM of up to three stationary terms (the
@@ -40,10 +41,47 @@ struct KernParams {
 // term t is base + (GPAK_PT * t + c) * cap.
 #define GPAK_PT 5
 #define GPAK_PARR(base, cap, t, c) ((base) + (size_t)(GPAK_PT * (t) + (c)) * (cap))
+// A device allocation and its owner: freed with whatever holds it, never copied.
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t n = 0;   // elements allocated
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  operator T *() const { return p; }
+  // room for at least `elems` elements: grows only, contents are not kept.  false: the allocation failed, the buffer is empty
+  bool reserve(size_t elems) {
+    if (n >= elems) return true;
+    release();
+    if (hipMalloc(&p, sizeof(T) * elems) != hipSuccess) { p = nullptr; return false; }
+    n = elems;
+    return true;
+  }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr; n = 0;
+  }
+};
+
 struct DevPoints {
   double *base = nullptr;
   int n = 0;    // valid points
   int cap = 0;  // allocated points (multiple of GPAK_TILE)
+};
+// A point set with its owner: what a context allocates.  The launchers take the DevPoints it is (dev_api.hip makes such
+// views of points it does not own).
+struct DevPointsBuf : DevPoints {
+  DevBuf<double> mem;
+  bool reserve(int points) {   // as DevBuf::reserve
+    if (cap >= points) return true;
+    release();
+    if (!mem.reserve(GPAK_PT * GPAK_MAX_TERMS * (size_t)points)) return false;
+    base = mem; cap = points;
+    return true;
+  }
+  void release() { mem.release(); base = nullptr; n = cap = 0; }
 };
 
 // ---- tuning, part 2: kernel selection ------------------------------------------------------------------------
@@ -69,23 +107,37 @@ const GpakKernelTuning &gpak_tuning();
 
 struct gpak_multi;   // multi.hip: one process driving several GPUs (gpak_create_multi)
 
-struct gpak_ctx {
-  gpak_multi *multi = nullptr;   // set: every call is forwarded to the group, the fields below are unused
-  int device = 0;
-  int cu_count = 0;                 // compute units of the device (gpak_potrf_block_co)
-  int precision = GPAK_F64;
+// The streams and events of a context.  A base of gpak_ctx and not members of it, so that they are destroyed AFTER the
+// context's buffers have been freed -- the order gpak_destroy has always had: the first hipFree waits for the device.
+struct gpak_queues {
   hipStream_t stream = nullptr;     // main stream: fill, bulk trailing updates, solves
   hipStream_t stream_hi = nullptr;  // high-priority stream: panel factorisation (look-ahead)
   hipStream_t stream_tail = nullptr;  // CU-masked copy of the main stream for the tail's bulk updates (optional)
   hipStream_t stream_bulk = nullptr;  // the bulk updates' own queue before the tail: created like stream_tail but with every CU enabled (optional)
   hipStream_t stream_fs = nullptr;  // forward substitution riding along with the factorisation, off the panel chain
   hipStream_t stream_x = nullptr;   // tail: K=128 updates of the next block column, sub-panel by sub-panel
+  hipEvent_t ev[10] = {};            // timing
+  std::vector<hipEvent_t> ev_pool;   // timing events around the trailing updates
+  std::vector<hipEvent_t> ev_sync;   // cross-stream dependencies of the look-ahead pipeline
+  gpak_queues() = default;
+  gpak_queues(const gpak_queues &) = delete;
+  ~gpak_queues();   // api.hip.  Nothing of the device for a group's context, which has none of these
+};
+
+struct gpak_ctx : gpak_queues {
+  gpak_multi *multi = nullptr;   // set: every call is forwarded to the group; the fields below are unused and own nothing
+  int device = 0;
+  int cu_count = 0;                 // compute units of the device (gpak_potrf_block_co)
+  int precision = GPAK_F64;
   std::string err;
 
-  // training set
+  // what of the device contents below is current: every validity fact, changed through its events only
+  CtxState state;
+
+  // training set (release_train, api.hip, says which buffers go with it)
   int N = 0, Np = 0, ld = 0, d = 0;
-  double *dX = nullptr;      // raw input columns (3 or 4), SoA with stride Np (4 arrays, the 4th zero for d = 3)
-  double *dy = nullptr;      // Np (padded with 0)
+  DevBuf<double> dX;         // raw input columns (3 or 4), SoA with stride Np (4 arrays, the 4th zero for d = 3)
+  DevBuf<double> dy;         // Np (padded with 0)
   std::vector<double> hX;    // host copy of X (col-major N x d), for pooled means
   double xsum[4] = {0, 0, 0, 0};
 
@@ -101,81 +153,62 @@ struct gpak_ctx {
   double kdiag = 0;          // diag_Compute of the composition (Kernel.cpp:127-136)
 
   // device state
-  DevPoints U;               // transformed training points
-  double *dM = nullptr;      // Np x ld matrix buffer: B then L (lower)
-  double *dInv = nullptr;    // (Np/128) inverted 128x128 diagonal blocks of L
-  double *dInv512 = nullptr; // explicit (L_bb^-1)^T of the bw x bw diagonal blocks (bw = bwd_bw; back substitution)
+  DevPointsBuf U;            // transformed training points
+  DevBuf<double> dM;         // Np x ld matrix buffer: B then L (lower)
+  DevBuf<double> dInv;       // (Np/128) inverted 128x128 diagonal blocks of L
+  DevBuf<double> dInv512;    // explicit (L_bb^-1)^T of the bw x bw diagonal blocks (bw = bwd_bw; back substitution)
   int bwd_bw = 512;          // block width dInv512 was sized and is being built for
-  double *dT512 = nullptr;   // bwd_fused = 2: per block column the stacked [R_b ; T_b], T_b = L[b, b-1]^T R_b (2 bw x bw: solve.hip)
-  // what gpak_backsolve (solve.hip) may use with the current factor: set by ensure_factor after a successful
-  // factorisation, reset by factor_changed (api.hip)
-  enum Backsolve {
-    BS_BLOCKS128,            // the inverted 128-blocks only
-    BS_INV_STEP,             // explicit inverses in dInv512, three launches per step (bwd_fused 0)
-    BS_INV_FAR,              // ... far column dots under the diagonal step (bwd_fused 1)
-    BS_RT                    // [R_b ; T_b] in dT512, one launch per step (bwd_fused 2)
-  } backsolve = BS_BLOCKS128;
-  double *dAlpha = nullptr;  // Np
-  double *dWork = nullptr;   // 4*Np scratch vectors
-  double *dRed = nullptr;    // small reduction scratch
-  int *dInfo = nullptr;      // first failing column (1-based) or 0
-  unsigned long long *dTickets = nullptr;   // ticketed bulk updates: 8 list words per bulk launch, zeroed per factorisation
-  int tickets_cap = 0;       // bulk launches dTickets has room for
-  enum { M_NONE, M_B, M_L } mstate = M_NONE;
-  bool alpha_ok = false, nlz_ok = false;
-  int failed_col = 0;
+  DevBuf<double> dT512;      // bwd_fused = 2: per block column the stacked [R_b ; T_b], T_b = L[b, b-1]^T R_b (2 bw x bw: solve.hip)
+  DevBuf<double> dAlpha;     // Np
+  DevBuf<double> dWork;      // 4*Np scratch vectors
+  // (the buffers that outlive a training set are declared in the reverse of the order gpak_destroy has always freed them
+  // in: members go last-declared first, and the order of the frees decides which addresses the next context is given)
+  DevBuf<unsigned long long> dTickets;   // ticketed bulk updates: 8 list words per bulk launch, zeroed per factorisation
+  DevBuf<int> dInfo;         // first failing column (1-based) or 0
+  DevBuf<double> dRed;       // small reduction scratch
   double quad = 0, sumlp = 0, logdet = 0, nlz = 0;
 
-  // prediction buffers (grown on demand, kept across calls)
-  DevPoints Upred, Tq;       // train / test-batch points centred on the pooled train+test mean
-  double *dXte = nullptr;    // 4 x pred_cap raw test columns (SoA)
-  double *dWt = nullptr;     // pred_cap x Np cross-kernel, test-major (transposed kX)
-  double *dPv = nullptr;     // 2 x pred_cap: mean, sum of squares
-  double *dPart = nullptr;   // 64 x pred_cap partial sums
-  int pred_cap = 0;
-  size_t wt_elems = 0;
-  // block-support prediction (gpak_predict_block): a batch's discretisation points, raw (4 columns) and transformed
-  // point-major (gpak_transform_blocks_f64), blk_points points of blk_terms terms each
-  double *dXblk = nullptr, *dTblk = nullptr;
-  size_t blk_points = 0;
-  int blk_terms = 0;
+  // prediction buffers (grown on demand, kept across calls and training sets; declared in reverse like the three above)
+  DevBuf<double> dPart;      // 64 x pred_cap partial sums
+  DevBuf<double> dPv;        // 2 x pred_cap: mean, sum of squares
+  DevBuf<double> dWt;        // pred_cap x Np cross-kernel, test-major (transposed kX)
+  DevBuf<double> dXte;       // 4 x pred_cap raw test columns (SoA)
+  DevPointsBuf Tq, Upred;    // test-batch / train points centred on the pooled train+test mean
+  int pred_cap = 0;          // dXte, dPv, dPart and Tq grow together on it
   // joint prediction / simulation (gpak_predict_joint, gpak_sample_joint): the joint_cap x joint_cap covariance and then
   // its factor (leading dimension skewed like dWt's), that factor's inverted 128-blocks and failing column, and the
-  // normals / realisations (joint_cap x joint_s each)
-  double *dC = nullptr, *dCinv = nullptr, *dXi = nullptr, *dZ = nullptr;
-  int *dCinfo = nullptr;
+  // normals / realisations
+  DevBuf<double> dZ, dXi;
+  DevBuf<int> dCinfo;
+  DevBuf<double> dCinv, dC;
   int joint_cap = 0;
-  size_t joint_elems = 0, joint_s = 0;
-  // fp32 prediction (ctx created with GPAK_F32): fp32 images of L and of the inverse blocks
-  float *dLf = nullptr, *dInvf = nullptr;
+  // block-support prediction (gpak_predict_block): a batch's discretisation points, raw (4 columns) and transformed
+  // point-major (gpak_transform_blocks_f64), blk_points points of blk_terms terms each
+  DevBuf<double> dTblk, dXblk;
+  size_t blk_points = 0;
+  int blk_terms = 0;
+  // fp32 prediction (ctx created with GPAK_F32): fp32 images of L and of the inverse blocks (CtxState::image)
+  DevBuf<float> dLf, dInvf;
   long ldLf = 0;             // leading dimension of dLf (Np + skew)
-  bool lf_ok = false;
 
   // gradient buffers (allocated on the first gpak_grad)
-  double *dG = nullptr;      // Np x ld: L^-T (upper triangular)
-  double *dBinv = nullptr;   // Np x ld: B^-1, lower tiles
-  double *dF = nullptr;      // Np: f = K*alpha of the last logLikelihood()
-  double *dGpart = nullptr;  // per-workgroup partial sums of the pair pass
-  size_t gpart_elems = 0;
-  // leave-one-out (gpak_loo): a slab of rows of L^-T of its own when the gradient has not allocated dG
-  double *dLoo = nullptr;
-  size_t loo_elems = 0;
+  DevBuf<double> dG;         // Np x ld: L^-T (upper triangular)
+  DevBuf<double> dBinv;      // Np x ld: B^-1, lower tiles.  Allocated with dG: dG != NULL means that dBinv exists too
+  DevBuf<double> dF;         // Np: f = K*alpha of the last logLikelihood()
+  DevBuf<double> dGpart;     // per-workgroup partial sums of the pair pass; shared scratch whose contents nobody keeps
+  // leave-one-out (gpak_loo): a slab of rows of L^-T of its own when the gradient has not allocated dG; leave-group-out
+  // (gpak_cv_groups) holds all of L^-T, in dG when the gradient has allocated it, otherwise here (gpak_loo_workspace)
+  DevBuf<double> dLoo;
   int loo_rows = 0;           // GPAK_OPT_LOO_ROWS: rows of L^-T held at once (0: the default, 16384)
-  // leave-group-out (gpak_cv_groups) holds all of L^-T: in dG when the gradient has allocated it, otherwise in dLoo grown
-  // to Np x ld.  The substitution, the Gram pass and the solve pass of the last call, in ms:
+  // the substitution, the Gram pass and the solve pass of the last gpak_cv_groups, in ms
   double cvg_ms[3] = {0, 0, 0};
 
   // options
   GpakSchedule sched;         // this context's copy of the schedule set (gpak_set_option changes it)
-  bool memoise = false;
   bool profile = false;
-  bool z_ok = false;          // dWork[Np..2Np) holds L^-1 (y/sn2) of the current factor
 
   // timing
   gpak_phase_times times;
-  hipEvent_t ev[10];
-  std::vector<hipEvent_t> ev_pool;   // timing events around the trailing updates
-  std::vector<hipEvent_t> ev_sync;   // cross-stream dependencies of the look-ahead pipeline
 };
 
 #define GPAK_HIP(call)                                                                  \
@@ -323,7 +356,7 @@ int gpak_kmatvec_splits(int nP, int nQ);
 void gpak_launch_kmatvec(hipStream_t st, const DevPoints &P, int p_off, int np, const double *w, const DevPoints &Q,
                          const KernParams &kp, double *scratch, int splits, double *out, int scratch_rows = 0);
 void gpak_launch_sum_splits(hipStream_t st, const double *part, int part_ld, int splits, int n, double *out);
-int gpak_alloc_points(gpak_ctx *ctx, DevPoints &p, int cap);
+int gpak_alloc_points(gpak_ctx *ctx, DevPointsBuf &p, int cap);   // DevPointsBuf::reserve with the context's error text
 void gpak_pooled_mean(const double *s1, long n, const double *s2, long m, double *mu);
 int gpak_ensure_U(gpak_ctx *ctx);
 
@@ -340,6 +373,7 @@ void gpak_launch_gemm_nt(hipStream_t st, int mt, int nt, int K, double alpha, co
 
 void gpak_launch_gemm_nt_k0map(hipStream_t st, int mt, int nt, int K, double alpha, const double *A, long lda,
                                const double *B, long ldb, double *C, long ldc, int skip_shift, int k0_mul, int k0_add);
+int gpak_calibrate_impl(gpak_ctx *ctx, double *scratch, size_t scratch_bytes, double *tflops, double *gbs);
 void gpak_launch_gemm_cyclic(hipStream_t st, int mt, int nt, int K, const double *Pv, long ldp, double *Clocal,
                              long ldc, int rt0, int P, int rank, int tpb, int lt0);
 
@@ -378,7 +412,7 @@ void gpak_launch_trsv_bwd2(hipStream_t st, int Np, const double *L, long ld, con
 // OP = per block column R_b (and, with_T, T_b in the rows below it: gpak_launch_diag_inverse with extra = NB)
 void gpak_launch_trsv_bwd3(hipStream_t st, int Np, const double *L, long ld, const double *z, double *out, double *scratch,
                            const double *OP, size_t op_stride, int RL, bool with_T, int NB);
-// out = L^-T z with whatever the context's current factor supports (gpak_ctx::backsolve); z is read-only, scratch
+// out = L^-T z with whatever the context's current factor supports (CtxState::backsolve); z is read-only, scratch
 // holds what the launcher it picks asks for: at most max(8 + bw / 32, 18) * bw doubles, bw = ctx->bwd_bw
 void gpak_backsolve(gpak_ctx *ctx, hipStream_t st, const double *z, double *out, double *scratch);
 void gpak_launch_trsv_fwd_block(hipStream_t st, int Np, int J, int W, const double *L, long ld,
@@ -397,7 +431,10 @@ void gpak_launch_scale(hipStream_t st, int n, const double *in, double s, double
 void gpak_launch_axpy(hipStream_t st, int n, double a, const double *x, double *y);  // y += a x
 
 // ---- predict.hip ------------------------------------------------------------------------
-void gpak_predict_release(gpak_ctx *ctx);
+// pool_sum / pool_M: column sums and count of the WHOLE test set when Xte is a slice of it, or nullptr
+int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, double *var, const double *pool_sum,
+                      long pool_M);
+int gpak_solve_chol_impl(gpak_ctx *ctx, double *X_host, int k);
 // gpak_predict_block / gpak_block_cross on a single-GPU context whose factor and alpha are current
 int gpak_predict_block_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mean, double *var, int flags,
                             double *Kbar_host);
@@ -428,7 +465,6 @@ int gpak_build_kp(int nterms, const int *kinds, const double *pars, double bias,
                   KernParams *out, double *kdiag_out);
 
 // ---- grad.hip ---------------------------------------------------------------------------
-void gpak_grad_release(gpak_ctx *ctx);
 // gpak_grad / gpak_grad_hyb and gpak_grad_exact on a single-GPU context whose factor and alpha are current
 int gpak_grad_impl(gpak_ctx *ctx, double *g, int ng);
 int gpak_grad_exact_impl(gpak_ctx *ctx, double *g, int ng);
@@ -445,6 +481,8 @@ void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *ex
 // at least `elems` doubles in ctx->dGpart (contents are not kept); G = L^-T of the current factor as one Np x Np matrix
 // (leading dimension ldg) on the context's stream
 int gpak_grad_scratch(gpak_ctx *ctx, size_t elems);
+// room for `elems` doubles of L^-T in ctx->dLoo (gpak_loo, gpak_cv_groups); false: it does not fit (the HIP error is cleared)
+bool gpak_loo_workspace(gpak_ctx *ctx, size_t elems);
 void gpak_grad_g_full(gpak_ctx *ctx, double *G, long ldg);
 
 // ---- cv_groups.hip ----------------------------------------------------------------------

@@ -168,15 +168,6 @@ __global__ __launch_bounds__(1024) void gpak_lpdhyp_f64(int N, const double *__r
   if (threadIdx.x == 0) out[0] = sh[0];
 }
 
-void gpak_grad_release(gpak_ctx *ctx) {
-  if (ctx->dG) hipFree(ctx->dG);
-  if (ctx->dBinv) hipFree(ctx->dBinv);
-  if (ctx->dGpart) hipFree(ctx->dGpart);
-  if (ctx->dLoo) hipFree(ctx->dLoo);
-  ctx->dG = ctx->dBinv = ctx->dGpart = ctx->dLoo = nullptr;
-  ctx->gpart_elems = ctx->loo_elems = 0;
-}
-
 // Rot (Kernel.cpp:1399-1410) and, when D is given, its true derivatives D[a] = dRot / d angle_a,
 // a = 0..2 = AngleX, AngleY, AngleZ
 void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]) {
@@ -250,13 +241,11 @@ static int grad_binv(gpak_ctx *ctx) {
   hipStream_t st = ctx->stream;
   const int Np = ctx->Np;
   const long ld = ctx->ld;
-  if (!ctx->dG) {
-    if (hipMalloc(&ctx->dG, sizeof(double) * (size_t)ld * Np) != hipSuccess ||
-        hipMalloc(&ctx->dBinv, sizeof(double) * (size_t)ld * Np) != hipSuccess) {
-      ctx->err = "device allocation failed for the gradient workspaces (2 N x N matrices)";
-      gpak_grad_release(ctx);
-      return GPAK_ENOMEM;
-    }
+  if (!ctx->dG.reserve((size_t)ld * Np) || !ctx->dBinv.reserve((size_t)ld * Np)) {
+    ctx->err = "device allocation failed for the gradient workspaces (2 N x N matrices)";
+    ctx->dG.release(); ctx->dBinv.release();   // never one without the other: dG != NULL says that both exist
+    ctx->dGpart.release(); ctx->dLoo.release();
+    return GPAK_ENOMEM;
   }
   GPAK_HIP(hipEventRecord(ctx->ev[7], st));
   // 1. G = L^-T: block columns of 512 of the factor in dM, their inverted diagonal blocks in dInv
@@ -273,20 +262,20 @@ static int grad_binv(gpak_ctx *ctx) {
 
 // per-workgroup partial sums of a pair pass: at least `elems` doubles in ctx->dGpart
 static int grad_partials(gpak_ctx *ctx, size_t elems) {
-  if (ctx->gpart_elems >= elems) return GPAK_OK;
-  if (ctx->dGpart) hipFree(ctx->dGpart);
-  ctx->dGpart = nullptr; ctx->gpart_elems = 0;
-  if (hipMalloc(&ctx->dGpart, sizeof(double) * elems) != hipSuccess) {
-    ctx->err = "device allocation failed for gradient partial sums";
-    return GPAK_ENOMEM;
-  }
-  ctx->gpart_elems = elems;
-  return GPAK_OK;
+  if (ctx->dGpart.reserve(elems)) return GPAK_OK;
+  ctx->err = "device allocation failed for gradient partial sums";
+  return GPAK_ENOMEM;
 }
 
 // what gpak_cv_groups (cv_groups.hip) shares with the passes of this file: the scratch buffer, and G = L^-T of the
 // context's factor as ONE Np x Np matrix (P = 1) in a buffer of the caller's
 int gpak_grad_scratch(gpak_ctx *ctx, size_t elems) { return grad_partials(ctx, elems); }
+// the L^-T workspace of gpak_loo (a slab) and gpak_cv_groups (the whole matrix) when the gradient has not allocated dG
+bool gpak_loo_workspace(gpak_ctx *ctx, size_t elems) {
+  if (ctx->dLoo.reserve(elems)) return true;
+  (void)hipGetLastError();
+  return false;
+}
 
 void gpak_grad_g_full(gpak_ctx *ctx, double *G, long ldg) {
   const int GNB = 512;
@@ -803,12 +792,7 @@ int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *su
     for (;;) {
       P = (T + rt - 1) / rt;
       lds = (long)my_tiles(Np, P, 0) * PB + pad;
-      const size_t need = (size_t)lds * Np;
-      if (ctx->loo_elems >= need) break;
-      if (ctx->dLoo) hipFree(ctx->dLoo);
-      ctx->dLoo = nullptr; ctx->loo_elems = 0;
-      if (hipMalloc(&ctx->dLoo, sizeof(double) * need) == hipSuccess) { ctx->loo_elems = need; break; }
-      (void)hipGetLastError();
+      if (gpak_loo_workspace(ctx, (size_t)lds * Np)) break;
       if (rt == 1) {
         ctx->err = "device allocation failed for the leave-one-out workspace (128 rows of L^-T do not fit)";
         return GPAK_ENOMEM;

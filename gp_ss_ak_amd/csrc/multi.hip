@@ -13,17 +13,13 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <limits>
 #include <mutex>
 #include <set>
 #include <thread>
 
-#include "../../include/gpak_dist.h"
-#include "gpak_internal.h"
+#include "multi.h"
 
-int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, double *var, const double *pool_sum,
-                      long pool_M);
 // dist.hip (not part of the C-ABI): all communicators of one process made by ONE ncclCommInitAll call
 extern "C" int gpak_dist_rccl_init_all(int n, const int *devices, void **comms, std::string &err);
 extern "C" void gpak_dist_rccl_destroy(void *comm);
@@ -493,7 +489,6 @@ int gpak_multi_grad(gpak_multi *g, double *grad10) {
 
 // GradLL of any composition on a group: ExpAns(+Bias) is distributed (gpak_multi_grad); other compositions take the
 // children's getGradients on device 0 from the DISTRIBUTED factor (imported into the replica, nothing is factored again)
-int gpak_multi_on_replica0(gpak_multi *g, const std::function<int(gpak_ctx *)> &f, bool wants_factor);
 int gpak_multi_grad_hyb(gpak_multi *g, double *grad, int ng) {
   if (!g->general_kernel) {
     if (ng != 10) { g->err = "the ExpAns(+Bias) composition has 10 gradient entries"; return GPAK_EINVAL; }

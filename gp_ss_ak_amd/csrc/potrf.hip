@@ -607,12 +607,9 @@ int gpak_potrf_blocked(gpak_ctx *ctx) {
   // the whole factorisation (one command; a memset in front of every bulk launch would cost a hand-off each)
   const bool tickets = sc.bulk_tickets;
   if (tickets) {
-    if (ctx->tickets_cap < nJ) {
-      if (ctx->dTickets) GPAK_HIP(hipFree(ctx->dTickets));
-      ctx->dTickets = nullptr;
-      ctx->tickets_cap = 0;
-      GPAK_HIP(hipMalloc(&ctx->dTickets, sizeof(unsigned long long) * 8 * (size_t)nJ));
-      ctx->tickets_cap = nJ;
+    if (!ctx->dTickets.reserve(8 * (size_t)nJ)) {
+      ctx->err = std::string("hipMalloc(&ctx->dTickets, sizeof(unsigned long long) * 8 * (size_t)nJ): ") + hipGetErrorString(hipGetLastError());
+      return GPAK_EHIP;
     }
     GPAK_HIP(hipMemsetAsync(ctx->dTickets, 0, sizeof(unsigned long long) * 8 * (size_t)nJ, su));
   }
@@ -732,9 +729,8 @@ int gpak_potrf_blocked(gpak_ctx *ctx) {
   }
   if (info != init) {
     // padded columns (>= N) are identity and cannot fail
-    ctx->failed_col = info;
+    ctx->state.factorisation_failed(info);
     return GPAK_ENOTPD;
   }
-  ctx->failed_col = 0;
-  return GPAK_OK;
+  return GPAK_OK;   // the caller tells ctx->state under which options (ensure_factor, api.hip)
 }

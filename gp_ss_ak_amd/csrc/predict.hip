@@ -46,43 +46,11 @@ __global__ __launch_bounds__(256) void gpak_rowdot_part_f64(const double *__rest
   part[(size_t)blockIdx.y * part_ld + t] = s;
 }
 
-void gpak_predict_release(gpak_ctx *ctx) {
-  if (ctx->dXblk) hipFree(ctx->dXblk);
-  if (ctx->dTblk) hipFree(ctx->dTblk);
-  ctx->dXblk = ctx->dTblk = nullptr;
-  ctx->blk_points = 0;
-  if (ctx->dC) hipFree(ctx->dC);
-  if (ctx->dCinv) hipFree(ctx->dCinv);
-  if (ctx->dCinfo) hipFree(ctx->dCinfo);
-  if (ctx->dXi) hipFree(ctx->dXi);
-  if (ctx->dZ) hipFree(ctx->dZ);
-  ctx->dC = ctx->dCinv = ctx->dXi = ctx->dZ = nullptr;
-  ctx->dCinfo = nullptr;
-  ctx->joint_cap = 0; ctx->joint_elems = 0; ctx->joint_s = 0;
-  if (ctx->Upred.base) hipFree(ctx->Upred.base);
-  if (ctx->Tq.base) hipFree(ctx->Tq.base);
-  ctx->Upred = DevPoints(); ctx->Tq = DevPoints();
-  if (ctx->dXte) hipFree(ctx->dXte);
-  if (ctx->dWt) hipFree(ctx->dWt);
-  if (ctx->dPv) hipFree(ctx->dPv);
-  if (ctx->dPart) hipFree(ctx->dPart);
-  if (ctx->dLf) hipFree(ctx->dLf);
-  if (ctx->dInvf) hipFree(ctx->dInvf);
-  ctx->dLf = ctx->dInvf = nullptr;
-  ctx->lf_ok = false;
-  ctx->dXte = ctx->dWt = ctx->dPv = ctx->dPart = nullptr;
-  ctx->pred_cap = 0; ctx->wt_elems = 0;
-}
-
 static int ensure_predict_bufs(gpak_ctx *ctx, int cap, bool want_var) {
   if (ctx->pred_cap < cap) {
-    if (ctx->dXte) hipFree(ctx->dXte);
-    if (ctx->dPv) hipFree(ctx->dPv);
-    if (ctx->dPart) hipFree(ctx->dPart);
-    ctx->dXte = ctx->dPv = ctx->dPart = nullptr;
-    if (hipMalloc(&ctx->dXte, sizeof(double) * 4 * (size_t)cap) != hipSuccess ||
-        hipMalloc(&ctx->dPv, sizeof(double) * 2 * (size_t)cap) != hipSuccess ||
-        hipMalloc(&ctx->dPart, sizeof(double) * 64 * (size_t)cap) != hipSuccess) {
+    ctx->pred_cap = 0;
+    ctx->dXte.release(); ctx->dPv.release(); ctx->dPart.release();   // all three go before the first comes back
+    if (!ctx->dXte.reserve(4 * (size_t)cap) || !ctx->dPv.reserve(2 * (size_t)cap) || !ctx->dPart.reserve(64 * (size_t)cap)) {
       ctx->err = "device allocation failed for prediction buffers";
       return GPAK_ENOMEM;
     }
@@ -94,15 +62,24 @@ static int ensure_predict_bufs(gpak_ctx *ctx, int cap, bool want_var) {
   if (rc) return rc;
   // (pred_cap + skew) x Np: the batch is stored with a skewed leading dimension (gpak_predict_impl)
   size_t need = want_var ? ((size_t)ctx->pred_cap + 64 * (size_t)std::max(0, ctx->sched.pred_ld_skew)) * ctx->Np : 0;
-  if (need > ctx->wt_elems) {
-    if (ctx->dWt) hipFree(ctx->dWt);
-    ctx->dWt = nullptr; ctx->wt_elems = 0;
-    if (hipMalloc(&ctx->dWt, sizeof(double) * need) != hipSuccess) {
-      ctx->err = "device allocation failed for the cross-kernel batch";
-      return GPAK_ENOMEM;
-    }
-    ctx->wt_elems = need;
+  if (!ctx->dWt.reserve(need)) {
+    ctx->err = "device allocation failed for the cross-kernel batch";
+    return GPAK_ENOMEM;
   }
+  return GPAK_OK;
+}
+
+// the raw (4 columns) and the transformed coordinates of `points` discretisation points under nterms terms (the block and
+// the joint calls)
+static int ensure_block_points(gpak_ctx *ctx, size_t points, int nterms) {
+  if (ctx->blk_points >= points && ctx->blk_terms >= nterms) return GPAK_OK;
+  ctx->blk_points = 0;
+  ctx->dXblk.release(); ctx->dTblk.release();
+  if (!ctx->dXblk.reserve(4 * points) || !ctx->dTblk.reserve(GPAK_PT * nterms * points)) {
+    ctx->err = "device allocation failed for the blocks' discretisation points";
+    return GPAK_ENOMEM;
+  }
+  ctx->blk_points = points; ctx->blk_terms = nterms;
   return GPAK_OK;
 }
 
@@ -142,21 +119,19 @@ static void forward_subst_batch(gpak_ctx *ctx, double *Wt, long ldw, int mbp) {
 
 // fp32 images of the factor for a GPAK_F32 context (rebuilt when the factor changes)
 static int ensure_f32_factor(gpak_ctx *ctx) {
-  if (ctx->lf_ok) return GPAK_OK;
+  if (ctx->state.image) return GPAK_OK;
   const int Np = ctx->Np, T = Np / PB;
   // k-columns 128 KiB apart (Np = 32768 floats) would all fall on the same L2 channel / HBM bank group: skew the
   // leading dimension by 256 B like the fp64 matrix (gpak_set_train)
   ctx->ldLf = Np + 64L * std::max(0, ctx->sched.pred_ld_skew);
-  if (!ctx->dLf) {
-    if (hipMalloc(&ctx->dLf, sizeof(float) * (size_t)ctx->ldLf * Np) != hipSuccess ||
-        hipMalloc(&ctx->dInvf, sizeof(float) * (size_t)T * 2 * PB * PB) != hipSuccess) {
-      ctx->err = "device allocation failed for the fp32 factor image";
-      return GPAK_ENOMEM;
-    }
+  // allocated once per training set (release_train, api.hip)
+  if (!ctx->dLf.reserve((size_t)ctx->ldLf * Np) || !ctx->dInvf.reserve((size_t)T * 2 * PB * PB)) {
+    ctx->err = "device allocation failed for the fp32 factor image";
+    return GPAK_ENOMEM;
   }
   gpak_launch_lower_to_f32(ctx->stream, ctx->dM, ctx->ld, Np, ctx->dLf, ctx->ldLf);
   gpak_launch_vec_to_f32(ctx->stream, ctx->dInv, (size_t)T * 2 * PB * PB, ctx->dInvf);
-  ctx->lf_ok = true;
+  ctx->state.image_built();
   return GPAK_OK;
 }
 
@@ -254,7 +229,7 @@ int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, do
       if (f32) {
         // fp32 arithmetic for the M-proportional work (cross-kernel, substitution, row sums);
         // the cross-kernel uses the direct distance form (cancellation form is meaningless in fp32)
-        float *Wf = reinterpret_cast<float *>(ctx->dWt);
+        float *Wf = reinterpret_cast<float *>(ctx->dWt.p);
         gpak_launch_fill_f32(st, ctx->Tq, ctx->Upred, mbp, Np, kp, Wf, ldw);
         forward_subst_batch_f32(ctx, Wf, ldw, mbp);
         gpak_launch_rowsumsq_f32(st, Wf, ldw, mbp, Np, vs, ctx->dPart, cap);
@@ -305,18 +280,7 @@ int gpak_predict_block_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, dou
   if ((size_t)cap * nd > ((size_t)1 << 30)) { ctx->err = "too many discretisation points per block"; return GPAK_EINVAL; }
   int rc = ensure_predict_bufs(ctx, cap, true);
   if (rc) return rc;
-  const size_t points = (size_t)cap * nd;
-  if (ctx->blk_points < points || ctx->blk_terms < kp.nterms) {
-    if (ctx->dXblk) hipFree(ctx->dXblk);
-    if (ctx->dTblk) hipFree(ctx->dTblk);
-    ctx->dXblk = ctx->dTblk = nullptr; ctx->blk_points = 0;
-    if (hipMalloc(&ctx->dXblk, sizeof(double) * 4 * points) != hipSuccess ||
-        hipMalloc(&ctx->dTblk, sizeof(double) * GPAK_PT * kp.nterms * points) != hipSuccess) {
-      ctx->err = "device allocation failed for the blocks' discretisation points";
-      return GPAK_ENOMEM;
-    }
-    ctx->blk_points = points; ctx->blk_terms = kp.nterms;
-  }
+  if ((rc = ensure_block_points(ctx, (size_t)cap * nd, kp.nterms))) return rc;
   hipEvent_t e0 = ctx->ev[5], e1 = ctx->ev[6];
   GPAK_HIP(hipEventRecord(e0, st));
 
@@ -435,41 +399,23 @@ int gpak_joint_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mea
   const bool want_c = sample || cov_host;
   int rc = ensure_predict_bufs(ctx, cap, true);
   if (rc) return rc;
-  const size_t points = (size_t)cap * nd;
-  if (ctx->blk_points < points || ctx->blk_terms < kp.nterms) {
-    if (ctx->dXblk) hipFree(ctx->dXblk);
-    if (ctx->dTblk) hipFree(ctx->dTblk);
-    ctx->dXblk = ctx->dTblk = nullptr; ctx->blk_points = 0;
-    if (hipMalloc(&ctx->dXblk, sizeof(double) * 4 * points) != hipSuccess ||
-        hipMalloc(&ctx->dTblk, sizeof(double) * GPAK_PT * kp.nterms * points) != hipSuccess) {
-      ctx->err = "device allocation failed for the blocks' discretisation points";
-      return GPAK_ENOMEM;
-    }
-    ctx->blk_points = points; ctx->blk_terms = kp.nterms;
-  }
+  if ((rc = ensure_block_points(ctx, (size_t)cap * nd, kp.nterms))) return rc;
   const long ldw = cap + 32L * std::max(0, ctx->sched.pred_ld_skew), ldc = ldw;   // the same 256-byte skew
-  if (want_c && (ctx->joint_cap < cap || ctx->joint_elems < (size_t)ldc * cap)) {
-    if (ctx->dC) hipFree(ctx->dC);
-    if (ctx->dCinv) hipFree(ctx->dCinv);
-    ctx->dC = ctx->dCinv = nullptr; ctx->joint_cap = 0; ctx->joint_elems = 0;
-    if (!ctx->dCinfo && hipMalloc(&ctx->dCinfo, sizeof(int) * 4) != hipSuccess) ctx->dCinfo = nullptr;
-    if (!ctx->dCinfo || hipMalloc(&ctx->dC, sizeof(double) * (size_t)ldc * cap) != hipSuccess ||
-        hipMalloc(&ctx->dCinv, sizeof(double) * (size_t)(cap / PB) * 2 * PB * PB) != hipSuccess) {
+  if (want_c && (ctx->joint_cap < cap || ctx->dC.n < (size_t)ldc * cap)) {
+    ctx->joint_cap = 0;
+    ctx->dC.release(); ctx->dCinv.release();
+    if (!ctx->dCinfo.reserve(4) || !ctx->dC.reserve((size_t)ldc * cap) || !ctx->dCinv.reserve((size_t)(cap / PB) * 2 * PB * PB)) {
       ctx->err = "device allocation failed for the joint covariance of the blocks";
       return GPAK_ENOMEM;
     }
-    ctx->joint_cap = cap; ctx->joint_elems = (size_t)ldc * cap;
+    ctx->joint_cap = cap;
   }
-  if (sample && ctx->joint_s < (size_t)M * S) {
-    if (ctx->dXi) hipFree(ctx->dXi);
-    if (ctx->dZ) hipFree(ctx->dZ);
-    ctx->dXi = ctx->dZ = nullptr; ctx->joint_s = 0;
-    if (hipMalloc(&ctx->dXi, sizeof(double) * (size_t)M * S) != hipSuccess ||
-        hipMalloc(&ctx->dZ, sizeof(double) * (size_t)M * S) != hipSuccess) {
+  if (sample && ctx->dZ.n < (size_t)M * S) {   // dZ comes last: where it stands, dXi does
+    ctx->dXi.release(); ctx->dZ.release();
+    if (!ctx->dXi.reserve((size_t)M * S) || !ctx->dZ.reserve((size_t)M * S)) {
       ctx->err = "device allocation failed for the normals and the realisations";
       return GPAK_ENOMEM;
     }
-    ctx->joint_s = (size_t)M * S;
   }
   hipEvent_t e0 = ctx->ev[5], e1 = ctx->ev[6];
   GPAK_HIP(hipEventRecord(e0, st));
@@ -551,7 +497,7 @@ int gpak_solve_chol_impl(gpak_ctx *ctx, double *X_host, int k) {
   hipStream_t st = ctx->stream;
   const int N = ctx->N, Np = ctx->Np;
   double *w0 = ctx->dWork, *w1 = ctx->dWork + Np, *w2 = ctx->dWork + 2 * (size_t)Np;
-  ctx->z_ok = false;
+  ctx->state.work_vectors_overwritten();
   for (int c = 0; c < k; c++) {
     GPAK_HIP(hipMemsetAsync(w0, 0, sizeof(double) * Np, st));
     GPAK_HIP(hipMemcpyAsync(w0, X_host + (size_t)c * N, sizeof(double) * N, hipMemcpyHostToDevice, st));

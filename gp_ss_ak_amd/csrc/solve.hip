@@ -453,21 +453,21 @@ void gpak_launch_trsv_bwd3(hipStream_t st, int Np, const double *L, long ld, con
   }
 }
 
-// The back substitution of a context: whichever of the above its current factor supports (gpak_ctx::backsolve)
+// The back substitution of a context: whichever of the above its current factor supports (CtxState::backsolve)
 void gpak_backsolve(gpak_ctx *ctx, hipStream_t st, const double *z, double *out, double *scratch) {
   const int Np = ctx->Np, bw = ctx->bwd_bw;
   const size_t blk = (size_t)bw * bw;
-  switch (ctx->backsolve) {
-    case gpak_ctx::BS_RT:
+  switch (ctx->state.backsolve) {
+    case CtxState::BS_RT:
       gpak_launch_trsv_bwd3(st, Np, ctx->dM, ctx->ld, z, out, scratch, ctx->dT512, 2 * blk, 2 * bw, true, bw);
       break;
-    case gpak_ctx::BS_INV_FAR:
+    case CtxState::BS_INV_FAR:
       gpak_launch_trsv_bwd3(st, Np, ctx->dM, ctx->ld, z, out, scratch, ctx->dInv512, blk, bw, false, bw);
       break;
-    case gpak_ctx::BS_INV_STEP:
+    case CtxState::BS_INV_STEP:
       gpak_launch_trsv_bwd2(st, Np, ctx->dM, ctx->ld, ctx->dInv, z, out, scratch, ctx->dInv512, bw);
       break;
-    case gpak_ctx::BS_BLOCKS128:
+    case CtxState::BS_BLOCKS128:
       gpak_launch_trsv_bwd2(st, Np, ctx->dM, ctx->ld, ctx->dInv, z, out, scratch, nullptr, bw);
       break;
   }

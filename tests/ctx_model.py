@@ -6,11 +6,12 @@ single features to (the CPU checker in oracle/, exact_grad_ref, loo_ref, block_r
 (training set, kernel, operation), so a long sequence costs each distinct state once.  It restates the statuses the header
 promises (GPAK_ESTATE before a training set or parameters, GPAK_ENOTIMPL, GPAK_EINVAL, GPAK_ENOTPD with quiet NaN).
 
-CachingModel is the opposite: a Python restatement of the VALIDITY LOGIC of csrc/api.hip -- which call marks what as
-built, which call drops it -- that answers every question from the state its flags point at.  Unmutated it equals
-ModelGpak step for step.  Each name in MUTATIONS drops one invalidation; tests/test_ctx_sequences.py proves on the CPU
-that every one of them is caught by a named sequence, i.e. that the sequences would notice the corresponding slip in
-api.hip.
+CachingModel is the opposite: a Python restatement of the VALIDITY LOGIC of a context -- CtxState (csrc/ctx_state.h) and
+the calls of csrc/api.hip that raise its events: which call builds what, which call drops it -- that answers every
+question from the state its flags point at.  Unmutated it equals ModelGpak step for step.  Each name in MUTATIONS drops
+one invalidation; tests/test_ctx_sequences.py proves on the CPU that every one of them is caught by a named sequence, i.e.
+that the sequences would notice the corresponding slip.  It logs the events it passes through under the names of
+CtxState's members: tests/test_ctx_state.py replays them through the C++ struct itself and compares the two, flag by flag.
 
 GroupCaching does the same for a group (gpak_create_multi): the flags of csrc/multi.hip, RankCore::have_result of
 csrc/dist.hip and the replica contexts' flags, with GROUP_MUTATIONS; it also counts the evaluations gpak_timing reports.
@@ -32,6 +33,7 @@ OK, ENOTPD, EINVAL, ESTATE, ENOMEM, ENOTIMPL = 0, 1, 2, 3, 4, 5
 F64, F32 = 0, 1
 DIST_EXPANSION, DIST_DIRECT = 0, 1
 OPT_MEMOISE, OPT_NB_OUTER, OPT_NB_WIDE, OPT_POTRF_CO, OPT_TAIL_MAX_NP, OPT_BWD_FUSED, OPT_LOO_ROWS = 1, 2, 5, 10, 13, 12, 14
+OPT_INV512 = 9
 NPARS = {xref.EXPANS: 8, xref.EXP: 2, xref.RBF: 3}
 SIGMA_AT = {xref.EXPANS: 6, xref.EXP: 1, xref.RBF: 2}
 
@@ -346,10 +348,12 @@ def _spoil(out):
 
 
 class CachingModel(ModelGpak):
-    """The flags of gpak_ctx (csrc/gpak_internal.h) as csrc/api.hip sets and clears them.  A `snapshot` names the state
-    (training set, kernel) a cached quantity was built from: uS the transformed points U, fS the factor in dM, aS alpha,
-    nS the nlZ terms, lfS the fp32 image of the factor.  Answers come from ModelGpak AT that snapshot; `taint` holds the
-    buffers whose contents are not what their flag says."""
+    """The facts of CtxState (csrc/ctx_state.h) as its events change them, and the calls of csrc/api.hip as they raise the
+    events.  The ladder: the transformed points U, the factor in dM, alpha, the nlZ terms; off the factor hang z (L^-1 y/sn2
+    sits in dWork), the back substitution it supports and the fp32 image.  Where the struct keeps a flag the model keeps a
+    `snapshot`, the state (training set, kernel) the quantity was built from: uS, fS, aS, nS, lfS.  Answers come from
+    ModelGpak AT that snapshot; `taint` holds the buffers whose contents are not what their flag says.  `events` lists
+    every event passed through, as the line tests/ctx_state_driver.cpp reads; flags() is what the driver prints."""
 
     def __init__(self, precision=F64, cache=None, mut=()):
         super().__init__(precision, cache)
@@ -360,6 +364,8 @@ class CachingModel(ModelGpak):
         self.uS = self.fS = self.aS = self.nS = self.lfS = None
         self.bufA = self.bufN = None          # what dAlpha / the nlZ terms physically hold
         self.z_ok = self.z_clobbered = False
+        self.backsolve = 0                    # CtxState::Backsolve of the current factor
+        self.events = []
         self.taint = set()
         self.failed_col = 0
         self.failS = None
@@ -388,23 +394,44 @@ class CachingModel(ModelGpak):
         return m
 
     def _invalidate(self):
+        """CtxState::drop_factor: the rungs from the factor up and the factor's side facts"""
         self.fS = self.aS = self.nS = None
+        self._drop_side_facts()
+
+    def _drop_side_facts(self):
+        self.z_ok = self.z_clobbered = False
+        self.backsolve = 0
+        if "f32 image kept" in self.mut and self.lfS is not None:
+            self.dropped.append(("f32 image kept", self.lfS))
+        else:
+            self.lfS = None
+
+    def flags(self):
+        """(points, rung, z, backsolve, image, failed_col, factorisations) as tests/ctx_state_driver.cpp prints them.  A
+        fact is held when its flag is up AND the buffer holds what the flag says: a mutation that writes into a buffer
+        behind its flag's back (`predict leaks pooled mean`) shows here as the fact lost."""
+        rung = 3 if self.nS is not None else 2 if self.aS is not None else 1 if self.fS is not None else 0
+        return (int(self.uS is not None and "U" not in self.taint), rung, int(self.z_ok), self.backsolve,
+                int(self.lfS is not None), self.failed_col, self.evals)
 
     # -- state --------------------------------------------------------------------------------------------------
     def set_option(self, opt, value):
         super().set_option(opt, value)
         if opt == OPT_MEMOISE:
             self.memoise = int(value) != 0
+            self.events.append(f"set_memoise {int(self.memoise)}")
 
     def set_train(self, X, y):
         super().set_train(X, y)
-        self.fS = self.lfS = self.uS = None               # release_train
-        if "set_train keeps alpha" in self.mut and self.aS is not None:
-            self.dropped.append(("set_train keeps alpha", self.aS))
-        else:
-            self.aS = self.nS = None
+        kept = (self.aS, self.nS)
+        self.uS = self.lfS = None                         # release_train frees both; new_training_set:
+        self._invalidate()
+        if "set_train keeps alpha" in self.mut and kept[0] is not None:
+            self.dropped.append(("set_train keeps alpha", kept[0]))
+            self.aS, self.nS = kept
         self.evals = 0
         self.taint.discard("U")
+        self.events.append("new_training_set")
 
     def set_params(self, expans, bias, sn2, dist_mode=DIST_DIRECT):
         e = tuple(float(v) for v in expans)
@@ -420,6 +447,7 @@ class CachingModel(ModelGpak):
         if not (same and self.memoise):
             self._invalidate()
             self.uS = None
+        self.events.append("same_kernel" if same and self.memoise else "new_kernel")
 
     def set_kernel(self, terms, bias, white, sn2, dist_mode=DIST_DIRECT):
         super().set_kernel(terms, bias, white, sn2, dist_mode)
@@ -434,6 +462,7 @@ class CachingModel(ModelGpak):
             self.dropped.append(("set_kernel keeps U", self.uS))
         else:
             self.uS = None
+        self.events.append("new_kernel")
 
     # -- the ensure_* chain of api.hip -----------------------------------------------------------------------------
     def _ensure_U(self):
@@ -442,14 +471,8 @@ class CachingModel(ModelGpak):
         if self.uS is None or self.uS[0] != self.tkey:          # U.n == N
             self.uS = self._cur()
             self.taint.discard("U")
+            self.events.append("points_built")
         return OK
-
-    def _factor_changed(self):
-        self.z_ok = self.z_clobbered = False
-        if "f32 image kept" in self.mut and self.lfS is not None:
-            self.dropped.append(("f32 image kept", self.lfS))
-        else:
-            self.lfS = None
 
     def _ensure_factor(self):
         if self.fS is not None:
@@ -457,13 +480,17 @@ class CachingModel(ModelGpak):
         rc = self._ensure_U()
         if rc:
             return rc
-        self._factor_changed()
+        # factorisation_started.  The rungs are down already (no factor: nothing above it) and are left alone here, so that
+        # a mutation that kept one of them up is still seen by what comes next, as it was when each fact was a flag of its own
+        self._drop_side_facts()
         self.evals += 1
+        self.events.append("factorisation_started")
         col = self._at(self.uS)._fit()["col"]
         self.taint.discard("factor")
         if col:
             self.failed_col = col
             self.failS = self.uS
+            self.events.append(f"factorisation_failed {col}")
             return ENOTPD
         if "recovery keeps failed_column" in self.mut and self.failed_col:
             self.dropped.append(("recovery keeps failed_column", self.failed_col))
@@ -473,6 +500,10 @@ class CachingModel(ModelGpak):
         if "U" in self.taint:
             self.taint.add("factor")
         self.z_ok = True                                  # the forward substitution of y / sn2 rides along
+        # how the factor is substituted backwards is settled by the options it was built under (factorisation_succeeded)
+        inv512, fused = self.opts.get(OPT_INV512, 1) != 0, self.opts.get(OPT_BWD_FUSED, 2)
+        self.backsolve = 0 if not inv512 else {2: 3, 1: 2}.get(fused, 1)
+        self.events.append(f"factorisation_succeeded 1 {int(inv512)} {fused}")
         return OK
 
     def _ensure_alpha(self):
@@ -490,6 +521,7 @@ class CachingModel(ModelGpak):
             self.taint.add("alpha")
         self.z_ok = self.z_clobbered = False              # the back substitution consumes L^-1 y / sn2
         self.aS = self.bufA = self.fS
+        self.events += ["work_vectors_overwritten", "alpha_built"]
         return OK
 
     def _ensure_nlz(self):
@@ -498,6 +530,7 @@ class CachingModel(ModelGpak):
             return rc
         if self.nS is None:
             self.nS = self.bufN = self.aS
+            self.events.append("nlz_built")
             self.taint.discard("nlz")
             if "alpha" in self.taint:
                 self.taint.add("nlz")
@@ -525,6 +558,7 @@ class CachingModel(ModelGpak):
             else:
                 self._ensure_U()
                 self._invalidate()
+                self.events.append("matrix_overwritten")
         return self._answer("gram", "U", ("uS",), ("U",), want_d2)
 
     def factor(self):
@@ -550,6 +584,7 @@ class CachingModel(ModelGpak):
                 self.z_clobbered = True
             else:
                 self.z_ok = False
+                self.events.append("work_vectors_overwritten")
         return out
 
     def logLikelihood(self):
@@ -566,6 +601,7 @@ class CachingModel(ModelGpak):
             if self.precision == F32 and want_var:
                 if self.lfS is None:
                     self.lfS = self.fS
+                    self.events.append("image_built")
                 snaps.append("lfS")
             if self.kern["mode"] == DIST_EXPANSION and "predict leaks pooled mean" in self.mut and self.uS is not None:
                 self.dropped.append(("predict leaks pooled mean", self.uS))

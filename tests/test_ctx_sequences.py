@@ -35,9 +35,10 @@ SEPARATION = 1000.0
 # the error text before a context exists
 EXCLUDED = {"gpak_calibrate", "gpak_reload_tuning", "gpak_global_error"}
 # Steps held to the model alone, (sequence, step) -> why their bits legitimately depend on earlier calls.
-# How a context substitutes backwards is settled when it FACTORS (api.hip ensure_factor: the explicit 512-block inverses and
-# the [R ; T] stacks are built beside the factorisation's forward substitution only), so GPAK_OPT_INV512 / GPAK_OPT_BWD_FUSED
-# changed afterwards take effect at the next factorisation.  Until then the long-lived context keeps the back substitution
+# How a context substitutes backwards is settled when it FACTORS (CtxState::factorisation_succeeded, csrc/ctx_state.h, takes
+# the options the factor was built under: the explicit 512-block inverses and the [R ; T] stacks are built beside the
+# factorisation's forward substitution only), so GPAK_OPT_INV512 / GPAK_OPT_BWD_FUSED changed afterwards take effect at the
+# next factorisation.  Until then the long-lived context keeps the back substitution
 # of the options it factored under while a fresh context, given the current options, uses another: the same alpha and
 # solve_chol in another summation order (measured: they differ in the last bits, and are equal again after gpak_set_params).
 _BACKSOLVE = "options of the back substitution changed since the factorisation"
