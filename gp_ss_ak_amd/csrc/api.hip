@@ -472,7 +472,8 @@ static int ensure_factor(gpak_ctx *ctx) {
   ctx->times.accumulated_ms[0] += ctx->times.gram_ms;
   ctx->times.accumulated_ms[1] += ctx->times.factor_ms;
   ctx->times.gram_bytes = 8.0 * ((double)ctx->Np * (ctx->Np + GPAK_TILE) / 2.0);
-  if (rc == GPAK_ENOTPD) ctx->err = "B = I + K/sn2 is not positive definite";   // gpak_potrf_blocked has told ctx->state
+  if (rc == GPAK_ENOTPD)   // gpak_potrf_blocked has told ctx->state
+    ctx->err = "B = I + K/sn2 is not positive definite at column " + std::to_string(ctx->state.failed_col);
   if (rc) return rc;
   // how a context substitutes backwards is settled here, by the options it factored under
   ctx->state.factorisation_succeeded(ctx->sched.fwd_in_factor, ctx->sched.inv512, ctx->sched.bwd_fused);

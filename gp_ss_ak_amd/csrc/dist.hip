@@ -413,7 +413,7 @@ int core_step_factored(RankCore *h, int failed_col) {
   h->failed_col = failed_col;
   h->tp[2] = h->time_event(h->s_bulk);
   if (failed_col) {
-    h->err = "B = I + K/sn2 is not positive definite";
+    h->err = "B = I + K/sn2 is not positive definite at column " + std::to_string(failed_col);
     RCHK(h->E.stream_sync(h->E.self, h->s_bulk));
     return GPAK_ENOTPD;   // Chol_fail -> quiet NaN (GP_Utils.cpp:1145-1158)
   }

@@ -391,5 +391,6 @@ int gpak_grid_get_alpha(gpak_grid *h, double *alpha_host) {
 }
 
 int gpak_grid_get_stats(gpak_grid *h, gpak_dist_stats *out) { return core_get_stats(h, out); }
+int gpak_grid_failed_column(const gpak_grid *h) { return h ? h->failed_col : 0; }
 
 }  // extern "C"

@@ -104,6 +104,7 @@ DIST_SYMBOLS = ["gpak_dist_create", "gpak_dist_destroy", "gpak_dist_last_error",
                 "gpak_dist_failed_column", "gpak_group_rank_stats", "gpak_create_multi_with_engines",
                 "gpak_grid_create", "gpak_grid_destroy", "gpak_grid_last_error", "gpak_grid_init_rccl", "gpak_grid_set_train",
                 "gpak_grid_set_params", "gpak_grid_nlz", "gpak_grid_nlz_terms", "gpak_grid_get_alpha", "gpak_grid_get_stats",
+                "gpak_grid_failed_column",
                 "gpak_dev_vec_scale", "gpak_dev_vec_sum"]
 
 
@@ -143,6 +144,7 @@ def _load():
     lib.gpak_grid_nlz_terms.argtypes = [_vp, _dp, _dp, _dp]
     lib.gpak_grid_get_alpha.argtypes = [_vp, _dp]
     lib.gpak_grid_get_stats.argtypes = [_vp, C.POINTER(Stats)]
+    lib.gpak_grid_failed_column.argtypes = [_vp]
     return lib
 
 
@@ -306,6 +308,10 @@ class DistRank:
         self._check(self._lib.gpak_dist_get_alpha(self._h, a.ctypes.data_as(_dp)))
         return a
 
+    def failed_column(self):
+        """Failing column (1-based, the same on every rank) of the last nlz() that was NaN, 0 if it succeeded."""
+        return int(self._lib.gpak_dist_failed_column(self._h))
+
     def stats(self):
         s = Stats()
         self._check(self._lib.gpak_dist_get_stats(self._h, C.byref(s)))
@@ -371,6 +377,10 @@ class GridRank:
         a = np.zeros(self.N)
         self._check(self._lib.gpak_grid_get_alpha(self._h, a.ctypes.data_as(_dp)))
         return a
+
+    def failed_column(self):
+        """As DistRank.failed_column: the shared core's value, min-reduced over the grid."""
+        return int(self._lib.gpak_grid_failed_column(self._h))
 
     def stats(self):
         s = Stats()

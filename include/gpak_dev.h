@@ -20,7 +20,8 @@
  * 16-byte accesses need an even one) and write nothing then; the others trust the caller.  A call with nothing to do (no rows, no columns) writes nothing.  A call
  * writes only the elements named in its description: never the rows between Np (or nrows) and the leading dimension,
  * never a 128 x 128 tile above the diagonal where "lower tiles" is said.  tests/test_dev_ops.py holds the entry points
- * to that one at a time, except gpak_dev_stream_create / gpak_dev_stream_destroy.
+ * to that one at a time -- gpak_dev_factor_panel_co per element against a long-double factor and its *info against
+ * matrices that fail at a chosen column (group `panel`) -- except gpak_dev_stream_create / gpak_dev_stream_destroy.
  */
 #ifndef GPAK_DEV_H
 #define GPAK_DEV_H
@@ -57,8 +58,12 @@ int gpak_dev_fill_b(void *stream, const double *u, int cap, int n, int Np, int J
 
 /* Factor block column [J, J+W) in place: its W x W diagonal block (128 columns at a time) and
  * the panel below.  inv receives (W/128) x 2 x 128 x 128 doubles (inverse and inverse-transpose
- * of each 128 x 128 diagonal block).  *info (device int, pre-set to INT_MAX by the caller)
- * gets the minimum failing global column (1-based) if the block is not positive definite. */
+ * of each 128 x 128 diagonal block, the second the exact transpose of the first).  *info (device int, pre-set to
+ * INT_MAX by the caller) gets the minimum of its value and the first failing global column (1-based) if the block is
+ * not positive definite -- a pivot that is not > 0, a NaN included; a success leaves it as it was.  The return code is
+ * GPAK_OK either way: the status travels in *info.  Only the lower triangle is read.  Written: the lower triangle
+ * (exact zeros above the diagonal inside the diagonal 16 x 16 tiles) and the rows below; never a 128 x 128 tile
+ * above the diagonal; the 16 x 16 tiles above the diagonal inside a diagonal 128 x 128 tile may be overwritten. */
 int gpak_dev_factor_panel(void *stream, double *blk, long ld, int Np, int J, int W, double *inv, int *info);
 /* The same with a placement hint: coresident != 0 selects the 4-wave / 80-VGPR build of the 128 x 128 block kernel,
  * which fits on a compute unit beside two resident trailing-update workgroups; use it when the bulk update runs on a

@@ -219,6 +219,8 @@ int gpak_grid_nlz(gpak_grid *h, double *nlz);
 int gpak_grid_nlz_terms(gpak_grid *h, double *quad, double *sumlp, double *logdet);
 int gpak_grid_get_alpha(gpak_grid *h, double *alpha_host);
 int gpak_grid_get_stats(gpak_grid *h, gpak_dist_stats *out);   /* bytes_broadcast = what THIS rank received */
+/* failing column (1-based, min-reduced: the same on every rank) of the last GPAK_ENOTPD, 0 if none */
+int gpak_grid_failed_column(const gpak_grid *h);
 
 /* TEST entry point: a gpak_create_multi group (one host thread per rank, in-process transport, the gpak_ctx surface of
  * logLikelihood / alpha / gradient; no prediction: there are no device replicas) over n_ranks CALLER-SUPPLIED engines.

@@ -65,6 +65,19 @@ long-double sums against orc.grad_ref_q on the symmetric Q of the same lower tri
 the linear assembly (the oracle is a float64 sum of the same terms in another order), the rounding of M_p itself on
 either side (derived in the case), and, for the sn2 entry, the oracle's own f = K alpha.
 
+The panel factorisation alone (group `panel`: gpak_dev_factor_panel_co).  Operands G G^T / W + 2 I on the diagonal block
+(a junk upper triangle: only the lower one is read) and standard_normal rows below; W = 128 .. 1024, J = 0 / 384, 0 / 128 /
+640 rows below, either build.  Reference in long double: chol_ld (128-column steps, products through mm_ld), P L^-T for
+the rows below, the inverse of each 128-block.  Bound, the substitutions' house rule: 8 x the worst error of the float64
+restatement of the device's blocked algorithm (np_engine.blocked_factor_panel) against long double on the same input,
+relative to s_L = |L| tril(|L^-1| |L||L^T| |L^-T|) for L, |P||L^-T| (I + s_L^T |L^-T|) for the rows below and
+|X| (|L_kk| + s_L,kk) |X| for a block inverse X; the residual |A - L L^T| of what came back, in long double, within
+(W + 2) u |L||L^T| times 8 x the restatement's own residual ratio.  The second image of `inv` is the transpose of the
+first in bits; the diagonal 16-tiles come back with exact zeros above the diagonal; 128-tiles above the diagonal, rows
+above J, skew rows and guard bands keep their bits (the 16-tiles above the diagonal inside a diagonal 128-block are
+scratch).  `info`: matrices built to fail at a chosen column (tests/failcol_ref.py: D[k] = -1, an exact zero pivot, a
+NaN; two failing blocks; pre-set values on either side), the fixture's own rules asserted on the CPU first.
+
 Long-double products of float64 operands are formed from exact pieces: each operand is cut into 17-bit slices per row
 (integers times a power of two), a float64 BLAS product of two slices with K <= 2048 is exact (17 + 17 + 11 < 53 bits)
 in any order, and the slice products are summed in long double, smallest first (`mm_ld`; test_dev_ops holds it against
@@ -92,7 +105,7 @@ SENTINEL = np.uint64(0x7FF8A5A5DEADBEEF)     # a quiet NaN with a payload: arith
 OK, EINVAL = 0, 2
 INT_MAX = 0x7FFFFFFF
 D4, HYB = 0x10, 0x20
-GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill", "grad", "pairs")
+GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill", "grad", "pairs", "panel")
 
 
 def long_double_ok():
@@ -606,8 +619,8 @@ def factored_block(ops, key, W, Np, J, below):
     """Block column [J, J+W) of an Np-row matrix (ld = Np + 32): rows above J hold the sentinel (nothing may read
     them), the diagonal block is G G^T / W + 2 I (condition number of order 10) factored by ONE factor_panel_co call of
     the engine and read back, and the rows below are `below` (untouched by the factorisation: it is told Np = J + W).
-    Returns (payload, ld, inv, L).  The factorisation is checked INDIRECTLY here, through the operations that use the
-    factor (tests/test_gpu_parity.py::test_block_kernel_directly is its own test); what is checked on the spot is that
+    Returns (payload, ld, inv, L).  The factorisation itself is held to long double by the group `panel`; what is checked
+    on the spot here is that
     gpak_dev_factor_panel on the same input gives the same bits (it is factor_panel_co(..., 0): csrc/dev_api.hip), the
     run-twice check of the cases for an operation whose result they memoise."""
     def make():
@@ -1632,6 +1645,260 @@ for _c in ("expans+bias", "expans d4"):
 for _d in (3, 4):
     case("pairs", f"grad_finish[d={_d}]", ["gpak_dev_grad_finish", "gpak_dev_grad_finish_d"] if _d == 3 else ["gpak_dev_grad_finish_d"],
          d=_d)(_finish)
+
+
+# ---- the panel factorisation alone (group `panel`: gpak_dev_factor_panel_co) ------------------------------------------
+def chol_ld(A):
+    """lower Cholesky factor of a symmetric float64 matrix (its lower triangle is read) in long double: 128-column steps,
+    the products through mm_ld.  Returns (L, [inverse of each 128 x 128 diagonal block of L])."""
+    W = A.shape[0]
+    L = (np.tril(A) + np.tril(A, -1).T).astype(LD)
+    invs = []
+    for j in range(0, W, TILE):
+        D = L[j:j + TILE, j:j + TILE]
+        for c in range(TILE):
+            D[c, c] = np.sqrt(D[c, c] - D[c, :c] @ D[c, :c])
+            D[c + 1:, c] = (D[c + 1:, c] - D[c + 1:, :c] @ D[c, :c]) / D[c, c]
+            D[c, c + 1:] = 0
+        invs.append(tri_inv_ld(D))
+        if j + TILE < W:
+            P = mm_ld(L[j + TILE:, j:j + TILE], invs[-1])
+            L[j + TILE:, j:j + TILE] = P
+            L[j + TILE:, j + TILE:] -= mm_ld(P, P)
+    return np.tril(L), invs
+
+
+def rows_ld(P, L, invs):
+    """P L^-T in long double by block forward substitution with the 128-block inverses of chol_ld"""
+    X = P.astype(LD)
+    W = L.shape[0]
+    for j in range(0, W, TILE):
+        X[:, j:j + TILE] = mm_ld(X[:, j:j + TILE], invs[j // TILE])
+        if j + TILE < W:
+            X[:, j + TILE:] -= mm_ld(X[:, j:j + TILE], L[j + TILE:, j:j + TILE])
+    return X
+
+
+def panel_operands(W, below):
+    """(A = G G^T / W + 2 I, the rows below: standard_normal, a junk upper triangle) -- functions of W (and `below`) alone,
+    so that every J and either build share one reference"""
+    def make():
+        rng = rng_for(f"panel-group[W={W}]")
+        G = rng.standard_normal((W, W))
+        A = G @ G.T / W + 2.0 * np.eye(W)
+        A = np.tril(A) + np.tril(A, -1).T
+        junk = 1e3 * rng.standard_normal((W, W))
+        return A, junk
+    A, junk = memo(("panel-A", W), make)
+    P = memo(("panel-P", W, below), lambda: rng_for(f"panel-group[W={W},below={below}]").standard_normal((below, W)))
+    return A, P, junk
+
+
+def panel_reference(W, below):
+    """long double: L, P L^-T, the inverses of the 128-blocks; the scales the errors are relative to (|L^-1|-type, as
+    subst_bound's); and the float64 restatement of the device's blocked algorithm (np_engine.blocked_factor_panel) on the
+    same input, whose error against long double sets the tolerance"""
+    def make():
+        from np_engine import blocked_factor_panel
+        A, P, _junk = panel_operands(W, below)
+        L, invs = memo(("panel-chol", W), lambda: chol_ld(A))
+        X = rows_ld(P, L, invs) if below else np.zeros((0, W), dtype=LD)
+        L64 = L.astype(np.float64)
+        aL = np.abs(L64)
+        aLi = np.abs(np.linalg.inv(L64))
+        # first-order error of a Cholesky factor: dL = L tril(L^-1 dA L^-T) with |dA| <= c u |L| |L^T|
+        sL = np.tril(aL @ np.tril(aLi @ (aL @ aL.T) @ aLi.T))
+        # the rows below carry their own substitution error and the factor's: P L^-T dL^T L^-T
+        pl = np.abs(P) @ aLi.T
+        sP = pl + pl @ sL.T @ aLi.T
+        sI = []
+        for k in range(W // TILE):
+            c = slice(k * TILE, (k + 1) * TILE)
+            Xk = np.abs(invs[k]).astype(np.float64)
+            sI.append(Xk @ (aL[c, c] + sL[c, c]) @ Xk)       # the inversion's own |X| |L| |X| and the factor's error through it
+        M = np.vstack([A, P])
+        inv = np.zeros((W // TILE, 2, TILE, TILE))
+        assert blocked_factor_panel(M, W, inv, 0) == []
+        return dict(L=L, X=X, invs=invs, sL=sL, sP=sP, sI=sI, numL=np.tril(M[:W]), numP=M[W:], numI=inv)
+    return memo(("panel-ref", W, below), make)
+
+
+def _ratio(num, ref, scale):
+    err = np.abs(np.asarray(num, dtype=LD) - ref).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0.0, err / scale)
+    return float(r.max()) if r.size else 0.0
+
+
+def panel_input(A_upper, A, P, J, Np, ld):
+    """the block column as it goes in: the sentinel above row J, the lower triangle of A with `A_upper` above the diagonal,
+    the rows below"""
+    W = A.shape[0]
+    M = np.empty((Np, W))
+    M[:] = sentinel(1)[0]
+    M[J:J + W] = np.tril(A) + np.triu(A_upper, 1)
+    M[J + W:] = P
+    return Mat(M, ld)
+
+
+def upper16(W):
+    """elements of the W x W block above the diagonal: inside the diagonal 16 x 16 tiles (exact zeros come back); in the
+    16-tiles above the diagonal of a diagonal 128-block (the block kernel neither reads nor writes them, but the in-panel
+    update of a later diagonal 128-tile is a whole-tile product and does: scratch); in the 128-tiles strictly above the
+    diagonal (never written: they keep their bits)"""
+    i, j = np.arange(W)[:, None], np.arange(W)[None, :]
+    return (i < j) & (i // 16 == j // 16), (i // 16 < j // 16) & (i // TILE == j // TILE), i // TILE < j // TILE
+
+
+def _panel(ops, name, W, J, below, mirror=False):
+    """gpak_dev_factor_panel_co alone: accuracy against long double, what it writes, either build, a junk upper triangle"""
+    A, P, junk = panel_operands(W, below)
+    ref = panel_reference(W, below)
+    Np, nblk = J + W + below, W // TILE
+    ld = Np + 32
+    res = Result()
+
+    def run(upper, co, label):
+        blk, inv = panel_input(upper, A, P, J, Np, ld), Mat(sentinel(nblk * 2 * TILE * TILE))
+        info = np.full(4, INT_MAX, dtype=np.int32)
+        res.rc(label, ops.call("factor_panel_co", blk, ld, Np, J, W, inv, info, co))
+        res.rc(label + ": info stays INT_MAX", int(info[0] != INT_MAX or (info[1:] != INT_MAX).any()))
+        return blk, inv
+
+    blk, inv = run(junk, 0, "factor_panel_co")
+    blk1, inv1 = run(junk, 1, "factor_panel_co[coresident]")
+    res.rc("coresident: the same bits", int(not (np.array_equal(bits(blk.full), bits(blk1.full))
+                                                  and np.array_equal(bits(inv.full), bits(inv1.full)))))
+    zero16, scratch16, keep128 = upper16(W)
+    pad = lambda m, fill: np.vstack([np.full((J, W), fill, dtype=bool), m, np.full((below, W), not fill, dtype=bool)])
+    if mirror:                # only the lower triangle is read: a symmetric input gives the same bits where the call writes
+        blk2, inv2 = run(A, 0, "factor_panel_co[symmetric input]")
+        wr = pad(~(scratch16 | keep128), False)
+        res.rc("junk above the diagonal: the same bits", int(not (np.array_equal(bits(blk.get()[wr]), bits(blk2.get()[wr]))
+                                                                 and np.array_equal(bits(inv.full), bits(inv2.full)))))
+    # ---- the tolerance: 8 x the restatement's worst error against long double, relative to the scales
+    rL = _ratio(ref["numL"], ref["L"], ref["sL"])
+    rP = _ratio(ref["numP"], ref["X"], ref["sP"])
+    rI = max(_ratio(ref["numI"][k, 1], ref["invs"][k], ref["sI"][k]) for k in range(nblk))
+    res.info["numpy_vs_longdouble[L]"], res.info["numpy_vs_longdouble[P]"], res.info["numpy_vs_longdouble[inv]"] = rL, rP, rI
+    full_ref = np.zeros((Np, W), dtype=LD)
+    full_ref[J:J + W], full_ref[J + W:] = ref["L"], ref["X"]
+    bound = np.zeros((Np, W))
+    bound[J:J + W], bound[J + W:] = 8.0 * rL * ref["sL"], 8.0 * rP * ref["sP"]
+    # rows above J and the 128-tiles above the diagonal: bit-identical
+    res.add("blk", blk, full_ref, bound, pad(~(scratch16 | keep128), False), free=np.vstack([np.zeros((J, W), dtype=bool), scratch16, np.zeros((below, W), dtype=bool)]))
+    iref, ibound = np.zeros((nblk, 2, TILE, TILE), dtype=LD), np.zeros((nblk, 2, TILE, TILE))
+    for k in range(nblk):
+        iref[k, 0], iref[k, 1] = ref["invs"][k].T, ref["invs"][k]          # memory [c][r] of L^-1, then of L^-T
+        ibound[k, 0], ibound[k, 1] = 8.0 * rI * ref["sI"][k].T, 8.0 * rI * ref["sI"][k]
+    res.add("inv", inv, iref.reshape(-1, 1), ibound.reshape(-1, 1), True)
+    iv = inv.data.reshape(nblk, 2, TILE, TILE)
+    res.rc("inv: the second image is the transpose of the first, in bits",
+           int(not all(np.array_equal(bits(iv[k, 1]), bits(iv[k, 0].T.copy())) for k in range(nblk))))
+    out = blk.get()[J:J + W]
+    res.rc("exact zeros above the diagonal of the diagonal 16-tiles", int(bits(out[zero16].copy()).any()))
+    # ---- the residual on the diagonal block, in long double
+    Lh = np.tril(out)
+    rb = (W + 2) * U * (np.abs(Lh) @ np.abs(Lh).T)
+    low = np.tril(np.ones((W, W), dtype=bool))
+
+    def resid(Lx):
+        return np.abs(A.astype(LD) - mm_ld(Lx, Lx)).astype(np.float64)
+    rR = float((memo(("panel-resid", W), lambda: resid(ref["numL"]))[low] / ((W + 2) * U * (np.abs(ref["numL"]) @ np.abs(ref["numL"]).T))[low]).max())
+    res.info["numpy_residual_ratio"] = rR
+    res.add("residual", Mat(np.where(low, resid(Lh), 0.0)), 0.0, 8.0 * rR * rb, low)
+    return res
+
+
+for _W in (128, 256, 512):
+    for _J in (0, 384):
+        for _b in (0, 128, 640):
+            case("panel", f"factor_panel[W={_W},J={_J},below={_b}]", ["gpak_dev_factor_panel_co"], W=_W, J=_J, below=_b,
+                 mirror=(_b == 128))(_panel)
+for _J, _b in ((0, 128), (384, 640), (384, 0)):
+    case("panel", f"factor_panel[W=1024,J={_J},below={_b}]", ["gpak_dev_factor_panel_co"], W=1024, J=_J, below=_b,
+         mirror=(_b == 128))(_panel)
+
+
+PANEL_INFO_W, PANEL_INFO_J, PANEL_INFO_BELOW = 512, 384, 128
+PANEL_INFO_K = (0, 15, 16, 127, 128, 300, 511)
+
+
+def _panel_info(ops, name, what):
+    """*info of gpak_dev_factor_panel_co: pre-set by the caller, gets the MINIMUM failing global column (1-based); the
+    status travels in it, the return code is GPAK_OK."""
+    import failcol_ref as fr
+    W, J, below = PANEL_INFO_W, PANEL_INFO_J, PANEL_INFO_BELOW
+    Np = J + W + below
+    ld = Np + 32
+    L = memo(("panel-info-L", W), lambda: fr.ldl_factor(W, 20260305))
+    P = memo(("panel-info-P", W), lambda: rng_for("panel-info").standard_normal((below, W)))
+    res = Result()
+
+    def run(A, preset, co=0):
+        blk, inv = panel_input(A, A, P, J, Np, ld), Mat(sentinel(W // TILE * 2 * TILE * TILE))
+        info = np.full(4, INT_MAX, dtype=np.int32)
+        info[0] = preset
+        res.rc(f"{name}: return code", ops.call("factor_panel_co", blk, ld, Np, J, W, inv, info, co))
+        res.rc(f"{name}: the ints beside info", int((info[1:] != INT_MAX).any()))
+        res.add("blk", blk, free=np.arange(Np)[:, None] >= J).add("inv", inv, free=True)     # guards, skew rows, rows above J
+        return int(info[0]), blk
+
+    def want(label, got, expected):
+        res.rc(f"{name}: {label}", got, expected)
+
+    good = L @ L.T
+    if what == "success":
+        want("a success leaves INT_MAX", run(good, INT_MAX)[0], INT_MAX)
+        want("a success leaves a pre-set 5", run(good, 5)[0], 5)
+        want("a success leaves INT_MAX [coresident]", run(good, INT_MAX, 1)[0], INT_MAX)
+        return res
+    if what in ("-1", "0", "nan"):
+        d = {"-1": -1.0, "0": 0.0, "nan": np.nan}[what]
+        for k in PANEL_INFO_K:
+            A = fr.ldl_panel(L, k, d)
+            fr.assert_ldl_discriminates(A, k, d)                   # the fixture first, on the CPU
+            for co in (0, 1):
+                want(f"D[{k}] = {what}, coresident {co}", run(A, INT_MAX, co)[0], J + k + 1)
+        return res
+    if what == "two failures":
+        # blockdiag of two L D L^T blocks: the first fails at k1 (in the first 128-block), the second at k2 (in the third)
+        k1, k2, h = 70, 40, W // 2
+        La, Lb = fr.ldl_factor(h, 11), fr.ldl_factor(h, 12)
+        A = np.zeros((W, W))
+        A[:h, :h], A[h:, h:] = fr.ldl_panel(La, k1), fr.ldl_panel(Lb, k2)
+        assert fr.reference_info(A) == k1 + 1 and fr.reference_info(A[h:, h:]) == k2 + 1
+        for co in (0, 1):
+            want(f"the first of two failures, coresident {co}", run(A, INT_MAX, co)[0], J + k1 + 1)
+        want("the second alone", run(np.block([[La @ La.T, np.zeros((h, h))], [np.zeros((h, h)), A[h:, h:]]]), INT_MAX)[0], J + h + k2 + 1)
+        return res
+    if what == "pre-set":
+        k = 300
+        A = fr.ldl_panel(L, k)
+        fr.assert_ldl_discriminates(A, k, -1.0)
+        want("a pre-set value below the failing column survives", run(A, J + k - 2)[0], J + k - 2)
+        want("a pre-set value above it is replaced", run(A, J + k + 50)[0], J + k + 1)
+        want("a pre-set value equal to it stays", run(A, J + k + 1)[0], J + k + 1)
+        return res
+    assert what == "flip"
+    # a 1 -> -1 flip of one D entry changes nothing left of column k: columns [0, k) of the block column (the rows below
+    # included) come back with the bits of the successful factorisation of the same L
+    _i, ok = run(good, INT_MAX)
+    for k in (15, 16, 127, 128, 300, 511):
+        A = fr.ldl_panel(L, k)
+        assert np.array_equal(bits(np.tril(A)[:, :k].copy()), bits(np.tril(good)[:, :k].copy()))
+        got, bad = run(A, INT_MAX)
+        want(f"flip at {k}: info", got, J + k + 1)
+        a, b = ok.get()[J:, :k], bad.get()[J:, :k]
+        low = np.arange(Np - J)[:, None] >= np.arange(k)[None, :]
+        diff = (bits(a.copy()) != bits(b.copy())) & low
+        res.info[f"first column that differs, flip at {k}"] = float(np.argmax(diff.any(axis=0)) if diff.any() else k)
+        want(f"flip at {k}: columns [0, {k}) keep their bits", int(diff.any()), 0)
+    return res
+
+
+for _what in ("success", "-1", "0", "nan", "two failures", "pre-set", "flip"):
+    case("panel", f"factor_panel info[{_what}]", ["gpak_dev_factor_panel_co"], what=_what)(_panel_info)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -65,7 +65,7 @@ def main():
             gp.set_params(e, synth.DEFAULT_BIAS, sn2, a.mode)
         nlz = gp.nlz()
     st = gp.stats()
-    res.update({"nlz": nlz, "stats": st})
+    res.update({"nlz": nlz, "stats": st, "failed_column": gp.failed_column()})
     if nlz == nlz:
         q, s, l = gp.nlz_terms()
         res.update({"alpha": gp.get_alpha().tolist(), "logdet": l, "quad": q, "sumlp": s})

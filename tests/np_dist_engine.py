@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from gp_ss_ak_amd import dist as gd
-from np_engine import NumpyEngine, TILE
+from np_engine import NumpyEngine, TILE, blocked_factor_panel
 
 
 def _arr(ptr, n, dtype=np.float64):
@@ -216,25 +216,12 @@ class NumpyDistEngine:
             # rows J .. Np of the block column through a strided view: `blk` may be a VIRTUAL base (the grid layout passes
             # block - J so that global row J is the block's first local row), which a reshape by ld cannot address
             self.calls.append(("factor", J, st))
-            import scipy.linalg as sl
             M = _strided(int(blk) + 8 * J, Np - J, W, ld)
-            D = np.tril(M[:W, :])
-            D = D + np.tril(D, -1).T
-            infon = _arr(info, 1, np.int32)
-            try:
-                L = sl.cholesky(D, lower=True)
-            except sl.LinAlgError:
-                k = next(i for i in range(1, W + 1) if np.linalg.eigvalsh(D[:i, :i]).min() <= 0)
-                infon[0] = min(int(infon[0]), J + k)
-                L = np.eye(W)
-            M[:W, :] = L
-            if Np - J > W:
-                M[W:, :] = sl.solve_triangular(L, M[W:, :].T, lower=True).T
-            iv = inv_blocks(inv, W)
-            for k in range(W // TILE):
-                X = np.linalg.inv(L[k * TILE:(k + 1) * TILE, k * TILE:(k + 1) * TILE])
-                iv[k, 0] = X.T
-                iv[k, 1] = X
+            reports = blocked_factor_panel(M, W, inv_blocks(inv, W), J)
+            self.last_reports = reports                # launch order: what a last-writer-wins report would keep
+            if reports:
+                infon = _arr(info, 1, np.int32)
+                infon[0] = min(int(infon[0]), min(reports))
 
         def update_block(st, panel, ldp, prow0, W, blk, ld, Np, Jc, Wc):
             self.calls.append(("update_block", Jc, st))
@@ -278,7 +265,12 @@ class NumpyDistEngine:
         def diag_inverse(st, panel, ldp, row0, J, W, inv, rinv):
             M = _strided(panel, W + (J - row0), W, ldp)
             L = np.tril(M[J - row0:J - row0 + W, :])
-            _strided(rinv, W, W, 512)[:] = np.linalg.inv(L).T
+            try:
+                _strided(rinv, W, W, 512)[:] = np.linalg.inv(L).T
+            except np.linalg.LinAlgError:
+                # only after a FAILED factorisation, which the schedules run to the end: what follows the failing column is
+                # garbage on the device too (a failed pivot is replaced by 1 and the arithmetic goes on; it may overflow)
+                _strided(rinv, W, W, 512)[:] = np.nan
 
         def logdiag_block(st, blk, ld, J, W, N, out):
             nc = max(0, min(W, N - J))

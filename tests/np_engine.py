@@ -11,6 +11,88 @@ import torch
 TILE = 128
 
 
+PANEL_MID = 512          # csrc/potrf_plan.h GPAK_PANEL_MID
+
+
+def potrf16(S):
+    """One 16 x 16 diagonal block as csrc/potrf.hip's diag_block does it: Gaussian elimination by rows on [S | I] (S
+    symmetric), pivot r scaled by 1 / sqrt(d), a pivot that is not > 0 replaced by 1.  Returns (U^T = L with leftovers
+    above the diagonal, L^-1 with exact zeros above it, first bad pivot or 16)."""
+    X = np.hstack([S, np.eye(16)])
+    bad = 16
+    for r in range(16):
+        d = X[r, r]
+        if not d > 0.0:
+            bad = min(bad, r)
+            d = 1.0
+        g = np.sqrt(d)
+        xr = X[r] * (1.0 / g)
+        xr[r] = g
+        X[r] = xr
+        if r < 15:
+            X[r + 1:] -= np.outer(xr[r + 1:16], xr)
+    return X[:, :16].T, X[:, 16:], bad
+
+
+def potrf128(D):
+    """The 128 x 128 block kernel restated: 16-wide right-looking steps, the panel formed as a product with the explicit
+    inverse of the 16 x 16 diagonal block, the block's inverse by block forward substitution on R = I in right-looking
+    form.  D: only its lower triangle is read.  Returns (L lower with exact zeros above the diagonal of its diagonal
+    16-tiles, L^-1, [failing local columns, 1-based, one per 16-block that failed])."""
+    T = np.tril(D) + np.tril(D, -1).T
+    Y, R, reports = np.zeros((TILE, TILE)), np.eye(TILE), []
+    for kb in range(8):
+        c = slice(16 * kb, 16 * kb + 16)
+        below = slice(16 * kb + 16, TILE)
+        Lkk, Dinv, bad = potrf16(T[c, c])
+        if bad < 16:
+            reports.append(16 * kb + bad + 1)
+        T[c, c] = np.tril(Lkk)
+        done = slice(0, 16 * kb + 16)
+        Y[c, done] = Dinv @ R[c, done]                 # phase A (and the diagonal inverse itself: R[c, c] = I)
+        if kb < 7:
+            P = T[below, c] @ Dinv.T                   # P := P inv(D)^T
+            T[below, c] = P
+            T[below, below] -= P @ P.T                 # the upper half is never read again
+            R[below, done] -= P @ Y[c, done]           # phase B
+    return np.tril(T), np.tril(Y), reports
+
+
+def blocked_factor_panel(M, W, inv, col0):
+    """gpak_factor_panel of csrc/potrf.hip in float64 on M = rows [J, Np) of the block column (a view, written in place):
+    pieces of PANEL_MID columns, inside them 128-column steps (potrf128, P := P inv^T, the K = 128 update of the rest of
+    the piece), after each piece the K = piece update of the rest of the panel -- lower 128-tiles only, the 16-tiles above
+    the diagonal of a diagonal 128-block neither read nor written.  inv: (W / 128, 2, 128, 128) view, both images written
+    whole.  Returns the failing columns reported (1-based, global through col0), in launch order: *info gets their
+    minimum (atomicMin)."""
+    rows = M.shape[0]
+    reports = []
+
+    def update(c0, c1, k0, k1):
+        """columns [c0, c1) -= P[:, k0:k1] P[c0:c1, k0:k1]^T for the rows from c0 on, lower 128-tiles"""
+        for t0 in range(c0, c1, TILE):
+            M[t0:, t0:t0 + TILE] -= M[t0:, k0:k1] @ M[t0:t0 + TILE, k0:k1].T
+
+    for p0 in range(0, W, PANEL_MID):
+        p1 = min(W, p0 + PANEL_MID)
+        for j in range(p0, p1, TILE):
+            blk = M[j:j + TILE, j:j + TILE]
+            L, X, rep = potrf128(blk)
+            reports += [col0 + j + r for r in rep]
+            keep = np.kron(np.triu(np.ones((8, 8), dtype=bool), 1), np.ones((16, 16), dtype=bool))
+            blk[...] = np.where(keep, blk, L)
+            iv = inv[j // TILE]
+            iv[0] = X.T                                # memory [c][r] of L^-1 (column-major, ld 128)
+            iv[1] = X                                  # ... of L^-T
+            if j + TILE < rows:
+                M[j + TILE:, j:j + TILE] = M[j + TILE:, j:j + TILE] @ X.T
+                if j + TILE < p1:
+                    update(j + TILE, p1, j, j + TILE)
+        if p1 < W and p1 < rows:
+            update(p1, W, p0, p1)
+    return reports
+
+
 class NumpyEngine:
     def empty(self, n, dtype=None):
         return torch.zeros(int(n), dtype=dtype or torch.float64)
@@ -128,23 +210,9 @@ class NumpyEngine:
 
     def factor_panel(self, blk, ld, Np, J, W, inv, info):
         M = blk.numpy().reshape(W, ld).T
-        D = np.tril(M[J:J + W, :])
-        D = D + np.tril(D, -1).T
-        try:
-            L = sl.cholesky(D, lower=True)
-        except sl.LinAlgError:
-            # leading minor that fails, 1-based global column
-            k = next(i for i in range(1, W + 1) if np.linalg.eigvalsh(D[:i, :i]).min() <= 0)
-            info[0] = min(int(info[0]), J + k)
-            L = np.eye(W)
-        M[J:J + W, :] = L
-        if J + W < Np:
-            M[J + W:Np, :] = sl.solve_triangular(L, M[J + W:Np, :].T, lower=True).T
-        iv = inv.numpy().reshape(W // TILE, 2, TILE, TILE)
-        for k in range(W // TILE):
-            X = np.linalg.inv(L[k * TILE:(k + 1) * TILE, k * TILE:(k + 1) * TILE])
-            iv[k, 0] = X.T   # stored column-major: memory [c][r] = X[r][c]
-            iv[k, 1] = X     # inverse transpose, column-major
+        reports = blocked_factor_panel(M[J:Np], W, inv.numpy().reshape(W // TILE, 2, TILE, TILE), J)
+        if reports:                                    # the first failing column, 1-based and global: atomicMin
+            info[0] = min(int(info[0]), min(reports))
 
     def pack(self, src, ld, row0, nrows, ncols, dst):
         dst.view(ncols, nrows).copy_(src.view(ncols, ld)[:, row0:row0 + nrows])

@@ -104,14 +104,15 @@ def test_the_sequences_meet_the_statuses_the_header_promises():
     assert {"logLikelihood", "loo", "predict_block", "predict_joint", "sample_joint"} <= set(nan_steps)
     cols = [int(w["res"][1][0][0]) for w in fail if w["method"] == "failed_column"]
     assert cols[0] == 0 and all(c >= 1 for c in cols[1:-1]) and cols[-1] == 0 and len(cols) >= 4
+    assert cols == [0, 1, 1, 1, cs.BAD200_COLUMN, 0]           # the columns themselves: the last failure is past the first tile
 
 
 # mutation -> (the named sequence that catches it, index and method of its first step off the model).  That step is the
 # first one after the call whose invalidation was dropped that reads what the call should have invalidated: the very next
 # step everywhere but for `gram keeps factor` (gram at 5; solve_alpha at 6 returns the alpha the context still rightly holds;
 # the variance at 7 reads the matrix buffer), `predict leaks pooled mean` (prediction at 7; loo and compute_k do not read the
-# training points' transformed copy, the Gram matrix at 10 does) and `recovery keeps failed_column` (good parameters at 33,
-# the factorisation at 34, the question at 35).
+# training points' transformed copy, the Gram matrix at 10 does) and `recovery keeps failed_column` (good parameters at 36,
+# the factorisation at 37, the question at 38: the column it keeps is 200, the failure before it, not 1).
 CAUGHT_BY = {
     "memo ignores composition": ("memo", 6, "logLikelihood"),
     "gram keeps factor": ("gram between [direct]", 7, "posteriorMeanVar"),
@@ -121,7 +122,7 @@ CAUGHT_BY = {
     "solve_chol keeps z": ("solve scratch", 4, "solve_alpha"),
     "predict leaks pooled mean": ("gram between [expansion]", 10, "gram"),
     "f32 image kept": ("f32", 5, "posteriorMeanVar"),
-    "recovery keeps failed_column": ("fail and recover", 35, "failed_column"),
+    "recovery keeps failed_column": ("fail and recover", 38, "failed_column"),
 }
 
 
@@ -155,6 +156,8 @@ def test_each_mutation_is_caught(mutation):
     print(f"{mutation}: '{name}' step {rec['i']} ({rec['method']} {rec['kw']}) is {ratio:.3g} bounds off the model")
     assert dropped and all(d[0] == mutation for d in dropped)
     assert rec["method"] == method and (index is None or rec["i"] == index), (rec["i"], rec["method"])
+    if mutation == "recovery keeps failed_column":       # the value kept is the column of the LAST failure, which is not 1
+        assert dropped[0][1] == cs.BAD200_COLUMN and int(rec["res"][1][0][0]) == cs.BAD200_COLUMN
     # the step before it in the same context changed or kept the state (one after the dropped invalidation) or, where the
     # kept quantity is read later only, every compared step in between agreed with the model (first_divergence)
     assert rec["i"] > 0
@@ -429,13 +432,13 @@ def test_the_group_sequences_meet_what_the_issue_names():
     assert {("out of order (group)", m) for m in ("logLikelihood", "gram", "posteriorMeanVar", "solve_chol", "chol_upper")} <= seen[cs.ESTATE]
     assert {("fail and recover (group)", m) for m in ("posteriorMeanVar", "solve_chol", "chol_upper", "GradLL")} <= seen[cs.ENOTPD]
     fail = expected(cs.GROUP_BY_NAME["fail and recover (group)"])
-    assert sum(1 for w in fail if w["method"] == "logLikelihood" and np.isnan(w["res"][1][0]).all()) == 3
+    assert sum(1 for w in fail if w["method"] == "logLikelihood" and np.isnan(w["res"][1][0]).all()) == 4
     cols = [int(w["res"][1][0][0]) for w in fail if w["method"] == "failed_column"]
-    assert cols[0] == 0 and cols[1] >= 1 and cols[2] >= 1 and cols[3] == 0
+    assert cols == [0, 1, 1, cs.BAD200_COLUMN, 0]
     # the counts the hazards are about: they restart at the new set's first factorisation; a failing ask counts every time;
     # gram, compute_k, the imports and the refused calls count for nothing
     assert list(counts_of(cs.GROUP_BY_NAME["group count"]).values()) == [1, 1, 1, 1, 2, 2, 0, 1, 2, 2, 3]
-    assert list(counts_of(cs.GROUP_BY_NAME["fail and recover (group)"]).values()) == [2, 3, 10, 11, 12]   # seven more failing asks between the second and the third timing
+    assert list(counts_of(cs.GROUP_BY_NAME["fail and recover (group)"]).values()) == [2, 3, 10, 11, 12, 13]   # seven more failing asks between the second and the third timing
     assert set(counts_of(cs.GROUP_BY_NAME["refusals (group)"]).values()) == {1}
     assert list(counts_of(cs.GROUP_BY_NAME["gram between (group) [direct]"]).values()) == [2, 2, 2]
     methods = {m for s in cs.GROUP_SEQUENCES if not s["name"].startswith("random") for _c, m, _kw in s["steps"]}
@@ -457,7 +460,7 @@ GROUP_CAUGHT_BY = {
     "set_params keeps replica params": ("late replicas [P=2]", 4, "posteriorMeanVar", "answer"),
     "gram keeps replica factor": ("gram between (group) [direct]", 14, "posteriorMeanVar", "answer"),
     "set_params keeps general_kernel": ("compositions (group)", 8, "GradLL", "answer"),
-    "recovery keeps failed_column": ("fail and recover (group)", 24, "failed_column", "answer"),
+    "recovery keeps failed_column": ("fail and recover (group)", 28, "failed_column", "answer"),
     "import keeps f32 image": ("f32 (group)", 4, "posteriorMeanVar", "answer"),
 }
 # A mutation that changes only WHERE something is computed gives the same values and the same count on the models.  `gram
@@ -505,6 +508,8 @@ def test_each_group_mutation_is_caught(mutation):
     print(f"{mutation}: '{name}' step {rec['i']} ({rec['method']} {rec['kw']}): {what} {detail}")
     assert dropped and all(d[0] == mutation for d in dropped)
     assert (rec["i"], rec["method"], what) == (index, method, how), (rec["i"], rec["method"], what)
+    if mutation == "recovery keeps failed_column":       # the column it keeps is the last failure's, which is not 1
+        assert int(rec["res"][1][0][0]) == cs.BAD200_COLUMN
 
 
 @pytest.mark.parametrize("mutation", cm.GROUP_REDUNDANT)

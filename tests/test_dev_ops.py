@@ -9,7 +9,10 @@ masks and bounds agree with what the project itself says the operations do.  GPU
 libgpak_hip.so, one fresh process per group.
 
 Not covered here: gpak_dev_stream_create / gpak_dev_stream_destroy.  The two linear-algebra operations of the
-distributed gradient, gpak_dev_grad_g_rows and gpak_dev_grad_binv_rows, are the group `grad`; the group `pairs` holds
+distributed gradient, gpak_dev_grad_g_rows and gpak_dev_grad_binv_rows, are the group `grad`; the group `panel` holds
+gpak_dev_factor_panel_co ALONE -- per element against a long-double Cholesky factor at W = 128 .. 1024, what it writes,
+either build of the block kernel, and `info`: the minimum failing global column for matrices that fail at a chosen
+column (tests/failcol_ref.py); the group `pairs` holds
 either pair pass of csrc/grad.hip alone (gpak_dev_grad_pair_sums, gpak_dev_grad_pairs_rows) to a long-double sum over
 the pairs, slot by slot, and the host ends of that chain (gpak_dev_grad_consts through the oracle, gpak_dev_grad_finish /
 _finish_d).
@@ -138,6 +141,7 @@ def test_the_checks_bite():
     rec = dc.summarise(name, cases[name](Wrong("short k")), cases[name](Wrong("short k")))
     assert not rec["ok"] and float(rec["ratio"]) > 1e10, rec
     _the_pair_checks_bite()
+    _the_panel_checks_bite()
 
 
 def _the_pair_checks_bite():
@@ -161,6 +165,60 @@ def _the_pair_checks_bite():
             assert rec["violations"] == {"binv": 1}, (how, rec)
         else:
             assert float(rec["ratio"]) >= want and not rec["violations"], (how, rec)
+
+
+def _the_panel_checks_bite():
+    """The same for the group `panel`: wrong panel factorisations built on the float64 restatement -- `col0` dropped (the
+    column within the panel), the tile-local column, the last writer of `info` winning over the minimum, the second image
+    of `inv` not transposed, one element above the diagonal written -- each fail at least one case; the good engine
+    passes them all."""
+    good = dc.numpy_ops()
+
+    class WrongPanel:
+        name = "wrong"
+
+        def __init__(self, how):
+            self.how = how
+
+        def call(self, name, *a):
+            if name not in ("factor_panel", "factor_panel_co"):
+                return good.call(name, *a)
+            blk, ld, Np, J, W, inv, info = a[:7]
+            mine = np.full(4, dc.INT_MAX, dtype=np.int32)
+            rc = good.call(name, *(a[:6] + (mine,) + a[7:]))
+            col = int(mine[0])
+            if col != dc.INT_MAX:
+                if self.how == "col0 dropped":
+                    col -= J
+                elif self.how == "tile-local column":
+                    col = (col - 1) % dc.TILE + 1
+                elif self.how == "last writer wins":
+                    info[0] = good.nde.last_reports[-1]          # a plain store: no minimum, the pre-set value lost
+                    col = dc.INT_MAX
+                info[0] = min(int(info[0]), col)
+            iv = (inv.data if isinstance(inv, dc.Mat) else inv).reshape(W // dc.TILE, 2, dc.TILE, dc.TILE)
+            if self.how == "inv not transposed":
+                iv[:, 1] = iv[:, 0]
+            if self.how == "above the diagonal":
+                blk.get()[J + 3, 5] = 1e-300                     # inside the first diagonal 16-tile
+            return rc
+
+    panel = [(n, f) for g, n, _e, f in dc.CASES if g == "panel"]
+    assert len(panel) == 28
+    quick = [(n, f) for n, f in panel if "info" in n or "W=128," in n or n == "factor_panel[W=256,J=384,below=128]"]
+    for n, f in quick:
+        rec = dc.summarise(n, f(good), f(good))
+        assert rec["ok"], rec
+    fails = {}
+    for how in ("col0 dropped", "tile-local column", "last writer wins", "inv not transposed", "above the diagonal"):
+        fails[how] = [n for n, f in quick if not dc.summarise(n, f(WrongPanel(how)), f(WrongPanel(how)))["ok"]]
+        print(how, "fails", fails[how])
+        assert fails[how], how
+    info_cases = {n for n, _f in quick if "info" in n}
+    assert "factor_panel info[-1]" in fails["col0 dropped"] and "factor_panel info[-1]" in fails["tile-local column"]
+    assert {"factor_panel info[two failures]", "factor_panel info[pre-set]"} <= set(fails["last writer wins"])
+    assert set(fails["inv not transposed"]) == {n for n, _f in quick} - info_cases      # every accuracy case, no info case
+    assert set(fails["above the diagonal"]) >= {n for n, _f in quick} - info_cases
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------

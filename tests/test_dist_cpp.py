@@ -43,7 +43,7 @@ def run_world(world, n, nb, engine="numpy", mode=1, sn2=None, steps=1, timeout=9
                    "--steps", str(steps), "--grad", str(grad), "--corrupt", str(corrupt), "--out",
                    os.path.join(d, f"r{r}.json")]
             if sn2 is not None:
-                cmd += ["--sn2", str(sn2)]
+                cmd += ["--sn2", repr(float(sn2))]            # the text round-trips: the worker gets the same double
             if grid is not None:
                 cmd += ["--grid", f"{grid[0]}x{grid[1]}"]
             if ncols != 3:
@@ -155,6 +155,42 @@ def test_plain_stream_mode_can_be_forced(orc):
 def test_cpp_schedule_chol_fail_is_nan_on_every_rank():
     res = run_world(2, 300, 128, sn2=-0.5)
     assert all(r["nlz"] != r["nlz"] for r in res)                   # NaN (GP_Utils.cpp:1145-1146)
+    assert [r["failed_column"] for r in res] == [1, 1]
+
+
+# ---- the failing column past column 1 (tests/failcol_ref.py): the min-reduce over the ranks ------------------------------
+def _failing_world(world, n, nb, k, grid=None, engine="numpy"):
+    """One world whose factorisation fails at column k: every rank reports k (an integer, no tolerance) and a NaN nlZ.
+    Returns the rank that owns the failing diagonal block, the only one whose own `info` holds k before the reduce."""
+    import failcol_ref as fr
+    sn2, f = fr.drill_case(n, k)                       # asserts the fixture rules on the CPU first
+    res = run_world(world, n, nb, sn2=sn2, grid=grid, engine=engine)
+    assert [r["failed_column"] for r in res] == [k] * world, ([r["failed_column"] for r in res], k, f)
+    assert all(r["nlz"] != r["nlz"] for r in res)
+    b = (k - 1) // nb
+    return b % world if grid is None else b % grid[0] + grid[0] * (b % grid[1])
+
+
+# (3, 700, 128): 129 is rank 1's first column, 257 rank 2's, 385 the first of rank 0's SECOND block column, 700 the last
+# valid column (rank 2); (2, 600, 256): 300 lies in rank 1's block
+@pytest.mark.parametrize("world,n,nb,k,owner", [(3, 700, 128, 129, 1), (3, 700, 128, 257, 2), (3, 700, 128, 385, 0),
+                                                (3, 700, 128, 700, 2), (2, 600, 256, 300, 1)])
+def test_cpp_schedule_failing_column_is_the_same_on_every_rank(world, n, nb, k, owner):
+    assert _failing_world(world, n, nb, k) == owner
+
+
+# the diagonal blocks of a 2 x 2 grid belong to ranks 0 and 3 only (rank = b % Pr + Pr * (b % Pc)): 130 and 500 are rank 3's
+# (blocks 1 and 3), 300 is in rank 0's SECOND diagonal block; ranks 1 and 2 never factor, they take part in the min-reduce
+@pytest.mark.parametrize("k,owner", [(130, 3), (300, 0), (500, 3)])
+def test_grid_layout_failing_column_is_the_same_on_every_rank(k, owner):
+    assert _failing_world(4, 500, 128, k, grid=(2, 2)) == owner
+
+
+@pytest.mark.gpu
+def test_failing_column_hip_engine_one_d_and_grid():
+    """k = 300 lies in rank 1's block column of the 1-D world; k = 385 in diagonal block 1 of the grid, rank 3's."""
+    assert _failing_world(2, 900, 256, 300, engine="hip") == 1
+    assert _failing_world(4, 1300, 256, 385, grid=(2, 2), engine="hip") == 3
 
 
 @pytest.mark.gpu
