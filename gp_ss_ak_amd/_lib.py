@@ -21,6 +21,9 @@ SYMBOLS = [
 LOO_GRAD_SYMBOLS = ["gpak_loo_grad"]
 # every symbol include/gpak_cv_groups.h declares (tests/test_cv_groups.py checks the header and this list agree)
 CV_GROUPS_SYMBOLS = ["gpak_cv_groups"]
+# every symbol include/gpak_dev_f32.h declares (tests/test_dev_ops.py checks the header and this list agree)
+DEV_F32_SYMBOLS = ["gpak_dev_gemm_nt_f32", "gpak_dev_fill_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32",
+                   "gpak_dev_rowsumsq_f32", "gpak_dev_fwd_subst_f32"]
 
 
 class PhaseTimes(C.Structure):
@@ -55,10 +58,10 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). gp_ss_ak_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + DEV_F32_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
-                           f"gpak_cv_groups.h: {missing}")
+                           f"gpak_cv_groups.h / gpak_dev_f32.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -98,5 +101,14 @@ def load():
     lib.gpak_timing.argtypes = [vp, C.POINTER(PhaseTimes)]
     lib.gpak_calibrate.argtypes = [vp, dp, dp]
     lib.gpak_reload_tuning.restype = None
+    # include/gpak_dev_f32.h: the stream first, every pointer a device pointer
+    fp, ip = C.c_void_p, C.POINTER(C.c_int)
+    lib.gpak_dev_gemm_nt_f32.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, fp, C.c_long, fp, C.c_long, C.c_float, fp, C.c_long]
+    lib.gpak_dev_fill_f32.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_double, C.c_int,
+                                      fp, C.c_long]
+    lib.gpak_dev_lower_to_f32.argtypes = [vp, vp, C.c_long, C.c_int, fp, C.c_long]
+    lib.gpak_dev_vec_to_f32.argtypes = [vp, vp, C.c_long, fp]
+    lib.gpak_dev_rowsumsq_f32.argtypes = [vp, fp, C.c_long, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    lib.gpak_dev_fwd_subst_f32.argtypes = [vp, fp, C.c_long, C.c_int, C.c_int, fp, C.c_long, fp, ip, C.c_int]
     _lib = lib
     return lib

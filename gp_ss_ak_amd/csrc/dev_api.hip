@@ -1,10 +1,12 @@
 // dev_api.hip -- device-pointer level C-ABI (include/gpak_dev.h): what one rank of the
 // block-column-cyclic multi-GPU factorisation runs on the block columns it owns.
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../include/gpak_dev.h"
+#include "../../include/gpak_dev_f32.h"
 #include "gpak_internal.h"
 
 // view of points [off, n) of a transformed set: same array stride (cap), shifted base
@@ -276,6 +278,68 @@ int gpak_dev_gemv_t(void *stream, const double *A, long ld, int nrows, int W, co
 
 int gpak_dev_vec_axpy(void *stream, int n, double a, const double *x, double *y) {
   gpak_launch_axpy((hipStream_t)stream, n, a, x, y);
+  return status();
+}
+
+// ---- the fp32 prediction kernels alone (include/gpak_dev_f32.h): argument checks, then the product's own launcher ----
+static bool misaligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+int gpak_dev_gemm_nt_f32(void *stream, int mt, int nt, int K, float alpha, const float *A, long lda, const float *B,
+                         long ldb, float beta, float *C, long ldc) {
+  if (mt <= 0 || nt <= 0) return GPAK_OK;
+  if (K < GPAK_TILE || K % GPAK_TILE) return GPAK_EINVAL;
+  if (lda < (long)mt * GPAK_TILE || ldb < (long)nt * GPAK_TILE || ldc < (long)mt * GPAK_TILE) return GPAK_EINVAL;
+  if ((lda | ldb | ldc) & 3) return GPAK_EINVAL;   // 16-B operand loads and stores
+  if (!A || !B || !C || misaligned(A, 16) || misaligned(B, 16) || misaligned(C, 16)) return GPAK_EINVAL;
+  if (A == C && (nt != 1 || K != GPAK_TILE)) return GPAK_EINVAL;
+  gpak_launch_gemm_nt_f32((hipStream_t)stream, mt, nt, K, alpha, A, lda, B, ldb, beta, C, ldc);
+  return status();
+}
+
+int gpak_dev_fill_f32(void *stream, const double *uP, int capP, int nP, const double *uQ, int capQ, int nQ, int rows_p,
+                      int cols_p, const double *kern, double bias, int dist_mode, float *C, long ld) {
+  if (rows_p <= 0 || rows_p % GPAK_TILE || cols_p <= 0 || cols_p % 64) return GPAK_EINVAL;
+  if (capP < rows_p || (capP & 1) || nP < 0 || nP > rows_p || nQ < 0 || nQ > cols_p || nQ > capQ) return GPAK_EINVAL;
+  if (!uP || !uQ || !C || !kern || misaligned(uP, 16) || misaligned(C, 8) || ld < rows_p || (ld & 1)) return GPAK_EINVAL;
+  KernParams kp = make_kp(kern, bias, (dist_mode & (GPAK_DIST_HYB | GPAK_DIST_D4)) | GPAK_DIST_DIRECT, nullptr);
+  if (kp.nterms < 1) return GPAK_EINVAL;
+  kp.white = 0.0;   // Kern_White contributes nothing to a train x test block
+  DevPoints P = as_points(uP, capP, nP), Q = as_points(uQ, capQ, nQ);
+  gpak_launch_fill_f32((hipStream_t)stream, P, Q, rows_p, cols_p, kp, C, ld);
+  return status();
+}
+
+int gpak_dev_lower_to_f32(void *stream, const double *L, long ld, int Np, float *out, long ldo) {
+  if (Np <= 0 || ld < Np || ldo < Np || !L || !out) return GPAK_EINVAL;
+  gpak_launch_lower_to_f32((hipStream_t)stream, L, ld, Np, out, ldo);
+  return status();
+}
+
+int gpak_dev_vec_to_f32(void *stream, const double *in, long n, float *out) {
+  if (n <= 0) return n == 0 ? GPAK_OK : GPAK_EINVAL;
+  if (!in || !out) return GPAK_EINVAL;
+  gpak_launch_vec_to_f32((hipStream_t)stream, in, (size_t)n, out);
+  return status();
+}
+
+int gpak_dev_rowsumsq_f32(void *stream, const float *V, long ldv, int rows, int cols, int splits, double *part,
+                          int part_ld) {
+  if (rows <= 0 || cols <= 0 || splits < 1 || splits > cols || ldv < rows || part_ld < rows || !V || !part) return GPAK_EINVAL;
+  gpak_launch_rowsumsq_f32((hipStream_t)stream, V, ldv, rows, cols, splits, part, part_ld);
+  return status();
+}
+
+int gpak_dev_fwd_subst_f32(void *stream, float *Wt, long ldw, int mrows, int Np, const float *Lf, long ldLf,
+                           const float *invf, const int *levels, int nlevels) {
+  if (mrows <= 0 || mrows % GPAK_TILE || Np <= 0 || Np % GPAK_TILE) return GPAK_EINVAL;
+  if (ldw < mrows || ldLf < Np || ((ldw | ldLf) & 3)) return GPAK_EINVAL;
+  if (!Wt || !Lf || !invf || misaligned(Wt, 16) || misaligned(Lf, 16) || misaligned(invf, 16)) return GPAK_EINVAL;
+  if (nlevels < 0 || nlevels > 8 || (nlevels > 0 && !levels)) return GPAK_EINVAL;
+  std::vector<int> lv(levels, levels + nlevels);
+  for (int k = 0; k < nlevels; k++)
+    if (k == 0 ? lv[0] != GPAK_TILE : (lv[k] <= lv[k - 1] || lv[k] % lv[k - 1])) return GPAK_EINVAL;
+  const GpakFsF32 f = {(hipStream_t)stream, Lf, ldLf, invf};
+  gpak_forward_subst_f32(f, Wt, ldw, mrows, Np, lv);
   return status();
 }
 

@@ -386,6 +386,17 @@ void gpak_launch_fill_f32(hipStream_t st, const DevPoints &P, const DevPoints &Q
                           const KernParams &kp, float *C, long ld);
 void gpak_launch_rowsumsq_f32(hipStream_t st, const float *V, long ldv, int rows, int cols, int splits,
                               double *part, int part_ld);
+// What the fp32 forward substitution reads beside the batch (predict.hip): the fp32 image of the factor and of the
+// inverse diagonal blocks (pairs of 128 x 128, the first image of a pair is used).  A context's own (gpak_predict_impl) or
+// a caller's (gpak_dev_fwd_subst_f32).
+struct GpakFsF32 {
+  hipStream_t stream;
+  const float *Lf;
+  long ldLf;
+  const float *invf;
+};
+// Wt (mrows x Np, ld ldw) := Wt Lf^-T by the ladder `levels` (ascending block widths, the first 128; empty: 128 / 512)
+void gpak_forward_subst_f32(const GpakFsF32 &f, float *Wt, long ldw, int mrows, int Np, std::vector<int> levels);
 
 // ---- potrf.hip --------------------------------------------------------------------------
 // Factor the 128x128 block at A (ld) in place (lower), write its inverse to inv (128x128, ld 128).

@@ -144,10 +144,10 @@ static int ensure_f32_factor(gpak_ctx *ctx) {
 // (profiles/r03_f32_accumulation.txt).  The products therefore run on gpak_gemm_nt_f32_rsw (fp32 chunks of K = 128
 // summed in fp64, gemm_f32.hip): 7.4e-7 whatever the ladder, which is then chosen for speed alone.
 // GPAK_FS_LEVELS_F32="128,512" restores the two-level scheme (A/B runs).
-static void fs_block_f32(gpak_ctx *ctx, float *Wt, long ldw, int mt, int J0, int W, const std::vector<int> &lv, int k) {
-  hipStream_t st = ctx->stream;
+static void fs_block_f32(const GpakFsF32 &f, float *Wt, long ldw, int mt, int J0, int W, const std::vector<int> &lv, int k) {
+  hipStream_t st = f.stream;
   if (k == 0) {   // W == 128: product with the explicit inverse of the diagonal block
-    const float *inv = ctx->dInvf + (size_t)(J0 / PB) * 2 * PB * PB;
+    const float *inv = f.invf + (size_t)(J0 / PB) * 2 * PB * PB;
     float *Wj = Wt + (size_t)J0 * ldw;
     gpak_launch_gemm_nt_f32(st, mt, 1, PB, 1.f, Wj, ldw, inv, PB, 0.f, Wj, ldw);
     return;
@@ -155,20 +155,18 @@ static void fs_block_f32(gpak_ctx *ctx, float *Wt, long ldw, int mt, int J0, int
   const int cw = lv[k - 1];
   for (int j0 = J0; j0 < J0 + W; j0 += cw) {
     const int w = std::min(cw, J0 + W - j0);
-    fs_block_f32(ctx, Wt, ldw, mt, j0, w, lv, k - 1);
+    fs_block_f32(f, Wt, ldw, mt, j0, w, lv, k - 1);
     const int nrest = (J0 + W - j0 - w) / PB;
     if (nrest > 0)
-      gpak_launch_gemm_nt_f32(st, mt, nrest, w, -1.f, Wt + (size_t)j0 * ldw, ldw, ctx->dLf + (j0 + w) + (size_t)j0 * ctx->ldLf, ctx->ldLf,
+      gpak_launch_gemm_nt_f32(st, mt, nrest, w, -1.f, Wt + (size_t)j0 * ldw, ldw, f.Lf + (j0 + w) + (size_t)j0 * f.ldLf, f.ldLf,
                               1.f, Wt + (size_t)(j0 + w) * ldw, ldw);
   }
 }
-static void forward_subst_batch_f32(gpak_ctx *ctx, float *Wt, long ldw, int mbp) {
-  std::vector<int> lv;
-  for (int v : ctx->sched.fs_levels) if (v > 0) lv.push_back(v);
+void gpak_forward_subst_f32(const GpakFsF32 &f, float *Wt, long ldw, int mrows, int Np, std::vector<int> lv) {
   if (lv.empty()) lv = {PB, 512};
-  lv.push_back(ctx->Np > lv.back() ? ctx->Np : lv.back() + 1);   // the whole matrix is the top block
+  lv.push_back(Np > lv.back() ? Np : lv.back() + 1);   // the whole matrix is the top block
   // the top block's width need not be a multiple of its children's: fs_block_f32 clips the last child
-  fs_block_f32(ctx, Wt, ldw, mbp / PB, 0, ctx->Np, lv, (int)lv.size() - 1);
+  fs_block_f32(f, Wt, ldw, mrows / PB, 0, Np, lv, (int)lv.size() - 1);
 }
 
 // pool_sum / pool_M: column sums and count of the WHOLE test set when Xte is a slice of it (multi-GPU prediction
@@ -231,7 +229,10 @@ int gpak_predict_impl(gpak_ctx *ctx, const double *Xte, long M, double *mean, do
         // the cross-kernel uses the direct distance form (cancellation form is meaningless in fp32)
         float *Wf = reinterpret_cast<float *>(ctx->dWt.p);
         gpak_launch_fill_f32(st, ctx->Tq, ctx->Upred, mbp, Np, kp, Wf, ldw);
-        forward_subst_batch_f32(ctx, Wf, ldw, mbp);
+        const GpakFsF32 fs = {st, ctx->dLf, ctx->ldLf, ctx->dInvf};
+        std::vector<int> lv;
+        for (int v : ctx->sched.fs_levels) if (v > 0) lv.push_back(v);
+        gpak_forward_subst_f32(fs, Wf, ldw, mbp, Np, lv);
         gpak_launch_rowsumsq_f32(st, Wf, ldw, mbp, Np, vs, ctx->dPart, cap);
       } else {
         gpak_launch_fill(st, ctx->Tq, ctx->Upred, mbp, Np, kp, 1.0, 0.0, 0.0, 0, ctx->dWt, ldw, nullptr);

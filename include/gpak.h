@@ -43,7 +43,9 @@ typedef struct gpak_ctx gpak_ctx;
  * configs[4]): the M-proportional prediction work -- cross-kernel, forward substitution with M
  * right-hand sides, variance row sums -- runs in fp32 on the fp32 MFMA (twice the fp64 matrix
  * rate); Gram fill, factorisation, alpha, nlZ, gradient and the predictive MEAN stay fp64 (one
- * 0.2 s factorisation is noise beside a 1e6-point prediction). */
+ * 0.2 s factorisation is noise beside a 1e6-point prediction).  Each of those fp32 kernels can be
+ * run alone on caller-owned device buffers through gpak_dev_f32.h (tests: group `f32` of
+ * tests/dev_ops_cases.py). */
 #define GPAK_F64 0
 #define GPAK_F32 1
 

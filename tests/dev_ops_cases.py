@@ -78,6 +78,49 @@ above J, skew rows and guard bands keep their bits (the 16-tiles above the diago
 scratch).  `info`: matrices built to fail at a chosen column (tests/failcol_ref.py: D[k] = -1, an exact zero pivot, a
 NaN; two failing blocks; pre-set values on either side), the fixture's own rules asserted on the CPU first.
 
+The fp32 prediction kernels alone (group `f32`: include/gpak_dev_f32.h, thin wrappers over the launchers of
+csrc/gemm_f32.hip and the ladder of csrc/predict.hip that a GPAK_F32 context runs).  Buffers of floats carry float guard
+bands and a float sentinel NaN (`Mat(..., dtype=F32)`); leading dimensions are skewed by multiples of 4 floats (16-byte
+loads); a build of the product is selected as the product selects it, through GPAK_F32_ACC / GPAK_F32_RSD / GPAK_F32_TILE
+and gpak_reload_tuning (`ops.f32_build`), and the environment is put back afterwards.  u32 = 2^-24, u64 = 2^-53;
+references are long double on the float operands taken exactly.
+  * gemm_nt_f32: six builds x seven shapes (F32_BUILDS, F32_SHAPES: one tile, an even and an odd number of row tiles,
+    one to five chunks of K, the 8 x 8 super-tile crossed in both directions, three super-rows on one super-column) x
+    (alpha, beta) = (1, 0) on a C of NaN, (-1, 1), (0.75, -0.5), and in place (A == C) where nt = 1 and K = 128; A carries
+    row scales 10^-3 .. 10^3.  Bounds per element, for any order of summation.  Plain builds: a float32 sum of K products
+    is at most K roundings deep, alpha and the fused beta c add two: (K + 2) u32 (|alpha| sum|a||b| + |beta||c|).  Wide
+    builds: a chunk of 128 summed in float32, 128 u32 sum|a||b| (130 with the second order and, at K = 128 where the plain
+    kernel runs, the rounding of alpha * sum); conversions to float64 are exact; K / 128 additions, alpha * total and the
+    fused beta c in float64, (K / 128 + 3) u64 of the magnitudes; ONE rounding to float, u32 |exact result|.
+    The four wide builds differ in the prefetch ring and the occupancy only, so they must give the same bits (asserted).
+  * That the wide build is wide: (2, 1, 4096), operands uniform on [0.5, 1.5).  Tolerance, the house rule: 8 x the worst
+    error, relative to sum|terms|, of the float32 restatement of the chunked scheme (f32_product, products rounded and
+    added one k at a time) against long double, measured in the case; the case first asserts that the restatement of
+    plain accumulation over all K is at least 2 tolerances out (measured: chunked 2.5 u32, plain 63 u32, margin 3.1).
+  * fill_f32: nP = 131 of 256 rows, nQ = 70 of 128 columns, drill-hole points, P[130] == Q[33], rows from n on of every
+    transformed array the sentinel; six compositions, a White child that must change no bit; rows >= nP and columns >= nQ
+    +0.0f.  Bound per element: sum_m var2_m e^(-s_m) (c0 + c1 s_m) u32 + (terms + 2) u32 |k|, s_m the exponential's
+    argument.  The operation count of gpak_fill_f32 per term: the distance in float64 (4 differences, 4 squares, 3
+    additions: 6 u64, nothing beside u32) and ONE conversion to float; ExpSqrt: sqrtf, a negation, __expf = v_exp_f32 of
+    the argument times log2(e) (one product, one rounded constant); RBF: the conversion of iw, an exact halving, one
+    product with d, then the same __expf; the conversion of var2 and one product (or fused multiply-add) into k; the
+    conversion of the bias and one addition per term.  The MI355X guides state no accuracy for v_exp_f32, v_sqrt_f32 or
+    the float conversions (they say only that hipcc keeps f32 subnormals), so each of those is taken as 2 ulp = 4 u32;
+    a float product or sum is one rounding, u32, by the format.  A relative error in the argument is s times that in
+    the result.  ExpSqrt: the conversion of d is 4 u32 of d = 2 u32 of s, sqrtf 4, the product with log2(e) and the
+    constant 2: c1 = 8.  RBF: conversions of d and iw 4 + 4, the product 1, log2(e) 2: c1 = 11.  On the result: v_exp_f32
+    4, the conversion of var2 4, the product 1: c0 = 9.  Hence FILL32_C0 = 10, FILL32_C1 = 12 for every term.  The sum:
+    `terms` additions of positive numbers, u32 |k| each, and the bias's conversion, for which the form leaves 2 u32 |k|.
+  * lower_to_f32 / vec_to_f32: the bits of np.float32(.) (round to nearest even: halfway cases, results in and below
+    the float denormals, signed zeros, 3e38), +0.0f above the diagonal, the factor's upper triangle the sentinel.
+  * rowsumsq_f32: every partial to (columns of the split + 2) u64 sum v^2, their sum on the host to (cols + 2) u64 sum v^2;
+    rows = 1 .. 300, splits with a shorter last one, of one column, of odd length (cols = 639 is this module's addition).
+  * fwd_subst_f32: the 640-row factor of the group `grad`, imaged by the two conversions; levels 128 / 512, 128 / 256, 128,
+    128 / 256 / 1024 (the last child of a block clipped at one or two levels), under the default and the plain build.
+    Tolerance as for solve_rows: 8 x the error of f32_ladder (the same recursion on f32_product, one k at a time) against
+    W Lf^-T in long double, relative to |W||Lf^-T|.
+The eleven wrong engines of test_the_checks_bite each fail a named case of this group.
+
 Long-double products of float64 operands are formed from exact pieces: each operand is cut into 17-bit slices per row
 (integers times a power of two), a float64 BLAS product of two slices with K <= 2048 is exact (17 + 17 + 11 < 53 bits)
 in any order, and the slice products are summed in long double, smallest first (`mm_ld`; test_dev_ops holds it against
@@ -102,37 +145,44 @@ GUARD = 256
 U = 2.0 ** -53
 LD = np.longdouble
 SENTINEL = np.uint64(0x7FF8A5A5DEADBEEF)     # a quiet NaN with a payload: arithmetic on it shows, a copy keeps it
+SENTINEL32 = np.uint32(0x7FC5BEEF)           # the same for float buffers (group `f32`)
+F32 = np.float32
+U32 = 2.0 ** -24
 OK, EINVAL = 0, 2
 INT_MAX = 0x7FFFFFFF
 D4, HYB = 0x10, 0x20
-GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill", "grad", "pairs", "panel")
+GROUPS = ("gemm", "solve_rows", "trsv", "reduce", "fill", "grad", "pairs", "panel", "f32")
 
 
 def long_double_ok():
     return np.finfo(np.longdouble).eps < 1e-18
 
 
-def sentinel(n):
+def sentinel(n, dtype=np.float64):
+    if np.dtype(dtype) == np.float32:
+        return np.full(int(n), SENTINEL32, dtype=np.uint32).view(np.float32)
     return np.full(int(n), SENTINEL, dtype=np.uint64).view(np.float64)
 
 
 def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
 
 
 class Mat:
-    """rows x cols column-major doubles with leading dimension ld inside a guarded buffer; the skew rows hold the
-    sentinel.  `before` is the payload as it went in."""
+    """rows x cols column-major doubles (or floats: dtype) with leading dimension ld inside a guarded buffer; the skew
+    rows hold the sentinel.  `before` is the payload as it went in."""
 
-    def __init__(self, M, ld=None):
-        M = np.asarray(M, dtype=np.float64)
+    def __init__(self, M, ld=None, dtype=np.float64):
+        M = np.asarray(M, dtype=dtype)
         if M.ndim == 1:
             M = M[:, None]
         self.rows, self.cols = M.shape
         self.ld = int(ld) if ld is not None else self.rows
-        body = sentinel(self.cols * self.ld).reshape(self.cols, self.ld)
+        self.sent = SENTINEL32 if M.dtype == np.float32 else SENTINEL
+        body = sentinel(self.cols * self.ld, dtype).reshape(self.cols, self.ld)
         body[:, :self.rows] = M.T
-        self.full = np.concatenate([sentinel(GUARD), body.ravel(), sentinel(GUARD)])
+        self.full = np.concatenate([sentinel(GUARD, dtype), body.ravel(), sentinel(GUARD, dtype)])
         self.n = self.cols * self.ld
         self.before = self.data.copy()
 
@@ -148,7 +198,7 @@ class Mat:
 
     def guards_ok(self):
         f = bits(self.full)
-        return bool((f[:GUARD] == SENTINEL).all() and (f[GUARD + self.n:] == SENTINEL).all())
+        return bool((f[:GUARD] == self.sent).all() and (f[GUARD + self.n:] == self.sent).all())
 
     def lift(self, m2d):
         """rows x cols boolean -> mask over the payload (False in the skew rows)"""
@@ -269,7 +319,19 @@ SIG = {
     "vec_axpy": "idpp", "vec_scale": "ipdp", "vec_sum": "ipp", "grad_g_rows": "iiiiPPp", "grad_binv_rows": "iiiippp",
     "grad_pair_sums": "ipipiiippliihddipp", "grad_pairs_rows": "pipiiippppiihddipp",
     "grad_finish": "hddiHH", "grad_finish_d": "hddiiHH", "grad_consts": "hHH",
+    # include/gpak_dev_f32.h (group `f32`): f float, I host int array (a list)
+    "gemm_nt_f32": "iiifplplfpl", "fill_f32": "piipiiiihdipl", "lower_to_f32": "plipl", "vec_to_f32": "plp",
+    "rowsumsq_f32": "pliiipi", "fwd_subst_f32": "pliiplpIi",
 }
+F32_OPS = ("gemm_nt_f32", "fill_f32", "lower_to_f32", "vec_to_f32", "rowsumsq_f32", "fwd_subst_f32")
+F32_ENV = ("GPAK_F32_ACC", "GPAK_F32_RSD", "GPAK_F32_TILE")
+
+
+class Off:
+    """a pointer `elems` elements into a Mat's payload (a misaligned operand for a refusal)"""
+
+    def __init__(self, mat, elems):
+        self.mat, self.elems = mat, int(elems)
 HOST_ONLY = ("grad_finish", "grad_finish_d", "grad_consts")       # no stream argument; H: a host array, read or written
 
 
@@ -326,11 +388,59 @@ def precheck(name, a):
     if name == "update_cyclic":
         nb, lb0, n_local, last_width = a[7], a[10], a[11], a[12]
         return OK if (n_local - 1) * (nb // TILE) + last_width // TILE - lb0 * (nb // TILE) <= 0 else None
+    # include/gpak_dev_f32.h; a Mat's payload is 16-byte aligned, an Off by a multiple of 4 floats keeps that
+    odd = lambda x, per: isinstance(x, Off) and x.elems % per != 0
+    same = lambda x, y: (x.mat if isinstance(x, Off) else x) is (y.mat if isinstance(y, Off) else y)
+    if name == "gemm_nt_f32":
+        mt, nt, K, _al, A, lda, B, ldb, _be, Cm, ldc = a
+        if mt <= 0 or nt <= 0:
+            return OK
+        if K < TILE or K % TILE or lda < mt * TILE or ldb < nt * TILE or ldc < mt * TILE or (lda | ldb | ldc) & 3:
+            return EINVAL
+        if odd(A, 4) or odd(B, 4) or odd(Cm, 4) or (same(A, Cm) and (nt != 1 or K != TILE)):
+            return EINVAL
+        return None
+    if name == "fill_f32":
+        _uP, capP, nP, _uQ, capQ, nQ, rows_p, cols_p, kern, _bias, mode, _C, ld = a
+        if rows_p <= 0 or rows_p % TILE or cols_p <= 0 or cols_p % 64 or capP < rows_p or capP & 1:
+            return EINVAL
+        if nP < 0 or nP > rows_p or nQ < 0 or nQ > cols_p or nQ > capQ or ld < rows_p or ld & 1:
+            return EINVAL
+        if mode & HYB:
+            nt, kinds = int(kern[0]), [int(k) for k in kern[1:4]]
+            if nt < 1 or nt > 3 or any(k not in (0, 1, 2) for k in kinds[:nt]):
+                return EINVAL
+        return None
+    if name == "lower_to_f32":
+        _L, ld, Np, _out, ldo = a
+        return EINVAL if Np <= 0 or ld < Np or ldo < Np else None
+    if name == "vec_to_f32":
+        return None if a[1] > 0 else (OK if a[1] == 0 else EINVAL)
+    if name == "rowsumsq_f32":
+        _V, ldv, rows, cols, splits, _part, part_ld = a
+        return EINVAL if rows <= 0 or cols <= 0 or splits < 1 or splits > cols or ldv < rows or part_ld < rows else None
+    if name == "fwd_subst_f32":
+        Wt, ldw, mrows, Np, Lf, ldLf, invf, levels, nlevels = a
+        if mrows <= 0 or mrows % TILE or Np <= 0 or Np % TILE or ldw < mrows or ldLf < Np or (ldw | ldLf) & 3:
+            return EINVAL
+        if odd(Wt, 4) or odd(Lf, 4) or odd(invf, 4) or nlevels < 0 or nlevels > 8:
+            return EINVAL
+        lv = list(levels)[:nlevels]
+        if any((v != TILE) if k == 0 else (v <= lv[k - 1] or v % lv[k - 1]) for k, v in enumerate(lv)):
+            return EINVAL
+        return None
     return None
 
 
 def _buf(x):
     return x.full if isinstance(x, Mat) else x
+
+
+def pay(x):
+    """the payload of a Mat (from `elems` on for an Off), or the array itself"""
+    if isinstance(x, Off):
+        return x.mat.data[x.elems:]
+    return x.data if isinstance(x, Mat) else x
 
 
 class NumpyOps:
@@ -339,20 +449,26 @@ class NumpyOps:
     name = "numpy"
 
     def __init__(self, mut=()):
-        """mut: deliberate faults of the pair pass (np_dist_engine.pair_sums), for test_the_checks_bite"""
+        """mut: deliberate faults of the pair pass (np_dist_engine.pair_sums) or of the float32 restatements (F32Restated),
+        for test_the_checks_bite"""
         import torch
         from np_dist_engine import NumpyDistEngine
         self.torch = torch
         self.nde = NumpyDistEngine(poison_upper=False)
         self.eng = self.nde.np
         self.mut = tuple(mut)
+        self.f32 = F32Restated(mut=self.mut)
+
+    def f32_build(self, env=None):
+        """the build of the fp32 product the calls that follow run under: the GPAK_F32_* variables of the library"""
+        self.f32.wide = (env or {}).get("GPAK_F32_ACC") != "plain"
 
     @staticmethod
     def _ptr(x):
         if x is None:
             return None
         if isinstance(x, Mat):
-            return x.full.ctypes.data + 8 * GUARD
+            return x.full.ctypes.data + x.full.itemsize * GUARD
         return x.ctypes.data
 
     def _t(self, x):
@@ -363,6 +479,8 @@ class NumpyOps:
         rc = precheck(name, a)
         if rc is not None:
             return rc
+        if name in F32_OPS:
+            return getattr(self.f32, name)(*a)
         if name == "coldot":
             blk, ld, Np, J, W, x, s = a
             self.eng.coldot(self._t(blk), ld, Np, J, W, self._t(x), self._t(s))
@@ -432,12 +550,25 @@ class HipOps:
     arrays, runs, synchronises and downloads them again (guard bands included)."""
     name = "hip"
     _ct = {"p": C.c_void_p, "i": C.c_int, "l": C.c_long, "d": C.c_double, "h": C.POINTER(C.c_double), "P": C.POINTER(C.c_void_p),
-           "H": C.POINTER(C.c_double)}
+           "H": C.POINTER(C.c_double), "f": C.c_float, "I": C.POINTER(C.c_int)}
 
     def __init__(self):
         from py_schedule import HipEngine
         self.eng = HipEngine(0)
         self.lib = self.eng.lib
+
+    def f32_build(self, env=None):
+        """Select the build of the fp32 product as the product does: the GPAK_F32_* variables and gpak_reload_tuning.
+        No argument: the environment as the process found it."""
+        if not hasattr(self, "_env0"):
+            self._env0 = {k: os.environ.get(k) for k in F32_ENV}
+        for k in F32_ENV:
+            v = (env or {}).get(k) if env is not None else self._env0[k]
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        self.lib.gpak_reload_tuning()
 
     def call(self, name, *a):
         assert len(a) == len(SIG[name]), name
@@ -449,9 +580,11 @@ class HipOps:
         dev, conv, keep = {}, [], []
 
         def ptr(v):
+            if isinstance(v, Off):
+                return ptr(v.mat) + v.elems * v.mat.full.itemsize
             if id(v) not in dev:
                 dev[id(v)] = (v, self.eng.from_numpy(_buf(v)))
-            return dev[id(v)][1].data_ptr() + (8 * GUARD if isinstance(v, Mat) else 0)
+            return dev[id(v)][1].data_ptr() + (_buf(v).itemsize * GUARD if isinstance(v, Mat) else 0)
 
         for kind, v in zip(SIG[name], a):
             if kind == "p":
@@ -461,6 +594,9 @@ class HipOps:
                 conv.append(keep[-1])
             elif kind == "h":
                 keep.append((C.c_double * len(v))(*[float(t) for t in v]))
+                conv.append(keep[-1])
+            elif kind == "I":
+                keep.append((C.c_int * max(len(v), 1))(*[int(t) for t in v]))
                 conv.append(keep[-1])
             else:
                 conv.append(v)
@@ -489,9 +625,10 @@ def covered_entry_points():
 
 
 def declared_entry_points():
-    """every gpak_dev_* function include/gpak_dev.h declares, and the vector pieces of include/gpak_dist.h"""
+    """every gpak_dev_* function include/gpak_dev.h and include/gpak_dev_f32.h declare, and the vector pieces of
+    include/gpak_dist.h"""
     names = set()
-    for h in ("gpak_dev.h", "gpak_dist.h"):
+    for h in ("gpak_dev.h", "gpak_dev_f32.h", "gpak_dist.h"):
         with open(os.path.join(ROOT, "include", h)) as f:
             names |= set(re.findall(r"^int (gpak_dev_\w+)\(", f.read(), flags=re.M))
     return sorted(names)
@@ -1899,6 +2036,596 @@ def _panel_info(ops, name, what):
 
 for _what in ("success", "-1", "0", "nan", "two failures", "pre-set", "flip"):
     case("panel", f"factor_panel info[{_what}]", ["gpak_dev_factor_panel_co"], what=_what)(_panel_info)
+
+
+# ---- the fp32 prediction kernels alone (group `f32`: include/gpak_dev_f32.h) ---------------------------------------
+# u32 = 2^-24, u64 = 2^-53; references in long double on the float operands taken exactly.  Derivations: the module
+# docstring, "The fp32 prediction kernels alone".
+F32_BUILDS = {       # the GPAK_F32_* environment of each build the launcher of csrc/gemm_f32.hip can pick
+    "wide,rsd=2": {"GPAK_F32_RSD": "2"}, "wide,rsd=4": {}, "wide,rsd=8": {"GPAK_F32_RSD": "8"},
+    "wide,rsd=16": {"GPAK_F32_RSD": "16"}, "plain": {"GPAK_F32_ACC": "plain"},
+    "plain,tile=64": {"GPAK_F32_ACC": "plain", "GPAK_F32_TILE": "64"},
+}
+F32_WIDE = tuple(b for b in F32_BUILDS if b.startswith("wide"))
+F32_SHAPES = ((1, 1, 128), (2, 1, 128), (3, 2, 128), (1, 1, 256), (2, 3, 384), (9, 9, 256), (17, 1, 640))
+F32_AB = ((1.0, 0.0), (-1.0, 1.0), (0.75, -0.5))
+F32_POS_K = 4096
+
+
+def f32_sum_k(A, B, k0, k1, sequential):
+    """sum over k in [k0, k1) of A[:, k] B[:, k] in float32: each product rounded, then added, one k at a time
+    (sequential), or in the order of the host's float32 BLAS"""
+    if not sequential:
+        return np.asarray(A[:, k0:k1] @ B[:, k0:k1].T, dtype=F32)
+    acc = np.zeros((A.shape[0], B.shape[0]), dtype=F32)
+    for k in range(k0, k1):
+        acc += np.multiply.outer(A[:, k], B[:, k])
+    return acc
+
+
+def f32_product(A, B, alpha, beta, C0, wide, sequential=False):
+    """beta C0 + alpha A B^T as csrc/gemm_f32.hip forms it.  wide (and K > 128): chunks of 128 accumulated in float32 from
+    zero, the chunk sums added in float64, alpha * total + beta * C0 in float64, rounded once.  Otherwise one float32 sum
+    over all of K, alpha * sum rounded, then the fused beta * C0 + that.  beta == 0 never reads C0."""
+    A, B = np.ascontiguousarray(A, dtype=F32), np.ascontiguousarray(B, dtype=F32)
+    K = A.shape[1]
+    if wide and K > TILE:
+        tot = np.zeros((A.shape[0], B.shape[0]))
+        for c in range(0, K, TILE):
+            tot += f32_sum_k(A, B, c, min(K, c + TILE), sequential).astype(np.float64)
+        v = float(alpha) * tot
+        if beta != 0:
+            v = v + float(beta) * np.asarray(C0, dtype=np.float64)
+        return v.astype(F32)
+    v = F32(alpha) * f32_sum_k(A, B, 0, K, sequential)
+    if beta != 0:
+        v = (float(beta) * np.asarray(C0, dtype=np.float64) + v.astype(np.float64)).astype(F32)
+    return v
+
+
+def f32_ladder(W, Lf, iv, levels, wide, sequential=False, mut=()):
+    """fs_block_f32 (csrc/predict.hip) in float32 on W (mrows x Np), in place: a block of width lv[k] child by child of
+    width lv[k-1] (the last one clipped), W_j := W_j inv(D_j)^T at 128 columns, after each child ONE update of the rest of
+    the block.  iv: (Np / 128, 2, 128, 128), the pairs of inverse blocks as they lie in memory."""
+    lv = list(levels) or [TILE, 512]
+    Np = W.shape[1]
+    lv.append(Np if Np > lv[-1] else lv[-1] + 1)
+
+    def block(J0, Wd, k):
+        if k == 0:
+            c = slice(J0, J0 + TILE)
+            Binv = iv[J0 // TILE, 1 if "f32 inv transposed" in mut else 0].T      # B[n, k] = memory[n + 128 k]
+            W[:, c] = f32_product(W[:, c], Binv, 1.0, 0.0, None, wide, sequential)
+            return
+        cw = lv[k - 1]
+        for j0 in range(J0, J0 + Wd, cw):
+            w = min(cw, J0 + Wd - j0)
+            if not ("f32 clip skipped" in mut and w < cw):
+                block(j0, w, k - 1)
+            if J0 + Wd - j0 - w > 0:
+                rest = slice(j0 + w, J0 + Wd)
+                W[:, rest] = f32_product(W[:, j0:j0 + w], Lf[rest, j0:j0 + w], -1.0, 1.0, W[:, rest], wide, sequential)
+    block(0, Np, len(lv) - 1)
+    return W
+
+
+class F32Restated:
+    """The operations of include/gpak_dev_f32.h restated in NumPy float32 / float64 on the cases' buffers.  mut: deliberate
+    faults (test_the_checks_bite)."""
+
+    def __init__(self, mut=()):
+        self.mut, self.wide = tuple(mut), True
+
+    @staticmethod
+    def _view(x, rows, cols, ld):
+        return pay(x)[:cols * ld].reshape(cols, ld).T[:rows]
+
+    def gemm_nt_f32(self, mt, nt, K, alpha, A, lda, B, ldb, beta, Cm, ldc):
+        m, n = mt * TILE, nt * TILE
+        a, b = self._view(A, m, K, lda).copy(), self._view(B, n, K, ldb).copy()
+        Cv = self._view(Cm, m, n, ldc)
+        c0 = Cv.copy()
+        if "f32 short k" in self.mut and K > TILE:
+            K -= TILE
+        plain = "f32 plain" in self.mut
+        v = f32_product(a[:, :K], b[:, :K], alpha, beta, c0, self.wide and not plain, sequential=plain)
+        if "f32 beta0" in self.mut and beta == 0:
+            v = v + F32(0) * c0
+        if "f32 unpermuted" in self.mut:      # MFMA tile i of a wave's 64 rows holds the rows 4 j + i
+            v = v.reshape(m // 64, 16, 4, n).transpose(0, 2, 1, 3).reshape(m, n)
+        Cv[...] = v
+        return OK
+
+    def fill_f32(self, uP, capP, nP, uQ, capQ, nQ, rows_p, cols_p, kern, bias, mode, Cm, ld):
+        from np_engine import NumpyEngine
+        terms, white = NumpyEngine.decode_kern(kern) if mode & HYB else ([(0, [float(t) for t in kern[:8]])], 0.0)
+        up, uq = pay(uP)[:15 * capP].reshape(15, capP), pay(uQ)[:15 * capQ].reshape(15, capQ)
+        keep = nP + 1 if ("f32 pair kept" in self.mut and nP & 1 and nP < rows_p) else nP
+        sel = [0, 1, 2] if "f32 no col4" in self.mut else [0, 1, 2, 4]
+        k = np.full((keep, nQ), F32(bias), dtype=F32)
+        with np.errstate(invalid="ignore"):
+            for t, (kind, p) in enumerate(terms):
+                P, Q = up[5 * t:5 * t + 5][sel][:, :keep], uq[5 * t:5 * t + 5][sel][:, :nQ]
+                d = ((P[:, :, None] - Q[:, None, :]) ** 2).sum(axis=0).astype(F32)      # the distance in float64, rounded once
+                if kind == 2 and "f32 rbf as exp" not in self.mut:
+                    k += F32(p[2] * p[2]) * np.exp((F32(-0.5) * F32(p[1])) * d)
+                else:
+                    k += F32((p[6] if kind == 0 else p[2] if kind == 2 else p[1]) ** 2) * np.exp(-np.sqrt(d))
+                if "f32 white" in self.mut and t == 0:
+                    k += np.where(d == 0, F32(white), F32(0))
+        out = np.zeros((rows_p, cols_p), dtype=F32)
+        out[:keep, :nQ] = k
+        self._view(Cm, rows_p, cols_p, ld)[...] = out
+        return OK
+
+    def lower_to_f32(self, L, ld, Np, out, ldo):
+        Lv = self._view(L, Np, Np, ld)
+        low = np.arange(Np)[:, None] >= np.arange(Np)[None, :]
+        with np.errstate(all="ignore"):
+            self._view(out, Np, Np, ldo)[...] = np.where(low, np.where(low, Lv, 0.0).astype(F32), F32(0))
+        return OK
+
+    def vec_to_f32(self, vin, n, out):
+        with np.errstate(all="ignore"):
+            pay(out)[:n] = pay(vin)[:n].astype(F32)
+        return OK
+
+    def rowsumsq_f32(self, V, ldv, rows, cols, splits, part, part_ld):
+        Vv = self._view(V, rows, cols, ldv).astype(np.float64)
+        cps = (cols + splits - 1) // splits
+        pv = pay(part)[:splits * part_ld].reshape(splits, part_ld)
+        for s in range(splits):
+            c0, c1 = s * cps, min(cols, (s + 1) * cps)
+            if "f32 odd tail" in self.mut and (c1 - c0) & 1:
+                c1 -= 1
+            pv[s, :rows] = (Vv[:, c0:c1] ** 2).sum(axis=1) if c1 > c0 else 0.0
+        return OK
+
+    def fwd_subst_f32(self, Wt, ldw, mrows, Np, Lf, ldLf, invf, levels, nlevels):
+        Wv = self._view(Wt, mrows, Np, ldw)
+        iv = pay(invf)[:Np // TILE * 2 * TILE * TILE].reshape(Np // TILE, 2, TILE, TILE)
+        Wv[...] = f32_ladder(Wv.copy(), self._view(Lf, Np, Np, ldLf).copy(), iv, list(levels)[:nlevels], self.wide, mut=self.mut)
+        return OK
+
+
+# -- the product -------------------------------------------------------------------------------------
+def f32_operands(mt, nt, K):
+    """A with row scales 10^-3 .. 10^3 (a permuted row shows), B and C standard_normal, all float32; A B^T in long double"""
+    def make():
+        rng = rng_for(f"gemm_nt_f32[{mt},{nt},{K}]")
+        A = (rng.standard_normal((mt * TILE, K)) * 10.0 ** rng.integers(-3, 4, (mt * TILE, 1))).astype(F32)
+        B, C0 = rng.standard_normal((nt * TILE, K)).astype(F32), rng.standard_normal((mt * TILE, nt * TILE)).astype(F32)
+        A64, B64 = A.astype(np.float64), B.astype(np.float64)
+        return A, B, C0, mm_ld(A64, B64), np.abs(A64) @ np.abs(B64).T
+    return memo(("f32 operands", mt, nt, K), make)
+
+
+def f32_bound(wide, K, alpha, beta, aprod, C0, exact):
+    mag = abs(alpha) * aprod + abs(beta) * np.abs(C0)
+    if wide:
+        return 130 * U32 * abs(alpha) * aprod + U32 * np.abs(exact).astype(np.float64) + (K // TILE + 3) * U * mag
+    return (K + 2) * U32 * mag
+
+
+def _gemm_f32(ops, name, build, mt, nt, K):
+    env = F32_BUILDS[build]
+    wide = build in F32_WIDE
+    A0, B0, C00, prod, aprod = f32_operands(mt, nt, K)
+    m, n = mt * TILE, nt * TILE
+    lda, ldb, ldc = m + 36, n + 40, m + 44
+    res = Result()
+    ops.f32_build(env)
+    try:
+        for alpha, beta in F32_AB:
+            A, B = Mat(A0, lda, F32), Mat(B0, ldb, F32)
+            Cm = Mat(np.full((m, n), np.nan) if beta == 0 else C00, ldc, F32)      # beta == 0: C is never read
+            res.rc(f"gemm_nt_f32[{alpha},{beta}]", ops.call("gemm_nt_f32", mt, nt, K, alpha, A, lda, B, ldb, beta, Cm, ldc))
+            c0 = np.zeros((m, n)) if beta == 0 else C00.astype(np.float64)
+            exact = LD(alpha) * prod + LD(beta) * c0
+            res.add(f"C[{alpha},{beta}]", Cm, exact, f32_bound(wide, K, alpha, beta, aprod, c0, exact), True)
+            res.add(f"A[{alpha},{beta}]", A).add(f"B[{alpha},{beta}]", B)
+        if nt == 1 and K == TILE:              # the inverse product of the ladder: A == C, alpha = 1, beta = 0
+            A, B = Mat(A0, lda, F32), Mat(B0, ldb, F32)
+            res.rc("gemm_nt_f32[in place]", ops.call("gemm_nt_f32", mt, 1, K, 1.0, A, lda, B, ldb, 0.0, A, lda))
+            res.add("A=C[in place]", A, prod, f32_bound(wide, K, 1.0, 0.0, aprod, np.zeros((m, n)), prod), True).add("B[in place]", B)
+    finally:
+        ops.f32_build()
+    return res
+
+
+for _b in F32_BUILDS:
+    for _mt, _nt, _K in F32_SHAPES:
+        case("f32", f"gemm_nt_f32[{_b}][{_mt},{_nt},{_K}]", ["gpak_dev_gemm_nt_f32"], build=_b, mt=_mt, nt=_nt, K=_K)(_gemm_f32)
+
+
+def _gemm_f32_agree(ops, name, mt, nt, K):
+    """The four wide builds differ in the prefetch ring and the occupancy only: per accumulator the same MFMAs in the
+    same order, the same float64 additions, the same epilogue -- the same bits."""
+    A0, B0, C00, _prod, _aprod = f32_operands(mt, nt, K)
+    m, n = mt * TILE, nt * TILE
+    lda, ldb, ldc = m + 36, n + 40, m + 44
+    res, first = Result(), None
+    try:
+        for b in F32_WIDE:
+            ops.f32_build(F32_BUILDS[b])
+            A, B, Cm = Mat(A0, lda, F32), Mat(B0, ldb, F32), Mat(C00, ldc, F32)
+            res.rc(b, ops.call("gemm_nt_f32", mt, nt, K, 0.75, A, lda, B, ldb, -0.5, Cm, ldc))
+            first = Cm if first is None else first
+            res.rc(f"elements of {b} that differ from {F32_WIDE[0]}", int(np.count_nonzero(bits(Cm.full) != bits(first.full))))
+            res.add(b, Cm, free=True)
+    finally:
+        ops.f32_build()
+    return res
+
+
+for _mt, _nt, _K in ((2, 3, 384), (9, 9, 256)):
+    case("f32", f"gemm_nt_f32[the wide builds agree][{_mt},{_nt},{_K}]", ["gpak_dev_gemm_nt_f32"], mt=_mt, nt=_nt, K=_K)(_gemm_f32_agree)
+
+
+def f32_positive():
+    """(2, 1, F32_POS_K) with both operands uniform on [0.5, 1.5): every term positive, a running float32 sum grows
+    linearly.  The worst error relative to sum|terms| of the chunked and of the plain restatement against long double."""
+    def make():
+        rng, K = rng_for("gemm_nt_f32[positive]"), F32_POS_K
+        A, B = rng.uniform(0.5, 1.5, (2 * TILE, K)).astype(F32), rng.uniform(0.5, 1.5, (TILE, K)).astype(F32)
+        A64, B64 = A.astype(np.float64), B.astype(np.float64)
+        exact = sum(mm_ld(A64[:, c:c + 2048], B64[:, c:c + 2048]) for c in range(0, K, 2048))
+        s = exact.astype(np.float64)                                    # = sum|terms|
+        err = lambda v: float((np.abs(v.astype(LD) - exact).astype(np.float64) / s).max())
+        chunked = err(f32_product(A, B, 1.0, 0.0, None, True, sequential=True))
+        plain = err(f32_product(A, B, 1.0, 0.0, None, False, sequential=True))
+        return A, B, exact, s, chunked, plain
+    return memo(("f32 positive",), make)
+
+
+def _gemm_f32_is_wide(ops, name, build):
+    A0, B0, exact, s, chunked, plain = f32_positive()
+    tol = 8.0 * chunked                                                 # the house rule, relative to sum|terms|
+    K, lda, ldb, ldc = F32_POS_K, 2 * TILE + 36, TILE + 40, 2 * TILE + 44
+    res = Result()
+    res.info["chunked restatement: error / (u32 sum|terms|)"] = chunked / U32
+    res.info["plain restatement: error / (u32 sum|terms|)"] = plain / U32
+    res.info["plain / tolerance"] = plain / tol
+    res.rc("the plain restatement is within 2 x the tolerance: the input does not discriminate", int(plain < 2 * tol))
+    ops.f32_build(F32_BUILDS[build])
+    try:
+        A, B, Cm = Mat(A0, lda, F32), Mat(B0, ldb, F32), Mat(np.full((2 * TILE, TILE), np.nan), ldc, F32)
+        res.rc("gemm_nt_f32", ops.call("gemm_nt_f32", 2, 1, K, 1.0, A, lda, B, ldb, 0.0, Cm, ldc))
+    finally:
+        ops.f32_build()
+    return res.add("C", Cm, exact, tol * s, True).add("A", A).add("B", B)
+
+
+for _b in F32_WIDE:
+    case("f32", f"gemm_nt_f32[{_b}][accumulates wide]", ["gpak_dev_gemm_nt_f32"], build=_b)(_gemm_f32_is_wide)
+
+
+def _gemm_f32_refused(ops, name):
+    rng = rng_for(name)
+    m, K = TILE, 2 * TILE
+    lda = m + 36
+    A, B, Cm = (Mat(rng.standard_normal((m, K)).astype(F32), lda, F32) for _ in range(3))
+    res = Result()
+    call = lambda label, want, *a: res.rc(label, ops.call("gemm_nt_f32", *a), want)
+    call("K=64", EINVAL, 1, 1, 64, 1.0, A, lda, B, lda, 0.0, Cm, lda)
+    call("K=192", EINVAL, 1, 1, 192, 1.0, A, lda, B, lda, 0.0, Cm, lda)
+    call("K=0", EINVAL, 1, 1, 0, 1.0, A, lda, B, lda, 0.0, Cm, lda)
+    call("lda no multiple of 4", EINVAL, 1, 1, TILE, 1.0, A, lda + 2, B, lda, 0.0, Cm, lda)
+    call("ldb below the rows", EINVAL, 1, 1, TILE, 1.0, A, lda, B, TILE - 4, 0.0, Cm, lda)
+    call("ldc below the rows", EINVAL, 1, 2, TILE, 1.0, A, lda, B, lda, 0.0, Cm, TILE - 4)
+    call("A misaligned", EINVAL, 1, 1, TILE, 1.0, Off(A, 1), lda, B, lda, 0.0, Cm, lda)
+    call("C misaligned", EINVAL, 1, 1, TILE, 1.0, A, lda, B, lda, 0.0, Off(Cm, 2), lda)
+    call("A == C, nt=2", EINVAL, 1, 2, TILE, 1.0, A, lda, B, lda, 0.0, A, lda)
+    call("A == C, K=256", EINVAL, 1, 1, K, 1.0, A, lda, B, lda, 0.0, A, lda)
+    call("mt=0", OK, 0, 1, TILE, 1.0, A, lda, B, lda, 0.0, Cm, lda)
+    call("nt=0", OK, 1, 0, TILE, 1.0, A, lda, B, lda, 0.0, Cm, lda)
+    return res.add("A", A).add("B", B).add("C", Cm)
+
+
+case("f32", "gemm_nt_f32->EINVAL / no-op", ["gpak_dev_gemm_nt_f32"])(_gemm_f32_refused)
+
+
+# -- the cross-kernel fill ----------------------------------------------------------------------------
+FILL32_NP, FILL32_ROWS, FILL32_NQ, FILL32_COLS = 131, 256, 70, 128
+FILL32_TWIN = (130, 33)                # P[130] (the last valid row: a lane's first element) == Q[33]
+FILL32_C0, FILL32_C1 = 10.0, 12.0      # the module docstring derives them
+FILL32_COMPS = {                       # name -> (terms, input columns, Sigma_White)
+    "expans": ([(0, None)], 3, 0.0), "expans+exp": ([(0, None), (1, EXP_P)], 3, 0.0), "rbf": ([(2, RBF_P)], 3, 0.0),
+    "expans+rbf+bias,white=0.1": (HYB_TERMS, 3, HYB_WHITE), "expans+exp+rbf": ([(0, None), (1, EXP_P), (2, RBF_P)], 3, 0.0),
+    "expans d4": ([(0, None)], 4, 0.0),
+}
+
+
+class Fill32Data:
+    """nP test-side and nQ train-side drill-hole points, one pair coincident, transformed by the engine under test; rows
+    from n on of every transformed array hold the sentinel.  The cross-kernel in long double and its bound."""
+
+    def __init__(self, ops, comp):
+        from gp_ss_ak_amd import synth
+        terms, cols, white = FILL32_COMPS[comp]
+        E = np.array(synth.DEFAULT_EXPANS, dtype=np.float64)
+        self.terms = [(k, list(E) if p is None else list(p)) for k, p in terms]
+        self.bias, self.white = synth.DEFAULT_BIAS, white
+        nP, nQ, capP, capQ = FILL32_NP, FILL32_NQ, FILL32_ROWS, FILL32_COLS
+        self.hyb = not (len(terms) == 1 and terms[0][0] == 0)
+        self.mode = 1 | (D4 if cols == 4 else 0) | (HYB if self.hyb else 0)
+        self.kern = serialise(self.terms, white) if self.hyb else list(E)
+        self.kern_no_white = serialise(self.terms, 0.0) if self.hyb else list(E)
+        X, _y = synth.drillholes4(nP + nQ) if cols == 4 else synth.drillholes(nP + nQ)
+        X = np.array(X, dtype=np.float64)
+        X[nP + FILL32_TWIN[1]] = X[FILL32_TWIN[0]]
+        mu = np.zeros(4)
+        mu[:cols] = X.sum(axis=0) / len(X)
+
+        def transformed(Xs, cap):
+            n = len(Xs)
+            xs = np.zeros((4, cap))
+            xs[:cols, :n] = Xs.T
+            u, u2 = np.zeros(15 * cap), np.zeros(15 * cap)
+            for v in (u, u2):
+                assert ops.call("transform_k", xs.ravel(), cap, n, cap, self.kern, self.mode, mu, v) == OK
+            assert np.array_equal(bits(u), bits(u2)), "two transforms of the same points differ"
+            u = u.reshape(15, cap).copy()
+            u[:, n:] = sentinel(1)[0]
+            return u
+        self.uP, self.uQ = transformed(X[:nP], capP), transformed(X[nP:], capQ)
+        nt = len(self.terms)
+        k, k3, ev = LD(self.bias), LD(self.bias), 0.0
+        for t, (kind, p) in enumerate(self.terms):
+            P, Q = self.uP[5 * t:5 * t + 5, :nP].astype(LD), self.uQ[5 * t:5 * t + 5, :nQ].astype(LD)
+            d3 = sum((P[c][:, None] - Q[c][None, :]) ** 2 for c in (0, 1, 2))
+            d2 = d3 + (P[4][:, None] - Q[4][None, :]) ** 2
+            var2 = LD(np.float64(p[6 if kind == 0 else 2 if kind == 2 else 1]) ** 2)
+            arg = (lambda d: LD(0.5) * LD(p[1]) * d) if kind == 2 else np.sqrt
+            k, k3 = k + var2 * np.exp(-arg(d2)), k3 + var2 * np.exp(-arg(d3))
+            ev = ev + (var2 * np.exp(-arg(d2))).astype(np.float64) * (FILL32_C0 + FILL32_C1 * arg(d2).astype(np.float64)) * U32
+        self.k, self.k3 = k, k3
+        self.bound = ev + (nt + 2) * U32 * np.abs(k).astype(np.float64)
+        self.twin_exact = float(self.bias + sum(np.float64(p[6 if kd == 0 else 2 if kd == 2 else 1]) ** 2 for kd, p in self.terms))
+
+
+def fill32_data(ops, comp):
+    return memo(("fill32", ops.name, comp), lambda: Fill32Data(ops, comp))
+
+
+def _fill_f32(ops, name, comp):
+    d = fill32_data(ops, comp)
+    nP, nQ, rows_p, cols_p = FILL32_NP, FILL32_NQ, FILL32_ROWS, FILL32_COLS
+    ld = rows_p + 34
+    uP, uQ = Mat(d.uP.ravel()), Mat(d.uQ.ravel())
+    Cm = Mat(rng_for(name).standard_normal((rows_p, cols_p)), ld, F32)
+    res = Result().rc("fill_f32", ops.call("fill_f32", uP, rows_p, nP, uQ, cols_p, nQ, rows_p, cols_p, d.kern, d.bias, d.mode, Cm, ld))
+    ref, bound = np.zeros((rows_p, cols_p), dtype=LD), np.zeros((rows_p, cols_p))
+    ref[:nP, :nQ], bound[:nP, :nQ] = d.k, d.bound
+    res.add("C", Cm, ref, bound, True).add("uP", uP).add("uQ", uQ)
+    pad = np.ones((rows_p, cols_p), dtype=bool)
+    pad[:nP, :nQ] = False
+    res.rc("rows >= nP or columns >= nQ that are not +0.0f", int(np.count_nonzero(bits(Cm.get()[pad].copy()))))
+    i, j = FILL32_TWIN
+    res.info["coincident pair: |k - (bias + sum var2)| / u32"] = abs(float(Cm.get()[i, j]) - d.twin_exact) / U32
+    if comp == "expans d4":
+        res.rc("the 4th column moves no element by 100 bounds", int(not (np.abs(d.k - d.k3).astype(np.float64) > 100 * d.bound).any()))
+    if d.white:                          # Kern_White contributes nothing to a train x test block: the same bits without it
+        C2 = Mat(Cm.was(), ld, F32)
+        res.rc("fill_f32[white=0]", ops.call("fill_f32", uP, rows_p, nP, uQ, cols_p, nQ, rows_p, cols_p, d.kern_no_white, d.bias,
+                                            d.mode, C2, ld))
+        res.rc("elements Sigma_White changes", int(np.count_nonzero(bits(C2.full) != bits(Cm.full)))).add("C[white=0]", C2, free=True)
+    return res
+
+
+for _c in FILL32_COMPS:
+    case("f32", f"fill_f32[{_c}]", ["gpak_dev_fill_f32", "gpak_dev_transform_k"], comp=_c)(_fill_f32)
+
+
+def _fill_f32_refused(ops, name):
+    d = fill32_data(ops, "expans+exp")
+    rows_p, cols_p, ld = FILL32_ROWS, FILL32_COLS, FILL32_ROWS + 34
+    uP, uQ = Mat(d.uP.ravel()), Mat(d.uQ.ravel())
+    Cm = Mat(rng_for(name).standard_normal((rows_p, cols_p)), ld, F32)
+    res = Result()
+    good = dict(capP=rows_p, nP=FILL32_NP, capQ=cols_p, nQ=FILL32_NQ, rows_p=rows_p, cols_p=cols_p, kern=d.kern, ld=ld)
+    four = list(d.kern)
+    four[0] = 4
+    for label, ch in (("rows_p=192", dict(rows_p=192)), ("cols_p=96", dict(cols_p=96)), ("capP below rows_p", dict(capP=rows_p - 2)),
+                      ("nP above rows_p", dict(nP=rows_p + 1)), ("nQ above cols_p", dict(nQ=cols_p + 1)), ("ld odd", dict(ld=ld + 1)),
+                      ("ld below rows_p", dict(ld=rows_p - 2)), ("four children", dict(kern=four))):
+        a = dict(good, **ch)
+        res.rc(label, ops.call("fill_f32", uP, a["capP"], a["nP"], uQ, a["capQ"], a["nQ"], a["rows_p"], a["cols_p"], a["kern"], d.bias,
+                               d.mode, Cm, a["ld"]), EINVAL)
+    return res.add("C", Cm).add("uP", uP).add("uQ", uQ)
+
+
+case("f32", "fill_f32->EINVAL", ["gpak_dev_fill_f32"])(_fill_f32_refused)
+
+
+# -- the conversions ------------------------------------------------------------------------------------
+F32_EDGE_VALUES = (          # halfway cases between two floats, float denormals and below, signed zeros, the largest magnitudes
+    1.0 + 2.0 ** -24, 1.0 + 3 * 2.0 ** -24, 1.0 + 2.0 ** -24 + 2.0 ** -52, 1.0 + 2.0 ** -24 - 2.0 ** -53, -(1.0 + 2.0 ** -24),
+    2.0 ** -126, 2.0 ** -127, 2.0 ** -140, 1.5 * 2.0 ** -149, 2.5 * 2.0 ** -149, 2.0 ** -150, 2.0 ** -150 * (1 + 2.0 ** -52),
+    -(2.0 ** -150), 1e-40, 1e-46, -1e-46, 1e-300, 0.0, -0.0, 3e38, -3e38, 16777217.0)
+
+
+def _convert_f32(ops, name):
+    rng = rng_for(name)
+    Np = 256
+    ld, ldo = Np + 34, Np + 68
+    L = rng.standard_normal((Np, Np))
+    low = np.arange(Np)[:, None] >= np.arange(Np)[None, :]
+    pos = np.argwhere(low)
+    pick = pos[rng.permutation(len(pos))[:4 * len(F32_EDGE_VALUES)]]
+    for q, (r, c) in enumerate(pick):
+        L[r, c] = F32_EDGE_VALUES[q % len(F32_EDGE_VALUES)]
+    for q, v in enumerate(F32_EDGE_VALUES[:Np]):         # and on the diagonal
+        L[q + 3, q + 3] = v
+    L[~low] = sentinel(1)[0]                                 # above the diagonal nothing is read
+    Lm, out = Mat(L, ld), Mat(rng.standard_normal((Np, Np)), ldo, F32)
+    res = Result().rc("lower_to_f32", ops.call("lower_to_f32", Lm, ld, Np, out, ldo))
+    with np.errstate(all="ignore"):
+        want = np.where(low, np.where(low, L, 0.0).astype(F32), F32(0))
+    res.rc("lower_to_f32: elements whose bits are not np.float32(L) / +0.0f", int(np.count_nonzero(bits(out.get().copy()) != bits(want))))
+    res.add("out", out, want.astype(LD), np.zeros((Np, Np)), True).add("L", Lm)
+    for n in (1, 255, 256, 2 * TILE * TILE + 1):
+        v = rng.standard_normal(n + 1)
+        v[:min(n, len(F32_EDGE_VALUES))] = F32_EDGE_VALUES[:n]
+        vin, vout = Mat(v), Mat(rng.standard_normal(n + 1), dtype=F32)
+        res.rc(f"vec_to_f32[n={n}]", ops.call("vec_to_f32", vin, n, vout))
+        with np.errstate(all="ignore"):
+            w = v[:n].astype(F32)
+        res.rc(f"vec_to_f32[n={n}]: elements whose bits are not np.float32(in)", int(np.count_nonzero(bits(vout.get()[:n, 0].copy()) != bits(w))))
+        idx = np.arange(n + 1)[:, None] < n
+        res.add(f"out[n={n}]", vout, np.concatenate([w, [0]]).astype(LD), np.zeros(n + 1), idx).add(f"in[n={n}]", vin)
+    o2 = Mat(np.zeros((8, 8)), dtype=F32)
+    res.rc("lower_to_f32[ldo below Np]", ops.call("lower_to_f32", Lm, ld, Np, o2, Np - 4), EINVAL)
+    res.rc("lower_to_f32[Np=0]", ops.call("lower_to_f32", Lm, ld, 0, o2, ldo), EINVAL)
+    res.rc("vec_to_f32[n=0]", ops.call("vec_to_f32", Lm, 0, o2), OK)
+    return res.add("o2", o2)
+
+
+case("f32", "lower_to_f32,vec_to_f32[Np=256]", ["gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32"])(_convert_f32)
+
+
+# -- the row sums of squares -----------------------------------------------------------------------------
+def _rowsumsq_f32(ops, name, rows, cols, splits):
+    rng = rng_for(name)
+    ldv, part_ld = rows + 36, rows + 7
+    V = Mat(rng.standard_normal((rows, cols)).astype(F32), ldv, F32)
+    part = Mat(rng.standard_normal((part_ld, splits)), part_ld)
+    res = Result().rc("rowsumsq_f32", ops.call("rowsumsq_f32", V, ldv, rows, cols, splits, part, part_ld))
+    v2 = V.was().astype(LD) ** 2
+    cps = (cols + splits - 1) // splits
+    ref, bound = np.zeros((part_ld, splits), dtype=LD), np.zeros((part_ld, splits))
+    for s in range(splits):
+        c0, c1 = s * cps, min(cols, (s + 1) * cps)
+        ref[:rows, s] = v2[:, c0:c1].sum(axis=1)
+        bound[:rows, s] = (max(c1 - c0, 0) + 2) * U * ref[:rows, s].astype(np.float64)
+    res.add("part", part, ref, bound, np.arange(part_ld)[:, None] < rows).add("V", V)
+    tot, tref = part.get()[:rows].astype(LD).sum(axis=1), v2.sum(axis=1)
+    err = np.abs(tot - tref).astype(np.float64)
+    r = np.where(err == 0, 0.0, err / ((cols + 2) * U * tref.astype(np.float64)))
+    r[~np.isfinite(err)] = np.inf
+    res.info["sum over the splits: worst error / bound"] = float(r.max())
+    return res.rc("rows whose sum over the splits is outside (cols + 2) u64 sum v^2", int(np.count_nonzero(~(r <= 1.0))))
+
+
+for _rows in (1, 255, 256, 300):
+    for _cols, _sp in ((640, 1), (640, 3), (640, 64), (5, 5), (639, 3)):
+        case("f32", f"rowsumsq_f32[rows={_rows},cols={_cols},splits={_sp}]", ["gpak_dev_rowsumsq_f32"], rows=_rows, cols=_cols,
+             splits=_sp)(_rowsumsq_f32)
+
+
+def _rowsumsq_f32_refused(ops, name):
+    rng = rng_for(name)
+    V, part = Mat(rng.standard_normal((8, 5)), 12, F32), Mat(rng.standard_normal((9, 5)), 9)
+    res = Result()
+    for label, a in (("splits=0", (12, 8, 5, 0, 9)), ("splits above cols", (12, 8, 5, 6, 9)), ("rows=0", (12, 0, 5, 1, 9)),
+                     ("ldv below rows", (7, 8, 5, 1, 9)), ("part_ld below rows", (12, 8, 5, 1, 7))):
+        res.rc(label, ops.call("rowsumsq_f32", V, a[0], a[1], a[2], a[3], part, a[4]), EINVAL)
+    return res.add("V", V).add("part", part)
+
+
+case("f32", "rowsumsq_f32->EINVAL", ["gpak_dev_rowsumsq_f32"])(_rowsumsq_f32_refused)
+
+
+# -- the ladder of the forward substitution -------------------------------------------------------------
+LADDER_NP = 640
+LADDER_LEVELS = ((128, 512), (128, 256), (128,), (128, 256, 1024))
+
+
+class Ladder32:
+    """The 640-row factor of the group `grad`, its fp32 image through gpak_dev_lower_to_f32 and its inverse blocks through
+    gpak_dev_vec_to_f32 (the conversions feed the substitution as in the product), and Lf^-1 in long double."""
+
+    def __init__(self, ops):
+        f = factor_for(ops, LADDER_NP, 256)
+        Np = LADDER_NP
+        self.ld, self.ldLf = Np + 34, Np + 68
+        low = np.arange(Np)[:, None] >= np.arange(Np)[None, :]
+        Lm = Mat(np.where(low, f.L, sentinel(1)[0]), self.ld)
+        Lf = Mat(rng_for("ladder Lf").standard_normal((Np, Np)), self.ldLf, F32)
+        inv = np.concatenate([p.inv for p in f.cols])
+        assert inv.size == Np // TILE * 2 * TILE * TILE
+        invm, invf = Mat(inv), Mat(np.zeros(inv.size), dtype=F32)
+        assert ops.call("lower_to_f32", Lm, self.ld, Np, Lf, self.ldLf) == OK and ops.call("vec_to_f32", invm, inv.size, invf) == OK
+        assert Lf.guards_ok() and invf.guards_ok()
+        self.Lf, self.invf = Lf.get().copy(), invf.get()[:, 0].copy()
+        assert np.array_equal(bits(self.invf), bits(inv.astype(F32))) and not np.triu(self.Lf, 1).any()
+        self.Li = tri_inv_ld(self.Lf.astype(np.float64))
+        self.aLi = np.abs(self.Li).astype(np.float64)
+        self._rhs = {}
+
+    def rhs(self, mrows):
+        """W standard_normal (two columns more than Np: not the call's), W Lf^-T in long double, |W| |Lf^-T|"""
+        if mrows not in self._rhs:
+            W = rng_for(f"ladder W[{mrows}]").standard_normal((mrows, LADDER_NP + 2)).astype(F32)
+            W64 = W[:, :LADDER_NP].astype(np.float64)
+            self._rhs[mrows] = (W, mm_ld(W64, self.Li), np.abs(W64) @ self.aLi.T)
+        return self._rhs[mrows]
+
+
+def ladder32(ops):
+    return memo(("ladder32", ops.name), lambda: Ladder32(ops))
+
+
+def _ladder_f32(ops, name, mrows, levels, build):
+    d = ladder32(ops)
+    Np, ldw = LADDER_NP, mrows + 36
+    W0, ref, scale = d.rhs(mrows)
+    Wt, Lf, invf = Mat(W0, ldw, F32), Mat(d.Lf, d.ldLf, F32), Mat(d.invf, dtype=F32)
+    res = Result()
+    ops.f32_build(F32_BUILDS[build])
+    try:
+        res.rc("fwd_subst_f32", ops.call("fwd_subst_f32", Wt, ldw, mrows, Np, Lf, d.ldLf, invf, list(levels), len(levels)))
+    finally:
+        ops.f32_build()
+    num = memo(("ladder num", ops.name, mrows, levels, build), lambda: f32_ladder(
+        W0[:, :Np].copy(), d.Lf, d.invf.reshape(Np // TILE, 2, TILE, TILE), levels, build in F32_WIDE, sequential=True))
+    bound = subst_bound(res, "Wt", num, ref, scale)
+    pad = lambda x: np.concatenate([x, np.zeros((mrows, 2), dtype=x.dtype)], axis=1)
+    res.add("Wt", Wt, pad(ref), pad(bound), np.arange(Np + 2)[None, :] < Np)        # columns >= Np: untouched
+    return res.add("Lf", Lf).add("invf", invf)
+
+
+for _lv in LADDER_LEVELS:
+    for _m in (128, 256):
+        for _b in ("wide,rsd=4", "plain"):
+            case("f32", f"fwd_subst_f32[levels={','.join(map(str, _lv))},mrows={_m},{_b}]",
+                 ["gpak_dev_fwd_subst_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32"], mrows=_m, levels=_lv, build=_b)(_ladder_f32)
+
+
+def _ladder_f32_default(ops, name):
+    """nlevels = 0 is 128 / 512: the same bits"""
+    d = ladder32(ops)
+    Np, mrows = LADDER_NP, 128
+    ldw = mrows + 36
+    W0, _ref, _scale = d.rhs(mrows)
+    res, outs = Result(), []
+    for lv in ((), (128, 512)):
+        Wt, Lf, invf = Mat(W0, ldw, F32), Mat(d.Lf, d.ldLf, F32), Mat(d.invf, dtype=F32)
+        res.rc(f"fwd_subst_f32[nlevels={len(lv)}]", ops.call("fwd_subst_f32", Wt, ldw, mrows, Np, Lf, d.ldLf, invf, list(lv), len(lv)))
+        res.add(f"Wt[nlevels={len(lv)}]", Wt, free=np.arange(Np + 2)[None, :] < Np)
+        outs.append(Wt)
+    return res.rc("elements that differ from levels = 128, 512", int(np.count_nonzero(bits(outs[0].full) != bits(outs[1].full))))
+
+
+case("f32", "fwd_subst_f32[nlevels=0]", ["gpak_dev_fwd_subst_f32"])(_ladder_f32_default)
+
+
+def _ladder_f32_refused(ops, name):
+    d = ladder32(ops)
+    Np, mrows = LADDER_NP, 128
+    ldw = mrows + 36
+    Wt, Lf, invf = Mat(d.rhs(mrows)[0], ldw, F32), Mat(d.Lf, d.ldLf, F32), Mat(d.invf, dtype=F32)
+    res = Result()
+    for label, lv, m, ld_ in (("levels do not ascend", (128, 512, 256), mrows, ldw), ("first level 256", (256, 512), mrows, ldw),
+                              ("512 is no multiple of 384", (128, 384, 512), mrows, ldw), ("a level twice", (128, 128), mrows, ldw),
+                              ("mrows=64", (128, 512), 64, ldw), ("ldw no multiple of 4", (128, 512), mrows, ldw + 2)):
+        res.rc(label, ops.call("fwd_subst_f32", Wt, ld_, m, Np, Lf, d.ldLf, invf, list(lv), len(lv)), EINVAL)
+    res.rc("Np=576", ops.call("fwd_subst_f32", Wt, ldw, mrows, 576, Lf, d.ldLf, invf, [128], 1), EINVAL)
+    res.rc("Wt misaligned", ops.call("fwd_subst_f32", Off(Wt, 2), ldw, mrows, Np, Lf, d.ldLf, invf, [128], 1), EINVAL)
+    return res.add("Wt", Wt).add("Lf", Lf).add("invf", invf)
+
+
+case("f32", "fwd_subst_f32->EINVAL", ["gpak_dev_fwd_subst_f32"])(_ladder_f32_refused)
 
 
 # ------------------------------------------------------------------------------------------------

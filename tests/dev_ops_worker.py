@@ -2,7 +2,7 @@
 line per case (name, worst error / bound ratio, elements written that must not be, guard bands, return codes, whether
 two runs agreed bit for bit, and the measured float64-vs-long-double ratios that set the substitution tolerances).
 
-    python tests/dev_ops_worker.py --engine {hip,numpy} --group {gemm,solve_rows,trsv,reduce,fill,grad,pairs,panel}
+    python tests/dev_ops_worker.py --engine {hip,numpy} --group {gemm,solve_rows,trsv,reduce,fill,grad,pairs,panel,f32}
 
 Exit status 0: every case RAN (whether it passed is in its line); 3: no usable long double on this host.
 """

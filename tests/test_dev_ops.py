@@ -17,11 +17,16 @@ either pair pass of csrc/grad.hip alone (gpak_dev_grad_pair_sums, gpak_dev_grad_
 the pairs, slot by slot, and the host ends of that chain (gpak_dev_grad_consts through the oracle, gpak_dev_grad_finish /
 _finish_d).
 
+The group `f32` holds the fp32 prediction kernels of a GPAK_F32 context alone (include/gpak_dev_f32.h): the three builds
+of the fp32 product and its wide accumulation, the cross-kernel fill under every composition, the conversions, the row
+sums and the ladder of the forward substitution.
+
 Worst error / bound per group on an MI355X, and the float64-vs-long-double ratios that set the substitution
 tolerances: DESIGN.md, "Device-level operations alone".
 """
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -142,6 +147,7 @@ def test_the_checks_bite():
     assert not rec["ok"] and float(rec["ratio"]) > 1e10, rec
     _the_pair_checks_bite()
     _the_panel_checks_bite()
+    _the_f32_checks_bite()
 
 
 def _the_pair_checks_bite():
@@ -219,6 +225,55 @@ def _the_panel_checks_bite():
     assert {"factor_panel info[two failures]", "factor_panel info[pre-set]"} <= set(fails["last writer wins"])
     assert set(fails["inv not transposed"]) == {n for n, _f in quick} - info_cases      # every accuracy case, no info case
     assert set(fails["above the diagonal"]) >= {n for n, _f in quick} - info_cases
+
+
+def _the_f32_checks_bite():
+    """The same for the group `f32`: wrong fp32 kernels built on the float32 restatements (dev_ops_cases.F32Restated) each
+    fail the case named beside them; the good engine passes every one of those cases."""
+    cases = {n: f for _g, n, _e, f in dc.CASES}
+    wrong = (("f32 short k", "gemm_nt_f32[wide,rsd=4][1,1,256]"),                        # one 128-chunk of k dropped
+             ("f32 plain", "gemm_nt_f32[wide,rsd=4][accumulates wide]"),                 # plain accumulation, positive operands
+             ("f32 unpermuted", "gemm_nt_f32[plain][1,1,128]"),                          # rows 4 j + i left in MFMA order
+             ("f32 beta0", "gemm_nt_f32[wide,rsd=4][3,2,128]"),                          # beta applied when it is 0: NaN leaks
+             ("f32 rbf as exp", "fill_f32[rbf]"),                                        # the RBF child with the exponential profile
+             ("f32 no col4", "fill_f32[expans d4]"),                                     # the 4th column ignored
+             ("f32 pair kept", "fill_f32[expans]"),                                      # second element of the last valid row pair kept
+             ("f32 white", "fill_f32[expans+rbf+bias,white=0.1]"),                       # White added on the coincident pair
+             ("f32 clip skipped", "fwd_subst_f32[levels=128,512,mrows=128,wide,rsd=4]"), # the clipped last child skipped
+             ("f32 inv transposed", "fwd_subst_f32[levels=128,mrows=128,plain]"),        # the transposed image of an inverse block
+             ("f32 odd tail", "rowsumsq_f32[rows=255,cols=5,splits=5]"))                 # an odd split's last column dropped
+    good = dc.numpy_ops()
+    for _how, name in wrong:
+        ok = dc.summarise(name, cases[name](good), cases[name](good))
+        assert ok["ok"] and float(ok["ratio"]) < 1, ok
+    for how, name in wrong:
+        eng = dc.NumpyOps(mut=[how])
+        rec = dc.summarise(name, cases[name](eng), cases[name](eng))
+        print(how, "fails", name, "ratio", rec["ratio"], rec["violations"], [t for t in rec["rc"] if t[1] != t[2]])
+        assert not rec["ok"], (how, rec)
+        assert rec["guards_ok"] and rec["deterministic"], (how, rec)        # it fails for the value, not for a stray store
+
+
+def test_f32_header_binding_and_library_agree():
+    """include/gpak_dev_f32.h, the binding's list and the library's exports name the same functions, each has a signature
+    in dev_ops_cases.SIG, and gpak_dev.h still includes nothing of it."""
+    import ctypes
+    from gp_ss_ak_amd import _lib
+    with open(os.path.join(ROOT, "include", "gpak_dev_f32.h")) as f:
+        txt = f.read()
+    declared = sorted(set(re.findall(r"^int (gpak_dev_\w+)\(", txt, flags=re.M)))
+    assert declared == sorted(_lib.DEV_F32_SYMBOLS) == sorted("gpak_dev_" + k for k in dc.F32_OPS)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in declared:
+        assert hasattr(lib, name), name
+    assert set(declared) <= set(dc.declared_entry_points())
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:                 # plain C, like the headers test_abi.py compiles
+        src = os.path.join(d, "t.c")
+        with open(src, "w") as f:
+            f.write('#include "gpak_dev_f32.h"\nint main(void){return GPAK_OK;}\n')
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", src, "-o",
+                               os.path.join(d, "t.o")])
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------

@@ -137,6 +137,53 @@ def test_fp32_prediction_context(orc):
     g32.close()
 
 
+F32_COMPOSITIONS = {       # name -> (terms or None for set_params, Sigma_White, input columns)
+    "expans+exp": ([(gpak.KERN_EXPANS, E), (gpak.KERN_EXP, [0.7, 0.8])], 0.0, 3),
+    "rbf": ([(gpak.KERN_RBF, [0.5, 0.9, 0.5])], 0.0, 3),
+    "expans+rbf+bias+white": ([(gpak.KERN_EXPANS, E), (gpak.KERN_RBF, [0.5, 0.9, 0.5])], 0.1, 3),
+    "defaults, 4 columns": (None, 0.0, 4),
+}
+
+
+@pytest.mark.parametrize("N", [300, 1100])
+@pytest.mark.parametrize("comp", list(F32_COMPOSITIONS))
+def test_fp32_context_other_compositions(comp, N):
+    """A GPAK_F32 context against a GPAK_F64 context on the same data under the compositions set_params never reaches:
+    the RBF branch, the loop over terms, a White child and the 4th input column of the fp32 cross-kernel.  Np = 384 is one
+    clipped top block of the ladder, Np = 1152 = 512 + 512 + 128; M = 1 .. 257 pads to one or two 256-row batches, and
+    M = 700 under GPAK_OPT_PRED_BATCH = 256 makes three batches with the last one partial.  Bounds: the project's own --
+    mean 1e-9, variance 2e-4 of the largest fp64 variance (test_fp32_prediction_context); without the variance a GPAK_F32
+    context runs no fp32 code and returns the bytes of the fp64 mean."""
+    terms, white, cols = F32_COMPOSITIONS[comp]
+    X, y = synth.drillholes4(N) if cols == 4 else synth.drillholes(N)
+    ctx = []
+    try:
+        for prec in (gpak.F64, gpak.F32):
+            g = gpak.Gpak(0, prec)
+            ctx.append(g)
+            g.set_train(X, y)
+            if terms is None:
+                g.set_params(E, BIAS, SN2, gpak.DIST_DIRECT)
+            else:
+                g.set_kernel(terms, BIAS, white, SN2, gpak.DIST_DIRECT)
+        g64, g32 = ctx
+        for M, batch in ((1, 0), (255, 0), (256, 0), (257, 0), (700, 256)):
+            Xte = synth.test_points4(M) if cols == 4 else synth.test_points(M)
+            for g in ctx:         # both: the batch decides the splits of the mean's sums, and so its last bits
+                g.set_option(gpak.OPT_PRED_BATCH, batch)
+            m64, v64 = g64.posteriorMeanVar(Xte)
+            m32, v32 = g32.posteriorMeanVar(Xte)
+            mean_only, none = g32.posteriorMeanVar(Xte, want_var=False)
+            dm, dv = rel(m32, m64), np.abs(v32 - v64).max() / v64.max()
+            print(f"{comp}, N={N}, M={M}, batch={batch}: mean {dm:.3g}, variance {dv:.3g} of the largest fp64 variance")
+            assert dm <= 1e-9, (M, dm)
+            assert dv <= 2e-4, (M, dv)
+            assert none is None and mean_only.tobytes() == m64.tobytes(), M
+    finally:
+        for g in ctx:
+            g.close()
+
+
 @pytest.mark.parametrize("mode", [gpak.DIST_DIRECT, gpak.DIST_EXPANSION])
 def test_other_kernel_compositions(gp, orc, mode):
     """f-4: HybKerns{ExpAns, Exp, RBF} + Bias + White through gpak_set_kernel: Gram, nlZ, alpha, prediction.
