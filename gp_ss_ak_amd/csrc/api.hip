@@ -6,6 +6,7 @@
 #include <cstring>
 #include <limits>
 
+#include "../../include/gpak_cv_folds.h"
 #include "multi.h"
 
 #define GPAK_MULTI_ERR(rc_) do { int v_ = (rc_); if (v_) ctx->err = gpak_multi_error(ctx->multi); return v_; } while (0)
@@ -161,6 +162,7 @@ gpak_queues::~gpak_queues() {
   for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
   for (auto e : ev_pool) hipEventDestroy(e);
   for (auto e : ev_sync) hipEventDestroy(e);
+  for (auto e : ev_cvf) hipEventDestroy(e);
   for (hipStream_t s : {stream_hi, stream_fs, stream_x, stream_tail, stream_bulk, stream}) if (s) hipStreamDestroy(s);
 }
 
@@ -825,29 +827,26 @@ int gpak_loo_grad(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary) {
   return rc;
 }
 
-int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,
-                   gpak_cv_groups_summary *summary) {
-  if (!ctx) return GPAK_EINVAL;
-  // what the call refuses is refused before anything is factored
-  int rc = single_gpu_call(ctx, "gpak_cv_groups", true, true, CtxState::NONE);
-  if (rc) return rc;
+// The labels of gpak_cv_groups / gpak_cv_folds (`who`, with its colon), checked, and the samples sorted by (group, sample)
+// with a counting sort: perm, and offs = where each group starts in it.  max_group: the largest group allowed (0: any)
+static int group_lists(gpak_ctx *ctx, const std::string &who, const int *group, int n_groups, int max_group,
+                       std::vector<int> &perm, std::vector<int> &offs) {
   const int N = ctx->N;
-  const std::string who = "gpak_cv_groups: ";
   if (!group) { ctx->err = who + "group is NULL"; return GPAK_EINVAL; }
   if (n_groups < 1 || n_groups > N) {
     ctx->err = who + "n_groups = " + std::to_string(n_groups) + " is outside [1, N = " + std::to_string(N) + "]";
     return GPAK_EINVAL;
   }
-  // the samples sorted by (group, sample): a counting sort
-  std::vector<int> offs((size_t)n_groups + 1, 0), perm((size_t)N);
+  offs.assign((size_t)n_groups + 1, 0);
+  perm.resize((size_t)N);
   for (int i = 0; i < N; i++) {
     if (group[i] < 0 || group[i] >= n_groups) {
       ctx->err = who + "sample " + std::to_string(i) + " has label " + std::to_string(group[i]) + ", outside [0, " +
                  std::to_string(n_groups) + ")";
       return GPAK_EINVAL;
     }
-    if (++offs[(size_t)group[i] + 1] == GPAK_CV_GROUP_MAX + 1) {
-      ctx->err = who + "group " + std::to_string(group[i]) + " has more than " + std::to_string(GPAK_CV_GROUP_MAX) +
+    if (++offs[(size_t)group[i] + 1] == max_group + 1 && max_group > 0) {
+      ctx->err = who + "group " + std::to_string(group[i]) + " has more than " + std::to_string(max_group) +
                  " samples (sample " + std::to_string(i) + " is one too many)";
       return GPAK_EINVAL;
     }
@@ -856,12 +855,30 @@ int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, 
     if (offs[(size_t)g + 1] == 0) { ctx->err = who + "label " + std::to_string(g) + " is not used"; return GPAK_EINVAL; }
     offs[(size_t)g + 1] += offs[g];
   }
-  {
-    std::vector<int> at(offs.begin(), offs.end() - 1);
-    for (int i = 0; i < N; i++) perm[(size_t)at[group[i]]++] = i;
+  std::vector<int> at(offs.begin(), offs.end() - 1);
+  for (int i = 0; i < N; i++) perm[(size_t)at[group[i]]++] = i;
+  return GPAK_OK;
+}
+
+// gpak_cv_groups and gpak_cv_folds (folds: no limit on a group, and flags): what the call refuses is refused before
+// anything is factored
+static int cv_call(gpak_ctx *ctx, const char *name, bool folds, const int *group, int n_groups, double *mean, double *var,
+                   double *group_logp, gpak_cv_groups_summary *summary, int flags) {
+  if (!ctx) return GPAK_EINVAL;
+  int rc = single_gpu_call(ctx, name, true, true, CtxState::NONE);
+  if (rc) return rc;
+  const int N = ctx->N;
+  const std::string who = std::string(name) + ": ";
+  std::vector<int> offs, perm;
+  if ((rc = group_lists(ctx, who, group, n_groups, folds ? 0 : GPAK_CV_GROUP_MAX, perm, offs))) return rc;
+  if (flags & ~GPAK_CV_FOLDS_NO_BATCH) {
+    ctx->err = who + "flags = " + std::to_string(flags) + " has bits other than GPAK_CV_FOLDS_NO_BATCH";
+    return GPAK_EINVAL;
   }
   rc = ensure_nlz(ctx);
-  if (rc == GPAK_OK) return gpak_cv_groups_impl(ctx, perm.data(), offs.data(), n_groups, mean, var, group_logp, summary);
+  if (rc == GPAK_OK)
+    return folds ? gpak_cv_folds_impl(ctx, perm.data(), offs.data(), n_groups, mean, var, group_logp, summary, flags)
+                 : gpak_cv_groups_impl(ctx, perm.data(), offs.data(), n_groups, mean, var, group_logp, summary);
   if (rc == GPAK_ENOTPD) {   // the training factor
     fill_nan(mean, N);
     fill_nan(var, N);
@@ -872,6 +889,16 @@ int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, 
     }
   }
   return rc;
+}
+
+int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,
+                   gpak_cv_groups_summary *summary) {
+  return cv_call(ctx, "gpak_cv_groups", false, group, n_groups, mean, var, group_logp, summary, 0);
+}
+
+int gpak_cv_folds(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,
+                  gpak_cv_groups_summary *summary, int flags) {
+  return cv_call(ctx, "gpak_cv_folds", true, group, n_groups, mean, var, group_logp, summary, flags);
 }
 
 static int block_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *var,

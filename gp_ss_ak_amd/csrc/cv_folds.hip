@@ -1,0 +1,372 @@
+// cv_folds.hip -- k-fold cross-validation from the Cholesky factor on gfx950 (gpak_cv_folds): gpak_cv_groups for groups
+// of any size.
+//
+// The mathematics is that of cv_groups.hip.  With G = L^-T as one matrix and alpha = Ky^-1 y, for a group with index set
+// I of m samples:  S = G_I G_I^T = R R^T,  T = R^-T,  w = T^T alpha_I,  e_I = sn2 T w,  var_i = sn2 sum_{j >= i} T_ij^2.
+// On the context's stream, one host synchronisation at the end:
+//   1. G: gpak_grad_g_full, into dG when the gradient owns one, else into dLoo (exactly as gpak_cv_groups_impl);
+//   2. the groups of at most GPAK_CV_GROUP_MAX samples: the two batched kernels of cv_groups.hip on compacted lists, one
+//      launch each -- a labelling without a larger group gives the bytes of gpak_cv_groups;
+//   3. every other group alone, in ascending group number, in workspaces sized by the largest of them:
+//        gpak_cvf_pack_f64      P = the group's rows of G from the 128-tile k0 of its smallest row on, zero rows up to
+//                               m_p = m rounded up to 128
+//        gpak_launch_gemm_nt    S = P P^T on the lower 128-tiles (K = Np - k0, beta = 0): the N^3 / k product
+//        gpak_cvf_pad_f64       the padding of S becomes the identity
+//        gpak_factor_panel      R, 512 columns at a time with the K = W update to their right; inverse blocks and an
+//                               info word of the group's own
+//        gpak_grad_g_of         T = R^-T, over P
+//        gpak_cvf_w_f64, gpak_cvf_ev_f64, gpak_cvf_sums_f64   w; e, var, mean; log det R and the group's three sums
+// Orders of summation.  S_ij: one accumulator chain of the product's tile over k ascending from k0; the kernel the
+// launcher picks depends on (m_p, Np - k0) and the process-wide tuning alone.  w_j: thread t of 256 adds rows t, t + 256,
+// ... ascending, then a fixed tree.  e_i, var_i: four chains over the columns j = q (mod 4), j ascending, combined as
+// (0 + 1) + (2 + 3).  The group's sums: thread t adds i = t, t + 256, ..., then a fixed tree.  Every one of them is a
+// function of the group's member set and the factor: not of the other groups, the label numbering, the grid or the
+// buffer that holds G.
+#include <climits>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "../../include/gpak_cv_folds.h"
+#include "../../include/gpak_dev_cv.h"
+#include "gpak_internal.h"
+
+#define CVF_TB 128        // the product's tile
+#define CVF_PACK_COLS 32  // columns of P per workgroup of the pack: 8 per wave, all in flight at once
+
+static int cvf_pad128(int m) { return (m + CVF_TB - 1) / CVF_TB * CVF_TB; }
+
+// P[r, c] = G[rows[r], k0 + c] for r < m and 0 for m <= r < m_p, c < ncols.  Workgroup (x, y): rows 128 x .. 128 x + 127,
+// columns 32 y .. 32 y + 31.  Lanes run along r, two rows each: a wave stores 1 KiB contiguous per column (16 B per lane
+// when VEC: P 16-byte aligned and ldp even) and reads its 128 rows of one column of G -- 1 KiB contiguous where the
+// members are consecutive samples, one 8-byte word per 128-byte line where they are scattered.  Wave w takes the columns
+// w, w + 4, ... of the 32; its 8 loads per row are issued before the first store.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gpak_cvf_pack_f64(const double *__restrict__ G, long ld, const int *__restrict__ rows,
+                                                         int m, int k0, int ncols, double *__restrict__ P, long ldp) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r0 = blockIdx.x * CVF_TB + 2 * lane;          // < m_p: the grid has m_p / 128 workgroups along x
+  const bool la = r0 < m, lb = r0 + 1 < m;
+  const double *ga = G + (size_t)k0 * ld + (la ? rows[r0] : 0);
+  const double *gb = G + (size_t)k0 * ld + (lb ? rows[r0 + 1] : 0);
+  const int c0 = blockIdx.y * CVF_PACK_COLS + w;
+  double a[CVF_PACK_COLS / 4], b[CVF_PACK_COLS / 4];
+#pragma unroll
+  for (int u = 0; u < CVF_PACK_COLS / 4; u++) {
+    const int c = c0 + 4 * u;
+    const bool in = c < ncols;
+    a[u] = (in && la) ? ga[(size_t)c * ld] : 0.0;
+    b[u] = (in && lb) ? gb[(size_t)c * ld] : 0.0;
+  }
+#pragma unroll
+  for (int u = 0; u < CVF_PACK_COLS / 4; u++) {
+    const int c = c0 + 4 * u;
+    if (c >= ncols) continue;
+    double *p = P + (size_t)c * ldp + r0;
+    if (VEC) {
+      *reinterpret_cast<double2 *>(p) = make_double2(a[u], b[u]);
+    } else {
+      p[0] = a[u];
+      p[1] = b[u];
+    }
+  }
+}
+
+void gpak_launch_pack_rows(hipStream_t st, const double *G, long ld, int Np, const int *rows, int m, int k0, double *P,
+                           long ldp) {
+  const int mp = cvf_pad128(m), ncols = Np - k0;
+  const dim3 grid(mp / CVF_TB, (ncols + CVF_PACK_COLS - 1) / CVF_PACK_COLS);
+  const bool vec = (reinterpret_cast<size_t>(P) & 15) == 0 && (ldp & 1) == 0;
+  if (vec) hipLaunchKernelGGL(gpak_cvf_pack_f64<true>, grid, dim3(256), 0, st, G, ld, rows, m, k0, ncols, P, ldp);
+  else hipLaunchKernelGGL(gpak_cvf_pack_f64<false>, grid, dim3(256), 0, st, G, ld, rows, m, k0, ncols, P, ldp);
+}
+
+extern "C" int gpak_dev_pack_rows(void *stream, const double *G, long ld, int Np, const int *rows, int m, int k0, double *P,
+                                  long ldp) {
+  if (!G || !rows || !P || m < 1 || m > Np || k0 < 0 || k0 >= Np || ld < Np || ldp < cvf_pad128(m)) return GPAK_EINVAL;
+  gpak_launch_pack_rows((hipStream_t)stream, G, ld, Np, rows, m, k0, P, ldp);
+  return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP;
+}
+
+// rows and columns m .. mp - 1 of the lower triangle of S become the identity (the product left zeros there: the rows of
+// P beyond m are zero), so that the factorisation runs over whole tiles and a padded column is never a failing pivot
+__global__ __launch_bounds__(256) void gpak_cvf_pad_f64(double *__restrict__ S, long lds, int m, int mp) {
+  const int np = mp - m;                                   // < 128
+  for (int e = threadIdx.x; e < np * np; e += 256) {
+    const int i = m + e % np, j = m + e / np;
+    if (i >= j) S[(size_t)i + (size_t)j * lds] = i == j ? 1.0 : 0.0;
+  }
+}
+
+// w_j = sum_{i <= j} T_ij alpha_I,i: workgroup j.  Thread t adds the rows t, t + 256, ... in ascending order, then the tree.
+__global__ __launch_bounds__(256) void gpak_cvf_w_f64(const double *__restrict__ T, long ldt, const int *__restrict__ rows,
+                                                      const double *__restrict__ alpha, double *__restrict__ wv) {
+  __shared__ double red[256];
+  const int j = blockIdx.x, t = threadIdx.x;
+  const double *col = T + (size_t)j * ldt;
+  double s = 0.0;
+  for (int i = t; i <= j; i += 256) s = fma(col[i], alpha[rows[i]], s);
+  red[t] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) red[t] += red[t + h];
+    __syncthreads();
+  }
+  if (t == 0) wv[j] = red[0];
+}
+
+// e_i = sn2 sum_{j >= i} T_ij w_j and var_i = sn2 sum_{j >= i} T_ij^2 in one pass over the upper triangle of T, then
+// mean and var through the group's rows.  Workgroup: 64 rows (the lanes: a wave reads 512 contiguous bytes of a column),
+// wave q the columns j = q (mod 4) in ascending order; the four chains are added as (0 + 1) + (2 + 3).  A group whose
+// factorisation failed (info) gets NaN.
+__global__ __launch_bounds__(256) void gpak_cvf_ev_f64(const double *__restrict__ T, long ldt, int m,
+                                                       const double *__restrict__ wv, const int *__restrict__ rows,
+                                                       const double *__restrict__ y, double sn2, const int *__restrict__ info,
+                                                       double *__restrict__ ev, double *__restrict__ vv,
+                                                       double *__restrict__ mean, double *__restrict__ var) {
+  __shared__ double re[4][64], rv[4][64];
+  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * 64, i = i0 + lane;
+  const bool live = i < m;
+  double e = 0.0, v = 0.0;
+  if (live) {
+    const double *row = T + i;
+#pragma unroll 4
+    for (int j = i0 + q; j < m; j += 4) {
+      const double x = j >= i ? row[(size_t)j * ldt] : 0.0;
+      e = fma(x, wv[j], e);
+      v = fma(x, x, v);
+    }
+  }
+  re[q][lane] = e;
+  rv[q][lane] = v;
+  __syncthreads();
+  if (q == 0 && live) {
+    e = sn2 * ((re[0][lane] + re[1][lane]) + (re[2][lane] + re[3][lane]));
+    v = sn2 * ((rv[0][lane] + rv[1][lane]) + (rv[2][lane] + rv[3][lane]));
+    if (*info != INT_MAX) e = v = __longlong_as_double(0x7ff8000000000000LL);
+    ev[i] = e;
+    vv[i] = v;
+    const int n = rows[i];
+    mean[n] = y[n] - e;
+    var[n] = v;
+  }
+}
+
+// one workgroup: gsum[0..2] = sum e_i^2, sum e_i^2 / var_i, alpha_I . e_I and logp from those and sum log R_ii.  Thread t
+// adds i = t, t + 256, ... in ascending order, then the tree.
+__global__ __launch_bounds__(256) void gpak_cvf_sums_f64(const double *__restrict__ R, long ldr, int m,
+                                                         const double *__restrict__ ev, const double *__restrict__ vv,
+                                                         const int *__restrict__ rows, const double *__restrict__ alpha,
+                                                         double sn2, const int *__restrict__ info, double *__restrict__ logp,
+                                                         double *__restrict__ gsum) {
+  __shared__ double red[4][256];
+  const int t = threadIdx.x;
+  double sse = 0.0, ssr = 0.0, md = 0.0, ld = 0.0;
+  for (int i = t; i < m; i += 256) {
+    const double e = ev[i];
+    sse = fma(e, e, sse);
+    ssr += e * e / vv[i];
+    md = fma(alpha[rows[i]], e, md);
+    ld += log(R[(size_t)i + (size_t)i * ldr]);
+  }
+  red[0][t] = sse; red[1][t] = ssr; red[2][t] = md; red[3][t] = ld;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h)
+#pragma unroll
+      for (int k = 0; k < 4; k++) red[k][t] += red[k][t + h];
+    __syncthreads();
+  }
+  if (t == 0) {
+    const bool bad = *info != INT_MAX;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    gsum[0] = bad ? nan : red[0][0];
+    gsum[1] = bad ? nan : red[1][0];
+    gsum[2] = bad ? nan : red[2][0];
+    logp[0] = bad ? nan : -0.5 * red[2][0] - 0.5 * (m * log(sn2) - 2.0 * red[3][0]) - 0.5 * m * 1.8378770664093454836;   // log 2 pi
+  }
+}
+
+// the substitution, the batched small groups, and pack / product / factor + inverse + finish summed over the other groups
+// of the context's last gpak_cv_folds, in ms.  Not part of the C-ABI (no header declares it): tools/time_cv_folds.py
+// reads it through the shared object.
+extern "C" int gpak_cv_folds_last_split(gpak_ctx *ctx, double *ms5) {
+  if (!ctx || !ms5 || ctx->multi) return GPAK_EINVAL;
+  for (int k = 0; k < 5; k++) ms5[k] = ctx->cvf_ms[k];
+  return GPAK_OK;
+}
+
+int gpak_cv_folds_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *mean, double *var,
+                       double *group_logp, gpak_cv_groups_summary *summary, int flags) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np;
+  const long ld = ctx->ld;
+  const bool batch = !(flags & GPAK_CV_FOLDS_NO_BATCH);
+  // the two kinds of groups.  Small: compacted lists for the batched kernels.  Large: where each starts in perm.
+  std::vector<int> small_id, large_id, sperm, soffs(1, 0);
+  std::vector<long long> soff(1, 0);
+  int max_size = 0, max_small = 0, mp_max = 0;
+  size_t nP = 0;
+  for (int g = 0; g < n_groups; g++) {
+    const int o = offs[g], m = offs[g + 1] - o;
+    max_size = std::max(max_size, m);
+    if (batch && m <= GPAK_CV_GROUP_MAX) {
+      small_id.push_back(g);
+      sperm.insert(sperm.end(), perm + o, perm + o + m);
+      soffs.push_back((int)sperm.size());
+      soff.push_back(soff.back() + gpak_cvg_s_elems(m));
+      max_small = std::max(max_small, m);
+    } else {
+      large_id.push_back(g);
+      const int mp = cvf_pad128(m), k0 = perm[o] / CVF_TB * CVF_TB;   // the members are sorted: perm[o] is the smallest row
+      mp_max = std::max(mp_max, mp);
+      nP = std::max(nP, (size_t)mp * (size_t)(Np - k0));              // >= mp * mp: T = R^-T fits where P was
+    }
+  }
+  const size_t nSm = small_id.size(), nL = large_id.size(), nG = (size_t)n_groups;
+  // where G goes: as gpak_cv_groups_impl
+  double *G = ctx->dG;
+  if (!G) {
+    if (!gpak_loo_workspace(ctx, (size_t)ld * Np)) {
+      ctx->err = "gpak_cv_folds: device allocation failed for L^-T as one N x N matrix (" +
+                 std::to_string((size_t)ld * Np * sizeof(double)) + " bytes)";
+      return GPAK_ENOMEM;
+    }
+    G = ctx->dLoo;
+  }
+  if (nL) {
+    const size_t nS = (size_t)mp_max * mp_max, nI = (size_t)(mp_max / CVF_TB) * 2 * CVF_TB * CVF_TB;
+    const char *what = nullptr;
+    size_t bytes = 0;
+    if (!ctx->dCvfP.reserve(nP)) { what = "P, the packed rows of L^-T of the largest group"; bytes = nP; }
+    else if (!ctx->dCvfS.reserve(nS)) { what = "S = P P^T of the largest group"; bytes = nS; }
+    else if (!ctx->dCvfInv.reserve(nI)) { what = "the inverse blocks of S's factor"; bytes = nI; }
+    else if (!ctx->dCvfVec.reserve(3 * (size_t)mp_max)) { what = "the vectors w, e, var"; bytes = 3 * (size_t)mp_max; }
+    if (what) {
+      (void)hipGetLastError();
+      ctx->err = std::string("gpak_cv_folds: device allocation failed for ") + what + " (" +
+                 std::to_string(bytes * sizeof(double)) + " bytes; the largest group has " + std::to_string(max_size) + " samples)";
+      return GPAK_ENOMEM;
+    }
+    while (ctx->ev_cvf.size() < 3 * nL) {
+      hipEvent_t e;
+      GPAK_HIP(hipEventCreate(&e));
+      ctx->ev_cvf.push_back(e);
+    }
+  }
+  // scratch in the gradient's partial-sum buffer: the S of every small group, mean, var (N each), then per kind of group
+  // logp and the three sums (small groups first); then the index lists
+  const size_t nSs = (size_t)soff.back();
+  const size_t n_dbl = nSs + 2 * (size_t)N + 4 * nG;
+  const size_t n_ll = nSm + 1, n_int = sperm.size() + (nSm + 1) + (size_t)N + (1 + nL);
+  int rc = gpak_grad_scratch(ctx, n_dbl + n_ll + (n_int + 1) / 2);
+  if (rc) return rc;
+  double *dS = ctx->dGpart, *dmean = dS + nSs, *dvar = dmean + N;
+  double *dlogp_s = dvar + N, *dgsum_s = dlogp_s + nSm, *dlogp_l = dgsum_s + 3 * nSm, *dgsum_l = dlogp_l + nL;
+  long long *dsoff = reinterpret_cast<long long *>(dgsum_l + 3 * nL);
+  int *dsperm = reinterpret_cast<int *>(dsoff + n_ll), *dsoffs = dsperm + sperm.size(), *dperm = dsoffs + nSm + 1;
+  int *dinfo = dperm + N;                                   // [0]: the batched groups; [1 + k]: one-at-a-time group k
+  const std::vector<int> info0(1 + nL, INT_MAX);
+  GPAK_HIP(hipMemcpyAsync(dinfo, info0.data(), sizeof(int) * (1 + nL), hipMemcpyHostToDevice, st));
+  if (nSm) {
+    GPAK_HIP(hipMemcpyAsync(dsoff, soff.data(), sizeof(long long) * n_ll, hipMemcpyHostToDevice, st));
+    GPAK_HIP(hipMemcpyAsync(dsperm, sperm.data(), sizeof(int) * sperm.size(), hipMemcpyHostToDevice, st));
+    GPAK_HIP(hipMemcpyAsync(dsoffs, soffs.data(), sizeof(int) * (nSm + 1), hipMemcpyHostToDevice, st));
+  }
+  if (nL) GPAK_HIP(hipMemcpyAsync(dperm, perm, sizeof(int) * N, hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipEventRecord(ctx->ev[7], st));
+  gpak_grad_g_full(ctx, G, ld);
+  GPAK_HIP(hipEventRecord(ctx->ev[5], st));
+  if (nSm) {
+    gpak_cvg_launch_gram(ctx, G, ld, (int)nSm, dsperm, dsoffs, dsoff, dS);
+    gpak_cvg_launch_solve(ctx, (int)nSm, max_small, dS, dsoff, dsperm, dsoffs, dmean, dvar, dlogp_s, dgsum_s, dinfo);
+  }
+  GPAK_HIP(hipEventRecord(ctx->ev[6], st));
+  double *P = ctx->dCvfP, *S = ctx->dCvfS, *inv = ctx->dCvfInv;
+  double *wv = ctx->dCvfVec, *ev = wv + mp_max, *vv = ev + mp_max;
+  for (size_t k = 0; k < nL; k++) {
+    const int g = large_id[k], o = offs[g], m = offs[g + 1] - o;
+    const int mp = cvf_pad128(m), mt = mp / CVF_TB, k0 = perm[o] / CVF_TB * CVF_TB;
+    const int *rows = dperm + o;
+    int *info = dinfo + 1 + k;
+    const long ldp = mp, lds = mp;
+    gpak_launch_pack_rows(st, G, ld, Np, rows, m, k0, P, ldp);
+    GPAK_HIP(hipEventRecord(ctx->ev_cvf[3 * k], st));
+    gpak_launch_gemm_nt(st, mt, mt, Np - k0, 1.0, P, ldp, P, ldp, 0.0, S, lds, 0, 0, true, false);
+    GPAK_HIP(hipEventRecord(ctx->ev_cvf[3 * k + 1], st));
+    if (mp > m) hipLaunchKernelGGL(gpak_cvf_pad_f64, dim3(1), dim3(256), 0, st, S, lds, m, mp);
+    for (int J = 0; J < mp; J += 512) {
+      const int W = std::min(512, mp - J), c0 = J + W, rest = (mp - c0) / CVF_TB;
+      gpak_factor_panel(st, S, lds, mp, J, W, inv, info, true, false, ctx->sched.potrf_co);
+      if (rest > 0) {
+        const double *Pn = S + c0 + (size_t)J * lds;
+        gpak_launch_gemm_nt(st, rest, rest, W, -1.0, Pn, lds, Pn, lds, 1.0, S + c0 + (size_t)c0 * lds, lds, 0, 0, true, false);
+      }
+    }
+    double *T = P;                                          // the product is done with P
+    const long ldt = mp;
+    gpak_grad_g_of(st, mp, S, lds, inv, T, ldt);
+    hipLaunchKernelGGL(gpak_cvf_w_f64, dim3(m), dim3(256), 0, st, T, ldt, rows, ctx->dAlpha, wv);
+    hipLaunchKernelGGL(gpak_cvf_ev_f64, dim3((m + 63) / 64), dim3(256), 0, st, T, ldt, m, wv, rows, ctx->dy, ctx->sn2, info, ev,
+                       vv, dmean, dvar);
+    hipLaunchKernelGGL(gpak_cvf_sums_f64, dim3(1), dim3(256), 0, st, S, lds, m, ev, vv, rows, ctx->dAlpha, ctx->sn2, info,
+                       dlogp_l + k, dgsum_l + 3 * k);
+    GPAK_HIP(hipEventRecord(ctx->ev_cvf[3 * k + 2], st));
+  }
+  GPAK_HIP(hipEventRecord(ctx->ev[9], st));
+  std::vector<double> hsum(4 * nG);   // as on the device: logp and the three sums of the small groups, then of the others
+  std::vector<int> hinfo(1 + nL, 0);
+  GPAK_HIP(hipMemcpyAsync(hsum.data(), dlogp_s, sizeof(double) * 4 * nG, hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * (1 + nL), hipMemcpyDeviceToHost, st));
+  if (mean) GPAK_HIP(hipMemcpyAsync(mean, dmean, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  if (var) GPAK_HIP(hipMemcpyAsync(var, dvar, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipStreamSynchronize(st));
+  GPAK_HIP(hipGetLastError());
+  float ms = 0, a = 0, b = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[9]));
+  GPAK_HIP(hipEventElapsedTime(&a, ctx->ev[7], ctx->ev[5]));
+  GPAK_HIP(hipEventElapsedTime(&b, ctx->ev[5], ctx->ev[6]));
+  double part[5] = {a, b, 0, 0, 0};
+  for (size_t k = 0; k < nL; k++) {
+    hipEvent_t before = k ? ctx->ev_cvf[3 * k - 1] : ctx->ev[6];
+    for (int s = 0; s < 3; s++) {
+      float t = 0;
+      GPAK_HIP(hipEventElapsedTime(&t, s ? ctx->ev_cvf[3 * k + s - 1] : before, ctx->ev_cvf[3 * k + s]));
+      part[2 + s] += t;
+    }
+  }
+  for (int k = 0; k < 5; k++) ctx->cvf_ms[k] = part[k];
+  // per group, in the caller's numbering: logp and the three sums
+  std::vector<const double *> lp_of(nG), gs_of(nG);
+  for (size_t k = 0; k < nSm; k++) { lp_of[small_id[k]] = &hsum[k]; gs_of[small_id[k]] = &hsum[nSm + 3 * k]; }
+  for (size_t k = 0; k < nL; k++) { lp_of[large_id[k]] = &hsum[4 * nSm + k]; gs_of[large_id[k]] = &hsum[4 * nSm + nL + 3 * k]; }
+  if (group_logp)
+    for (size_t g = 0; g < nG; g++) group_logp[g] = *lp_of[g];
+  if (summary) {
+    double sse = 0.0, ssr = 0.0, md = 0.0, lp = 0.0;
+    for (size_t g = 0; g < nG; g++) {   // ascending: a fixed order
+      lp += *lp_of[g];
+      sse += gs_of[g][0];
+      ssr += gs_of[g][1];
+      md += gs_of[g][2];
+    }
+    summary->mse = sse / N;
+    summary->mssr = ssr / N;
+    summary->msmd = md / N;
+    summary->log_pl = lp;
+    summary->ms = ms;
+    summary->groups = n_groups;
+    summary->max_size = max_size;
+  }
+  int failed = INT_MAX;   // the smallest group number whose S failed
+  if (hinfo[0] != INT_MAX) failed = small_id[(size_t)hinfo[0] - 1];
+  for (size_t k = 0; k < nL; k++)
+    if (hinfo[1 + k] != INT_MAX) { failed = std::min(failed, large_id[k]); break; }
+  if (failed != INT_MAX) {
+    ctx->err = "gpak_cv_folds: S = [B^-1]_II of group " + std::to_string(failed) + " is not positive definite";
+    return GPAK_ENOTPD;
+  }
+  return GPAK_OK;
+}

@@ -222,6 +222,30 @@ extern "C" int gpak_cv_groups_last_split(gpak_ctx *ctx, double *ms3) {
   return GPAK_OK;
 }
 
+// The two passes on device lists, on the context's stream (gpak_cv_folds runs them on its groups of at most CVG_MAX
+// samples): perm / offs / soff as the kernels take them, soff[g + 1] - soff[g] = gpak_cvg_s_elems(size of group g)
+long long gpak_cvg_s_elems(int s) { return (long long)cvg_pad16(s) * cvg_pad16(s); }
+void gpak_cvg_launch_gram(gpak_ctx *ctx, const double *G, long ld, int n_groups, const int *dperm, const int *doffs,
+                          const long long *dsoff, double *dS) {
+  hipLaunchKernelGGL(gpak_cvg_gram_f64, dim3(n_groups), dim3(256), 0, ctx->stream, G, ld, ctx->Np, dperm, doffs, dsoff, dS);
+}
+void gpak_cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
+                           const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
+                           int *dinfo) {
+  // more than 64 KiB of dynamic LDS needs the opt-in, once per kernel and per device
+  {
+    static std::atomic<unsigned long long> done_mask{0};
+    const unsigned long long bit = 1ull << (ctx->device & 63);
+    if (!(done_mask.load(std::memory_order_acquire) & bit)) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gpak_cvg_solve_f64), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)cvg_solve_lds(CVG_MAX));
+      done_mask.fetch_or(bit, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL(gpak_cvg_solve_f64, dim3(n_groups), dim3(256), cvg_solve_lds(max_size), ctx->stream, dS, dsoff, dperm,
+                     doffs, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, dlogp, dgsum, dinfo);
+}
+
 // gpak_cv_groups on a single-GPU context whose factor and alpha are current, the labels already checked (api.hip):
 // perm = the samples sorted by (group, sample), offs = where each group starts in it (n_groups + 1 entries)
 int gpak_cv_groups_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *mean, double *var,
@@ -263,23 +287,12 @@ int gpak_cv_groups_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_g
   GPAK_HIP(hipMemcpyAsync(dperm, perm, sizeof(int) * N, hipMemcpyHostToDevice, st));
   GPAK_HIP(hipMemcpyAsync(doffs, offs, sizeof(int) * (nG + 1), hipMemcpyHostToDevice, st));
   GPAK_HIP(hipMemcpyAsync(dinfo, &info0, sizeof(int), hipMemcpyHostToDevice, st));
-  // more than 64 KiB of dynamic LDS needs the opt-in, once per kernel and per device
-  {
-    static std::atomic<unsigned long long> done_mask{0};
-    const unsigned long long bit = 1ull << (ctx->device & 63);
-    if (!(done_mask.load(std::memory_order_acquire) & bit)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gpak_cvg_solve_f64), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)cvg_solve_lds(CVG_MAX));
-      done_mask.fetch_or(bit, std::memory_order_release);
-    }
-  }
   GPAK_HIP(hipEventRecord(ctx->ev[7], st));
   gpak_grad_g_full(ctx, G, ld);
   GPAK_HIP(hipEventRecord(ctx->ev[5], st));
-  hipLaunchKernelGGL(gpak_cvg_gram_f64, dim3(n_groups), dim3(256), 0, st, G, ld, Np, dperm, doffs, dsoff, dS);
+  gpak_cvg_launch_gram(ctx, G, ld, n_groups, dperm, doffs, dsoff, dS);
   GPAK_HIP(hipEventRecord(ctx->ev[6], st));
-  hipLaunchKernelGGL(gpak_cvg_solve_f64, dim3(n_groups), dim3(256), cvg_solve_lds(max_size), st, dS, dsoff, dperm, doffs,
-                     ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, dlogp, dgsum, dinfo);
+  gpak_cvg_launch_solve(ctx, n_groups, max_size, dS, dsoff, dperm, doffs, dmean, dvar, dlogp, dgsum, dinfo);
   GPAK_HIP(hipEventRecord(ctx->ev[9], st));
   std::vector<double> hsum(4 * nG), hmean, hvar;   // logp, then the three sums per group
   int info = 0;

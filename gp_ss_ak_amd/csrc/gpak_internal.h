@@ -119,6 +119,7 @@ struct gpak_queues {
   hipEvent_t ev[10] = {};            // timing
   std::vector<hipEvent_t> ev_pool;   // timing events around the trailing updates
   std::vector<hipEvent_t> ev_sync;   // cross-stream dependencies of the look-ahead pipeline
+  std::vector<hipEvent_t> ev_cvf;    // timing: three per one-at-a-time group of gpak_cv_folds
   gpak_queues() = default;
   gpak_queues(const gpak_queues &) = delete;
   ~gpak_queues();   // api.hip.  Nothing of the device for a group's context, which has none of these
@@ -202,6 +203,13 @@ struct gpak_ctx : gpak_queues {
   int loo_rows = 0;           // GPAK_OPT_LOO_ROWS: rows of L^-T held at once (0: the default, 16384)
   // the substitution, the Gram pass and the solve pass of the last gpak_cv_groups, in ms
   double cvg_ms[3] = {0, 0, 0};
+  // k-fold cross-validation (gpak_cv_folds), the groups above GPAK_CV_GROUP_MAX one at a time, sized by the largest such
+  // group (m_p = its size rounded up to 128) and kept across calls: the packed rows P of G (m_p x (Np - k0)) and then
+  // T = R^-T in its place, S = P P^T and then its factor R (m_p x m_p), R's inverted 128-blocks, the vectors w, e, var
+  DevBuf<double> dCvfVec, dCvfInv, dCvfS, dCvfP;
+  // the substitution, the batched small groups, and pack / product / factor + inverse + finish summed over the other
+  // groups of the last gpak_cv_folds, in ms
+  double cvf_ms[5] = {0, 0, 0, 0, 0};
 
   // options
   GpakSchedule sched;         // this context's copy of the schedule set (gpak_set_option changes it)
@@ -495,9 +503,29 @@ int gpak_grad_scratch(gpak_ctx *ctx, size_t elems);
 // room for `elems` doubles of L^-T in ctx->dLoo (gpak_loo, gpak_cv_groups); false: it does not fit (the HIP error is cleared)
 bool gpak_loo_workspace(gpak_ctx *ctx, size_t elems);
 void gpak_grad_g_full(gpak_ctx *ctx, double *G, long ldg);
+// the same driver on any lower factor held as one matrix: T = R^-T (n x n, n a multiple of 128, leading dimension ldt)
+// of the factor R at M (leading dimension ld) whose inverted 128-blocks (gpak_factor_panel's) are at inv
+void gpak_grad_g_of(hipStream_t st, int n, const double *M, long ld, const double *inv, double *T, long ldt);
 
 // ---- cv_groups.hip ----------------------------------------------------------------------
 // gpak_cv_groups on a single-GPU context whose factor and alpha are current and whose labels api.hip has checked: perm =
 // the samples sorted by (group, sample), offs = where each group starts in it (n_groups + 1 entries)
 int gpak_cv_groups_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *mean, double *var,
                         double *group_logp, gpak_cv_groups_summary *summary);
+// its two batched passes on device lists, on the context's stream: S of every group (gpak_cvg_s_elems(size) doubles each,
+// at Sbuf + soff[g]), then the group's outputs from its S; every group has at most GPAK_CV_GROUP_MAX samples
+long long gpak_cvg_s_elems(int s);
+void gpak_cvg_launch_gram(gpak_ctx *ctx, const double *G, long ld, int n_groups, const int *dperm, const int *doffs,
+                          const long long *dsoff, double *dS);
+void gpak_cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
+                           const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
+                           int *dinfo);
+
+// ---- cv_folds.hip -----------------------------------------------------------------------
+// P[r, c] = G[rows[r], k0 + c] (r < m; zero rows up to m_p = m rounded up to 128), c < Np - k0: gpak_cvf_pack_f64
+void gpak_launch_pack_rows(hipStream_t st, const double *G, long ld, int Np, const int *rows, int m, int k0, double *P,
+                           long ldp);
+// gpak_cv_folds on a single-GPU context whose factor and alpha are current and whose labels api.hip has checked (perm and
+// offs as for gpak_cv_groups_impl)
+int gpak_cv_folds_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *mean, double *var,
+                       double *group_logp, gpak_cv_groups_summary *summary, int flags);

@@ -285,6 +285,15 @@ void gpak_grad_g_full(gpak_ctx *ctx, double *G, long ldg) {
     return LBlockCol{ctx->dM + J + J * ld, ld, ctx->dInv + J / PB * 2 * PB * PB};
   }, G, ldg);
 }
+// the same driver on any lower factor held as ONE matrix: T = R^-T (n x n, n a multiple of 128, leading dimension ldt)
+// of the factor R at M (leading dimension ld) whose inverted 128-blocks are at inv (gpak_cv_folds: a fold's own S)
+void gpak_grad_g_of(hipStream_t st, int n, const double *M, long ld, const double *inv, double *T, long ldt) {
+  const int GNB = 512;
+  grad_g_subst(st, n, GNB, 1, 0, [&](int b) {
+    const size_t J = (size_t)b * GNB;
+    return LBlockCol{M + J + J * ld, ld, inv + J / PB * 2 * PB * PB};
+  }, T, ldt);
+}
 
 // ---------------------------------------------------------------------------------------
 // The as-written pass.  part[block][NSUM]:

@@ -23,6 +23,7 @@ OPT_LOO_ROWS = 14
 KERN_EXPANS, KERN_EXP, KERN_RBF = 0, 1, 2
 BLOCK_LATENT = 1
 JOINT_LATENT, JOINT_PRIOR = 1, 2
+NO_BATCH = 1      # GPAK_CV_FOLDS_NO_BATCH
 
 _dp = C.POINTER(C.c_double)
 
@@ -234,6 +235,21 @@ class Gpak:
         s = _lib.CvGroupsSummary()
         rc = self._check(self._lib.gpak_cv_groups(self._h, group.ctypes.data_as(C.POINTER(C.c_int)), int(values.size),
                                                   _p(mean), _p(var), _p(logp), C.byref(s)), allow=(ENOTPD,))
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        out["labels"] = values
+        return mean, var, logp, out
+
+    def cv_folds(self, labels, no_batch=False):
+        """k-fold cross-validation from the current factor (gpak_cv_folds): cv_groups for groups of any size, the same
+        (mean, var, logp, summary) with the same summary keys.  no_batch: every group, whatever its size, takes the
+        one-group-at-a-time path (GPAK_CV_FOLDS_NO_BATCH)."""
+        group, values = group_labels(labels, self.N)
+        mean, var, logp = np.zeros(self.N), np.zeros(self.N), np.zeros(values.size)
+        s = _lib.CvGroupsSummary()
+        rc = self._check(self._lib.gpak_cv_folds(self._h, group.ctypes.data_as(C.POINTER(C.c_int)), int(values.size),
+                                                 _p(mean), _p(var), _p(logp), C.byref(s), NO_BATCH if no_batch else 0),
+                         allow=(ENOTPD,))
         out = {name: getattr(s, name) for name, _ in s._fields_}
         out["status"] = rc
         out["labels"] = values

@@ -1,7 +1,8 @@
 // gp_ss_ak.cpp -- the reference's command line (gp_ss_ak.cpp:14-557) over the HIP hot path:
 //   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] train.txt [model]
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
-//   gp_ss_ak [-v n]               [device options] cv [-np] [--groups labels.txt] train.txt model [out_file]
+//   gp_ss_ak [-v n]               [device options] cv [-np] [--groups labels.txt | --folds labels.txt | --kfold K [--seed n]]
+//            train.txt model [out_file]
 //   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
 //   gp_ss_ak [-v n] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] [--nugget v] --realisations S (--seed n | --xi file)
 //            sim nodes.txt model train.txt [out_file]
@@ -13,7 +14,10 @@
 // cv (not a reference verb): leave-one-out cross-validation of a trained model on its training set, from one
 // factorisation (gpak_loo; one GPU only), written to <model>_loo.txt.  With --groups FILE (one integer label per training
 // sample, in input order; `#` lines are skipped) it leaves out whole groups instead -- a drill hole, a fold -- of at most
-// 128 samples each (gpak_cv_groups) and writes <model>_lgo.txt.
+// 128 samples each (gpak_cv_groups) and writes <model>_lgo.txt.  With --folds FILE (labels as for --groups) the groups may
+// have any size -- k folds of N / k samples, a hole of 150 (gpak_cv_folds) -- and it writes <model>_folds.txt; --kfold K
+// [--seed n, default 1] makes the labels itself: the fold of a sample is its position in a seeded permutation mod K
+// (kfold_assign.hpp), recorded in the Fold column.  The three options exclude each other.
 // block (not a reference verb): mean and standard deviation of the AVERAGE grade of rectangular blocks (gpak_predict_block;
 // one GPU only).  blocks.txt has the test file's format: block centres, and a last column that is read as y and carried
 // through.  Each block is discretised in the file's units into nx * ny * nz cell-centred points, which then pass through
@@ -38,6 +42,7 @@
 #include "block_points.hpp"
 #include "control.hpp"
 #include "gp_utils.hpp"
+#include "kfold_assign.hpp"
 #include "sim_normals.hpp"
 
 class GP_Cntrl : public Control {
@@ -57,7 +62,7 @@ class GP_Cntrl : public Control {
   void train();
   void test();
   void cv();
-  void readGroupLabels(const std::string &file, std::vector<long long> &labels) const;
+  void readGroupLabels(const std::string &file, std::vector<long long> &labels, const std::string &option) const;
   void block();
   void sim();
   void Help() const;
@@ -67,7 +72,7 @@ void GP_Cntrl::Help() const {
   std::cout << "\nGP_SS_AK hot path on MI355X\nCommand:\n \t ./gp_ss_ak [options] Command [Comnd-options] TrainDataFile.txt modelName\n"
             << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood).\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
-            << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time).\n"
+            << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
             << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]).\n";
 }
@@ -252,8 +257,9 @@ void GP_Cntrl::test() {
   exit(0);
 }
 
-// one integer label per line (or several, separated by blanks, tabs or commas); `#` lines are skipped
-void GP_Cntrl::readGroupLabels(const std::string &file, std::vector<long long> &labels) const {
+// one integer label per line (or several, separated by blanks, tabs or commas); `#` lines are skipped.  option: the
+// command-line option the file came with, for the error text
+void GP_Cntrl::readGroupLabels(const std::string &file, std::vector<long long> &labels, const std::string &option) const {
   std::ifstream in(file.c_str());
   if (!in.is_open()) ErrorTermination("File is " + file + " not readable");
   std::string line;
@@ -267,7 +273,7 @@ void GP_Cntrl::readGroupLabels(const std::string &file, std::vector<long long> &
       errno = 0;
       const long long v = strtoll(tok.c_str(), &end, 10);
       if (end == tok.c_str() || *end != '\0' || errno == ERANGE)
-        ErrorTermination("--groups: '" + tok + "' in " + file + " is not an integer label");
+        ErrorTermination(option + ": '" + tok + "' in " + file + " is not an integer label");
       labels.push_back(v);
     }
   }
@@ -279,7 +285,10 @@ void GP_Cntrl::cv() {
   if (gpus > 1)
     ErrorTermination("cv runs on one GPU only (leave-one-out cross-validation is not built for multi-GPU contexts): drop --gpus");
   bool yscale = true;
-  std::string groupsFile;
+  std::string groupsFile, foldsFile;
+  bool kfold_set = false, seed_set = sim_seed_set;
+  long kfold = 0;
+  unsigned long long seed = sim_seed_set ? sim_seed : 1;
   while (isFlgs()) {
     if (isArgFlg()) {
       if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
@@ -289,21 +298,45 @@ void GP_Cntrl::cv() {
         if (getArgNo() >= argc) ErrorTermination("--groups takes a file of labels");
         groupsFile = getArg();
       }
+      else if (isArg("--folds", "--folds")) {
+        incArg();
+        if (getArgNo() >= argc) ErrorTermination("--folds takes a file of labels");
+        foldsFile = getArg();
+      }
+      else if (isArg("--kfold", "--kfold")) {
+        incArg();
+        char *end = nullptr;
+        const std::string tok = getArg();
+        kfold = strtol(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0') ErrorTermination("--kfold takes the number of folds");
+        kfold_set = true;
+      }
+      else if (isArg("--seed", "--seed")) {
+        incArg();
+        char *end = nullptr;
+        const std::string tok = getArg();
+        seed = strtoull(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0') ErrorTermination("--seed takes a non-negative integer");
+        seed_set = true;
+      }
       else UnkFlg();
       incArg();
     } else setFlgs(false);
   }
+  if ((int)!groupsFile.empty() + (int)!foldsFile.empty() + (int)kfold_set > 1)
+    ErrorTermination("--groups, --folds and --kfold exclude each other: give one of them");
+  if (seed_set && !kfold_set) ErrorTermination("--seed goes with --kfold");
   if (getArgNo() + 1 >= argc) ErrorTermination("There are not enough input parameters: cv needs the training data and the model.");
   std::string trFile = getArg(), modelName = argv[getArgNo() + 1];
-  const bool grouped = !groupsFile.empty();
-  std::string LooOut = modelName + (grouped ? "_lgo.txt" : "_loo.txt");
+  const bool grouped = !groupsFile.empty(), folded = !foldsFile.empty() || kfold_set;
+  std::string LooOut = modelName + (grouped ? "_lgo.txt" : folded ? "_folds.txt" : "_loo.txt");
   if (getArgNo() + 2 < argc) LooOut = argv[getArgNo() + 2];
   int ds[2];
   readDataSize(trFile, ds);
   std::vector<long long> labels, values;   // as read; the sorted unique labels
   std::vector<int> group;                  // rank of each sample's label among them
   if (grouped) {                           // everything that can be refused is refused before a context exists
-    readGroupLabels(groupsFile, labels);
+    readGroupLabels(groupsFile, labels, "--groups");
     if ((int)labels.size() != ds[0])
       ErrorTermination("--groups: " + groupsFile + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(ds[0]) +
                        " training samples");
@@ -319,6 +352,26 @@ void GP_Cntrl::cv() {
                          " samples (leave-group-out holds a group in one workgroup's memory)");
     }
   }
+  if (folded) {                            // the same: refused before a context exists
+    if (kfold_set) {
+      if (kfold < 2 || kfold > ds[0])
+        ErrorTermination("--kfold: " + std::to_string(kfold) + " folds for " + std::to_string(ds[0]) +
+                         " training samples (2 <= K <= N is needed)");
+      gpak_kfold_assign(seed, (size_t)ds[0], (int)kfold, group);
+      labels.assign(group.begin(), group.end());
+    } else {
+      readGroupLabels(foldsFile, labels, "--folds");
+      if ((int)labels.size() != ds[0])
+        ErrorTermination("--folds: " + foldsFile + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(ds[0]) +
+                         " training samples");
+    }
+    values = labels;
+    std::sort(values.begin(), values.end());
+    values.erase(std::unique(values.begin(), values.end()), values.end());
+    group.resize(labels.size());
+    for (size_t i = 0; i < labels.size(); i++)
+      group[i] = (int)(std::lower_bound(values.begin(), values.end(), labels[i]) - values.begin());
+  }
   mat X, y;
   readDataFile(X, y, ds, trFile);
   prepareData(X, y, yscale, modelName);                         // the model's _Statistics.txt, as `test`
@@ -330,6 +383,37 @@ void GP_Cntrl::cv() {
   GPModel->initialize_vars();
   GPModel->logLikelihood();
   mat LooVals(y.n_rows, 1), LooVals_Var(y.n_rows, 1);
+  if (folded) {
+    mat logp(values.size(), 1);
+    gpak_cv_groups_summary gs;
+    GPModel->FoldCV(group, (int)values.size(), LooVals, LooVals_Var, logp, gs);
+    postData(X, LooVals, yscale, modelName);
+    postData_var(LooVals_Var, yscale, modelName);
+    postData(y, yscale, modelName);
+    double mse = 0, ym = 0, vy = 0;
+    for (size_t i = 0; i < y.n_elem; i++) { mse += (y[i] - LooVals[i]) * (y[i] - LooVals[i]); ym += y[i]; }
+    mse /= X.n_rows; ym /= y.n_elem;
+    for (size_t i = 0; i < y.n_elem; i++) vy += (y[i] - ym) * (y[i] - ym);
+    vy /= y.n_elem;
+    if (getVerbose() > 0) {
+      std::cout << "Mean Square Error of k-fold: " << mse << "\n" << "Var MSE Train: " << vy << "\n"
+                << "Mean standardised squared residual: " << gs.mssr << "\n" << "Mean squared Mahalanobis residual: " << gs.msmd << "\n"
+                << "Log predictive density of the groups: " << gs.log_pl << "\n" << "Folds: " << gs.groups << "\n"
+                << "CV ms: " << gs.ms << "\n";
+    } else { std::cout << mse << "\n" << vy << "\n" << gs.mssr << "\n" << gs.msmd << "\n" << gs.log_pl << "\n"; }
+    // rows in input order; the fifth column is what postData_var returns, as StdYh of _predict.txt
+    std::ofstream out(LooOut.c_str());
+    out << "# SampleNo, Fold, Y, Ycv, StdYcv, Inputs" << "\n";
+    for (size_t i = 0; i < y.n_elem; i++) {
+      out << (i + 1) << "\t" << labels[i] << "\t" << y[i] << "\t" << LooVals[i] << "\t" << LooVals_Var[i] << "\t";
+      for (size_t j = 0; j < X.n_cols; j++) out << X(i, j) << "\t";
+      out << "\n";
+    }
+    out.close();
+    writeTiming(*GPModel);
+    delete GPModel;
+    exit(0);
+  }
   if (grouped) {
     mat logp(values.size(), 1);
     gpak_cv_groups_summary gs;

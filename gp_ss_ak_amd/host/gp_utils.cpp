@@ -199,6 +199,18 @@ void GP_utils::GroupCV(const std::vector<int> &group, int n_groups, mat &mean, m
   if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_cv_groups", ctx);
 }
 
+void GP_utils::FoldCV(const std::vector<int> &group, int n_groups, mat &mean, mat &var, mat &logp,
+                      gpak_cv_groups_summary &s) const {
+  sync_params();
+  if (group.size() != Xinp.n_rows) { std::cerr << "FoldCV: one label per training sample is needed." << std::endl; exit(1); }
+  if (mean.n_elem != Xinp.n_rows) mean.resize(Xinp.n_rows, 1);
+  if (var.n_elem != Xinp.n_rows) var.resize(Xinp.n_rows, 1);
+  if (n_groups > 0 && logp.n_elem != (size_t)n_groups) logp.resize(n_groups, 1);
+  int rc = gpak_cv_folds(ctx, group.data(), n_groups, mean.memptr(), var.memptr(), logp.memptr(), &s, 0);
+  Chol_fail = (rc == GPAK_ENOTPD);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_cv_folds", ctx);
+}
+
 void GP_utils::BlockMeanVar(mat &mean, mat &var, const mat &Xd, int nd, bool latent) const {
   sync_params();
   const size_t M = nd > 0 ? Xd.n_rows / nd : 0;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/gpak.h"
+#include "../../include/gpak_cv_folds.h"
 #include "kernels.hpp"
 
 class ModelInfo {
@@ -124,6 +125,8 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // marginal variance (noise included) of every yTarg(i) given all the samples outside its group, N x 1 each, and the
   // joint log predictive density of each group (n_groups x 1); NaN on Chol_fail
   void GroupCV(const std::vector<int> &group, int n_groups, mat &mean, mat &var, mat &logp, gpak_cv_groups_summary &s) const;
+  // k-fold cross-validation (gpak_cv_folds): GroupCV for groups of any size
+  void FoldCV(const std::vector<int> &group, int n_groups, mat &mean, mat &var, mat &logp, gpak_cv_groups_summary &s) const;
   // block-support prediction (gpak_predict_block): mean and variance of the average of the field over each block, block
   // b = rows b * nd .. b * nd + nd of Xd; the variance includes sn2 / nd unless latent; M x 1 each, NaN on Chol_fail
   void BlockMeanVar(mat &mean, mat &var, const mat &Xd, int nd, bool latent) const;
