@@ -7,6 +7,7 @@
 #include <limits>
 
 #include "../../include/gpak_cv_folds.h"
+#include "../../include/gpak_cv_groups_grad.h"
 #include "multi.h"
 
 #define GPAK_MULTI_ERR(rc_) do { int v_ = (rc_); if (v_) ctx->err = gpak_multi_error(ctx->multi); return v_; } while (0)
@@ -860,6 +861,13 @@ static int group_lists(gpak_ctx *ctx, const std::string &who, const int *group, 
   return GPAK_OK;
 }
 
+// what the grouped calls answer when the training factor failed: their own summary type, written out
+static void nan_cv_summary(gpak_cv_groups_summary *summary, int n_groups) {
+  if (!summary) return;
+  summary->mse = summary->mssr = summary->msmd = summary->log_pl = std::numeric_limits<double>::quiet_NaN();
+  summary->ms = 0.0; summary->groups = n_groups; summary->max_size = 0;
+}
+
 // gpak_cv_groups and gpak_cv_folds (folds: no limit on a group, and flags): what the call refuses is refused before
 // anything is factored
 static int cv_call(gpak_ctx *ctx, const char *name, bool folds, const int *group, int n_groups, double *mean, double *var,
@@ -883,10 +891,7 @@ static int cv_call(gpak_ctx *ctx, const char *name, bool folds, const int *group
     fill_nan(mean, N);
     fill_nan(var, N);
     fill_nan(group_logp, n_groups);
-    if (summary) {   // its own summary type: written out
-      summary->mse = summary->mssr = summary->msmd = summary->log_pl = std::numeric_limits<double>::quiet_NaN();
-      summary->ms = 0.0; summary->groups = n_groups; summary->max_size = 0;
-    }
+    nan_cv_summary(summary, n_groups);
   }
   return rc;
 }
@@ -894,6 +899,24 @@ static int cv_call(gpak_ctx *ctx, const char *name, bool folds, const int *group
 int gpak_cv_groups(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,
                    gpak_cv_groups_summary *summary) {
   return cv_call(ctx, "gpak_cv_groups", false, group, n_groups, mean, var, group_logp, summary, 0);
+}
+
+int gpak_cv_groups_grad(gpak_ctx *ctx, const int *group, int n_groups, double *g, int ng, gpak_cv_groups_summary *summary) {
+  if (!ctx || !g) return GPAK_EINVAL;
+  // what the call refuses is refused before anything is factored: the context, the composition, then the labels with
+  // gpak_cv_groups' own check
+  int rc = single_gpu_call(ctx, "gpak_cv_groups_grad", true, true, CtxState::NONE);
+  if (rc == GPAK_OK) rc = gpak_cv_groups_grad_layout(ctx, ng);
+  if (rc) return rc;
+  std::vector<int> offs, perm;
+  if ((rc = group_lists(ctx, "gpak_cv_groups_grad: ", group, n_groups, GPAK_CV_GROUP_MAX, perm, offs))) return rc;
+  rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK) return gpak_cv_groups_grad_impl(ctx, perm.data(), offs.data(), n_groups, g, ng, summary);
+  if (rc == GPAK_ENOTPD) {   // the training factor
+    fill_nan(g, ng);
+    nan_cv_summary(summary, n_groups);
+  }
+  return rc;
 }
 
 int gpak_cv_folds(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,

@@ -11,6 +11,13 @@
 //   2. gpak_cvg_gram_f64    one workgroup per group: S from the group's rows of G, fp64 MFMA, lower 16 x 16 tiles;
 //   3. gpak_cvg_solve_f64   one workgroup per group: R, R^-1, e, var, logp and the group's three sums, S in LDS.
 // The summary is added on the host over the groups in ascending order.
+//
+// gpak_cv_groups_grad (grad.hip) runs the same two passes and needs, per group, the weights of the gradient of
+// F = -log_pl:  C_I = sn2 S^-1 + e_I e_I^T = Q_I Q_I^T  with, for X = R^-1 and w = X alpha_I (so e_I = sn2 X^T w),
+//   C_I = sn2 X^T (I + sn2 w w^T) X,   (I + beta w w^T)^2 = I + sn2 w w^T  for  beta = sn2 / (1 + sqrt(1 + sn2 |w|^2)),
+//   Q_I = sqrt(sn2) X^T + (beta / sqrt(sn2)) e_I w^T
+// -- a factor in closed form, no second Cholesky.  gpak_cvg_solve_f64<true> writes e_I and Q_I beside its other outputs
+// and gpak_cvg_mix_f64 multiplies the columns of Kinv by the Q_I, a bin of groups at a time.
 #include <atomic>
 #include <climits>
 #include <cmath>
@@ -114,11 +121,18 @@ __global__ __launch_bounds__(256) void gpak_cvg_gram_f64(const double *__restric
 //   w = X alpha_I,   e = sn2 X^T w,   var_i = sn2 sum_j X_ji^2
 // and thread 0 adds the group's sums in ascending order: gsum[3 g ..] = sum e_i^2, sum e_i^2 / var_i, alpha_I . e_I.
 // A pivot that is not positive: the group's outputs are NaN and info takes the smallest such g + 1.
+// kWeights (gpak_cv_groups_grad): the same arithmetic, and afterwards e_I scattered into E (an Np-vector the caller has
+// zeroed) and Q_I written ROW-major with pitch CVG_MAX at Qb + qoff[g] -- the diagonal block of the group's bin matrix,
+// whose rows are what gpak_cvg_mix_f64 stages; X, w and e are in LDS already and Q needs no more of it.  A failed group
+// writes neither.
+template <bool kWeights>
 __global__ __launch_bounds__(256) void gpak_cvg_solve_f64(const double *__restrict__ Sbuf, const long long *__restrict__ soff,
                                                           const int *__restrict__ perm, const int *__restrict__ offs,
                                                           const double *__restrict__ y, const double *__restrict__ alpha,
                                                           double sn2, double *__restrict__ mean, double *__restrict__ var,
-                                                          double *__restrict__ logp, double *__restrict__ gsum, int *info) {
+                                                          double *__restrict__ logp, double *__restrict__ gsum, int *info,
+                                                          double *__restrict__ E, double *__restrict__ Qb,
+                                                          const long long *__restrict__ qoff) {
   extern __shared__ double cvg_lds[];
   const int g = blockIdx.x, t = threadIdx.x;
   const int o = offs[g], s = offs[g + 1] - o, sp = cvg_pad16(s);
@@ -210,6 +224,93 @@ __global__ __launch_bounds__(256) void gpak_cvg_solve_f64(const double *__restri
     gsum[3 * g + 2] = md;
     logp[g] = -0.5 * md - 0.5 * (s * log(sn2) - 2.0 * ld) - 0.5 * s * 1.8378770664093454836;   // log 2 pi
   }
+  if (kWeights) {
+    double ww = 0.0;                         // |w|^2, the same chain in every thread
+    for (int j = 0; j < s; j++) ww = fma(wv[j], wv[j], ww);
+    const double rs = sqrt(sn2), br = sn2 / (1.0 + sqrt(fma(sn2, ww, 1.0))) / rs;
+    if (t < s) E[perm[o + t]] = ev[t];
+    double *Q = Qb + qoff[g];
+    for (int e = t; e < s * s; e += 256) {   // Q_ij = sqrt(sn2) X_ji + (beta / sqrt(sn2)) e_i w_j; X_ji = 0 for j < i
+      const int i = e / s, j = e - i * s;
+      const double x = j > i ? A[i * CVG_RP + j] : j == i ? xd[i] : 0.0;
+      Q[i * CVG_MAX + j] = fma(br * ev[i], wv[j], rs * x);
+    }
+  }
+}
+
+// H[:, cols] <- H[:, cols] Qbin in place, cols = perm[bstart[b] .. bstart[b + 1]) the columns of bin b = blockIdx.y (at most
+// CVG_MAX of them), rows the 128-row tile blockIdx.x.  Qbin is the bin's CVG_MAX x CVG_MAX matrix at Qb + b * CVG_MAX^2,
+// row-major: the Q_I of its groups on the diagonal, zero elsewhere (no structural-zero skipping: the dense product is
+// 2 * 128^2 flop per row and bin).  The scattered columns are each contiguous along the rows: a step of CVM_KC of them and
+// the same rows of Qbin are staged in LDS by all four waves, lanes along the rows / along Qbin's columns, while the next
+// step is on its way to registers.  Wave w owns the output row tiles 2 w and 2 w + 1 and all column tiles: every element
+// is ONE accumulator chain over k ascending, so two calls return the same bytes.  The tile's outputs stay in registers
+// until the last step has been staged -- by then every read of the tile is done, and no other workgroup touches its
+// elements: in place is safe.  Columns past the bin's width are neither read nor written.
+#define CVM_KC 16
+__global__ __launch_bounds__(256) void gpak_cvg_mix_f64(double *H, long ld, const int *__restrict__ perm,
+                                                        const int *__restrict__ bstart, const double *__restrict__ Qb) {
+  __shared__ double shA[CVM_KC * CVG_PITCH], shQ[CVM_KC * CVG_PITCH];
+  const int b = blockIdx.y;
+  const int p0 = bstart[b], width = bstart[b + 1] - p0;
+  const int nct = __builtin_amdgcn_readfirstlane((width + 15) >> 4);
+  const int kend = (width + CVM_KC - 1) / CVM_KC * CVM_KC;
+  const int t = threadIdx.x, lane = t & 63, l15 = lane & 15, l4 = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int r = t & 127, kh = t >> 7;        // staging: row r of the tile / column r of Qbin, steps kh * 8 .. kh * 8 + 7
+  double *Hr = H + (size_t)blockIdx.x * CVG_MAX;
+  const double *Q = Qb + (size_t)b * CVG_MAX * CVG_MAX;
+  cvg_d4 acc[2][8];
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+#pragma unroll
+    for (int c = 0; c < 8; c++) acc[h][c] = (cvg_d4){0.0, 0.0, 0.0, 0.0};
+  double va[8], vq[8];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      const int k = k0 + kh * 8 + u;
+      const bool live = k < width;
+      va[u] = live ? Hr[(size_t)r + (size_t)perm[p0 + (live ? k : 0)] * ld] : 0.0;
+      vq[u] = live ? Q[(size_t)k * CVG_MAX + r] : 0.0;
+    }
+  };
+  load(0);
+  for (int k0 = 0; k0 < kend; k0 += CVM_KC) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      shA[(kh * 8 + u) * CVG_PITCH + r] = va[u];
+      shQ[(kh * 8 + u) * CVG_PITCH + r] = vq[u];
+    }
+    __syncthreads();
+    if (k0 + CVM_KC < kend) load(k0 + CVM_KC);
+#pragma unroll
+    for (int kq = 0; kq < CVM_KC / 4; kq++) {
+      const double *ca = shA + (kq * 4 + l4) * CVG_PITCH + l15, *cq = shQ + (kq * 4 + l4) * CVG_PITCH + l15;
+      const double fa0 = ca[(2 * w) * 16], fa1 = ca[(2 * w + 1) * 16];
+#pragma unroll
+      for (int c = 0; c < 8; c++)
+        if (c < nct) {
+          const double fq = cq[c * 16];
+          acc[0][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, fa0, acc[0][c], 0, 0, 0);
+          acc[1][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, fa1, acc[1][c], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+  }
+  // lane holds of tile (rt, ct): row rt * 16 + l15, columns ct * 16 + l4 + 4 q
+#pragma unroll
+  for (int c = 0; c < 8; c++)
+    if (c < nct)
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int col = c * 16 + l4 + 4 * q;
+        if (col < width) {
+          double *out = Hr + (size_t)perm[p0 + col] * ld;
+          out[(2 * w) * 16 + l15] = acc[0][c][q];
+          out[(2 * w + 1) * 16 + l15] = acc[1][c][q];
+        }
+      }
 }
 
 static size_t cvg_solve_lds(int s) { return sizeof(double) * ((size_t)s * CVG_RP + 6 * CVG_MAX); }
@@ -229,21 +330,51 @@ void gpak_cvg_launch_gram(gpak_ctx *ctx, const double *G, long ld, int n_groups,
                           const long long *dsoff, double *dS) {
   hipLaunchKernelGGL(gpak_cvg_gram_f64, dim3(n_groups), dim3(256), 0, ctx->stream, G, ld, ctx->Np, dperm, doffs, dsoff, dS);
 }
-void gpak_cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
-                           const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
-                           int *dinfo) {
+template <bool kWeights>
+static void cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
+                             const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
+                             int *dinfo, double *dE, double *dQb, const long long *dqoff) {
   // more than 64 KiB of dynamic LDS needs the opt-in, once per kernel and per device
   {
     static std::atomic<unsigned long long> done_mask{0};
     const unsigned long long bit = 1ull << (ctx->device & 63);
     if (!(done_mask.load(std::memory_order_acquire) & bit)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gpak_cvg_solve_f64), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)cvg_solve_lds(CVG_MAX));
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gpak_cvg_solve_f64<kWeights>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)cvg_solve_lds(CVG_MAX));
       done_mask.fetch_or(bit, std::memory_order_release);
     }
   }
-  hipLaunchKernelGGL(gpak_cvg_solve_f64, dim3(n_groups), dim3(256), cvg_solve_lds(max_size), ctx->stream, dS, dsoff, dperm,
-                     doffs, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, dlogp, dgsum, dinfo);
+  hipLaunchKernelGGL(gpak_cvg_solve_f64<kWeights>, dim3(n_groups), dim3(256), cvg_solve_lds(max_size), ctx->stream, dS, dsoff,
+                     dperm, doffs, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, dlogp, dgsum, dinfo, dE, dQb, dqoff);
+}
+void gpak_cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
+                           const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
+                           int *dinfo) {
+  cvg_launch_solve<false>(ctx, n_groups, max_size, dS, dsoff, dperm, doffs, dmean, dvar, dlogp, dgsum, dinfo, nullptr, nullptr,
+                          nullptr);
+}
+void gpak_cvg_launch_solve_weights(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
+                                   const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp,
+                                   double *dgsum, int *dinfo, double *dE, double *dQb, const long long *dqoff) {
+  cvg_launch_solve<true>(ctx, n_groups, max_size, dS, dsoff, dperm, doffs, dmean, dvar, dlogp, dgsum, dinfo, dE, dQb, dqoff);
+}
+void gpak_cvg_launch_mix(gpak_ctx *ctx, double *H, long ld, int n_bins, const int *dperm, const int *dbstart, const double *dQb) {
+  hipLaunchKernelGGL(gpak_cvg_mix_f64, dim3(ctx->Np / CVG_MAX, n_bins), dim3(256), 0, ctx->stream, H, ld, dperm, dbstart, dQb);
+}
+
+// The bins of the column mix: consecutive groups of the (group, sample) order packed greedily into bins of at most
+// CVG_MAX columns -- a group opens a new bin when it does not fit the current one, so two adjacent bins hold more than
+// CVG_MAX columns together and there are at most 2 N / CVG_MAX + 1 of them.  first[b] = the first group of bin b,
+// first[n_bins] = n_groups (room for n_groups + 1 entries); returns n_bins.  sizes: every one in [1, CVG_MAX].  Not part
+// of the C-ABI (no header declares it): tests/test_cv_groups_grad.py holds it to these properties.
+extern "C" int gpak_cvg_pack_bins(const int *sizes, int n_groups, int *first) {
+  int nb = 0, fill = 0;
+  for (int g = 0; g < n_groups; g++) {
+    if (g == 0 || fill + sizes[g] > CVG_MAX) { first[nb++] = g; fill = 0; }
+    fill += sizes[g];
+  }
+  first[nb] = n_groups;
+  return nb;
 }
 
 // gpak_cv_groups on a single-GPU context whose factor and alpha are current, the labels already checked (api.hip):

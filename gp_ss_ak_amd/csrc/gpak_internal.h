@@ -493,6 +493,11 @@ int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *su
 int gpak_loo_grad_impl(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary);
 // its refusals, from the composition alone: GPAK_EINVAL for a wrong ng, GPAK_ENOTIMPL for a White child or a second ExpAns child
 int gpak_loo_grad_layout(gpak_ctx *ctx, int ng);
+// gpak_cv_groups_grad on a single-GPU context whose factor and alpha are current and whose labels api.hip has checked (perm
+// and offs as for gpak_cv_groups_impl); summary may be null.  Its refusals from the composition alone: the layout call
+int gpak_cv_groups_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *g, int ng,
+                             gpak_cv_groups_summary *summary);
+int gpak_cv_groups_grad_layout(gpak_ctx *ctx, int ng);
 // Rot (Kernel.cpp:1399-1410) of the ExpAns parameters e; D (optional): D[a] = dRot / d angle_a
 void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]);
 void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *expans, int d, int N, double sn2,
@@ -520,6 +525,18 @@ void gpak_cvg_launch_gram(gpak_ctx *ctx, const double *G, long ld, int n_groups,
 void gpak_cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
                            const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
                            int *dinfo);
+// the solve pass of gpak_cv_groups_grad: the same outputs, the same bytes, and the weights of the gradient -- e_I scattered
+// into dE (Np doubles, zeroed by the caller) and Q_I (Q_I Q_I^T = sn2 S^-1 + e_I e_I^T) row-major with pitch
+// GPAK_CV_GROUP_MAX at dQb + dqoff[g]
+void gpak_cvg_launch_solve_weights(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
+                                   const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp,
+                                   double *dgsum, int *dinfo, double *dE, double *dQb, const long long *dqoff);
+// the column mix: H[:, dperm[dbstart[b] .. dbstart[b + 1])] times bin b's 128 x 128 row-major matrix at dQb + b * 128^2, in
+// place, for every 128-row tile of the Np rows and every bin
+void gpak_cvg_launch_mix(gpak_ctx *ctx, double *H, long ld, int n_bins, const int *dperm, const int *dbstart, const double *dQb);
+// greedy bins of at most GPAK_CV_GROUP_MAX columns over consecutive groups: first[b] = first group of bin b,
+// first[n_bins] = n_groups; returns n_bins
+extern "C" int gpak_cvg_pack_bins(const int *sizes, int n_groups, int *first);
 
 // ---- cv_folds.hip -----------------------------------------------------------------------
 // P[r, c] = G[rows[r], k0 + c] (r < m; zero rows up to m_p = m rounded up to 128), c < Np - k0: gpak_cvf_pack_f64

@@ -5,7 +5,8 @@
 // Kern_Bias::getGradients (:370-377), FORMULAS AS WRITTEN (this is not the
 // true gradient -- the optimiser trajectory of the reference depends on it as it is).
 // gpak_grad_exact is the derivative of nlZ itself; gpak_loo (leave-one-out cross-validation) is step 1 below alone and
-// gpak_loo_grad the gradient of its pseudo-likelihood: the exact pass with another weight matrix; gpak_dev_grad_*
+// gpak_loo_grad the gradient of its pseudo-likelihood: the exact pass with another weight matrix; gpak_cv_groups_grad the
+// same for the leave-group-out criterion of gpak_cv_groups (cv_groups.hip has its two kernels); gpak_dev_grad_*
 // (further down) is the as-written gradient distributed over ranks by row blocks.
 //
 // Reference: Q = solve_chol(Lchol, diag(sW)) with N right-hand sides (2N^3 flops), ~15 N x N
@@ -18,8 +19,11 @@
 //      accumulates NSUM sums the gradient entries are made of: gpak_grad_pairs_f64<Pass>, Pass = RefPass (as written)
 //      or ExactPass.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
+#include <limits>
+#include <string>
 #include <vector>
 
 #include "../../include/gpak_dev.h"
@@ -1018,6 +1022,148 @@ int gpak_loo_grad_impl(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summa
   ctx->times.grad_ms = ms;
   ExactPass::assemble(ctx, red, g);
   loo_fill_summary(summary, lred, N, ms, 1);
+  return GPAK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The gradient of the leave-group-out criterion (gpak_cv_groups_grad): F = -log_pl of gpak_cv_groups.  With Ky = K + sn2 I =
+// sn2 B, Kinv = B^-1 / sn2, alpha = Kinv y and, for a group with index set I, S = [B^-1]_II = R R^T, X = R^-1,
+// w = X alpha_I, e_I = sn2 X^T w = y_I - mean_I:
+//   F = sum_g [ 1/2 alpha_I . e_I - 1/2 log |S / sn2| ] + N/2 log 2 pi.
+// d alpha = -Kinv dK alpha and d(Kinv)_II = -[Kinv dK Kinv]_II give
+//   dF / d theta = 1/2 sum_ij W_ij d(Ky)_ij / d theta,   W = Kinv C Kinv - v alpha^T - alpha v^T,
+//   C = blockdiag(C_I),  C_I = sn2 S^-1 + e_I e_I^T,  e = the N-vector of all e_I,  v = Kinv e.
+// C_I = Q_I Q_I^T in closed form (cv_groups.hip), so W = H H^T - v alpha^T - alpha v^T with H = Kinv[:, perm] blockdiag(Q_I);
+// the column order of H does not matter to H H^T, so H is mixed in place, column set by column set.  Groups of one sample:
+// C_i = 2 c_i of gpak_loo_grad and W is its W.  W is symmetric: the exact pass and its assembly serve unchanged, handed
+// sn2 = 1 and a zero alpha, as in gpak_loo_grad_impl.  Memory: the gradient's two N x N workspaces and the scratch buffer
+// (the S of every group, one 128 x 128 matrix per bin of the mix, vectors and lists).
+// ---------------------------------------------------------------------------------------
+// s_k = c for k < N, 0 on the padding
+__global__ __launch_bounds__(256) void gpak_lgo_colscale_f64(int N, int Np, double c, double *__restrict__ s) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < Np) s[i] = i < N ? c : 0.0;
+}
+
+int gpak_cv_groups_grad_layout(gpak_ctx *ctx, int ng) {
+  int te;
+  return grad_layout(ctx, "gpak_cv_groups_grad", ExactPass::white, ng, &te);
+}
+
+// gpak_cv_groups_grad on a single-GPU context whose factor and alpha are current, the labels already checked.  Everything
+// goes to the context's stream and the host waits once, at the end.  Afterwards dG holds H and dBinv holds W: no claim is
+// left behind (see gpak_loo_grad_impl: the context keeps no validity flag for either workspace).  dAlpha, the factor, nlZ
+// and the first two vectors of dWork are only read.
+int gpak_cv_groups_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *g, int ng,
+                             gpak_cv_groups_summary *summary) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np, T = Np / PB;
+  const long ld = ctx->ld;
+  int te = -1;
+  int rc = grad_layout(ctx, "gpak_cv_groups_grad", ExactPass::white, ng, &te);
+  if (rc) return rc;
+  // the lists of gpak_cv_groups_impl, and the bins of the column mix: bin b holds the positions bstart[b] .. bstart[b + 1]
+  // of perm; the Q of group g starts at (c0, c0) of its bin's row-major 128 x 128 matrix, c0 its first column in the bin
+  const size_t nG = (size_t)n_groups;
+  std::vector<long long> soff(nG + 1), qoff(nG);
+  std::vector<int> sizes(nG), first(nG + 1);
+  int max_size = 0;
+  soff[0] = 0;
+  for (size_t k = 0; k < nG; k++) {
+    sizes[k] = offs[k + 1] - offs[k];
+    max_size = std::max(max_size, sizes[k]);
+    soff[k + 1] = soff[k] + gpak_cvg_s_elems(sizes[k]);
+  }
+  const int n_bins = gpak_cvg_pack_bins(sizes.data(), n_groups, first.data());
+  std::vector<int> bstart((size_t)n_bins + 1);
+  for (int b = 0; b <= n_bins; b++) bstart[b] = offs[first[b]];
+  for (int b = 0; b < n_bins; b++)
+    for (int k = first[b]; k < first[b + 1]; k++)
+      qoff[k] = (long long)b * PB * PB + (long long)(offs[k] - bstart[b]) * (PB + 1);
+  // scratch in the gradient's partial-sum buffer: gpak_cv_groups' layout (the S of every group, mean, var, logp, the groups'
+  // three sums), then e (Np), the bins' matrices, the pair pass's block sums; then the lists
+  const size_t nS = (size_t)soff[nG], nQ = (size_t)n_bins * PB * PB, nP = (size_t)T * (Np / GT_COLS) * NSUM;
+  const size_t n_dbl = nS + 2 * (size_t)N + 4 * nG + (size_t)Np + nQ + nP;
+  const size_t n_ll = 2 * nG + 1, n_int = (size_t)N + nG + 1 + 1 + (size_t)n_bins + 1;
+  rc = grad_partials(ctx, n_dbl + n_ll + (n_int + 1) / 2);
+  if (rc) return rc;
+  rc = gpak_ensure_U(ctx);
+  if (rc) return rc;
+  double *dS = ctx->dGpart, *dmean = dS + nS, *dvar = dmean + N, *dlogp = dvar + N, *dgsum = dlogp + nG;
+  double *dE = dgsum + 3 * nG, *dQb = dE + Np, *part = dQb + nQ;
+  long long *dsoff = reinterpret_cast<long long *>(part + nP), *dqoff = dsoff + nG + 1;
+  int *dperm = reinterpret_cast<int *>(dqoff + nG), *doffs = dperm + N, *dinfo = doffs + nG + 1, *dbstart = dinfo + 1;
+  // five vectors of dWork behind the back substitution's scratch, as gpak_loo_grad_impl takes them
+  const int bw = ctx->bwd_bw;
+  double *bs_scratch = ctx->dWork + 2 * (size_t)Np;
+  double *vs = bs_scratch + (size_t)std::max(8 + bw / 32, 34) * bw, *vr = vs + Np, *vz = vr + Np, *vv = vz + Np, *zero = vv + Np;
+  const int info0 = INT_MAX;
+  GPAK_HIP(hipMemcpyAsync(dsoff, soff.data(), sizeof(long long) * (nG + 1), hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipMemcpyAsync(dqoff, qoff.data(), sizeof(long long) * nG, hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipMemcpyAsync(dperm, perm, sizeof(int) * N, hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipMemcpyAsync(doffs, offs, sizeof(int) * (nG + 1), hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipMemcpyAsync(dinfo, &info0, sizeof(int), hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipMemcpyAsync(dbstart, bstart.data(), sizeof(int) * ((size_t)n_bins + 1), hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipMemsetAsync(dE, 0, sizeof(double) * ((size_t)Np + nQ), st));   // e on the padding, the bins off their diagonal blocks
+  // 1. G = L^-T in dG, B^-1 in dBinv (records ev[7])
+  rc = grad_binv(ctx);
+  if (rc) return rc;
+  // 2. the two passes of gpak_cv_groups on dG, the solve pass with the weights e and Q
+  gpak_cvg_launch_gram(ctx, ctx->dG, ld, n_groups, dperm, doffs, dsoff, dS);
+  gpak_cvg_launch_solve_weights(ctx, n_groups, max_size, dS, dsoff, dperm, doffs, dmean, dvar, dlogp, dgsum, dinfo, dE, dQb, dqoff);
+  // 3. r = e / sn2 and v = B^-1 r = Kinv e by two substitutions on scratch vectors
+  gpak_launch_scale(st, Np, dE, 1.0 / ctx->sn2, vr);
+  gpak_launch_trsv_fwd(st, Np, ctx->dM, ld, ctx->dInv, vr, vz);
+  gpak_backsolve(ctx, st, vz, vv, bs_scratch);
+  // 4. Kinv, full and zero on the padding, into dG (G has been consumed)
+  hipLaunchKernelGGL(gpak_lgo_colscale_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, 1.0 / ctx->sn2, vs);
+  const dim3 lt(Np / LM_T, Np / LM_T);
+  hipLaunchKernelGGL(gpak_loo_mirror_scale_f64, lt, dim3(256), 0, st, N, ctx->dBinv, ld, vs, ctx->dG, ld);
+  // 5. H = Kinv[:, perm] blockdiag(Q_I), in place
+  gpak_cvg_launch_mix(ctx, ctx->dG, ld, n_bins, dperm, dbstart, dQb);
+  // 6. H H^T, lower tiles, into dBinv; H is full: the k-loop runs over all of Np
+  gpak_launch_gemm_nt(st, T, T, Np, 1.0, ctx->dG, ld, ctx->dG, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, false);
+  // 7. W = H H^T - v alpha^T - alpha v^T
+  hipLaunchKernelGGL(gpak_loo_rank2_f64, lt, dim3(256), 0, st, ctx->dBinv, ld, vv, ctx->dAlpha);
+  // 8. the exact pass with W for its weight
+  GPAK_HIP(hipMemsetAsync(zero, 0, sizeof(double) * Np, st));
+  pair_sums<ExactPass>(st, ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode, ctx->d, ctx->U.base, ctx->U.cap,
+                       ctx->dX, Np, N, Np, zero, ctx->dBinv, ld, 0, 0, 1.0, part, ctx->dRed + 8);
+  double red[NSUM];
+  std::vector<double> hsum(4 * nG);   // logp, then the three sums per group
+  int info = 0;
+  GPAK_HIP(hipMemcpyAsync(red, ctx->dRed + 8, sizeof(red), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipMemcpyAsync(hsum.data(), dlogp, sizeof(double) * 4 * nG, hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipMemcpyAsync(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipEventRecord(ctx->ev[3], st));
+  GPAK_HIP(hipEventSynchronize(ctx->ev[3]));
+  GPAK_HIP(hipGetLastError());
+  float ms = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[3]));
+  ctx->times.grad_ms = ms;
+  if (summary) {
+    double sse = 0.0, ssr = 0.0, md = 0.0, lp = 0.0;
+    for (size_t k = 0; k < nG; k++) {   // ascending, as gpak_cv_groups_impl adds them
+      lp += hsum[k];
+      sse += hsum[nG + 3 * k];
+      ssr += hsum[nG + 3 * k + 1];
+      md += hsum[nG + 3 * k + 2];
+    }
+    summary->mse = sse / N;
+    summary->mssr = ssr / N;
+    summary->msmd = md / N;
+    summary->log_pl = lp;
+    summary->ms = ms;
+    summary->groups = n_groups;
+    summary->max_size = max_size;
+  }
+  if (info != INT_MAX) {
+    for (int k = 0; k < ng; k++) g[k] = std::numeric_limits<double>::quiet_NaN();
+    ctx->err = "gpak_cv_groups_grad: S = [B^-1]_II of group " + std::to_string(info - 1) + " is not positive definite";
+    return GPAK_ENOTPD;
+  }
+  ExactPass::assemble(ctx, red, g);
   return GPAK_OK;
 }
 

@@ -240,6 +240,20 @@ class Gpak:
         out["labels"] = values
         return mean, var, logp, out
 
+    def cv_groups_grad(self, labels, ng=10):
+        """The gradient of -log_pl of cv_groups(labels) (gpak_cv_groups_grad): (g, summary), g in GradLL_exact's layout,
+        labels and summary as cv_groups takes and returns them (the summary's ms is the call's grad_ms).  On Chol_fail
+        status is ENOTPD and every number is NaN."""
+        group, values = group_labels(labels, self.N)
+        g = np.zeros(int(ng))
+        s = _lib.CvGroupsSummary()
+        rc = self._check(self._lib.gpak_cv_groups_grad(self._h, group.ctypes.data_as(C.POINTER(C.c_int)), int(values.size),
+                                                       _p(g), int(ng), C.byref(s)), allow=(ENOTPD,))
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        out["labels"] = values
+        return g, out
+
     def cv_folds(self, labels, no_batch=False):
         """k-fold cross-validation from the current factor (gpak_cv_folds): cv_groups for groups of any size, the same
         (mean, var, logp, summary) with the same summary keys.  no_batch: every group, whatever its size, takes the

@@ -30,9 +30,10 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
     }
     else if (isArg("--objective", "--objective")) {
       incArg();
-      if (getArg() == "nlz") loo_objective = false;
-      else if (getArg() == "loo") loo_objective = true;
-      else ErrorTermination("--objective takes nlz or loo");
+      if (getArg() == "nlz") loo_objective = lgo_objective = false;
+      else if (getArg() == "loo") { loo_objective = true; lgo_objective = false; }
+      else if (getArg() == "lgo") { lgo_objective = true; loo_objective = false; }
+      else ErrorTermination("--objective takes nlz or loo or lgo");
     }
     else if (isArg("-t", "--timing")) { incArg(); timing_file = getArg(); }   // "-" = stdout
     else if (isArg("--block-size", "--block-size") || isArg("--block-disc", "--block-disc")) {
@@ -64,6 +65,10 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
     ErrorTermination("--objective loo has an exact gradient only (gpak_loo_grad) and implies its driver: drop --gradient reference");
   if (loo_objective && gpus > 1)
     ErrorTermination("--objective loo runs on one GPU only (the leave-one-out gradient is not built for multi-GPU contexts): drop --gpus");
+  if (lgo_objective && gradient_set && !exact_gradient)
+    ErrorTermination("--objective lgo has an exact gradient only (gpak_cv_groups_grad) and implies its driver: drop --gradient reference");
+  if (lgo_objective && gpus > 1)
+    ErrorTermination("--objective lgo runs on one GPU only (the leave-group-out gradient is not built for multi-GPU contexts): drop --gpus");
   if (exact_gradient && gpus > 1)
     ErrorTermination("--gradient exact runs on one GPU only (the exact gradient is not built for multi-GPU contexts): drop --gpus or use --gradient reference");
 }

@@ -48,8 +48,9 @@ class Control {
   int gpus = 1;                  // --gpus n: block-column-cyclic multi-GPU context (gpak_create_multi)
   int precision = 0;             // --precision f64|f32: GPAK_F64 / GPAK_F32 (fp32 prediction work)
   bool exact_gradient = false;   // --gradient reference|exact: GradLL as the reference writes it / the derivative of nlZ
-  bool gradient_set = false;     // --gradient was given (an explicit `reference` cannot go with --objective loo)
+  bool gradient_set = false;     // --gradient was given (an explicit `reference` cannot go with --objective loo / lgo)
   bool loo_objective = false;    // --objective nlz|loo: train on nlZ / on -log_pl of the leave-one-out predictions (gpak_loo_grad)
+  bool lgo_objective = false;    // --objective lgo: on -log_pl of the leave-group-out predictions (gpak_cv_groups_grad; train --groups FILE)
   std::string timing_file;       // --timing file|-: JSON of gpak_phase_times after the verb
   // the `block` verb: --block-size dx,dy,dz (the file's units), --block-disc nx,ny,nz, --latent (no sn2 / nd)
   double block_size[3] = {0, 0, 0};

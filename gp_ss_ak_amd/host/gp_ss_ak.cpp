@@ -1,5 +1,6 @@
 // gp_ss_ak.cpp -- the reference's command line (gp_ss_ak.cpp:14-557) over the HIP hot path:
-//   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] train.txt [model]
+//   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] [--groups labels.txt]
+//            train.txt [model]
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
 //   gp_ss_ak [-v n]               [device options] cv [-np] [--groups labels.txt | --folds labels.txt | --kfold K [--seed n]]
 //            train.txt model [out_file]
@@ -10,7 +11,12 @@
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
 // (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only),
 // --objective nlz|loo (loo: `train` minimises -log_pl of the leave-one-out predictions, what `cv` reports, with its exact
-// gradient gpak_loo_grad and the exact gradient's driver; the objective column of the trace holds -log_pl; one GPU only).
+// gradient gpak_loo_grad and the exact gradient's driver; the objective column of the trace holds -log_pl; one GPU only;
+// lgo: the same for the leave-group-out predictions of `cv --groups`, with gpak_cv_groups_grad: `--objective lgo train
+// --groups FILE`, FILE as `cv --groups` reads it and held to the same checks before a context exists.  `train` reads the
+// samples with readDataFile, which fills row p from the p-th data line, and prepareData, which shifts and scales columns
+// in place; GP_utils hands Xinp and yTarg to gpak_set_train as they are.  No step reorders, drops or adds a row, so label
+// i of FILE belongs to training sample i of the context, exactly as in `cv`).
 // cv (not a reference verb): leave-one-out cross-validation of a trained model on its training set, from one
 // factorisation (gpak_loo; one GPU only), written to <model>_loo.txt.  With --groups FILE (one integer label per training
 // sample, in input order; `#` lines are skipped) it leaves out whole groups instead -- a drill hole, a fold -- of at most
@@ -52,6 +58,10 @@ class GP_Cntrl : public Control {
     GP_utils::setExactGradient(exact_gradient);
     GP_utils::setLooObjective(loo_objective);
   }
+  // FILE of --groups for leave-group-out: the labels as read, their sorted unique values and each sample's rank among them;
+  // everything that can be refused is refused here, before a context exists
+  void groupLabelsOf(const std::string &file, int n, std::vector<long long> &labels, std::vector<long long> &values,
+                     std::vector<int> &group) const;
   void writeTiming(const GP_utils &m) const {
     if (timing_file.empty()) return;
     const std::string j = m.timingJson();
@@ -70,7 +80,7 @@ class GP_Cntrl : public Control {
 
 void GP_Cntrl::Help() const {
   std::cout << "\nGP_SS_AK hot path on MI355X\nCommand:\n \t ./gp_ss_ak [options] Command [Comnd-options] TrainDataFile.txt modelName\n"
-            << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood).\n"
+            << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood; --objective lgo with train --groups file: the leave-group-out one).\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
@@ -81,7 +91,7 @@ void GP_Cntrl::train() {
   incArg();
   setMode("train");
   bool yscale = true, Knoise = true;
-  std::string optimiser = "LBFGS", modelName = "gp_model";
+  std::string optimiser = "LBFGS", modelName = "gp_model", groupsFile;
   std::vector<std::string> KernT;
   int iters = 100;
   while (isFlgs()) {
@@ -94,15 +104,30 @@ void GP_Cntrl::train() {
       else if (isArg("-#", "--iterations")) { incArg(); iters = getIntArg(); }
       else if (isArg("-kn", "--Knoise")) { incArg(); Knoise = getIntArg() != 0; }
       else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else if (isArg("--groups", "--groups")) {
+        incArg();
+        if (getArgNo() >= argc) ErrorTermination("--groups takes a file of labels");
+        groupsFile = getArg();
+      }
       else UnkFlg();
       incArg();
     } else setFlgs(false);
   }
+  if (lgo_objective && groupsFile.empty())
+    ErrorTermination("--objective lgo needs the groups to leave out: train --groups FILE (one integer label per training sample)");
+  if (!lgo_objective && !groupsFile.empty())
+    ErrorTermination("train --groups goes with --objective lgo (training on the leave-group-out criterion)");
   if (getArgNo() >= argc) ErrorTermination("There are not enough input parameters.");
   std::string trainFileName = getArg();
   if (getArgNo() + 1 < argc) modelName = argv[getArgNo() + 1];
   int ds[2];
   readDataSize(trainFileName, ds);
+  if (lgo_objective) {   // the labels of row i of the file are those of training sample i: see the header comment
+    std::vector<long long> labels, values;
+    std::vector<int> group;
+    groupLabelsOf(groupsFile, ds[0], labels, values, group);
+    GP_utils::setGroupObjective(group, (int)values.size());
+  }
   mat X, y;
   readDataFile(X, y, ds, trainFileName);
   prepareData(X, y, yscale, modelName);
@@ -279,6 +304,25 @@ void GP_Cntrl::readGroupLabels(const std::string &file, std::vector<long long> &
   }
 }
 
+void GP_Cntrl::groupLabelsOf(const std::string &file, int n, std::vector<long long> &labels, std::vector<long long> &values,
+                             std::vector<int> &group) const {
+  readGroupLabels(file, labels, "--groups");
+  if ((int)labels.size() != n)
+    ErrorTermination("--groups: " + file + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(n) +
+                     " training samples");
+  values = labels;
+  std::sort(values.begin(), values.end());
+  values.erase(std::unique(values.begin(), values.end()), values.end());
+  std::vector<int> count(values.size(), 0);
+  group.resize(labels.size());
+  for (size_t i = 0; i < labels.size(); i++) {
+    group[i] = (int)(std::lower_bound(values.begin(), values.end(), labels[i]) - values.begin());
+    if (++count[group[i]] == GPAK_CV_GROUP_MAX + 1)
+      ErrorTermination("--groups: group " + std::to_string(labels[i]) + " has more than " + std::to_string(GPAK_CV_GROUP_MAX) +
+                       " samples (leave-group-out holds a group in one workgroup's memory)");
+  }
+}
+
 void GP_Cntrl::cv() {
   incArg();
   setMode("cv");
@@ -335,23 +379,7 @@ void GP_Cntrl::cv() {
   readDataSize(trFile, ds);
   std::vector<long long> labels, values;   // as read; the sorted unique labels
   std::vector<int> group;                  // rank of each sample's label among them
-  if (grouped) {                           // everything that can be refused is refused before a context exists
-    readGroupLabels(groupsFile, labels, "--groups");
-    if ((int)labels.size() != ds[0])
-      ErrorTermination("--groups: " + groupsFile + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(ds[0]) +
-                       " training samples");
-    values = labels;
-    std::sort(values.begin(), values.end());
-    values.erase(std::unique(values.begin(), values.end()), values.end());
-    std::vector<int> count(values.size(), 0);
-    group.resize(labels.size());
-    for (size_t i = 0; i < labels.size(); i++) {
-      group[i] = (int)(std::lower_bound(values.begin(), values.end(), labels[i]) - values.begin());
-      if (++count[group[i]] == GPAK_CV_GROUP_MAX + 1)
-        ErrorTermination("--groups: group " + std::to_string(labels[i]) + " has more than " + std::to_string(GPAK_CV_GROUP_MAX) +
-                         " samples (leave-group-out holds a group in one workgroup's memory)");
-    }
-  }
+  if (grouped) groupLabelsOf(groupsFile, ds[0], labels, values, group);   // refused before a context exists
   if (folded) {                            // the same: refused before a context exists
     if (kfold_set) {
       if (kfold < 2 || kfold > ds[0])

@@ -14,6 +14,8 @@ int GP_utils::default_precision = GPAK_F64;
 int GP_utils::default_gpus = 1;
 bool GP_utils::exact_gradient = false;
 bool GP_utils::loo_objective = false;
+std::vector<int> GP_utils::group_labels;
+int GP_utils::group_count = 0;
 
 void GP_utils::create_ctx() {
   int rc;
@@ -123,9 +125,20 @@ double GP_utils::LooObjective() const {
   return -s.log_pl;   // NaN on Chol_fail
 }
 
+double GP_utils::GroupObjective() const {
+  sync_params();
+  if (group_labels.size() != Xinp.n_rows) { std::cerr << "GroupObjective: one label per training sample is needed." << std::endl; exit(1); }
+  gpak_cv_groups_summary s;
+  int rc = gpak_cv_groups(ctx, group_labels.data(), group_count, nullptr, nullptr, nullptr, &s);
+  Chol_fail = (rc == GPAK_ENOTPD);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_cv_groups", ctx);
+  return -s.log_pl;   // NaN on Chol_fail
+}
+
 double GP_utils::GradLL(mat &g) const {  // GP_Utils.cpp:1171-1262
   double nlz = std::numeric_limits<double>::quiet_NaN();
-  if (!loo_objective) {
+  const bool group_objective = !group_labels.empty();
+  if (!loo_objective && !group_objective) {
     nlz = logLikelihood();
     if (Chol_fail) return std::numeric_limits<double>::quiet_NaN();
   }
@@ -148,7 +161,16 @@ double GP_utils::GradLL(mat &g) const {  // GP_Utils.cpp:1171-1262
     ng += (int)c->getNPars();
   }
   std::vector<double> gd(ng);
-  if (loo_objective) {
+  if (group_objective) {
+    sync_params();
+    if (group_labels.size() != Xinp.n_rows) { std::cerr << "GradLL: one label per training sample is needed." << std::endl; exit(1); }
+    gpak_cv_groups_summary s;
+    int rc = gpak_cv_groups_grad(ctx, group_labels.data(), group_count, gd.data(), ng, &s);
+    Chol_fail = (rc == GPAK_ENOTPD);
+    if (Chol_fail) return std::numeric_limits<double>::quiet_NaN();
+    if (rc != GPAK_OK) gpak_host_fatal("gpak_cv_groups_grad", ctx);
+    nlz = -s.log_pl;
+  } else if (loo_objective) {
     sync_params();
     gpak_loo_summary s;
     int rc = gpak_loo_grad(ctx, gd.data(), ng, &s);

@@ -10,6 +10,7 @@
 
 #include "../../include/gpak.h"
 #include "../../include/gpak_cv_folds.h"
+#include "../../include/gpak_cv_groups_grad.h"
 #include "kernels.hpp"
 
 class ModelInfo {
@@ -109,15 +110,17 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   void get_GP_Pars(mat &param) const override;
   void set_GP_Pars(mat &param) const override;
   double Grad_Values(mat &g) const override { return GradLL(g); }
-  double ObjVal() const override { return loo_objective ? LooObjective() : logLikelihood(); }
+  double ObjVal() const override { return !group_labels.empty() ? GroupObjective() : loo_objective ? LooObjective() : logLikelihood(); }
   std::string getParName(unsigned int i) const override { return i < KerenlW->getNPars() ? KerenlW->getParamName(i) : "likelihood"; }
-  bool exactGradient() const override { return exact_gradient || loo_objective; }
+  bool exactGradient() const override { return exact_gradient || loo_objective || !group_labels.empty(); }
 
   double logLikelihood() const;   // NaN on Chol_fail (GP_Utils.cpp:1145-1158)
   // g is 1 x getNumPars(); the exact gradient (gpak_grad_exact) when exact_gradient is set; with loo_objective the
-  // gradient of LooObjective() (gpak_loo_grad), which is then the value returned
+  // gradient of LooObjective() (gpak_loo_grad), with the group objective that of GroupObjective() (gpak_cv_groups_grad);
+  // either is then the value returned
   double GradLL(mat &g) const;
   double LooObjective() const;    // -log_pl of gpak_loo at the current parameters; NaN on Chol_fail
+  double GroupObjective() const;  // -log_pl of gpak_cv_groups with setGroupObjective's labels; NaN on Chol_fail
   // leave-one-out cross-validation of the training set from the current factor (gpak_loo): mean and variance (noise
   // included) of every yTarg(i) given all the other samples, N x 1 each; NaN on Chol_fail
   void LooCV(mat &mean, mat &var, gpak_loo_summary &s) const;
@@ -158,6 +161,10 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // the CLI's --objective: false (default) = Optimise() minimises logLikelihood(); true = it minimises LooObjective()
   // with its exact gradient, through the exact gradient's driver
   static void setLooObjective(bool v) { loo_objective = v; }
+  // the CLI's --objective lgo: Optimise() minimises GroupObjective(), -log_pl of the leave-group-out predictions of
+  // gpak_cv_groups, with its exact gradient gpak_cv_groups_grad through the exact gradient's driver.  labels[i] in
+  // [0, n_groups) for every training sample, in training order, no group above GPAK_CV_GROUP_MAX; no labels: off
+  static void setGroupObjective(const std::vector<int> &labels, int n_groups) { group_labels = labels; group_count = n_groups; }
   // gpak_phase_times of this model's context as one JSON object (the CLI's --timing)
   std::string timingJson() const;
   bool Chol_failed() const { return Chol_fail; }
@@ -175,6 +182,8 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   gpak_ctx *ctx = nullptr;
   static int default_precision, default_gpus;
   static bool exact_gradient, loo_objective;
+  static std::vector<int> group_labels;   // setGroupObjective: empty = no group objective
+  static int group_count;
   void create_ctx();
   bool owns_kernel = false;
   mutable bool dirty = true;     // KUpdateStat / AlphaUpStatus (GP_Utils.h:257-279)
