@@ -25,6 +25,10 @@ CV_GROUPS_SYMBOLS = ["gpak_cv_groups"]
 CV_FOLDS_SYMBOLS = ["gpak_cv_folds"]
 # every symbol include/gpak_cv_groups_grad.h declares (tests/test_cv_groups_grad.py checks the header and this list agree)
 CV_GROUPS_GRAD_SYMBOLS = ["gpak_cv_groups_grad"]
+# every symbol include/gpak_cv_folds_grad.h declares (tests/test_cv_folds_grad.py checks the header and this list agree)
+CV_FOLDS_GRAD_SYMBOLS = ["gpak_cv_folds_grad"]
+# every symbol include/gpak_dev_cv_mix.h declares (the same test)
+DEV_CV_MIX_SYMBOLS = ["gpak_dev_mix_cols"]
 # every symbol include/gpak_dev_f32.h declares (tests/test_dev_ops.py checks the header and this list agree)
 DEV_F32_SYMBOLS = ["gpak_dev_gemm_nt_f32", "gpak_dev_fill_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32",
                    "gpak_dev_rowsumsq_f32", "gpak_dev_fwd_subst_f32"]
@@ -62,10 +66,12 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). gp_ss_ak_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS + DEV_F32_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS
+               + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DEV_F32_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
-                           f"gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_dev_f32.h: {missing}")
+                           "gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_cv_folds_grad.h / "
+                           f"gpak_dev_cv_mix.h / gpak_dev_f32.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -100,6 +106,9 @@ def load():
     lib.gpak_cv_groups.argtypes = [vp, C.POINTER(C.c_int), C.c_int, dp, dp, dp, C.POINTER(CvGroupsSummary)]
     lib.gpak_cv_folds.argtypes = [vp, C.POINTER(C.c_int), C.c_int, dp, dp, dp, C.POINTER(CvGroupsSummary), C.c_int]
     lib.gpak_cv_groups_grad.argtypes = [vp, C.POINTER(C.c_int), C.c_int, dp, C.c_int, C.POINTER(CvGroupsSummary)]
+    lib.gpak_cv_folds_grad.argtypes = [vp, C.POINTER(C.c_int), C.c_int, dp, C.c_int, C.POINTER(CvGroupsSummary), C.c_int]
+    # include/gpak_dev_cv_mix.h: the stream first, every pointer a device pointer
+    lib.gpak_dev_mix_cols.argtypes = [vp, vp, C.c_long, C.c_int, vp, C.c_int, vp, C.c_long, vp, C.c_long]
     lib.gpak_block_cross.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp]
     lib.gpak_predict_block.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.gpak_predict_joint.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]

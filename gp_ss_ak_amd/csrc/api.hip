@@ -7,6 +7,7 @@
 #include <limits>
 
 #include "../../include/gpak_cv_folds.h"
+#include "../../include/gpak_cv_folds_grad.h"
 #include "../../include/gpak_cv_groups_grad.h"
 #include "multi.h"
 
@@ -922,6 +923,32 @@ int gpak_cv_groups_grad(gpak_ctx *ctx, const int *group, int n_groups, double *g
 int gpak_cv_folds(gpak_ctx *ctx, const int *group, int n_groups, double *mean, double *var, double *group_logp,
                   gpak_cv_groups_summary *summary, int flags) {
   return cv_call(ctx, "gpak_cv_folds", true, group, n_groups, mean, var, group_logp, summary, flags);
+}
+
+int gpak_cv_folds_grad(gpak_ctx *ctx, const int *group, int n_groups, double *g, int ng, gpak_cv_groups_summary *summary,
+                       int flags) {
+  if (!ctx) return GPAK_EINVAL;
+  // what the call refuses is refused before anything is factored: the context, the arguments, the composition, then the
+  // labels with gpak_cv_folds' own check
+  const std::string who = "gpak_cv_folds_grad: ";
+  int rc = single_gpu_call(ctx, "gpak_cv_folds_grad", true, true, CtxState::NONE);
+  if (rc == GPAK_ESTATE) ctx->err = who + ctx->err;
+  if (rc) return rc;
+  if (!g) { ctx->err = who + "g is NULL"; return GPAK_EINVAL; }
+  if ((rc = gpak_cv_folds_grad_layout(ctx, ng))) return rc;
+  std::vector<int> offs, perm;
+  if ((rc = group_lists(ctx, who, group, n_groups, 0, perm, offs))) return rc;
+  if (flags & ~GPAK_CV_FOLDS_NO_BATCH) {
+    ctx->err = who + "flags = " + std::to_string(flags) + " has bits other than GPAK_CV_FOLDS_NO_BATCH";
+    return GPAK_EINVAL;
+  }
+  rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK) return gpak_cv_folds_grad_impl(ctx, perm.data(), offs.data(), n_groups, g, ng, summary, flags);
+  if (rc == GPAK_ENOTPD) {   // the training factor
+    fill_nan(g, ng);
+    nan_cv_summary(summary, n_groups);
+  }
+  return rc;
 }
 
 static int block_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, double *mean, double *var,

@@ -207,6 +207,8 @@ struct gpak_ctx : gpak_queues {
   // group (m_p = its size rounded up to 128) and kept across calls: the packed rows P of G (m_p x (Np - k0)) and then
   // T = R^-T in its place, S = P P^T and then its factor R (m_p x m_p), R's inverted 128-blocks, the vectors w, e, var
   DevBuf<double> dCvfVec, dCvfInv, dCvfS, dCvfP;
+  // gpak_cv_folds_grad: the weight factors Q_I (m_p x m_p each) of all those groups, one after another
+  DevBuf<double> dCvfQ;
   // the substitution, the batched small groups, and pack / product / factor + inverse + finish summed over the other
   // groups of the last gpak_cv_folds, in ms
   double cvf_ms[5] = {0, 0, 0, 0, 0};
@@ -498,6 +500,10 @@ int gpak_loo_grad_layout(gpak_ctx *ctx, int ng);
 int gpak_cv_groups_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *g, int ng,
                              gpak_cv_groups_summary *summary);
 int gpak_cv_groups_grad_layout(gpak_ctx *ctx, int ng);
+// gpak_cv_folds_grad on a single-GPU context whose factor and alpha are current and whose labels api.hip has checked
+int gpak_cv_folds_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *g, int ng,
+                            gpak_cv_groups_summary *summary, int flags);
+int gpak_cv_folds_grad_layout(gpak_ctx *ctx, int ng);
 // Rot (Kernel.cpp:1399-1410) of the ExpAns parameters e; D (optional): D[a] = dRot / d angle_a
 void gpak_rot_tables(const double *e, double R[3][3], double (*D)[3][3]);
 void gpak_grad_assemble(const KernParams &kp, const int *kinds, const double *expans, int d, int N, double sn2,
@@ -546,3 +552,31 @@ void gpak_launch_pack_rows(hipStream_t st, const double *G, long ld, int Np, con
 // offs as for gpak_cv_groups_impl)
 int gpak_cv_folds_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *mean, double *var,
                        double *group_logp, gpak_cv_groups_summary *summary, int flags);
+// what it shares with gpak_cv_folds_grad_impl (grad.hip).  The two kinds of groups of a labelling: the groups of at most
+// GPAK_CV_GROUP_MAX samples (unless !batch) as compacted lists for the batched kernels -- sperm / soffs as perm / offs, soff
+// the offsets of their S -- and the others, in ascending group number, with what their workspaces must hold
+struct gpak_cvf_plan {
+  int n_groups = 0, max_size = 0, max_small = 0, mp_max = 0;
+  size_t nP = 0, nQ = 0;                 // doubles of the largest P; of the Q of all one-at-a-time groups
+  std::vector<int> small_id, large_id, sperm, soffs;
+  std::vector<long long> soff;
+  std::vector<size_t> qoff;              // where one-at-a-time group k's Q (m_p x m_p, leading dimension m_p) starts in dCvfQ
+};
+void gpak_cvf_make_plan(const int *perm, const int *offs, int n_groups, int Np, bool batch, gpak_cvf_plan &pl);
+// the workspaces of the one-at-a-time groups and their timing events; grad: also dCvfQ, two scalars behind the vectors and
+// room for the Np x mp_max result of the column mix in dCvfP (and as much again for its gathered operand when it goes by GEMM).  GPAK_ENOMEM names the one that did not fit, as `who`
+int gpak_cvf_reserve(gpak_ctx *ctx, const char *who, const gpak_cvf_plan &pl, bool grad);
+// one-at-a-time group k on the context's stream: pack, product, factor, inverse, w, e, var and the group's sums (dlogp one
+// double, dgsum three, info one int); dE set (an Np-vector): e_I scattered into it and the group's Q written to dCvfQ
+int gpak_cvf_run_group(gpak_ctx *ctx, const gpak_cvf_plan &pl, size_t k, const int *perm, const int *offs, const double *G,
+                       const int *dperm, int *info, double *dmean, double *dvar, double *dlogp, double *dgsum, double *dE);
+// group_logp and the summary in the caller's numbering from hsum (logp and the three sums of the small groups, then of the
+// others) and GPAK_ENOTPD naming the smallest failed group from hinfo ([0] the batched groups, [1 + k] group k)
+int gpak_cvf_finish(gpak_ctx *ctx, const char *who, const gpak_cvf_plan &pl, const double *hsum, const int *hinfo, double ms,
+                    double *group_logp, gpak_cv_groups_summary *summary);
+// the column mix of one-at-a-time group k (cols: its m device column indices) on ctx->dG, through dCvfP: the fused kernel
+// or gather + GEMM + scatter, by the group's width; dCvfQ holds its Q as gpak_cvf_run_group wrote it for that choice
+void gpak_cvf_mix_group(gpak_ctx *ctx, const gpak_cvf_plan &pl, size_t k, const int *cols, int m);
+// H[:, cols] <- H[:, cols] Q through the workspace Z (gpak_dev_mix_cols, include/gpak_dev_cv_mix.h)
+void gpak_launch_mix_cols(hipStream_t st, double *H, long ld, int Np, const int *cols, int m, const double *Q, long ldq,
+                          double *Z, long ldz);

@@ -26,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/gpak_cv_folds.h"
 #include "../../include/gpak_dev.h"
 #include "gpak_internal.h"
 
@@ -1162,6 +1163,134 @@ int gpak_cv_groups_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, in
     for (int k = 0; k < ng; k++) g[k] = std::numeric_limits<double>::quiet_NaN();
     ctx->err = "gpak_cv_groups_grad: S = [B^-1]_II of group " + std::to_string(info - 1) + " is not positive definite";
     return GPAK_ENOTPD;
+  }
+  ExactPass::assemble(ctx, red, g);
+  return GPAK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The gradient of the k-fold criterion (gpak_cv_folds_grad): F = -log_pl of gpak_cv_folds, the derivation above with groups of
+// any size.  C_I = Q_I Q_I^T holds in the same closed form whatever the group's size, with X^T = T = R^-T of cv_folds.hip:
+//   Q_I = sqrt(sn2) T + (beta / sqrt(sn2)) e_I w^T,   beta = sn2 / (1 + sqrt(1 + sn2 |w|^2)).
+// The groups of at most GPAK_CV_GROUP_MAX samples take the passes of gpak_cv_groups_grad_impl on the compacted lists of
+// gpak_cv_folds_impl (without a larger group: the same launches on the same lists, the same bytes).  Every other group
+// runs gpak_cv_folds_impl's sequence (gpak_cvf_run_group) and leaves Q_I in dCvfQ; its columns of Kinv are mixed out of
+// place through dCvfP once Kinv stands in dG: up to two column tiles by gpak_cvf_mix_f64, wider by a gather, the bulk GEMM and
+// a scatter (gpak_cvf_mix_group).  Memory beyond gpak_cv_groups_grad's and gpak_cv_folds': dCvfQ, and dCvfP grown to
+// Np x m_p,max, twice that when the largest group goes by GEMM.
+// ---------------------------------------------------------------------------------------
+int gpak_cv_folds_grad_layout(gpak_ctx *ctx, int ng) {
+  int te;
+  return grad_layout(ctx, "gpak_cv_folds_grad", ExactPass::white, ng, &te);
+}
+
+int gpak_cv_folds_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, int n_groups, double *g, int ng,
+                            gpak_cv_groups_summary *summary, int flags) {
+  GPAK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int N = ctx->N, Np = ctx->Np, T = Np / PB;
+  const long ld = ctx->ld;
+  int te = -1;
+  int rc = grad_layout(ctx, "gpak_cv_folds_grad", ExactPass::white, ng, &te);
+  if (rc) return rc;
+  gpak_cvf_plan pl;
+  gpak_cvf_make_plan(perm, offs, n_groups, Np, !(flags & GPAK_CV_FOLDS_NO_BATCH), pl);
+  const size_t nSm = pl.small_id.size(), nL = pl.large_id.size(), nG = (size_t)n_groups;
+  // the bins of the small groups' column mix, over the compacted lists: as gpak_cv_groups_grad_impl
+  std::vector<long long> qoff(nSm);
+  std::vector<int> sizes(nSm), first(nSm + 1), bstart(1, 0);
+  int n_bins = 0;
+  if (nSm) {
+    for (size_t k = 0; k < nSm; k++) sizes[k] = pl.soffs[k + 1] - pl.soffs[k];
+    n_bins = gpak_cvg_pack_bins(sizes.data(), (int)nSm, first.data());
+    bstart.resize((size_t)n_bins + 1);
+    for (int b = 0; b <= n_bins; b++) bstart[b] = pl.soffs[first[b]];
+    for (int b = 0; b < n_bins; b++)
+      for (int k = first[b]; k < first[b + 1]; k++)
+        qoff[k] = (long long)b * PB * PB + (long long)(pl.soffs[k] - bstart[b]) * (PB + 1);
+  }
+  rc = gpak_cvf_reserve(ctx, "gpak_cv_folds_grad", pl, true);
+  if (rc) return rc;
+  // scratch in the gradient's partial-sum buffer: gpak_cv_folds' layout (the S of every small group, mean, var, then per kind
+  // of group logp and the three sums), then e (Np), the bins' matrices, the pair pass's block sums; then the lists
+  const size_t nSs = (size_t)pl.soff.back(), nQ = (size_t)n_bins * PB * PB, nPp = (size_t)T * (Np / GT_COLS) * NSUM;
+  const size_t n_dbl = nSs + 2 * (size_t)N + 4 * nG + (size_t)Np + nQ + nPp;
+  const size_t n_ll = 2 * nSm + 1, n_int = pl.sperm.size() + (nSm + 1) + (size_t)N + (1 + nL) + (size_t)n_bins + 1;
+  rc = grad_partials(ctx, n_dbl + n_ll + (n_int + 1) / 2);
+  if (rc) return rc;
+  rc = gpak_ensure_U(ctx);
+  if (rc) return rc;
+  double *dS = ctx->dGpart, *dmean = dS + nSs, *dvar = dmean + N;
+  double *dlogp_s = dvar + N, *dgsum_s = dlogp_s + nSm, *dlogp_l = dgsum_s + 3 * nSm, *dgsum_l = dlogp_l + nL;
+  double *dE = dgsum_l + 3 * nL, *dQb = dE + Np, *part = dQb + nQ;
+  long long *dsoff = reinterpret_cast<long long *>(part + nPp), *dqoff = dsoff + nSm + 1;
+  int *dsperm = reinterpret_cast<int *>(dqoff + nSm), *dsoffs = dsperm + pl.sperm.size(), *dperm = dsoffs + nSm + 1;
+  int *dinfo = dperm + N, *dbstart = dinfo + 1 + nL;        // dinfo[0]: the batched groups; [1 + k]: one-at-a-time group k
+  // five vectors of dWork behind the back substitution's scratch, as gpak_loo_grad_impl takes them
+  const int bw = ctx->bwd_bw;
+  double *bs_scratch = ctx->dWork + 2 * (size_t)Np;
+  double *vs = bs_scratch + (size_t)std::max(8 + bw / 32, 34) * bw, *vr = vs + Np, *vz = vr + Np, *vv = vz + Np, *zero = vv + Np;
+  const std::vector<int> info0(1 + nL, INT_MAX);
+  GPAK_HIP(hipMemcpyAsync(dinfo, info0.data(), sizeof(int) * (1 + nL), hipMemcpyHostToDevice, st));
+  if (nSm) {
+    GPAK_HIP(hipMemcpyAsync(dsoff, pl.soff.data(), sizeof(long long) * (nSm + 1), hipMemcpyHostToDevice, st));
+    GPAK_HIP(hipMemcpyAsync(dqoff, qoff.data(), sizeof(long long) * nSm, hipMemcpyHostToDevice, st));
+    GPAK_HIP(hipMemcpyAsync(dsperm, pl.sperm.data(), sizeof(int) * pl.sperm.size(), hipMemcpyHostToDevice, st));
+    GPAK_HIP(hipMemcpyAsync(dsoffs, pl.soffs.data(), sizeof(int) * (nSm + 1), hipMemcpyHostToDevice, st));
+    GPAK_HIP(hipMemcpyAsync(dbstart, bstart.data(), sizeof(int) * ((size_t)n_bins + 1), hipMemcpyHostToDevice, st));
+  }
+  if (nL) GPAK_HIP(hipMemcpyAsync(dperm, perm, sizeof(int) * N, hipMemcpyHostToDevice, st));
+  GPAK_HIP(hipMemsetAsync(dE, 0, sizeof(double) * ((size_t)Np + nQ), st));   // e on the padding, the bins off their diagonal blocks
+  // 1. G = L^-T in dG, B^-1 in dBinv (records ev[7])
+  rc = grad_binv(ctx);
+  if (rc) return rc;
+  // 2. the small groups: the two passes of gpak_cv_groups on dG, the solve pass with the weights e and Q
+  if (nSm) {
+    gpak_cvg_launch_gram(ctx, ctx->dG, ld, (int)nSm, dsperm, dsoffs, dsoff, dS);
+    gpak_cvg_launch_solve_weights(ctx, (int)nSm, pl.max_small, dS, dsoff, dsperm, dsoffs, dmean, dvar, dlogp_s, dgsum_s, dinfo, dE,
+                                  dQb, dqoff);
+  }
+  // 3. every other group alone: gpak_cv_folds' sequence, then its Q into the store and its e into dE
+  for (size_t k = 0; k < nL; k++)
+    if ((rc = gpak_cvf_run_group(ctx, pl, k, perm, offs, ctx->dG, dperm, dinfo + 1 + k, dmean, dvar, dlogp_l + k, dgsum_l + 3 * k, dE)))
+      return rc;
+  // 4. r = e / sn2 and v = B^-1 r = Kinv e by two substitutions on scratch vectors
+  gpak_launch_scale(st, Np, dE, 1.0 / ctx->sn2, vr);
+  gpak_launch_trsv_fwd(st, Np, ctx->dM, ld, ctx->dInv, vr, vz);
+  gpak_backsolve(ctx, st, vz, vv, bs_scratch);
+  // 5. Kinv, full and zero on the padding, into dG (G has been consumed)
+  hipLaunchKernelGGL(gpak_lgo_colscale_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, 1.0 / ctx->sn2, vs);
+  const dim3 lt(Np / LM_T, Np / LM_T);
+  hipLaunchKernelGGL(gpak_loo_mirror_scale_f64, lt, dim3(256), 0, st, N, ctx->dBinv, ld, vs, ctx->dG, ld);
+  // 6. H = Kinv[:, I] Q_I: the bins of the small groups in place,
+  if (nSm) gpak_cvg_launch_mix(ctx, ctx->dG, ld, n_bins, dsperm, dbstart, dQb);
+  // 7. every other group through dCvfP (the group sequences are done with it)
+  for (size_t k = 0; k < nL; k++) {
+    const int gk = pl.large_id[k], o = offs[gk];
+    gpak_cvf_mix_group(ctx, pl, k, dperm + o, offs[gk + 1] - o);
+  }
+  // 8. W = H H^T - v alpha^T - alpha v^T (lower tiles, into dBinv) and the exact pass with W for its weight
+  gpak_launch_gemm_nt(st, T, T, Np, 1.0, ctx->dG, ld, ctx->dG, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, false);
+  hipLaunchKernelGGL(gpak_loo_rank2_f64, lt, dim3(256), 0, st, ctx->dBinv, ld, vv, ctx->dAlpha);
+  GPAK_HIP(hipMemsetAsync(zero, 0, sizeof(double) * Np, st));
+  pair_sums<ExactPass>(st, ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode, ctx->d, ctx->U.base, ctx->U.cap,
+                       ctx->dX, Np, N, Np, zero, ctx->dBinv, ld, 0, 0, 1.0, part, ctx->dRed + 8);
+  double red[NSUM];
+  std::vector<double> hsum(4 * nG);   // as on the device: logp and the three sums of the small groups, then of the others
+  std::vector<int> hinfo(1 + nL, 0);
+  GPAK_HIP(hipMemcpyAsync(red, ctx->dRed + 8, sizeof(red), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipMemcpyAsync(hsum.data(), dlogp_s, sizeof(double) * 4 * nG, hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * (1 + nL), hipMemcpyDeviceToHost, st));
+  GPAK_HIP(hipEventRecord(ctx->ev[3], st));
+  GPAK_HIP(hipEventSynchronize(ctx->ev[3]));
+  GPAK_HIP(hipGetLastError());
+  float ms = 0;
+  GPAK_HIP(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[3]));
+  ctx->times.grad_ms = ms;
+  rc = gpak_cvf_finish(ctx, "gpak_cv_folds_grad", pl, hsum.data(), hinfo.data(), ms, nullptr, summary);
+  if (rc) {
+    for (int k = 0; k < ng; k++) g[k] = std::numeric_limits<double>::quiet_NaN();
+    return rc;
   }
   ExactPass::assemble(ctx, red, g);
   return GPAK_OK;

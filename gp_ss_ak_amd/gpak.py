@@ -269,6 +269,21 @@ class Gpak:
         out["labels"] = values
         return mean, var, logp, out
 
+    def cv_folds_grad(self, labels, ng=10, no_batch=False):
+        """The gradient of -log_pl of cv_folds(labels, no_batch) (gpak_cv_folds_grad): (g, summary), g in GradLL_exact's
+        layout, labels and summary as cv_folds takes and returns them (the summary's ms is the call's grad_ms): groups
+        of any size.  On Chol_fail status is ENOTPD and every number is NaN."""
+        group, values = group_labels(labels, self.N)
+        g = np.zeros(int(ng))
+        s = _lib.CvGroupsSummary()
+        rc = self._check(self._lib.gpak_cv_folds_grad(self._h, group.ctypes.data_as(C.POINTER(C.c_int)), int(values.size),
+                                                      _p(g), int(ng), C.byref(s), NO_BATCH if no_batch else 0),
+                         allow=(ENOTPD,))
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        out["labels"] = values
+        return g, out
+
     def _blocks(self, Xd, nd):
         Xd = _f(Xd)
         nd = int(nd)

@@ -1,6 +1,6 @@
 // gp_ss_ak.cpp -- the reference's command line (gp_ss_ak.cpp:14-557) over the HIP hot path:
-//   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters] [--groups labels.txt]
-//            train.txt [model]
+//   gp_ss_ak [-v n] [-pm m] [-np] [device options] train [-k ExpAns] [-kn 1] [-o LBFGS] [-# iters]
+//            [--groups labels.txt | --folds labels.txt | --kfold K [--seed n]] train.txt [model]
 //   gp_ss_ak [-v n] [-pm m]       [device options] test  test.txt model train.txt [out_file]
 //   gp_ss_ak [-v n]               [device options] cv [-np] [--groups labels.txt | --folds labels.txt | --kfold K [--seed n]]
 //            train.txt model [out_file]
@@ -13,7 +13,10 @@
 // --objective nlz|loo (loo: `train` minimises -log_pl of the leave-one-out predictions, what `cv` reports, with its exact
 // gradient gpak_loo_grad and the exact gradient's driver; the objective column of the trace holds -log_pl; one GPU only;
 // lgo: the same for the leave-group-out predictions of `cv --groups`, with gpak_cv_groups_grad: `--objective lgo train
-// --groups FILE`, FILE as `cv --groups` reads it and held to the same checks before a context exists.  `train` reads the
+// --groups FILE`, FILE as `cv --groups` reads it and held to the same checks before a context exists; `--objective lgo train
+// --folds FILE` and `--objective lgo train --kfold K [--seed n]` the same for groups of any size, with gpak_cv_folds_grad,
+// the labels read, made and checked as `cv --folds` / `cv --kfold` do it, so that `cv --kfold K --seed n` on the trained
+// model reports the criterion that was trained.  `train` reads the
 // samples with readDataFile, which fills row p from the p-th data line, and prepareData, which shifts and scales columns
 // in place; GP_utils hands Xinp and yTarg to gpak_set_train as they are.  No step reorders, drops or adds a row, so label
 // i of FILE belongs to training sample i of the context, exactly as in `cv`).
@@ -73,6 +76,20 @@ class GP_Cntrl : public Control {
   void test();
   void cv();
   void readGroupLabels(const std::string &file, std::vector<long long> &labels, const std::string &option) const;
+  // --folds FILE | --kfold K [--seed n] of `cv` and `train`: the options as given, and the labels they stand for
+  struct FoldOptions {
+    std::string file;
+    bool kfold_set = false, seed_set = false;
+    bool seed_here = false;               // --seed among the verb's own options (not only before the verb, where sim reads it)
+    long kfold = 0;
+    unsigned long long seed = 1;
+    bool given() const { return !file.empty() || kfold_set; }
+  };
+  bool foldOption(FoldOptions &o);   // the current argument is one of the three: taken (with its value); else false
+  // the labels of n training samples (read or made), their sorted unique values and each sample's rank among them;
+  // everything that can be refused is refused here, before a context exists
+  void foldLabelsOf(const FoldOptions &o, int n, std::vector<long long> &labels, std::vector<long long> &values,
+                    std::vector<int> &group) const;
   void block();
   void sim();
   void Help() const;
@@ -80,7 +97,7 @@ class GP_Cntrl : public Control {
 
 void GP_Cntrl::Help() const {
   std::cout << "\nGP_SS_AK hot path on MI355X\nCommand:\n \t ./gp_ss_ak [options] Command [Comnd-options] TrainDataFile.txt modelName\n"
-            << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood; --objective lgo with train --groups file: the leave-group-out one).\n"
+            << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood; --objective lgo with train --groups file: the leave-group-out one; with train --folds file / --kfold K [--seed n]: the same for groups of any size, k folds).\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
@@ -92,6 +109,9 @@ void GP_Cntrl::train() {
   setMode("train");
   bool yscale = true, Knoise = true;
   std::string optimiser = "LBFGS", modelName = "gp_model", groupsFile;
+  FoldOptions fo;
+  fo.seed_set = sim_seed_set;
+  if (sim_seed_set) fo.seed = sim_seed;
   std::vector<std::string> KernT;
   int iters = 100;
   while (isFlgs()) {
@@ -109,14 +129,21 @@ void GP_Cntrl::train() {
         if (getArgNo() >= argc) ErrorTermination("--groups takes a file of labels");
         groupsFile = getArg();
       }
+      else if (foldOption(fo)) {}
       else UnkFlg();
       incArg();
     } else setFlgs(false);
   }
-  if (lgo_objective && groupsFile.empty())
+  if ((int)!groupsFile.empty() + (int)!fo.file.empty() + (int)fo.kfold_set > 1)
+    ErrorTermination("--groups, --folds and --kfold exclude each other: give one of them");
+  if (fo.seed_set && !fo.kfold_set && (fo.seed_here || !fo.file.empty())) ErrorTermination("--seed goes with --kfold");
+  if (lgo_objective && groupsFile.empty() && !fo.given())
     ErrorTermination("--objective lgo needs the groups to leave out: train --groups FILE (one integer label per training sample)");
   if (!lgo_objective && !groupsFile.empty())
     ErrorTermination("train --groups goes with --objective lgo (training on the leave-group-out criterion)");
+  if (!lgo_objective && fo.given())
+    ErrorTermination(std::string("train ") + (fo.kfold_set ? "--kfold" : "--folds") +
+                     " goes with --objective lgo (training on the leave-group-out criterion)");
   if (getArgNo() >= argc) ErrorTermination("There are not enough input parameters.");
   std::string trainFileName = getArg();
   if (getArgNo() + 1 < argc) modelName = argv[getArgNo() + 1];
@@ -125,8 +152,13 @@ void GP_Cntrl::train() {
   if (lgo_objective) {   // the labels of row i of the file are those of training sample i: see the header comment
     std::vector<long long> labels, values;
     std::vector<int> group;
-    groupLabelsOf(groupsFile, ds[0], labels, values, group);
-    GP_utils::setGroupObjective(group, (int)values.size());
+    if (fo.given()) {
+      foldLabelsOf(fo, ds[0], labels, values, group);
+      GP_utils::setFoldObjective(group, (int)values.size());
+    } else {
+      groupLabelsOf(groupsFile, ds[0], labels, values, group);
+      GP_utils::setGroupObjective(group, (int)values.size());
+    }
   }
   mat X, y;
   readDataFile(X, y, ds, trainFileName);
@@ -323,16 +355,66 @@ void GP_Cntrl::groupLabelsOf(const std::string &file, int n, std::vector<long lo
   }
 }
 
+bool GP_Cntrl::foldOption(FoldOptions &o) {
+  if (isArg("--folds", "--folds")) {
+    incArg();
+    if (getArgNo() >= argc) ErrorTermination("--folds takes a file of labels");
+    o.file = getArg();
+    return true;
+  }
+  if (isArg("--kfold", "--kfold")) {
+    incArg();
+    char *end = nullptr;
+    const std::string tok = getArg();
+    o.kfold = strtol(tok.c_str(), &end, 10);
+    if (tok.empty() || *end != '\0') ErrorTermination("--kfold takes the number of folds");
+    o.kfold_set = true;
+    return true;
+  }
+  if (isArg("--seed", "--seed")) {
+    incArg();
+    char *end = nullptr;
+    const std::string tok = getArg();
+    o.seed = strtoull(tok.c_str(), &end, 10);
+    if (tok.empty() || *end != '\0') ErrorTermination("--seed takes a non-negative integer");
+    o.seed_set = o.seed_here = true;
+    return true;
+  }
+  return false;
+}
+
+void GP_Cntrl::foldLabelsOf(const FoldOptions &o, int n, std::vector<long long> &labels, std::vector<long long> &values,
+                            std::vector<int> &group) const {
+  if (o.kfold_set) {
+    if (o.kfold < 2 || o.kfold > n)
+      ErrorTermination("--kfold: " + std::to_string(o.kfold) + " folds for " + std::to_string(n) +
+                       " training samples (2 <= K <= N is needed)");
+    gpak_kfold_assign(o.seed, (size_t)n, (int)o.kfold, group);
+    labels.assign(group.begin(), group.end());
+  } else {
+    readGroupLabels(o.file, labels, "--folds");
+    if ((int)labels.size() != n)
+      ErrorTermination("--folds: " + o.file + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(n) +
+                       " training samples");
+  }
+  values = labels;
+  std::sort(values.begin(), values.end());
+  values.erase(std::unique(values.begin(), values.end()), values.end());
+  group.resize(labels.size());
+  for (size_t i = 0; i < labels.size(); i++)
+    group[i] = (int)(std::lower_bound(values.begin(), values.end(), labels[i]) - values.begin());
+}
+
 void GP_Cntrl::cv() {
   incArg();
   setMode("cv");
   if (gpus > 1)
     ErrorTermination("cv runs on one GPU only (leave-one-out cross-validation is not built for multi-GPU contexts): drop --gpus");
   bool yscale = true;
-  std::string groupsFile, foldsFile;
-  bool kfold_set = false, seed_set = sim_seed_set;
-  long kfold = 0;
-  unsigned long long seed = sim_seed_set ? sim_seed : 1;
+  std::string groupsFile;
+  FoldOptions fo;
+  fo.seed_set = sim_seed_set;
+  if (sim_seed_set) fo.seed = sim_seed;
   while (isFlgs()) {
     if (isArgFlg()) {
       if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
@@ -342,37 +424,17 @@ void GP_Cntrl::cv() {
         if (getArgNo() >= argc) ErrorTermination("--groups takes a file of labels");
         groupsFile = getArg();
       }
-      else if (isArg("--folds", "--folds")) {
-        incArg();
-        if (getArgNo() >= argc) ErrorTermination("--folds takes a file of labels");
-        foldsFile = getArg();
-      }
-      else if (isArg("--kfold", "--kfold")) {
-        incArg();
-        char *end = nullptr;
-        const std::string tok = getArg();
-        kfold = strtol(tok.c_str(), &end, 10);
-        if (tok.empty() || *end != '\0') ErrorTermination("--kfold takes the number of folds");
-        kfold_set = true;
-      }
-      else if (isArg("--seed", "--seed")) {
-        incArg();
-        char *end = nullptr;
-        const std::string tok = getArg();
-        seed = strtoull(tok.c_str(), &end, 10);
-        if (tok.empty() || *end != '\0') ErrorTermination("--seed takes a non-negative integer");
-        seed_set = true;
-      }
+      else if (foldOption(fo)) {}
       else UnkFlg();
       incArg();
     } else setFlgs(false);
   }
-  if ((int)!groupsFile.empty() + (int)!foldsFile.empty() + (int)kfold_set > 1)
+  if ((int)!groupsFile.empty() + (int)!fo.file.empty() + (int)fo.kfold_set > 1)
     ErrorTermination("--groups, --folds and --kfold exclude each other: give one of them");
-  if (seed_set && !kfold_set) ErrorTermination("--seed goes with --kfold");
+  if (fo.seed_set && !fo.kfold_set) ErrorTermination("--seed goes with --kfold");
   if (getArgNo() + 1 >= argc) ErrorTermination("There are not enough input parameters: cv needs the training data and the model.");
   std::string trFile = getArg(), modelName = argv[getArgNo() + 1];
-  const bool grouped = !groupsFile.empty(), folded = !foldsFile.empty() || kfold_set;
+  const bool grouped = !groupsFile.empty(), folded = fo.given();
   std::string LooOut = modelName + (grouped ? "_lgo.txt" : folded ? "_folds.txt" : "_loo.txt");
   if (getArgNo() + 2 < argc) LooOut = argv[getArgNo() + 2];
   int ds[2];
@@ -380,26 +442,7 @@ void GP_Cntrl::cv() {
   std::vector<long long> labels, values;   // as read; the sorted unique labels
   std::vector<int> group;                  // rank of each sample's label among them
   if (grouped) groupLabelsOf(groupsFile, ds[0], labels, values, group);   // refused before a context exists
-  if (folded) {                            // the same: refused before a context exists
-    if (kfold_set) {
-      if (kfold < 2 || kfold > ds[0])
-        ErrorTermination("--kfold: " + std::to_string(kfold) + " folds for " + std::to_string(ds[0]) +
-                         " training samples (2 <= K <= N is needed)");
-      gpak_kfold_assign(seed, (size_t)ds[0], (int)kfold, group);
-      labels.assign(group.begin(), group.end());
-    } else {
-      readGroupLabels(foldsFile, labels, "--folds");
-      if ((int)labels.size() != ds[0])
-        ErrorTermination("--folds: " + foldsFile + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(ds[0]) +
-                         " training samples");
-    }
-    values = labels;
-    std::sort(values.begin(), values.end());
-    values.erase(std::unique(values.begin(), values.end()), values.end());
-    group.resize(labels.size());
-    for (size_t i = 0; i < labels.size(); i++)
-      group[i] = (int)(std::lower_bound(values.begin(), values.end(), labels[i]) - values.begin());
-  }
+  if (folded) foldLabelsOf(fo, ds[0], labels, values, group);             // the same
   mat X, y;
   readDataFile(X, y, ds, trFile);
   prepareData(X, y, yscale, modelName);                         // the model's _Statistics.txt, as `test`

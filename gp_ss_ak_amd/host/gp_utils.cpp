@@ -15,6 +15,7 @@ int GP_utils::default_gpus = 1;
 bool GP_utils::exact_gradient = false;
 bool GP_utils::loo_objective = false;
 std::vector<int> GP_utils::group_labels;
+bool GP_utils::fold_objective = false;
 int GP_utils::group_count = 0;
 
 void GP_utils::create_ctx() {
@@ -129,9 +130,10 @@ double GP_utils::GroupObjective() const {
   sync_params();
   if (group_labels.size() != Xinp.n_rows) { std::cerr << "GroupObjective: one label per training sample is needed." << std::endl; exit(1); }
   gpak_cv_groups_summary s;
-  int rc = gpak_cv_groups(ctx, group_labels.data(), group_count, nullptr, nullptr, nullptr, &s);
+  int rc = fold_objective ? gpak_cv_folds(ctx, group_labels.data(), group_count, nullptr, nullptr, nullptr, &s, 0)
+                          : gpak_cv_groups(ctx, group_labels.data(), group_count, nullptr, nullptr, nullptr, &s);
   Chol_fail = (rc == GPAK_ENOTPD);
-  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_cv_groups", ctx);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal(fold_objective ? "gpak_cv_folds" : "gpak_cv_groups", ctx);
   return -s.log_pl;   // NaN on Chol_fail
 }
 
@@ -165,10 +167,11 @@ double GP_utils::GradLL(mat &g) const {  // GP_Utils.cpp:1171-1262
     sync_params();
     if (group_labels.size() != Xinp.n_rows) { std::cerr << "GradLL: one label per training sample is needed." << std::endl; exit(1); }
     gpak_cv_groups_summary s;
-    int rc = gpak_cv_groups_grad(ctx, group_labels.data(), group_count, gd.data(), ng, &s);
+    int rc = fold_objective ? gpak_cv_folds_grad(ctx, group_labels.data(), group_count, gd.data(), ng, &s, 0)
+                            : gpak_cv_groups_grad(ctx, group_labels.data(), group_count, gd.data(), ng, &s);
     Chol_fail = (rc == GPAK_ENOTPD);
     if (Chol_fail) return std::numeric_limits<double>::quiet_NaN();
-    if (rc != GPAK_OK) gpak_host_fatal("gpak_cv_groups_grad", ctx);
+    if (rc != GPAK_OK) gpak_host_fatal(fold_objective ? "gpak_cv_folds_grad" : "gpak_cv_groups_grad", ctx);
     nlz = -s.log_pl;
   } else if (loo_objective) {
     sync_params();

@@ -11,6 +11,7 @@
 #include "../../include/gpak.h"
 #include "../../include/gpak_cv_folds.h"
 #include "../../include/gpak_cv_groups_grad.h"
+#include "../../include/gpak_cv_folds_grad.h"
 #include "kernels.hpp"
 
 class ModelInfo {
@@ -116,11 +117,12 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
 
   double logLikelihood() const;   // NaN on Chol_fail (GP_Utils.cpp:1145-1158)
   // g is 1 x getNumPars(); the exact gradient (gpak_grad_exact) when exact_gradient is set; with loo_objective the
-  // gradient of LooObjective() (gpak_loo_grad), with the group objective that of GroupObjective() (gpak_cv_groups_grad);
+  // gradient of LooObjective() (gpak_loo_grad), with the group objective that of GroupObjective() (gpak_cv_groups_grad /
+  // gpak_cv_folds_grad);
   // either is then the value returned
   double GradLL(mat &g) const;
   double LooObjective() const;    // -log_pl of gpak_loo at the current parameters; NaN on Chol_fail
-  double GroupObjective() const;  // -log_pl of gpak_cv_groups with setGroupObjective's labels; NaN on Chol_fail
+  double GroupObjective() const;  // -log_pl of gpak_cv_groups with setGroupObjective's labels (of gpak_cv_folds with setFoldObjective's); NaN on Chol_fail
   // leave-one-out cross-validation of the training set from the current factor (gpak_loo): mean and variance (noise
   // included) of every yTarg(i) given all the other samples, N x 1 each; NaN on Chol_fail
   void LooCV(mat &mean, mat &var, gpak_loo_summary &s) const;
@@ -164,7 +166,10 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // the CLI's --objective lgo: Optimise() minimises GroupObjective(), -log_pl of the leave-group-out predictions of
   // gpak_cv_groups, with its exact gradient gpak_cv_groups_grad through the exact gradient's driver.  labels[i] in
   // [0, n_groups) for every training sample, in training order, no group above GPAK_CV_GROUP_MAX; no labels: off
-  static void setGroupObjective(const std::vector<int> &labels, int n_groups) { group_labels = labels; group_count = n_groups; }
+  static void setGroupObjective(const std::vector<int> &labels, int n_groups) { group_labels = labels; group_count = n_groups; fold_objective = false; }
+  // the same for groups of any size (train --folds / --kfold): GroupObjective() is -log_pl of gpak_cv_folds and its
+  // gradient gpak_cv_folds_grad
+  static void setFoldObjective(const std::vector<int> &labels, int n_groups) { group_labels = labels; group_count = n_groups; fold_objective = true; }
   // gpak_phase_times of this model's context as one JSON object (the CLI's --timing)
   std::string timingJson() const;
   bool Chol_failed() const { return Chol_fail; }
@@ -184,6 +189,7 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   static bool exact_gradient, loo_objective;
   static std::vector<int> group_labels;   // setGroupObjective: empty = no group objective
   static int group_count;
+  static bool fold_objective;             // setFoldObjective: the labels are folds of any size
   void create_ctx();
   bool owns_kernel = false;
   mutable bool dirty = true;     // KUpdateStat / AlphaUpStatus (GP_Utils.h:257-279)
