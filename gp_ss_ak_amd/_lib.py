@@ -29,6 +29,9 @@ CV_GROUPS_GRAD_SYMBOLS = ["gpak_cv_groups_grad"]
 CV_FOLDS_GRAD_SYMBOLS = ["gpak_cv_folds_grad"]
 # every symbol include/gpak_dev_cv_mix.h declares (the same test)
 DEV_CV_MIX_SYMBOLS = ["gpak_dev_mix_cols"]
+# every symbol include/gpak_design.h / include/gpak_dev_design.h declares (tests/test_design.py checks the headers and these lists agree)
+DESIGN_SYMBOLS = ["gpak_design"]
+DEV_DESIGN_SYMBOLS = ["gpak_dev_design_score"]
 # every symbol include/gpak_dev_f32.h declares (tests/test_dev_ops.py checks the header and this list agree)
 DEV_F32_SYMBOLS = ["gpak_dev_gemm_nt_f32", "gpak_dev_fill_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32",
                    "gpak_dev_rowsumsq_f32", "gpak_dev_fwd_subst_f32"]
@@ -53,6 +56,11 @@ class CvGroupsSummary(C.Structure):
                 ("ms", C.c_double), ("groups", C.c_int), ("max_size", C.c_int)]
 
 
+class DesignSummary(C.Structure):
+    _fields_ = [("var_before", C.c_double), ("var_after", C.c_double), ("ms", C.c_double), ("holes", C.c_int),
+                ("max_size", C.c_int), ("picks", C.c_int)]
+
+
 _lib = None
 
 
@@ -67,11 +75,12 @@ def load():
             "(hipcc --offload-arch=gfx950). gp_ss_ak_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS
-               + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DEV_F32_SYMBOLS if not hasattr(lib, s)]
+               + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DESIGN_SYMBOLS + DEV_DESIGN_SYMBOLS + DEV_F32_SYMBOLS
+               if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
                            "gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_cv_folds_grad.h / "
-                           f"gpak_dev_cv_mix.h / gpak_dev_f32.h: {missing}")
+                           f"gpak_dev_cv_mix.h / gpak_design.h / gpak_dev_design.h / gpak_dev_f32.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -109,6 +118,10 @@ def load():
     lib.gpak_cv_folds_grad.argtypes = [vp, C.POINTER(C.c_int), C.c_int, dp, C.c_int, C.POINTER(CvGroupsSummary), C.c_int]
     # include/gpak_dev_cv_mix.h: the stream first, every pointer a device pointer
     lib.gpak_dev_mix_cols.argtypes = [vp, vp, C.c_long, C.c_int, vp, C.c_int, vp, C.c_long, vp, C.c_long]
+    lib.gpak_design.argtypes = [vp, dp, C.c_long, C.c_int, dp, C.c_long, C.c_int, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, dp, dp,
+                                C.POINTER(C.c_int), dp, dp, C.POINTER(DesignSummary)]
+    # include/gpak_dev_design.h: the stream first, every pointer a device pointer
+    lib.gpak_dev_design_score.argtypes = [vp, vp, C.c_long, C.c_int, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, C.c_long, vp]
     lib.gpak_block_cross.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp]
     lib.gpak_predict_block.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.gpak_predict_joint.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]

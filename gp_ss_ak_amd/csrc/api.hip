@@ -831,25 +831,29 @@ int gpak_loo_grad(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summary) {
 
 // The labels of gpak_cv_groups / gpak_cv_folds (`who`, with its colon), checked, and the samples sorted by (group, sample)
 // with a counting sort: perm, and offs = where each group starts in it.  max_group: the largest group allowed (0: any)
+// The words of the one check: the labelled items, their count and the groups, as the call's documentation names them
+struct LabelWords { const char *arg, *count, *n, *item, *items, *group; };
+static const LabelWords kSampleWords = {"group", "n_groups", "N", "sample", "samples", "group"};
+static const LabelWords kHoleWords = {"hole", "H", "Mc", "point", "points", "hole"};
 static int group_lists(gpak_ctx *ctx, const std::string &who, const int *group, int n_groups, int max_group,
-                       std::vector<int> &perm, std::vector<int> &offs) {
-  const int N = ctx->N;
-  if (!group) { ctx->err = who + "group is NULL"; return GPAK_EINVAL; }
+                       std::vector<int> &perm, std::vector<int> &offs, int n_items = -1, const LabelWords &wd = kSampleWords) {
+  const int N = n_items < 0 ? ctx->N : n_items;
+  if (!group) { ctx->err = who + wd.arg + " is NULL"; return GPAK_EINVAL; }
   if (n_groups < 1 || n_groups > N) {
-    ctx->err = who + "n_groups = " + std::to_string(n_groups) + " is outside [1, N = " + std::to_string(N) + "]";
+    ctx->err = who + wd.count + " = " + std::to_string(n_groups) + " is outside [1, " + wd.n + " = " + std::to_string(N) + "]";
     return GPAK_EINVAL;
   }
   offs.assign((size_t)n_groups + 1, 0);
   perm.resize((size_t)N);
   for (int i = 0; i < N; i++) {
     if (group[i] < 0 || group[i] >= n_groups) {
-      ctx->err = who + "sample " + std::to_string(i) + " has label " + std::to_string(group[i]) + ", outside [0, " +
+      ctx->err = who + wd.item + " " + std::to_string(i) + " has label " + std::to_string(group[i]) + ", outside [0, " +
                  std::to_string(n_groups) + ")";
       return GPAK_EINVAL;
     }
     if (++offs[(size_t)group[i] + 1] == max_group + 1 && max_group > 0) {
-      ctx->err = who + "group " + std::to_string(group[i]) + " has more than " + std::to_string(max_group) +
-                 " samples (sample " + std::to_string(i) + " is one too many)";
+      ctx->err = who + wd.group + " " + std::to_string(group[i]) + " has more than " + std::to_string(max_group) + " " +
+                 wd.items + " (" + wd.item + " " + std::to_string(i) + " is one too many)";
       return GPAK_EINVAL;
     }
   }
@@ -997,6 +1001,51 @@ int gpak_sample_joint(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, co
                       double *Z, double *mean, int flags) {
   if (!ctx || !Xd || !Xi || !Z || M <= 0 || nd <= 0 || S <= 0 || !(nugget >= 0.0)) return GPAK_EINVAL;
   return joint_call(ctx, "gpak_sample_joint", Xd, M, nd, d, mean, nullptr, flags, Xi, S, nugget, Z);
+}
+
+// gpak_design (include/gpak_design.h): what the call refuses is refused before anything is factored
+int gpak_design(gpak_ctx *ctx, const double *Xt, long T, int nd, const double *Xc, long Mc, int d, const int *hole, int H,
+                const double *wt, int k, double *gain, double *reduction, double *var, int *picked, double *pick_gain,
+                double *var_after, gpak_design_summary *summary) {
+  if (!ctx) return GPAK_EINVAL;
+  const std::string who = "gpak_design: ";
+  int rc = single_gpu_call(ctx, "gpak_design", true, true, CtxState::NONE);
+  if (rc) return rc;
+  auto refuse = [&](const std::string &what) { ctx->err = who + what; return GPAK_EINVAL; };
+  if (T <= 0 || nd <= 0 || Mc <= 0)
+    return refuse("T = " + std::to_string(T) + ", nd = " + std::to_string(nd) + ", Mc = " + std::to_string(Mc) + " must all be positive");
+  if (d != ctx->d) return refuse("target and candidate points must have as many columns as the training set");
+  if (!Xt || !Xc || !gain) return refuse(std::string(!Xt ? "Xt" : !Xc ? "Xc" : "gain") + " is NULL");
+  // the block path's budget for the raw and transformed points, here of the one batch there is (gpak_joint_impl)
+  const long Tp = (T + 255) / 256 * 256, Mcp = (Mc + 255) / 256 * 256;
+  const size_t per_point = sizeof(double) * (4 + GPAK_PT * (size_t)ctx->kp.nterms);
+  if (Tp + Mcp > (1L << 24) || (double)Tp * nd + (double)Mcp > (double)((size_t)1 << 30) / (double)per_point)
+    return refuse("the targets' discretisation points and the candidates exceed the 1 GiB point budget of one batch (the stack is held at once)");
+  std::vector<int> offs, perm;
+  if ((rc = group_lists(ctx, who, hole, H, GPAK_CV_GROUP_MAX, perm, offs, (int)Mc, kHoleWords))) return rc;
+  for (long b = 0; wt && b < T; b++)
+    if (!(wt[b] >= 0.0) || !std::isfinite(wt[b]))
+      return refuse("weight " + std::to_string(b) + " is negative or not finite");
+  if (k < 0 || k > H) return refuse("k = " + std::to_string(k) + " is outside [0, H = " + std::to_string(H) + "]");
+  if (k > 0 && (!picked || !pick_gain)) return refuse(std::string(!picked ? "picked" : "pick_gain") + " is NULL with k > 0");
+  rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK)
+    return gpak_design_impl(ctx, Xt, T, nd, Xc, Mc, perm.data(), offs.data(), H, wt, k, gain, reduction, var, picked, pick_gain,
+                            var_after, summary);
+  if (rc == GPAK_ENOTPD) {
+    ctx->err = who + "the training factor failed (B = I + K/sn2 is not positive definite at column " +
+               std::to_string(ctx->state.failed_col) + ")";
+    fill_nan(gain, H);
+    fill_nan(reduction, (size_t)T * H);
+    fill_nan(var, T);
+    fill_nan(pick_gain, k);
+    fill_nan(var_after, T);
+    if (summary) {
+      summary->var_before = summary->var_after = std::numeric_limits<double>::quiet_NaN();
+      summary->ms = 0.0; summary->holes = H; summary->max_size = 0; summary->picks = 0;
+    }
+  }
+  return rc;
 }
 
 int gpak_timing(gpak_ctx *ctx, gpak_phase_times *out) {

@@ -6,7 +6,8 @@
 #include <vector>
 
 #include "../../include/gpak.h"
-#include "ctx_state.h"   // CtxState: what of a context's device contents is current (HIP-free)
+#include "../../include/gpak_design.h"   // gpak_design_summary (gpak_design_impl)
+#include "ctx_state.h"  // CtxState: what of a context's device contents is current (HIP-free)
 #include "potrf_plan.h"  // GPAK_TILE, GpakSchedule and the factorisation's schedule (HIP-free)
 
 // The covariance function as the device sees it: a SUM of up to three stationary terms (the
@@ -188,6 +189,8 @@ struct gpak_ctx : gpak_queues {
   DevBuf<double> dTblk, dXblk;
   size_t blk_points = 0;
   int blk_terms = 0;
+  // the fills, the substitution, the SYRK, the first score pass and the last pick's downdate of the last gpak_design, in ms
+  double design_ms[5] = {0, 0, 0, 0, 0};
   // fp32 prediction (ctx created with GPAK_F32): fp32 images of L and of the inverse blocks (CtxState::image)
   DevBuf<float> dLf, dInvf;
   long ldLf = 0;             // leading dimension of dLf (Np + skew)
@@ -463,6 +466,19 @@ int gpak_predict_block_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, dou
 // single-GPU context whose factor and alpha are current.  GPAK_ENOTPD: C + nugget I failed (mean valid, Z untouched).
 int gpak_joint_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mean, double *cov_host, int flags,
                     const double *Xi, int S, double nugget, double *Z);
+
+// what gpak_design_impl shares with the joint calls: dWt / dC / dCinv / the point buffers for a stack of `cap` rows (a
+// multiple of 256) and `points` discretisation points, sized and skewed as gpak_joint_impl sizes them (*ld = the leading
+// dimension of dWt and dC); and the substitution dWt := dWt L^-T over those rows on the context's stream
+int gpak_joint_reserve(gpak_ctx *ctx, int cap, size_t points, int nterms, long *ld);
+void gpak_joint_forward_subst(gpak_ctx *ctx, int cap, long ldw);
+
+// ---- design.hip -------------------------------------------------------------------------
+// gpak_design on a single-GPU context whose factor and alpha are current and whose arguments api.hip has checked: perm =
+// the candidate points sorted by (hole, point), offs = where each hole starts in it (H + 1 entries)
+int gpak_design_impl(gpak_ctx *ctx, const double *Xt, long T, int nd, const double *Xc, long Mc, const int *perm,
+                     const int *offs, int H, const double *wt, int k, double *gain, double *reduction, double *var,
+                     int *picked, double *pick_gain, double *var_after, gpak_design_summary *summary);
 
 // ---- the distributed factor as one rank holds it (dist.hip), handed to a single-GPU context of the SAME device
 // (multi.hip: group prediction and solve_chol reuse the factor instead of factoring a replica again) ----

@@ -117,6 +117,31 @@ static void forward_subst_batch(gpak_ctx *ctx, double *Wt, long ldw, int mbp) {
   fs_block_f64(ctx, Wt, ldw, mbp / PB, 0, ctx->Np, lv, (int)lv.size() - 1);
 }
 
+// the cap x cap covariance of the joint calls (leading dimension ldc), its inverted 128-blocks and its info word
+static int ensure_joint_cov(gpak_ctx *ctx, int cap, long ldc) {
+  if (ctx->joint_cap >= cap && ctx->dC.n >= (size_t)ldc * cap) return GPAK_OK;
+  ctx->joint_cap = 0;
+  ctx->dC.release(); ctx->dCinv.release();
+  if (!ctx->dCinfo.reserve(4) || !ctx->dC.reserve((size_t)ldc * cap) || !ctx->dCinv.reserve((size_t)(cap / PB) * 2 * PB * PB)) {
+    ctx->err = "device allocation failed for the joint covariance of the blocks";
+    return GPAK_ENOMEM;
+  }
+  ctx->joint_cap = cap;
+  return GPAK_OK;
+}
+
+// what gpak_design_impl (design.hip) shares with the joint calls: their buffers for a stack of `cap` rows and `points`
+// discretisation points, sized and skewed as gpak_joint_impl sizes them (*ld = the leading dimension of dWt and dC), and
+// the substitution dWt := dWt L^-T on the context's stream
+int gpak_joint_reserve(gpak_ctx *ctx, int cap, size_t points, int nterms, long *ld) {
+  int rc = ensure_predict_bufs(ctx, cap, true);
+  if (rc) return rc;
+  if ((rc = ensure_block_points(ctx, points, nterms))) return rc;
+  *ld = cap + 32L * std::max(0, ctx->sched.pred_ld_skew);
+  return ensure_joint_cov(ctx, cap, *ld);
+}
+void gpak_joint_forward_subst(gpak_ctx *ctx, int cap, long ldw) { forward_subst_batch(ctx, ctx->dWt, ldw, cap); }
+
 // fp32 images of the factor for a GPAK_F32 context (rebuilt when the factor changes)
 static int ensure_f32_factor(gpak_ctx *ctx) {
   if (ctx->state.image) return GPAK_OK;
@@ -402,15 +427,7 @@ int gpak_joint_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mea
   if (rc) return rc;
   if ((rc = ensure_block_points(ctx, (size_t)cap * nd, kp.nterms))) return rc;
   const long ldw = cap + 32L * std::max(0, ctx->sched.pred_ld_skew), ldc = ldw;   // the same 256-byte skew
-  if (want_c && (ctx->joint_cap < cap || ctx->dC.n < (size_t)ldc * cap)) {
-    ctx->joint_cap = 0;
-    ctx->dC.release(); ctx->dCinv.release();
-    if (!ctx->dCinfo.reserve(4) || !ctx->dC.reserve((size_t)ldc * cap) || !ctx->dCinv.reserve((size_t)(cap / PB) * 2 * PB * PB)) {
-      ctx->err = "device allocation failed for the joint covariance of the blocks";
-      return GPAK_ENOMEM;
-    }
-    ctx->joint_cap = cap;
-  }
+  if (want_c && (rc = ensure_joint_cov(ctx, cap, ldc))) return rc;
   if (sample && ctx->dZ.n < (size_t)M * S) {   // dZ comes last: where it stands, dXi does
     ctx->dXi.release(); ctx->dZ.release();
     if (!ctx->dXi.reserve((size_t)M * S) || !ctx->dZ.reserve((size_t)M * S)) {

@@ -338,6 +338,40 @@ class Gpak:
                                                 _p(mean), JOINT_LATENT if latent else 0), allow=(ENOTPD,))
         return Z, mean
 
+    def design(self, Xt, nd, Xc, holes, weights=None, pick=0, want_reduction=False):
+        """Infill drilling design (gpak_design): rank candidate holes by the estimation variance they would remove from the
+        target blocks.  Xt holds nd rows per target block (nd = 1: points), Xc one row per candidate point, holes one
+        integer label per candidate point (any values; the holes are numbered by sorted unique label and every output
+        follows that order), weights one non-negative number per target (None: all ones).  Returns (gain, picked,
+        pick_gain, extras): gain[h] = the weighted variance hole h alone removes, picked / pick_gain = the greedy plan of
+        `pick` holes (hole numbers and conditional gains in pick order), extras = {reduction (T x H, or None), var,
+        var_after, summary}, summary = {var_before, var_after, ms, holes, max_size, picks, status, labels}.  On
+        Chol_fail status is ENOTPD and every number is NaN."""
+        Xt, T, nd = self._blocks(Xt, nd)
+        Xc = _f(Xc)
+        if Xc.ndim != 2 or Xc.shape[1] != Xt.shape[1]:
+            raise GpakError(EINVAL, "Xc must have as many columns as Xt")
+        hole, values = group_labels(holes, Xc.shape[0])
+        H, k = int(values.size), int(pick)
+        wt = None
+        if weights is not None:
+            wt = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if wt.size != T:
+                raise GpakError(EINVAL, "weights must hold one entry per target")
+        gain = np.zeros(H)
+        red = np.zeros((T, H), order="F") if want_reduction else None
+        var, var_after = np.zeros(T), np.zeros(T)
+        picked, pick_gain = np.full(max(k, 0), -1, dtype=np.int32), np.zeros(max(k, 0))
+        s = _lib.DesignSummary()
+        rc = self._check(self._lib.gpak_design(self._h, _p(Xt), T, nd, _p(Xc), Xc.shape[0], Xt.shape[1],
+                                               hole.ctypes.data_as(C.POINTER(C.c_int)), H, _p(wt), k, _p(gain), _p(red), _p(var),
+                                               picked.ctypes.data_as(C.POINTER(C.c_int)), _p(pick_gain), _p(var_after),
+                                               C.byref(s)), allow=(ENOTPD,))
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        out["labels"] = values
+        return gain, picked, pick_gain, {"reduction": red, "var": var, "var_after": var_after, "summary": out}
+
     def last_error(self):
         return self._lib.gpak_last_error(self._h).decode()
 

@@ -58,6 +58,15 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       sim_nugget = strtod(getArg().c_str(), &end);
       if (end == getArg().c_str() || !(sim_nugget >= 0.0)) ErrorTermination("--nugget takes a non-negative value");
     }
+    else if (isArg("--pick", "--pick")) {
+      incArg();
+      char *end = nullptr;
+      const std::string tok = getArg();
+      const long v = strtol(tok.c_str(), &end, 10);
+      if (end == tok.c_str() || *end != '\0' || v < 0 || v > 1000000) ErrorTermination("--pick takes the number of holes to plan (0 or more)");
+      design_pick = (int)v;
+    }
+    else if (isArg("--weights", "--weights")) { incArg(); design_weights_file = getArg(); }
     else break;
     incArg();
   }

@@ -63,6 +63,9 @@ class Control {
   unsigned long long sim_seed = 0;
   std::string sim_xi_file;
   double sim_nugget = 0.0;
+  // the `design` verb: --pick k (a greedy plan of k holes), --weights file (one non-negative number per target)
+  int design_pick = 0;
+  std::string design_weights_file;
   std::string mode = "gp";
   mat params, MinData, MaxData, MeanData, StData;
   double MaxTotalin = 0, MinTotalin = 0, MaxTotalo = 0, MinTotalo = 0;

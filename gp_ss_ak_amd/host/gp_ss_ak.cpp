@@ -35,6 +35,15 @@
 // gpak_sample_joint; one GPU only).  nodes.txt is read as block reads its centres; without --block-size / --block-disc the
 // nodes are points.  The normals come from --xi (an M x S text matrix) or from --seed (std::mt19937_64 + Box-Muller,
 // sim_normals.hpp).  Written to <model>_sim.txt in input order: the conditional mean and the S realisations.
+// design (not a reference verb): ranks candidate drill holes by the estimation variance they would remove from the targets
+// (gpak_design; one GPU only):  gp_ss_ak [--block-size dx,dy,dz --block-disc nx,ny,nz] [--pick k] [--weights w.txt]
+// design --candidates cand.txt --holes holes.txt targets.txt model train.txt.  targets.txt and cand.txt are read as block
+// reads its centres (the last column is carried for the targets and ignored for the candidates; without --block-size /
+// --block-disc the targets are points); holes.txt holds one integer label per candidate point, read and checked as `cv
+// --groups` reads its labels and mapped to 0 .. H - 1 in ascending order; --weights one non-negative number per target.
+// Everything is checked before a context exists.  Written to <model>_design.txt, one line per hole in ascending label:
+// Hole, Samples, Gain, Share = gain / var_before, Pick = 1 .. k in pick order or 0, and for a picked hole its conditional
+// gain.  Variances are in the units of the model's standardised grade.
 // Same verbs, flags and files (<model>, <model>_Statistics.txt, <model>_predict.txt,
 // <model>_gnu.plt); -np/--no-prompt skips the two interactive stdin questions of `train`
 // (gp_ss_ak.cpp:235-285) and the gnuplot call of `test` (:503-505).
@@ -92,6 +101,7 @@ class GP_Cntrl : public Control {
                     std::vector<int> &group) const;
   void block();
   void sim();
+  void design();
   void Help() const;
 };
 
@@ -100,6 +110,7 @@ void GP_Cntrl::Help() const {
             << "Commands:\ntrain :\n \t To find hyperparameter by maxmizing likelihood (--objective loo: the leave-one-out pseudo-likelihood; --objective lgo with train --groups file: the leave-group-out one; with train --folds file / --kfold K [--seed n]: the same for groups of any size, k folds).\n"
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
+            << "design :\n \t To rank candidate drill holes by the estimation variance they would remove from targets ([--block-size dx,dy,dz --block-disc nx,ny,nz] [--pick k] [--weights file] design --candidates file --holes file targets model train).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
             << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]).\n";
 }
@@ -713,6 +724,138 @@ void GP_Cntrl::sim() {
   exit(0);
 }
 
+void GP_Cntrl::design() {
+  incArg();
+  setMode("design");
+  if (gpus > 1)
+    ErrorTermination("gpak_design is built for the single-GPU context (gpak_create) only: drop --gpus");
+  bool yscale = true;
+  std::string candFile, holeFile;
+  while (isFlgs()) {
+    if (isArgFlg()) {
+      if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
+      else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else if (isArg("--candidates", "--candidates")) {
+        incArg();
+        if (getArgNo() >= argc) ErrorTermination("--candidates takes a file of candidate points");
+        candFile = getArg();
+      }
+      else if (isArg("--holes", "--holes")) {
+        incArg();
+        if (getArgNo() >= argc) ErrorTermination("--holes takes a file of labels");
+        holeFile = getArg();
+      }
+      else UnkFlg();
+      incArg();
+    } else setFlgs(false);
+  }
+  if (candFile.empty() || holeFile.empty())
+    ErrorTermination("design needs --candidates FILE (the candidate points) and --holes FILE (one integer label per candidate point)");
+  if (block_size_set != block_disc_set)
+    ErrorTermination("design takes --block-size and --block-disc together (neither: the targets are points)");
+  if (getArgNo() + 2 >= argc)
+    ErrorTermination("There are not enough input parameters: design needs the targets, the model and the training data.");
+  std::string tgFile = getArg(), modelName = argv[getArgNo() + 1], trFile = argv[getArgNo() + 2];
+  const std::string DesignOut = modelName + "_design.txt";
+  int ds[2];
+  readDataSize(tgFile, ds);
+  mat C, y;
+  readDataFile(C, y, ds, tgFile);
+  if (C.n_cols != 3 && C.n_cols != 4) ErrorTermination("Targets need 3 or 4 input columns.");
+  readDataSize(candFile, ds);
+  mat Xc, yc;
+  readDataFile(Xc, yc, ds, candFile);              // the last column is read and ignored
+  if (Xc.n_cols != C.n_cols) ErrorTermination("--candidates: the candidate points need the targets' input columns.");
+  const size_t T = C.n_rows, Mc = Xc.n_rows;
+  // the labels with the checks of `cv --groups`, in the words of this verb
+  std::vector<long long> labels, values;
+  readGroupLabels(holeFile, labels, "--holes");
+  if (labels.size() != Mc)
+    ErrorTermination("--holes: " + holeFile + " holds " + std::to_string(labels.size()) + " labels for " + std::to_string(Mc) +
+                     " candidate points");
+  values = labels;
+  std::sort(values.begin(), values.end());
+  values.erase(std::unique(values.begin(), values.end()), values.end());
+  std::vector<int> hole(Mc), count(values.size(), 0);
+  for (size_t i = 0; i < Mc; i++) {
+    hole[i] = (int)(std::lower_bound(values.begin(), values.end(), labels[i]) - values.begin());
+    if (++count[hole[i]] == GPAK_CV_GROUP_MAX + 1)
+      ErrorTermination("--holes: hole " + std::to_string(labels[i]) + " has more than " + std::to_string(GPAK_CV_GROUP_MAX) +
+                       " points (the design holds a hole in one workgroup's memory)");
+  }
+  const int H = (int)values.size();
+  if (design_pick > H)
+    ErrorTermination("--pick: " + std::to_string(design_pick) + " holes to plan out of " + std::to_string(H));
+  std::vector<double> wt;
+  if (!design_weights_file.empty()) {
+    std::ifstream in(design_weights_file.c_str());
+    if (!in.is_open()) ErrorTermination("File is " + design_weights_file + " not readable");
+    std::string line;
+    while (std::getline(in, line)) {
+      if (!line.empty() && line[0] == '#') continue;
+      for (char &ch : line) if (ch == '\t' || ch == ',' || ch == '\r') ch = ' ';
+      std::istringstream ss(line);
+      std::string tok;
+      while (ss >> tok) {
+        char *end = nullptr;
+        const double v = strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end != '\0' || !(v >= 0.0) || !std::isfinite(v))
+          ErrorTermination("--weights: '" + tok + "' in " + design_weights_file + " is not a non-negative number");
+        wt.push_back(v);
+      }
+    }
+    if (wt.size() != T)
+      ErrorTermination("--weights: " + design_weights_file + " holds " + std::to_string(wt.size()) + " weights for " +
+                       std::to_string(T) + " targets");
+  }
+  // as block: discretise in the file's units, then standardise every point like a test point
+  const double point_size[3] = {0, 0, 0};
+  const int point_disc[3] = {1, 1, 1};
+  std::vector<double> pts;
+  const int nd = gpak_block_points(C.memptr(), C.n_rows, C.n_cols, block_size_set ? block_size : point_size,
+                                   block_disc_set ? block_disc : point_disc, pts);
+  mat Xd(C.n_rows * nd, C.n_cols), ydummy(C.n_rows * nd, 1);
+  for (size_t i = 0; i < pts.size(); i++) Xd[i] = pts[i];
+  prepareData(Xd, ydummy, false, modelName);       // the model's _Statistics.txt, as `test`
+  prepareData(Xc, yc, false, modelName);
+  GP_utils *GPModel = readGpFromFile(modelName, getVerbose());  // parameters at 6 significant digits (Q5)
+  readDataSize(trFile, ds);
+  mat Xtr, ytr;
+  readDataFile(Xtr, ytr, ds, trFile);
+  prepareData(Xtr, ytr, yscale, modelName);
+  GPModel->yTarg = ytr;
+  GPModel->Xinp = Xtr;
+  GPModel->setNumData((unsigned)Xtr.n_rows);
+  GPModel->initialize_vars();
+  GPModel->logLikelihood();
+  if (C.n_cols != GPModel->getInpDim()) ErrorTermination("Incorrect dimension of input data.");
+  std::vector<double> gain, pick_gain;
+  std::vector<int> picked;
+  gpak_design_summary s;
+  if (!GPModel->DesignHoles(Xd, nd, Xc, hole, H, wt.empty() ? nullptr : wt.data(), design_pick, gain, picked, pick_gain, s))
+    std::cerr << "The covariance of a candidate hole's assays is not positive definite: its gain is NaN" << std::endl;
+  // variances in the units of the model's standardised grade; Share and Pick carry no unit
+  std::cout << "Targets: " << T << " of " << nd << " points, candidate holes: " << H << " (" << Mc << " points, the largest "
+            << s.max_size << ")\nvar_before " << s.var_before << "  var_after " << s.var_after << "  device time " << s.ms
+            << " ms\n";
+  std::vector<int> rank((size_t)H, 0);
+  for (int p = 0; p < s.picks; p++) {
+    rank[picked[p]] = p + 1;
+    std::cout << "pick " << (p + 1) << ": hole " << values[picked[p]] << "  conditional gain " << pick_gain[p] << "\n";
+  }
+  std::ofstream out(DesignOut.c_str());
+  out << "# Hole, Samples, Gain, Share, Pick" << "\n";
+  for (int h = 0; h < H; h++) {
+    out << values[h] << "\t" << count[h] << "\t" << gain[h] << "\t" << gain[h] / s.var_before << "\t" << rank[h];
+    if (rank[h]) out << "\t" << pick_gain[rank[h] - 1];
+    out << "\n";
+  }
+  out.close();
+  writeTiming(*GPModel);
+  delete GPModel;
+  exit(0);
+}
+
 int main(int argc, char **argv) {
   GP_Cntrl ctl(argc, argv);
   if (ctl.getArgNo() >= argc) { ctl.Help(); return 1; }
@@ -722,6 +865,7 @@ int main(int argc, char **argv) {
   else if (verb == "cv") ctl.cv();
   else if (verb == "block") ctl.block();
   else if (verb == "sim") ctl.sim();
+  else if (verb == "design") ctl.design();
   else if (verb == "-h" || verb == "--help" || verb == "-?") { ctl.Help(); return 0; }
   else ctl.ErrorTermination("Invalid command provided.");
   return 0;

@@ -270,6 +270,21 @@ bool GP_utils::JointSample(mat &Z, mat &mean, const mat &Xd, int nd, const mat &
   return rc == GPAK_OK;
 }
 
+bool GP_utils::DesignHoles(const mat &Xd, int nd, const mat &Xc, const std::vector<int> &hole, int H, const double *wt, int k,
+                           std::vector<double> &gain, std::vector<int> &picked, std::vector<double> &pick_gain,
+                           gpak_design_summary &summary) const {
+  sync_params();
+  const size_t T = nd > 0 ? Xd.n_rows / nd : 0;
+  gain.assign((size_t)H, 0.0);
+  picked.assign((size_t)k, -1);
+  pick_gain.assign((size_t)k, 0.0);
+  int rc = gpak_design(ctx, Xd.memptr(), (long)T, nd, Xc.memptr(), (long)Xc.n_rows, (int)Xd.n_cols, hole.data(), H, wt, k,
+                       gain.data(), nullptr, nullptr, picked.data(), pick_gain.data(), nullptr, &summary);
+  Chol_fail = (rc == GPAK_ENOTPD && std::isnan(summary.var_before));   // the training factor; otherwise a hole's A_h
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_design", ctx);
+  return rc == GPAK_OK;
+}
+
 void GP_utils::Calc_Out(mat &yPred, mat &yVar, const mat &Xin) const { posteriorMeanVar(yPred, yVar, Xin); }
 
 void GP_utils::OptimisePars(unsigned int iters) {  // GP_Utils.cpp:1288-1301

@@ -12,6 +12,7 @@
 #include "../../include/gpak_cv_folds.h"
 #include "../../include/gpak_cv_groups_grad.h"
 #include "../../include/gpak_cv_folds_grad.h"
+#include "../../include/gpak_design.h"
 #include "kernels.hpp"
 
 class ModelInfo {
@@ -142,6 +143,12 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // factor of the covariance + nugget I.  Returns false when that matrix is not positive definite (Z NaN, mean valid);
   // everything NaN on Chol_fail
   bool JointSample(mat &Z, mat &mean, const mat &Xd, int nd, const mat &Xi, double nugget, bool latent) const;
+  // infill drilling design (gpak_design): the gain of each of the H candidate holes (hole[i] in [0, H) for candidate point i
+  // of Xc) on the target blocks Xd (nd points each; wt: one weight per block, or null) and a greedy plan of k of them;
+  // false when the A_h of some hole is not positive definite; everything NaN on Chol_fail
+  bool DesignHoles(const mat &Xd, int nd, const mat &Xc, const std::vector<int> &hole, int H, const double *wt, int k,
+                   std::vector<double> &gain, std::vector<int> &picked, std::vector<double> &pick_gain,
+                   gpak_design_summary &summary) const;
   void OptimisePars(unsigned int iters);
   void updateKernel() const;
   std::ostream &ShowKernelPars(std::ostream &os) const;
