@@ -32,6 +32,9 @@ DEV_CV_MIX_SYMBOLS = ["gpak_dev_mix_cols"]
 # every symbol include/gpak_design.h / include/gpak_dev_design.h declares (tests/test_design.py checks the headers and these lists agree)
 DESIGN_SYMBOLS = ["gpak_design"]
 DEV_DESIGN_SYMBOLS = ["gpak_dev_design_score"]
+# every symbol include/gpak_condition.h / include/gpak_dev_condition.h declares (tests/test_path.py checks the headers and these lists agree)
+CONDITION_SYMBOLS = ["gpak_condition", "gpak_sample_path"]
+DEV_CONDITION_SYMBOLS = ["gpak_dev_kmm", "gpak_dev_kmm_slabs", "gpak_dev_kmm_slab_len"]
 # every symbol include/gpak_dev_f32.h declares (tests/test_dev_ops.py checks the header and this list agree)
 DEV_F32_SYMBOLS = ["gpak_dev_gemm_nt_f32", "gpak_dev_fill_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32",
                    "gpak_dev_rowsumsq_f32", "gpak_dev_fwd_subst_f32"]
@@ -61,6 +64,11 @@ class DesignSummary(C.Structure):
                 ("max_size", C.c_int), ("picks", C.c_int)]
 
 
+class ConditionSummary(C.Structure):
+    _fields_ = [("solve_ms", C.c_double), ("prior_ms", C.c_double), ("product_ms", C.c_double), ("batches", C.c_int),
+                ("fused", C.c_int)]
+
+
 _lib = None
 
 
@@ -75,12 +83,14 @@ def load():
             "(hipcc --offload-arch=gfx950). gp_ss_ak_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS
-               + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DESIGN_SYMBOLS + DEV_DESIGN_SYMBOLS + DEV_F32_SYMBOLS
+               + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DESIGN_SYMBOLS + DEV_DESIGN_SYMBOLS + CONDITION_SYMBOLS + DEV_CONDITION_SYMBOLS
+               + DEV_F32_SYMBOLS
                if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
                            "gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_cv_folds_grad.h / "
-                           f"gpak_dev_cv_mix.h / gpak_design.h / gpak_dev_design.h / gpak_dev_f32.h: {missing}")
+                           "gpak_dev_cv_mix.h / gpak_design.h / gpak_dev_design.h / gpak_condition.h / gpak_dev_condition.h / "
+                           f"gpak_dev_f32.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -122,6 +132,15 @@ def load():
                                 C.POINTER(C.c_int), dp, dp, C.POINTER(DesignSummary)]
     # include/gpak_dev_design.h: the stream first, every pointer a device pointer
     lib.gpak_dev_design_score.argtypes = [vp, vp, C.c_long, C.c_int, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, C.c_long, vp]
+    ip = C.POINTER(C.c_int)
+    lib.gpak_condition.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, C.c_int, C.POINTER(ConditionSummary)]
+    lib.gpak_sample_path.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, C.c_int, ip, dp, dp, dp, dp, C.c_int, dp, dp, C.c_int,
+                                     C.POINTER(ConditionSummary)]
+    # include/gpak_dev_condition.h: the stream first, every pointer a device pointer
+    lib.gpak_dev_kmm.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, dp, C.c_double, C.c_int, vp, C.c_long,
+                                 C.c_int, vp, C.c_long, vp, C.c_long, vp]
+    lib.gpak_dev_kmm_slabs.argtypes = [C.c_int]
+    lib.gpak_dev_kmm_slab_len.argtypes = [C.c_int]
     lib.gpak_block_cross.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp]
     lib.gpak_predict_block.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.gpak_predict_joint.argtypes = [vp, dp, C.c_long, C.c_int, C.c_int, dp, dp, C.c_int]

@@ -1048,6 +1048,53 @@ int gpak_design(gpak_ctx *ctx, const double *Xt, long T, int nd, const double *X
   return rc;
 }
 
+// gpak_condition / gpak_sample_path (include/gpak_condition.h): the block calls' prologue and their answer to a failed factor
+static int condition_call(gpak_ctx *ctx, const char *name, const double *Xd, long M, int nd, int d, const double *Ysim,
+                          const double *Fsim, int S, double *Z, double *mean, int flags, gpak_condition_summary *summary,
+                          const GpakPathPrior *prior) {
+  int rc = single_gpu_call(ctx, name, true, false, CtxState::NONE, d, "block points");
+  if (rc) return rc;
+  if (flags & ~GPAK_COND_UNFUSED) {
+    ctx->err = std::string(name) + ": flags = " + std::to_string(flags) + " has bits other than GPAK_COND_UNFUSED";
+    return GPAK_EINVAL;
+  }
+  if (prior) {
+    if (!ctx->have_params) { ctx->err = "no parameters (gpak_set_params)"; return GPAK_ESTATE; }
+    for (int f = 0; f < prior->nfeat; f++)
+      if (prior->feat_term[f] < 0 || prior->feat_term[f] >= ctx->kp.nterms) {
+        ctx->err = std::string(name) + ": feature " + std::to_string(f) + " names term " + std::to_string(prior->feat_term[f]) +
+                   ", outside the composition's " + std::to_string(ctx->kp.nterms);
+        return GPAK_EINVAL;
+      }
+    if (!prior->b0 && ctx->kp.bias != 0.0) { ctx->err = std::string(name) + ": b0 is NULL and the constant is not 0"; return GPAK_EINVAL; }
+  }
+  rc = ensure_nlz(ctx);
+  if (rc == GPAK_OK) rc = gpak_condition_impl(ctx, Xd, M, nd, Ysim, Fsim, S, Z, mean, flags, summary, prior);
+  if (rc == GPAK_ENOTPD) {
+    fill_nan(Z, (size_t)M * S);
+    fill_nan(mean, M);
+  }
+  if (rc != GPAK_OK && summary) {
+    summary->solve_ms = summary->prior_ms = summary->product_ms = 0.0;
+    summary->batches = 0; summary->fused = (flags & GPAK_COND_UNFUSED) ? 0 : 1;
+  }
+  return rc;
+}
+
+int gpak_condition(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, const double *Ysim, const double *Fsim, int S, double *Z,
+                   double *mean, int flags, gpak_condition_summary *summary) {
+  if (!ctx || !Xd || !Ysim || !Z || M <= 0 || nd <= 0 || S <= 0) return GPAK_EINVAL;
+  return condition_call(ctx, "gpak_condition", Xd, M, nd, d, Ysim, Fsim, S, Z, mean, flags, summary, nullptr);
+}
+
+int gpak_sample_path(gpak_ctx *ctx, const double *Xd, long M, int nd, int d, int nfeat, const int *feat_term, const double *omega,
+                     const double *ab, const double *b0, const double *E, int S, double *Z, double *mean, int flags,
+                     gpak_condition_summary *summary) {
+  if (!ctx || !Xd || !Z || M <= 0 || nd <= 0 || S <= 0 || nfeat <= 0 || !feat_term || !omega || !ab || !E) return GPAK_EINVAL;
+  const GpakPathPrior prior = {nfeat, feat_term, omega, ab, b0, E};
+  return condition_call(ctx, "gpak_sample_path", Xd, M, nd, d, nullptr, nullptr, S, Z, mean, flags, summary, &prior);
+}
+
 int gpak_timing(gpak_ctx *ctx, gpak_phase_times *out) {
   if (!ctx || !out) return GPAK_EINVAL;
   if (ctx->multi) return gpak_multi_timing(ctx->multi, out);

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/gpak_dev.h"
+#include "../../include/gpak_dev_condition.h"
 #include "../../include/gpak_dev_f32.h"
 #include "gpak_internal.h"
 
@@ -108,6 +109,23 @@ int gpak_dev_transform_k(void *stream, const double *x, int xs, int n, int cap, 
   if (kp.nterms < 1) return GPAK_EINVAL;
   DevPoints p = as_points(u, cap, n);
   gpak_launch_transform((hipStream_t)stream, x, xs, n, kp, p);
+  return status();
+}
+
+// the fused product of gpak_condition alone (include/gpak_dev_condition.h)
+int gpak_dev_kmm_slabs(int n) { return n < 1 ? 0 : gpak_kmm_slabs((n + GPAK_TILE - 1) / GPAK_TILE * GPAK_TILE); }
+int gpak_dev_kmm_slab_len(int n) { return n < 1 ? 0 : gpak_kmm_slab_len((n + GPAK_TILE - 1) / GPAK_TILE * GPAK_TILE); }
+int gpak_dev_kmm(void *stream, const double *P, int cap, int nB, int nd, const double *u, int ucap, int n, const double *kern,
+                 double bias, int dist_mode, const double *A, long lda, int S, const double *F0, long ldf, double *Z, long ldz,
+                 double *scratch) {
+  if (!P || !u || !kern || !A || !Z || !scratch || nB < 1 || nd < 1 || n < 1 || S < 1 || cap < nB || ucap < n || lda < n || ldz < nB ||
+      (F0 && ldf < nB))
+    return GPAK_EINVAL;
+  KernParams kp = make_kp(kern, bias, dist_mode, nullptr);
+  if (kp.nterms < 1) return GPAK_EINVAL;
+  const DevPoints Q = as_points(u, ucap, n);
+  gpak_launch_kmm((hipStream_t)stream, P, cap, nB, nd, Q, (n + GPAK_TILE - 1) / GPAK_TILE * GPAK_TILE, kp, A, lda, S, F0, ldf, S, Z, ldz,
+                  scratch);
   return status();
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/gpak.h"
 #include "../../include/gpak_design.h"   // gpak_design_summary (gpak_design_impl)
+#include "../../include/gpak_condition.h"   // gpak_condition_summary (gpak_condition_impl)
 #include "ctx_state.h"  // CtxState: what of a context's device contents is current (HIP-free)
 #include "potrf_plan.h"  // GPAK_TILE, GpakSchedule and the factorisation's schedule (HIP-free)
 
@@ -191,6 +192,11 @@ struct gpak_ctx : gpak_queues {
   int blk_terms = 0;
   // the fills, the substitution, the SYRK, the first score pass and the last pick's downdate of the last gpak_design, in ms
   double design_ms[5] = {0, 0, 0, 0, 0};
+  // gpak_condition / gpak_sample_path (condition.hip), kept across calls: A (Np x (S + 1)) and, for the comparison path, its
+  // transpose; Ysim (Np x S) and Ysim^T / sn2 realisation-major for the batched substitution; a batch's Z and F0; the slab partials of the fused product / the GEMMs' output; and of the
+  // spectral prior the features of a chunk, W^T, the frequencies, the features' terms and sqrt(c) b0
+  DevBuf<double> dCondA, dCondAt, dCondY, dCondYt, dCondZ, dCondF, dCondPart, dCondPhi, dCondW, dCondOm, dCondB0;
+  DevBuf<int> dCondFt;
   // fp32 prediction (ctx created with GPAK_F32): fp32 images of L and of the inverse blocks (CtxState::image)
   DevBuf<float> dLf, dInvf;
   long ldLf = 0;             // leading dimension of dLf (Np + skew)
@@ -472,6 +478,32 @@ int gpak_joint_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, double *mea
 // dimension of dWt and dC); and the substitution dWt := dWt L^-T over those rows on the context's stream
 int gpak_joint_reserve(gpak_ctx *ctx, int cap, size_t points, int nterms, long *ld);
 void gpak_joint_forward_subst(gpak_ctx *ctx, int cap, long ldw);
+
+// the block path's buffers for batches of `cap` blocks (a multiple of 256) and `points` discretisation points; want_wt: also
+// the cross-kernel batch dWt, *ldw its leading dimension (skewed as gpak_predict_block_impl skews it)
+int gpak_block_reserve(gpak_ctx *ctx, int cap, size_t points, int nterms, bool want_wt, long *ldw);
+// the substitution of the prediction path on any test-major batch: Wt (rows x Np, rows a multiple of 128, leading dimension
+// ldw) := Wt L^-T on the context's stream
+void gpak_forward_subst_rows(gpak_ctx *ctx, double *Wt, long ldw, int rows);
+
+// ---- condition.hip ----------------------------------------------------------------------
+// the spectral prior of gpak_sample_path as api.hip has checked it (host pointers)
+struct GpakPathPrior {
+  int nfeat;
+  const int *feat_term;
+  const double *omega, *ab, *b0, *E;
+};
+// gpak_condition (prior == nullptr: Ysim and Fsim are the caller's) / gpak_sample_path (prior set: Ysim and Fsim are
+// ignored) on a single-GPU context whose factor and alpha are current and whose arguments api.hip has checked
+int gpak_condition_impl(gpak_ctx *ctx, const double *Xd, long M, int nd, const double *Ysim, const double *Fsim, int S, double *Z,
+                        double *mean, int flags, gpak_condition_summary *summary, const GpakPathPrior *prior);
+// Z (nB x S, ldz) = F0 (its first nF columns; null: zeros) + Kbar A by the fused kernel: P the blocks' points point-major
+// (gpak_transform_blocks_f64), Q the transformed samples, Np = Q.n rounded up to 128 (it fixes the slabs), scratch
+// gpak_kmm_slabs(Np) * nB * S doubles
+int gpak_kmm_slab_len(int Np);
+int gpak_kmm_slabs(int Np);
+void gpak_launch_kmm(hipStream_t st, const double *P, int cap, int nB, int nd, const DevPoints &Q, int Np, const KernParams &kp,
+                     const double *A, long lda, int S, const double *F0, long ldf, int nF, double *Z, long ldz, double *scratch);
 
 // ---- design.hip -------------------------------------------------------------------------
 // gpak_design on a single-GPU context whose factor and alpha are current and whose arguments api.hip has checked: perm =

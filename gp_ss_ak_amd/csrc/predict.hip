@@ -141,6 +141,17 @@ int gpak_joint_reserve(gpak_ctx *ctx, int cap, size_t points, int nterms, long *
   return ensure_joint_cov(ctx, cap, *ld);
 }
 void gpak_joint_forward_subst(gpak_ctx *ctx, int cap, long ldw) { forward_subst_batch(ctx, ctx->dWt, ldw, cap); }
+// the substitution of the prediction path on any test-major batch: Wt (rows x Np, rows a multiple of 128, leading dimension
+// ldw) := Wt L^-T on the context's stream
+void gpak_forward_subst_rows(gpak_ctx *ctx, double *Wt, long ldw, int rows) { forward_subst_batch(ctx, Wt, ldw, rows); }
+// what gpak_condition_impl (condition.hip) shares with the block path: its buffers, sized and skewed as
+// gpak_predict_block_impl sizes them; the cross-kernel batch only where the comparison path asks for it
+int gpak_block_reserve(gpak_ctx *ctx, int cap, size_t points, int nterms, bool want_wt, long *ldw) {
+  int rc = ensure_predict_bufs(ctx, cap, want_wt);
+  if (rc) return rc;
+  *ldw = cap + 32L * std::max(0, ctx->sched.pred_ld_skew);
+  return ensure_block_points(ctx, points, nterms);
+}
 
 // fp32 images of the factor for a GPAK_F32 context (rebuilt when the factor changes)
 static int ensure_f32_factor(gpak_ctx *ctx) {

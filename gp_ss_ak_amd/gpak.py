@@ -24,6 +24,7 @@ KERN_EXPANS, KERN_EXP, KERN_RBF = 0, 1, 2
 BLOCK_LATENT = 1
 JOINT_LATENT, JOINT_PRIOR = 1, 2
 NO_BATCH = 1      # GPAK_CV_FOLDS_NO_BATCH
+COND_UNFUSED = 1
 
 _dp = C.POINTER(C.c_double)
 
@@ -337,6 +338,63 @@ class Gpak:
         self._check(self._lib.gpak_sample_joint(self._h, _p(Xd), M, nd, Xd.shape[1], _p(xi), S, float(nugget), _p(Z),
                                                 _p(mean), JOINT_LATENT if latent else 0), allow=(ENOTPD,))
         return Z, mean
+
+    def _realisations(self, a, rows, what):
+        a = _f(a)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1, order="F")
+        if a.ndim != 2 or a.shape[0] != rows:
+            raise GpakError(EINVAL, f"{what} must hold {rows} rows")
+        return a
+
+    def _condition_out(self, rc, s):
+        out = {name: getattr(s, name) for name, _ in s._fields_}
+        out["status"] = rc
+        return out
+
+    def condition(self, Xd, nd, Ysim, Fsim=None, unfused=False):
+        """Conditioning by kriging (gpak_condition): Z = Fsim + Kbar (alpha 1' - Ky^-1 Ysim) for an unconditional draw
+        (Fsim: M x S at the nodes, None = zeros; Ysim: N x S of the noisy observations).  Returns (Z, mean, summary): Z is
+        M x S, mean = Kbar alpha, summary = {solve_ms, prior_ms, product_ms, batches, fused, status}.  unfused: the
+        comparison path (averaged fill + GEMM).  On Chol_fail status is ENOTPD and Z and mean are NaN."""
+        Xd, M, nd = self._blocks(Xd, nd)
+        Ysim = self._realisations(Ysim, self.N, "Ysim")
+        S = Ysim.shape[1]
+        if Fsim is not None:
+            Fsim = self._realisations(Fsim, M, "Fsim")
+            if Fsim.shape[1] != S:
+                raise GpakError(EINVAL, "Fsim and Ysim must hold as many realisations")
+        Z, mean = np.zeros((M, S), order="F"), np.zeros(M)
+        s = _lib.ConditionSummary()
+        rc = self._check(self._lib.gpak_condition(self._h, _p(Xd), M, nd, Xd.shape[1], _p(Ysim), _p(Fsim), S, _p(Z), _p(mean),
+                                                  COND_UNFUSED if unfused else 0, C.byref(s)), allow=(ENOTPD,))
+        return Z, mean, self._condition_out(rc, s)
+
+    def sample_path(self, Xd, nd, feat_term, omega, ab, b0, E, unfused=False):
+        """The spectral prior sampler followed by the conditioning (gpak_sample_path): feat_term[f] = the stationary term
+        of feature f, omega nfeat x 4 (row f = its frequency in that term's transformed coordinates), ab (2 nfeat) x S,
+        b0 S entries or None, E N x S unit normals.  Returns (Z, mean, summary) as condition does."""
+        Xd, M, nd = self._blocks(Xd, nd)
+        ft = np.ascontiguousarray(feat_term, dtype=np.int32).ravel()
+        nfeat = int(ft.size)
+        om = np.ascontiguousarray(omega, dtype=np.float64)
+        if om.shape != (nfeat, 4):
+            raise GpakError(EINVAL, "omega must be nfeat x 4")
+        ab = self._realisations(ab, 2 * nfeat, "ab")
+        S = ab.shape[1]
+        E = self._realisations(E, self.N, "E")
+        if E.shape[1] != S:
+            raise GpakError(EINVAL, "E and ab must hold as many realisations")
+        if b0 is not None:
+            b0 = np.ascontiguousarray(b0, dtype=np.float64).ravel()
+            if b0.size != S:
+                raise GpakError(EINVAL, "b0 must hold one entry per realisation")
+        Z, mean = np.zeros((M, S), order="F"), np.zeros(M)
+        s = _lib.ConditionSummary()
+        rc = self._check(self._lib.gpak_sample_path(self._h, _p(Xd), M, nd, Xd.shape[1], nfeat, ft.ctypes.data_as(C.POINTER(C.c_int)),
+                                                    _p(om), _p(ab), _p(b0), _p(E), S, _p(Z), _p(mean),
+                                                    COND_UNFUSED if unfused else 0, C.byref(s)), allow=(ENOTPD,))
+        return Z, mean, self._condition_out(rc, s)
 
     def design(self, Xt, nd, Xc, holes, weights=None, pick=0, want_reduction=False):
         """Infill drilling design (gpak_design): rank candidate holes by the estimation variance they would remove from the

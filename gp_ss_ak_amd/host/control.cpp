@@ -56,6 +56,7 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       incArg();
       char *end = nullptr;
       sim_nugget = strtod(getArg().c_str(), &end);
+      sim_nugget_set = true;
       if (end == getArg().c_str() || !(sim_nugget >= 0.0)) ErrorTermination("--nugget takes a non-negative value");
     }
     else if (isArg("--pick", "--pick")) {

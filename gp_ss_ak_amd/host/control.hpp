@@ -63,6 +63,10 @@ class Control {
   unsigned long long sim_seed = 0;
   std::string sim_xi_file;
   double sim_nugget = 0.0;
+  bool sim_nugget_set = false;
+  // sim --method joint (gpak_sample_joint, the default) | path (gpak_sample_path: any node count), --features F per stationary term
+  std::string sim_method = "joint";
+  int sim_features = 4096;
   // the `design` verb: --pick k (a greedy plan of k holes), --weights file (one non-negative number per target)
   int design_pick = 0;
   std::string design_weights_file;

@@ -6,7 +6,7 @@
 //            train.txt model [out_file]
 //   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
 //   gp_ss_ak [-v n] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] [--nugget v] --realisations S (--seed n | --xi file)
-//            sim nodes.txt model train.txt [out_file]
+//            sim [--method joint|path [--features F]] nodes.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
 // (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only),
@@ -35,6 +35,9 @@
 // gpak_sample_joint; one GPU only).  nodes.txt is read as block reads its centres; without --block-size / --block-disc the
 // nodes are points.  The normals come from --xi (an M x S text matrix) or from --seed (std::mt19937_64 + Box-Muller,
 // sim_normals.hpp).  Written to <model>_sim.txt in input order: the conditional mean and the S realisations.
+// sim --method path [--features F, default 4096] (with --seed; no --xi, no --nugget): the same file for ANY number of nodes
+// (gpak_sample_path): a spectral draw of the prior from F random frequencies per stationary term (sim_spectral.hpp; its
+// covariance is the prior's to O(1/sqrt(F))) conditioned on the data by kriging, which is exact; no M x M matrix exists.
 // design (not a reference verb): ranks candidate drill holes by the estimation variance they would remove from the targets
 // (gpak_design; one GPU only):  gp_ss_ak [--block-size dx,dy,dz --block-disc nx,ny,nz] [--pick k] [--weights w.txt]
 // design --candidates cand.txt --holes holes.txt targets.txt model train.txt.  targets.txt and cand.txt are read as block
@@ -112,7 +115,7 @@ void GP_Cntrl::Help() const {
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
             << "design :\n \t To rank candidate drill holes by the estimation variance they would remove from targets ([--block-size dx,dy,dz --block-disc nx,ny,nz] [--pick k] [--weights file] design --candidates file --holes file targets model train).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
-            << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]).\n";
+            << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]; sim --method path [--features F] with --seed n: any number of nodes, the prior from F random frequencies per term).\n";
 }
 
 void GP_Cntrl::train() {
@@ -631,14 +634,38 @@ void GP_Cntrl::sim() {
     if (isArgFlg()) {
       if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
       else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else if (isArg("--method", "--method")) {
+        incArg();
+        if (getArgNo() >= argc || (getArg() != "joint" && getArg() != "path")) ErrorTermination("--method takes joint or path");
+        sim_method = getArg();
+      }
+      else if (isArg("--features", "--features")) {
+        incArg();
+        char *end = nullptr;
+        const std::string tok = getArgNo() < argc ? getArg() : std::string();
+        const long v = strtol(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0' || v < 1 || v > 1000000) ErrorTermination("--features takes the number of frequencies per stationary term (1 or more)");
+        sim_features = (int)v;
+      }
+      // the verb's own options may also follow it
+      else if (isArg("--realisations", "--realizations")) { incArg(); sim_realisations = getIntArg(); sim_realisations_set = true; }
+      else if (isArg("--seed", "--seed")) { incArg(); sim_seed = strtoull(getArg().c_str(), nullptr, 10); sim_seed_set = true; }
+      else if (isArg("--latent", "--latent")) { block_latent = true; }
       else UnkFlg();
       incArg();
     } else setFlgs(false);
   }
+  const bool path = sim_method == "path";
+  // what --method path cannot take is refused here, before any file is read and before a context exists
+  if (path && !sim_xi_file.empty())
+    ErrorTermination("sim --method path draws every normal from --seed (frequencies, amplitudes, noise): drop --xi");
+  if (path && sim_nugget_set)
+    ErrorTermination("sim --method path factors no covariance of the nodes, so there is nothing for --nugget to regularise: drop --nugget");
+  if (path && !sim_seed_set) ErrorTermination("sim --method path needs --seed n");
   if (getArgNo() + 2 >= argc)
     ErrorTermination("There are not enough input parameters: sim needs the nodes, the model and the training data.");
   if (!sim_realisations_set || sim_realisations <= 0) ErrorTermination("sim needs --realisations S with S > 0");
-  if (sim_seed_set == !sim_xi_file.empty()) ErrorTermination("sim needs exactly one of --seed n and --xi file");
+  if (!path && sim_seed_set == !sim_xi_file.empty()) ErrorTermination("sim needs exactly one of --seed n and --xi file");
   if (block_size_set != block_disc_set)
     ErrorTermination("sim takes --block-size and --block-disc together (neither: the nodes are points)");
   std::string ndFile = getArg(), modelName = argv[getArgNo() + 1], trFile = argv[getArgNo() + 2];
@@ -650,9 +677,10 @@ void GP_Cntrl::sim() {
   readDataFile(C, y, ds, ndFile);
   if (C.n_cols != 3 && C.n_cols != 4) ErrorTermination("Nodes need 3 or 4 input columns.");
   const size_t M = C.n_rows, S = (size_t)sim_realisations;
-  // the normals, M x S column-major: realisation s is column s
-  mat Xi(M, S);
-  if (!sim_xi_file.empty()) {
+  // the normals, M x S column-major: realisation s is column s (--method path draws its own, gp_utils.cpp)
+  mat Xi(path ? 0 : M, path ? 0 : S);
+  if (path) {
+  } else if (!sim_xi_file.empty()) {
     std::ifstream in(sim_xi_file.c_str());
     if (!in.is_open()) ErrorTermination("File is " + sim_xi_file + " not readable");
     std::vector<double> vals;
@@ -700,12 +728,21 @@ void GP_Cntrl::sim() {
   GPModel->logLikelihood();
   if (C.n_cols != GPModel->getInpDim()) ErrorTermination("Incorrect dimension of input data.");
   mat MeanVals(M, 1), SimVals(M, S);
-  if (!GPModel->JointSample(SimVals, MeanVals, Xd, nd, Xi, sim_nugget, block_latent))
+  gpak_condition_summary ps = {0.0, 0.0, 0.0, 0, 1};
+  if (path) {
+    if (!GPModel->PathSample(SimVals, MeanVals, Xd, nd, sim_seed, sim_features, block_latent, ps))
+      std::cerr << "The training factor failed: the realisations are NaN" << std::endl;
+  } else if (!GPModel->JointSample(SimVals, MeanVals, Xd, nd, Xi, sim_nugget, block_latent))
     std::cerr << "The joint covariance of the nodes is not positive definite: the realisations are NaN (try --nugget)" << std::endl;
   postData(C, MeanVals, yscale, modelName);
   postData(SimVals, yscale, modelName);
   postData(y, yscale, modelName);
-  if (getVerbose() > 0)
+  if (getVerbose() > 0 && path)
+    std::cout << "Nodes: " << M << " of " << nd << " points, " << S << " realisations" << (block_latent ? ", latent" : "")
+              << ", spectral prior of " << sim_features << " frequencies per term (its covariance is the prior's to O(1/sqrt(F)); "
+              << "the conditioning on the data is exact); device ms: solves " << ps.solve_ms << ", prior " << ps.prior_ms
+              << ", product " << ps.product_ms << " in " << ps.batches << " batch(es)\n";
+  else if (getVerbose() > 0)
     std::cout << "Nodes: " << M << " of " << nd << " points, " << S << " realisations"
               << (block_latent ? ", latent" : "") << ", nugget " << sim_nugget << "\n";
   std::ofstream out(SimOut.c_str());

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/gpak.h"
+#include "sim_spectral.hpp"
 
 int GP_utils::default_precision = GPAK_F64;
 int GP_utils::default_gpus = 1;
@@ -267,6 +268,51 @@ bool GP_utils::JointSample(mat &Z, mat &mean, const mat &Xd, int nd, const mat &
                              mean.memptr(), latent ? GPAK_JOINT_LATENT : 0);
   Chol_fail = (rc == GPAK_ENOTPD && std::isnan(mean[0]));   // the training factor; otherwise the blocks' covariance
   if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_sample_joint", ctx);
+  return rc == GPAK_OK;
+}
+
+bool GP_utils::PathSample(mat &Z, mat &mean, const mat &Xd, int nd, unsigned long long seed, int features, bool latent,
+                          gpak_condition_summary &summary) const {
+  sync_params();
+  const size_t M = nd > 0 ? Xd.n_rows / nd : 0, N = Xinp.n_rows;
+  const int S = (int)Z.n_cols, dim = (int)Xd.n_cols;
+  if (mean.n_elem != M) mean.resize(M, 1);
+  if (Z.n_rows != M) Z.resize(M, S);
+  // the stationary terms of the composition in force, as sync_params hands them to the library
+  std::vector<int> kinds;
+  std::vector<double> pars;
+  double e[8], bias = 0.0, white = 0.0;
+  if (gpak_extract_expans_bias(KerenlW, e, &bias)) {
+    kinds.assign(1, GPAK_KERN_EXPANS);
+  } else if (!gpak_extract_composition(KerenlW, kinds, pars, &bias, &white) || kinds.empty()) {
+    std::cerr << "GP_utils: this kernel composition is not on the HIP path." << std::endl;
+    exit(1);
+  }
+  std::vector<GpakSpectralTerm> terms;
+  size_t off = 0;
+  for (int kind : kinds) {
+    GpakSpectralTerm t = {kind == GPAK_KERN_RBF ? GPAK_SPECTRAL_RBF : GPAK_SPECTRAL_EXPSQRT, 0.0};
+    if (kind == GPAK_KERN_RBF) t.iw = pars[off + 1];
+    off += kind == GPAK_KERN_EXPANS ? 8 : kind == GPAK_KERN_EXP ? 2 : 3;
+    terms.push_back(t);
+  }
+  GpakNormalStream z(seed);
+  std::vector<int> feat_term;
+  std::vector<double> omega;
+  gpak_spectral_frequencies(z, terms, features, dim, feat_term, omega);
+  const size_t nfeat = feat_term.size();
+  std::vector<double> ab(2 * nfeat * (size_t)S), b0((size_t)S), E(N * (size_t)S);
+  z.fill(ab.data(), ab.size());
+  z.fill(b0.data(), b0.size());
+  z.fill(E.data(), E.size());
+  int rc = gpak_sample_path(ctx, Xd.memptr(), (long)M, nd, dim, (int)nfeat, feat_term.data(), omega.data(), ab.data(), b0.data(),
+                            E.data(), S, Z.memptr(), mean.memptr(), 0, &summary);
+  Chol_fail = (rc == GPAK_ENOTPD);
+  if (rc != GPAK_OK && rc != GPAK_ENOTPD) gpak_host_fatal("gpak_sample_path", ctx);
+  if (rc == GPAK_OK && !latent) {
+    const double sd = std::sqrt((hyperlf(0) + white) / nd);
+    for (size_t i = 0; i < M * (size_t)S; i++) Z[i] += sd * z.next();
+  }
   return rc == GPAK_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/gpak_cv_folds.h"
 #include "../../include/gpak_cv_groups_grad.h"
 #include "../../include/gpak_cv_folds_grad.h"
+#include "../../include/gpak_condition.h"
 #include "../../include/gpak_design.h"
 #include "kernels.hpp"
 
@@ -143,6 +144,12 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // factor of the covariance + nugget I.  Returns false when that matrix is not positive definite (Z NaN, mean valid);
   // everything NaN on Chol_fail
   bool JointSample(mat &Z, mat &mean, const mat &Xd, int nd, const mat &Xi, double nugget, bool latent) const;
+  // conditional simulation at any node count (gpak_sample_path): a spectral draw of the prior from `features` frequencies
+  // per stationary term (sim_spectral.hpp), conditioned on the data by kriging; every normal comes from the one stream of
+  // `seed` in sim_spectral.hpp's order.  Unless latent, sqrt((sn2 + white) / nd) times a normal is added per node and
+  // realisation on the host.  Everything NaN on Chol_fail (then false)
+  bool PathSample(mat &Z, mat &mean, const mat &Xd, int nd, unsigned long long seed, int features, bool latent,
+                  gpak_condition_summary &summary) const;
   // infill drilling design (gpak_design): the gain of each of the H candidate holes (hole[i] in [0, H) for candidate point i
   // of Xc) on the target blocks Xd (nd points each; wt: one weight per block, or null) and a greedy plan of k of them;
   // false when the A_h of some hole is not positive definite; everything NaN on Chol_fail
