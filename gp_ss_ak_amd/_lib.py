@@ -35,6 +35,9 @@ DEV_DESIGN_SYMBOLS = ["gpak_dev_design_score"]
 # every symbol include/gpak_condition.h / include/gpak_dev_condition.h declares (tests/test_path.py checks the headers and these lists agree)
 CONDITION_SYMBOLS = ["gpak_condition", "gpak_sample_path"]
 DEV_CONDITION_SYMBOLS = ["gpak_dev_kmm", "gpak_dev_kmm_slabs", "gpak_dev_kmm_slab_len"]
+# every symbol include/gpak_local.h / include/gpak_dev_local.h declares (tests/test_local.py checks the headers and these lists agree)
+LOCAL_SYMBOLS = ["gpak_local_metric", "gpak_local_neighbours", "gpak_predict_local"]
+DEV_LOCAL_SYMBOLS = ["gpak_dev_local_krige"]
 # every symbol include/gpak_dev_f32.h declares (tests/test_dev_ops.py checks the header and this list agree)
 DEV_F32_SYMBOLS = ["gpak_dev_gemm_nt_f32", "gpak_dev_fill_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32",
                    "gpak_dev_rowsumsq_f32", "gpak_dev_fwd_subst_f32"]
@@ -69,6 +72,11 @@ class ConditionSummary(C.Structure):
                 ("fused", C.c_int)]
 
 
+class LocalSummary(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("krige_ms", C.c_double), ("nodes", C.c_long), ("empty", C.c_long),
+                ("notpd", C.c_long), ("batches", C.c_int), ("max_used", C.c_int)]
+
+
 _lib = None
 
 
@@ -84,13 +92,13 @@ def load():
     lib = C.CDLL(LIB_PATH)
     missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS
                + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DESIGN_SYMBOLS + DEV_DESIGN_SYMBOLS + CONDITION_SYMBOLS + DEV_CONDITION_SYMBOLS
-               + DEV_F32_SYMBOLS
+               + DEV_F32_SYMBOLS + LOCAL_SYMBOLS + DEV_LOCAL_SYMBOLS
                if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
                            "gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_cv_folds_grad.h / "
                            "gpak_dev_cv_mix.h / gpak_design.h / gpak_dev_design.h / gpak_condition.h / gpak_dev_condition.h / "
-                           f"gpak_dev_f32.h: {missing}")
+                           f"gpak_dev_f32.h / gpak_local.h / gpak_dev_local.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -157,5 +165,12 @@ def load():
     lib.gpak_dev_vec_to_f32.argtypes = [vp, vp, C.c_long, fp]
     lib.gpak_dev_rowsumsq_f32.argtypes = [vp, fp, C.c_long, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     lib.gpak_dev_fwd_subst_f32.argtypes = [vp, fp, C.c_long, C.c_int, C.c_int, fp, C.c_long, fp, ip, C.c_int]
+    # include/gpak_local.h; include/gpak_dev_local.h: the stream first, every pointer but kern a device pointer
+    lib.gpak_local_metric.argtypes = [vp, C.c_int, dp]
+    lib.gpak_local_neighbours.argtypes = [dp, C.c_long, C.c_int, dp, C.c_long, dp, C.c_int, C.c_double, C.c_int, ip, ip]
+    lib.gpak_predict_local.argtypes = [vp, dp, dp, C.c_long, C.c_int, dp, C.c_long, C.c_int, ip, C.c_int, dp, dp, C.c_int,
+                                       C.POINTER(LocalSummary)]
+    lib.gpak_dev_local_krige.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, dp, C.c_double, C.c_int,
+                                         C.c_double, C.c_double, vp, C.c_int, C.c_int, vp, vp, vp]
     _lib = lib
     return lib

@@ -1,0 +1,207 @@
+// local_search.cpp -- gpak_local_neighbours: see local_search.h.  No HIP in this file.
+#include "local_search.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <thread>
+#include <utility>
+#include <vector>
+
+namespace {
+
+// t = x G, the arithmetic local_search.h states (a test restates it in NumPy and expects the same bytes)
+inline void transform_point(const double *X, long n, long i, int d, const double *G, double *t) {
+  if (!G) {
+    for (int j = 0; j < d; j++) t[j] = X[i + (size_t)j * n];
+    return;
+  }
+  for (int j = 0; j < d; j++) {
+    double s = X[i] * G[(size_t)d * j];
+    for (int r = 1; r < d; r++) s = s + X[i + (size_t)r * n] * G[r + (size_t)d * j];
+    t[j] = s;
+  }
+}
+
+struct Grid {
+  int d = 3;
+  double lo[3] = {0, 0, 0}, h = 1.0, scale = 0.0;
+  int n[3] = {1, 1, 1};
+  std::vector<long> start;     // n0 n1 n2 + 1
+  std::vector<double> pts;     // the transformed samples in cell order, d per sample
+  std::vector<int> ids;        // their indices: ascending inside a cell
+  int cell_of(const double *t, int i) const {
+    const double f = std::floor((t[i] - lo[i]) / h);
+    return f <= 0.0 ? 0 : (f >= (double)(n[i] - 1) ? n[i] - 1 : (int)f);
+  }
+  size_t cell_index(int a0, int a1, int a2) const { return ((size_t)a0 * n[1] + a1) * n[2] + a2; }
+};
+
+bool build_grid(const double *Xs, long Ns, int d, const double *G, Grid &g) {
+  g.d = d;
+  std::vector<double> T((size_t)Ns * d);
+  double hi[3] = {0, 0, 0};
+  for (long i = 0; i < Ns; i++) {
+    double *t = &T[(size_t)i * d];
+    transform_point(Xs, Ns, i, d, G, t);
+    for (int j = 0; j < d; j++)
+      if (!std::isfinite(t[j])) return false;
+    for (int j = 0; j < 3; j++) {
+      if (i == 0 || t[j] < g.lo[j]) g.lo[j] = t[j];
+      if (i == 0 || t[j] > hi[j]) hi[j] = t[j];
+    }
+  }
+  double ext[3], vol = 1.0;
+  int m = 0;
+  for (int j = 0; j < 3; j++) {
+    ext[j] = hi[j] - g.lo[j];
+    if (!std::isfinite(ext[j])) return false;
+    if (ext[j] > 0.0) { vol *= ext[j]; m++; }
+    g.scale = std::max(g.scale, std::max(std::fabs(g.lo[j]), std::fabs(hi[j])));
+  }
+  // about four samples per cell over the dimensions that have an extent
+  const double cells = std::max(1.0, (double)Ns / 4.0);
+  g.h = m ? std::pow(vol / cells, 1.0 / m) : 1.0;
+  if (!(g.h > 0.0) || !std::isfinite(g.h)) g.h = 1.0;
+  // the cells grow until no dimension has more than 4096 of them and the grid no more than about 8 per sample.  No count is
+  // ever capped: a sample's cell is floor((t - lo) / h) in every dimension, which the ring bound of search_one relies on
+  for (;;) {
+    double total = 1.0, most = 1.0;
+    for (int j = 0; j < 3; j++) {
+      const double c = ext[j] > 0.0 ? std::floor(ext[j] / g.h) + 1.0 : 1.0;
+      most = std::max(most, c);
+      total *= c;
+      g.n[j] = c <= 4096.0 ? (int)c : 4096;
+    }
+    if (most <= 4096.0 && total <= 8.0 * (double)Ns + 64.0) break;
+    g.h *= 1.26;
+  }
+  const size_t nc = (size_t)g.n[0] * g.n[1] * g.n[2];
+  g.start.assign(nc + 1, 0);
+  std::vector<size_t> cell((size_t)Ns);
+  for (long i = 0; i < Ns; i++) {
+    const double *t = &T[(size_t)i * d];
+    const size_t c = g.cell_index(g.cell_of(t, 0), g.cell_of(t, 1), g.cell_of(t, 2));
+    cell[i] = c;
+    g.start[c + 1]++;
+  }
+  for (size_t c = 0; c < nc; c++) g.start[c + 1] += g.start[c];
+  std::vector<long> at(g.start.begin(), g.start.end() - 1);
+  g.pts.resize((size_t)Ns * d);
+  g.ids.resize((size_t)Ns);
+  for (long i = 0; i < Ns; i++) {   // ascending i: a cell's samples stay in index order
+    const long p = at[cell[i]]++;
+    g.ids[p] = (int)i;
+    for (int j = 0; j < d; j++) g.pts[(size_t)p * d + j] = T[(size_t)i * d + j];
+  }
+  return true;
+}
+
+typedef std::pair<double, int> Cand;   // (dist2, index): the order of the lists
+
+// the list of one centre; false: a transformed coordinate of the centre is not finite
+bool search_one(const Grid &g, const double *tc, int k, double radius, int *out, int *count) {
+  const int d = g.d;
+  const double r2max = radius * radius;
+  int ic[3], r0 = 0, r_end = 0;
+  double cmax = 0.0;
+  for (int j = 0; j < d; j++) {
+    if (!std::isfinite(tc[j])) return false;
+    cmax = std::max(cmax, std::fabs(tc[j]));
+  }
+  for (int j = 0; j < 3; j++) {
+    // a centre outside the grid is taken to the layer of cells just outside it: every sample is then at least as far from
+    // the centre as from that cell, so the ring bound below stays a lower bound, and the ring arithmetic stays small
+    const double f = std::floor((tc[j] - g.lo[j]) / g.h);
+    ic[j] = f < -1.0 ? -1 : (f > (double)g.n[j] ? g.n[j] : (int)f);
+    r0 = std::max(r0, std::max(-ic[j], ic[j] - (g.n[j] - 1)));
+    r_end = std::max(r_end, std::max(ic[j], g.n[j] - 1 - ic[j]));
+  }
+  // rounding in the cell assignment and in the differences: far below a cell, far above an ulp of any coordinate
+  const double slack = 1e-10 * (g.scale + cmax + g.h);
+  Cand heap[GPAK_LOCAL_SEARCH_MAX];
+  int nh = 0;
+  for (int r = r0; r <= r_end; r++) {
+    if (r > 0) {   // every sample not yet seen is at least (r - 1) h away
+      const double lb = (double)(r - 1) * g.h - slack;
+      if (lb > 0.0 && ((nh == k && heap[0].first < lb * lb) || (radius > 0.0 && lb > radius))) break;
+    }
+    const int a0lo = std::max(0, ic[0] - r), a0hi = std::min(g.n[0] - 1, ic[0] + r);
+    const int a1lo = std::max(0, ic[1] - r), a1hi = std::min(g.n[1] - 1, ic[1] + r);
+    for (int a0 = a0lo; a0 <= a0hi; a0++)
+      for (int a1 = a1lo; a1 <= a1hi; a1++) {
+        const bool shell = std::abs(a0 - ic[0]) == r || std::abs(a1 - ic[1]) == r;
+        int a2lo = std::max(0, ic[2] - r), a2hi = std::min(g.n[2] - 1, ic[2] + r), step = 1;
+        if (!shell) {   // only the two faces ic2 - r and ic2 + r
+          a2lo = ic[2] - r; a2hi = ic[2] + r; step = r > 0 ? 2 * r : 1;
+        }
+        for (long a2 = a2lo; a2 <= a2hi; a2 += step) {
+          if (a2 < 0 || a2 >= g.n[2]) continue;
+          const size_t c = g.cell_index(a0, a1, (int)a2);
+          for (long p = g.start[c]; p < g.start[c + 1]; p++) {
+            const double *t = &g.pts[(size_t)p * d];
+            double e = t[0] - tc[0];
+            double s = e * e;
+            for (int j = 1; j < d; j++) { e = t[j] - tc[j]; s = s + e * e; }
+            if (radius > 0.0 && !(s <= r2max)) continue;
+            const Cand cand(s, g.ids[p]);
+            if (nh < k) {
+              heap[nh++] = cand;
+              std::push_heap(heap, heap + nh);
+            } else if (cand < heap[0]) {
+              std::pop_heap(heap, heap + nh);
+              heap[nh - 1] = cand;
+              std::push_heap(heap, heap + nh);
+            }
+          }
+        }
+      }
+  }
+  std::sort_heap(heap, heap + nh);
+  for (int q = 0; q < k; q++) out[q] = q < nh ? heap[q].second : -1;
+  *count = nh;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int gpak_local_neighbours(const double *Xs, long Ns, int d, const double *Xc, long M, const double *G, int k,
+                                     double radius, int threads, int *nbr, int *used) {
+  if (!Xs || !Xc || !nbr || (d != 3 && d != 4) || k < 1 || k > GPAK_LOCAL_SEARCH_MAX || Ns < 1 || M < 1 || Ns > INT_MAX ||
+      std::isnan(radius))
+    return 2;
+  for (size_t i = 0; i < (size_t)Ns * d; i++)
+    if (!std::isfinite(Xs[i])) return 2;
+  for (size_t i = 0; i < (size_t)M * d; i++)
+    if (!std::isfinite(Xc[i])) return 2;
+  for (int i = 0; G && i < d * d; i++)
+    if (!std::isfinite(G[i])) return 2;
+  Grid g;
+  if (!build_grid(Xs, Ns, d, G, g)) return 2;
+  int nt = threads;
+  if (nt <= 0) nt = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  nt = (int)std::min<long>(std::min(nt, 256), M);   // a caller's number has a ceiling too
+  std::vector<int> bad((size_t)nt, 0);
+  // results go to a buffer of the call's own, so that a refusal writes nothing
+  std::vector<int> lists((size_t)k * M), counts((size_t)M);
+  auto slice = [&](int w) {
+    const long b0 = M * w / nt, b1 = M * (w + 1) / nt;
+    double tc[4];
+    for (long b = b0; b < b1; b++) {
+      transform_point(Xc, M, b, d, G, tc);
+      if (!search_one(g, tc, k, radius, &lists[(size_t)k * b], &counts[b])) { bad[w] = 1; return; }
+    }
+  };
+  if (nt == 1) {
+    slice(0);
+  } else {
+    std::vector<std::thread> pool;
+    for (int w = 0; w < nt; w++) pool.emplace_back(slice, w);
+    for (auto &th : pool) th.join();
+  }
+  for (int w = 0; w < nt; w++)
+    if (bad[w]) return 2;
+  std::copy(lists.begin(), lists.end(), nbr);
+  if (used) std::copy(counts.begin(), counts.end(), used);
+  return 0;
+}

@@ -25,6 +25,7 @@ BLOCK_LATENT = 1
 JOINT_LATENT, JOINT_PRIOR = 1, 2
 NO_BATCH = 1      # GPAK_CV_FOLDS_NO_BATCH
 COND_UNFUSED = 1
+LOCAL_LATENT, LOCAL_MAX = 1, 128
 
 _dp = C.POINTER(C.c_double)
 
@@ -75,6 +76,32 @@ def group_labels(labels, n=None):
         raise ValueError(f"labels must hold one entry per training sample: {a.size} for {int(n)}")
     values, group = np.unique(a, return_inverse=True)
     return np.ascontiguousarray(group.reshape(-1), dtype=np.int32), values
+
+
+def local_neighbours(Xs, Xc, k, G=None, radius=0.0, threads=0):
+    """The k nearest samples of every centre (gpak_local_neighbours; host code, no context): returns (nbr, used), nbr
+    M x k int32 -- row b the sample indices of centre b by ascending distance |(x - c) G|, then ascending index, -1 in the
+    unused slots -- and used (M) the counts.  G: d x d, or the 4 x 4 of Gpak.local_metric (its leading d x d part is
+    taken), or None for the identity; radius > 0 keeps only samples within it; threads <= 0: min(cores, 16)."""
+    Xs, Xc = _f(Xs), _f(Xc)
+    if Xs.ndim != 2 or Xc.ndim != 2 or Xs.shape[1] != Xc.shape[1]:
+        raise GpakError(EINVAL, "Xs and Xc must be matrices with as many columns")
+    d, M, k = Xs.shape[1], Xc.shape[0], int(k)
+    if G is not None:
+        G = np.asarray(G, dtype=np.float64)
+        if G.shape == (4, 4) and d == 3:
+            G = G[:3, :3]
+        if G.shape != (d, d):
+            raise GpakError(EINVAL, "G must be d x d (or the 4 x 4 of local_metric)")
+        G = np.asfortranarray(G)
+    nbr = np.full((max(M, 0), max(k, 0)), -1, dtype=np.int32)
+    used = np.zeros(max(M, 0), dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = _lib.load().gpak_local_neighbours(_p(Xs), Xs.shape[0], d, _p(Xc), M, _p(G), k, float(radius), int(threads),
+                                           nbr.ctypes.data_as(ip), used.ctypes.data_as(ip))
+    if rc != OK:
+        raise GpakError(rc, "gpak_local_neighbours refused its arguments (shapes, k outside 1..128, a coordinate that is not finite)")
+    return nbr, used
 
 
 class Gpak:
@@ -309,6 +336,30 @@ class Gpak:
         self._check(self._lib.gpak_predict_block(self._h, _p(Xd), M, nd, Xd.shape[1], _p(mean), _p(var),
                                                  BLOCK_LATENT if latent else 0), allow=(ENOTPD,))
         return mean, var
+
+    def local_metric(self, term=0):
+        """G (4 x 4) with |(x - x') G|^2 = D2 of stationary term `term` of the composition in force (gpak_local_metric)."""
+        G = np.zeros((4, 4), order="F")
+        self._check(self._lib.gpak_local_metric(self._h, int(term), _p(G)))
+        return G
+
+    def predict_local(self, Xs, ys, Xd, nd, nbr, want_var=True, latent=False):
+        """Moving-neighbourhood kriging (gpak_predict_local): node b (rows b * nd .. b * nd + nd of Xd) from the samples
+        (Xs, ys) that row b of nbr (M x k, -1 padded: local_neighbours) names.  Returns (mean, var, summary), summary a
+        dict of gpak_local_summary; var includes sn2 / nd unless latent.  The context needs parameters only."""
+        Xs = _f(Xs)
+        ys = np.ascontiguousarray(ys, dtype=np.float64).ravel()
+        Xd, M, nd = self._blocks(Xd, nd)
+        nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+        if Xs.ndim != 2 or ys.size != Xs.shape[0] or nbr.ndim != 2 or nbr.shape[0] != M or Xd.shape[1] != Xs.shape[1]:
+            raise GpakError(EINVAL, "Xs is Ns x d with Ns values ys, Xd has as many columns, nbr one row per node")
+        mean = np.zeros(M)
+        var = np.zeros(M) if want_var else None
+        s = _lib.LocalSummary()
+        self._check(self._lib.gpak_predict_local(self._h, _p(Xs), _p(ys), Xs.shape[0], Xs.shape[1], _p(Xd), M, nd,
+                                                 nbr.ctypes.data_as(C.POINTER(C.c_int)), nbr.shape[1], _p(mean), _p(var),
+                                                 LOCAL_LATENT if latent else 0, C.byref(s)))
+        return mean, var, {f: getattr(s, f) for f, _ in s._fields_}
 
     def predict_joint(self, Xd, nd, want_cov=True, latent=False, prior=False):
         """Mean (M) and full covariance (M x M, exactly symmetric) of the block averages (gpak_predict_joint); the

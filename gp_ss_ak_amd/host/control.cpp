@@ -68,6 +68,22 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       design_pick = (int)v;
     }
     else if (isArg("--weights", "--weights")) { incArg(); design_weights_file = getArg(); }
+    else if (isArg("--neighbours", "--neighbors")) {
+      incArg();
+      char *end = nullptr;
+      const std::string tok = getArgNo() < argc ? getArg() : std::string();
+      const long v = strtol(tok.c_str(), &end, 10);
+      local_neighbours = (tok.empty() || *end != '\0') ? -1 : v;   // the `local` verb refuses what is not 1..128
+      local_neighbours_set = true;
+    }
+    else if (isArg("--radius", "--radius")) {
+      incArg();
+      char *end = nullptr;
+      const std::string tok = getArgNo() < argc ? getArg() : std::string();
+      local_radius = strtod(tok.c_str(), &end);
+      if (tok.empty() || *end != '\0') local_radius = -1.0;         // the `local` verb refuses what is not positive
+      local_radius_set = true;
+    }
     else break;
     incArg();
   }

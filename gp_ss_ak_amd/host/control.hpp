@@ -70,6 +70,10 @@ class Control {
   // the `design` verb: --pick k (a greedy plan of k holes), --weights file (one non-negative number per target)
   int design_pick = 0;
   std::string design_weights_file;
+  // the `local` verb: --neighbours k (1..128 samples per node), --radius r (in ranges of the model's first term)
+  long local_neighbours = 0;
+  double local_radius = 0.0;
+  bool local_neighbours_set = false, local_radius_set = false;
   std::string mode = "gp";
   mat params, MinData, MaxData, MeanData, StData;
   double MaxTotalin = 0, MinTotalin = 0, MaxTotalo = 0, MinTotalo = 0;

@@ -7,6 +7,8 @@
 //   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
 //   gp_ss_ak [-v n] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] [--nugget v] --realisations S (--seed n | --xi file)
 //            sim [--method joint|path [--features F]] nodes.txt model train.txt [out_file]
+//   gp_ss_ak [-v n] --neighbours k [--radius r] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent]
+//            local nodes.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
 // (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only),
@@ -57,6 +59,7 @@
 #include <fstream>
 #include <iostream>
 #include <numeric>
+#include <chrono>
 #include <sstream>
 #include <string>
 
@@ -105,6 +108,7 @@ class GP_Cntrl : public Control {
   void block();
   void sim();
   void design();
+  void local();
   void Help() const;
 };
 
@@ -114,6 +118,7 @@ void GP_Cntrl::Help() const {
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
             << "design :\n \t To rank candidate drill holes by the estimation variance they would remove from targets ([--block-size dx,dy,dz --block-disc nx,ny,nz] [--pick k] [--weights file] design --candidates file --holes file targets model train).\n"
+            << "local :\n \t To estimate nodes or blocks from the k nearest of any number of samples (--neighbours k [--radius r] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes model samples).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
             << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]; sim --method path [--features F] with --seed n: any number of nodes, the prior from F random frequencies per term).\n";
 }
@@ -624,6 +629,90 @@ void GP_Cntrl::block() {
   exit(0);
 }
 
+// local (not a reference verb): moving-neighbourhood kriging (gpak_predict_local; one GPU only) -- every node from its k
+// nearest samples, so train.txt may hold any number of them (train on a subsample, estimate from all the assays):
+//   gp_ss_ak --neighbours k [--radius r] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes.txt model train.txt [out]
+// nodes.txt is read as block reads its centres (without the two block options the nodes are points); train.txt is
+// standardised with the model's _Statistics.txt.  The neighbours are searched from the node centres in the metric of the
+// model's first stationary term (gpak_local_metric), in which --radius is measured: 1 is one range.  Everything is checked
+// before a context exists.  Written to <model>_local.txt in input order.
+void GP_Cntrl::local() {
+  incArg();
+  setMode("local");
+  if (gpus > 1)
+    ErrorTermination("gpak_predict_local is built for the single-GPU context (gpak_create) only: drop --gpus");
+  bool yscale = true;
+  while (isFlgs()) {
+    if (isArgFlg()) {
+      if (isArg("-?", "--?") || isArg("-h", "--help")) { Help(); exit(0); }
+      else if (isArg("-np", "--no-prompt")) { no_prompt = true; }
+      else UnkFlg();
+      incArg();
+    } else setFlgs(false);
+  }
+  if (!local_neighbours_set || local_neighbours < 1 || local_neighbours > GPAK_LOCAL_MAX)
+    ErrorTermination("local needs --neighbours k, the samples per node, between 1 and 128");
+  if (local_radius_set && !(local_radius > 0.0)) ErrorTermination("--radius takes a positive distance (1 is one range of the model's first term)");
+  if (block_size_set != block_disc_set)
+    ErrorTermination("local takes --block-size and --block-disc together (neither: the nodes are points)");
+  if (getArgNo() + 2 >= argc)
+    ErrorTermination("There are not enough input parameters: local needs the nodes, the model and the samples.");
+  std::string ndFile = getArg(), modelName = argv[getArgNo() + 1], trFile = argv[getArgNo() + 2];
+  std::string LocalOut = modelName + "_local.txt";
+  if (getArgNo() + 3 < argc) LocalOut = argv[getArgNo() + 3];
+  const int k = (int)local_neighbours;
+  int ds[2];
+  readDataSize(ndFile, ds);
+  mat C, y;
+  readDataFile(C, y, ds, ndFile);
+  if (C.n_cols != 3 && C.n_cols != 4) ErrorTermination("Nodes need 3 or 4 input columns.");
+  readDataSize(trFile, ds);
+  mat Xtr, ytr;
+  readDataFile(Xtr, ytr, ds, trFile);
+  if (Xtr.n_cols != C.n_cols) ErrorTermination("The samples need the nodes' input columns.");
+  // as block: discretise in the file's units, then standardise every point like a test point
+  const double point_size[3] = {0, 0, 0};
+  const int point_disc[3] = {1, 1, 1};
+  std::vector<double> pts;
+  const int nd = gpak_block_points(C.memptr(), C.n_rows, C.n_cols, block_size_set ? block_size : point_size,
+                                   block_disc_set ? block_disc : point_disc, pts);
+  mat Xd(C.n_rows * nd, C.n_cols), ydummy(C.n_rows * nd, 1);
+  for (size_t i = 0; i < pts.size(); i++) Xd[i] = pts[i];
+  prepareData(C, y, yscale, modelName);            // the model's _Statistics.txt, as `test`
+  prepareData(Xd, ydummy, false, modelName);
+  prepareData(Xtr, ytr, yscale, modelName);
+  GP_utils *GPModel = readGpFromFile(modelName, getVerbose());  // the kernel only: the context gets no training set
+  if (C.n_cols != GPModel->getInpDim()) ErrorTermination("Incorrect dimension of input data.");
+  double G[16];
+  GPModel->LocalMetric(G);
+  std::vector<int> nbr, used;
+  const auto t0 = std::chrono::steady_clock::now();
+  GP_utils::LocalNeighbours(Xtr, C, G, k, local_radius_set ? local_radius : 0.0, nbr, used);
+  const double search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  mat LocalVals(y.n_rows, 1), LocalVals_Var(y.n_rows, 1);
+  gpak_local_summary s;
+  GPModel->LocalMeanVar(LocalVals, LocalVals_Var, Xtr, ytr, Xd, nd, nbr, k, block_latent, s);
+  postData(C, LocalVals, yscale, modelName);
+  postData_var(LocalVals_Var, yscale, modelName);
+  postData(y, yscale, modelName);
+  if (getVerbose() > 0)
+    std::cout << "Nodes: " << s.nodes << " of " << nd << " points from " << Xtr.n_rows << " samples, " << k << " neighbours at most"
+              << (block_latent ? ", latent variance" : "") << "; without a neighbour " << s.empty << ", not positive definite "
+              << s.notpd << "; search " << search_ms << " ms, device " << (s.upload_ms + s.krige_ms) << " ms\n";
+  // rows in input order; the fourth column is what postData_var returns, as StdYblock of _block.txt
+  std::ofstream out(LocalOut.c_str());
+  out << "# NodeNo, Y, Ylocal, StdYlocal, Neighbours, Inputs" << "\n";
+  for (size_t i = 0; i < y.n_elem; i++) {
+    out << (i + 1) << "\t" << y[i] << "\t" << LocalVals[i] << "\t" << LocalVals_Var[i] << "\t" << used[i] << "\t";
+    for (size_t j = 0; j < C.n_cols; j++) out << C(i, j) << "\t";
+    out << "\n";
+  }
+  out.close();
+  writeTiming(*GPModel);
+  delete GPModel;
+  exit(0);
+}
+
 void GP_Cntrl::sim() {
   incArg();
   setMode("sim");
@@ -903,6 +992,7 @@ int main(int argc, char **argv) {
   else if (verb == "block") ctl.block();
   else if (verb == "sim") ctl.sim();
   else if (verb == "design") ctl.design();
+  else if (verb == "local") ctl.local();
   else if (verb == "-h" || verb == "--help" || verb == "-?") { ctl.Help(); return 0; }
   else ctl.ErrorTermination("Invalid command provided.");
   return 0;

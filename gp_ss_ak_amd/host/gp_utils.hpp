@@ -14,6 +14,7 @@
 #include "../../include/gpak_cv_folds_grad.h"
 #include "../../include/gpak_condition.h"
 #include "../../include/gpak_design.h"
+#include "../../include/gpak_local.h"
 #include "kernels.hpp"
 
 class ModelInfo {
@@ -150,6 +151,14 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   // realisation on the host.  Everything NaN on Chol_fail (then false)
   bool PathSample(mat &Z, mat &mean, const mat &Xd, int nd, unsigned long long seed, int features, bool latent,
                   gpak_condition_summary &summary) const;
+  // moving-neighbourhood kriging (gpak_predict_local) of the blocks of Xd (as BlockMeanVar) from the samples (Xs, ys) that
+  // nbr (k per node, -1 padded: LocalNeighbours) names; the context needs the kernel only, no training set.  LocalMetric:
+  // G (4 x 4) of stationary term 0 (gpak_local_metric); LocalNeighbours: the k nearest samples of every centre in it
+  void LocalMetric(double G[16]) const;
+  static void LocalNeighbours(const mat &Xs, const mat &Xc, const double G[16], int k, double radius, std::vector<int> &nbr,
+                              std::vector<int> &used);
+  void LocalMeanVar(mat &mean, mat &var, const mat &Xs, const mat &ys, const mat &Xd, int nd, const std::vector<int> &nbr, int k,
+                    bool latent, gpak_local_summary &summary) const;
   // infill drilling design (gpak_design): the gain of each of the H candidate holes (hole[i] in [0, H) for candidate point i
   // of Xc) on the target blocks Xd (nd points each; wt: one weight per block, or null) and a greedy plan of k of them;
   // false when the A_h of some hole is not positive definite; everything NaN on Chol_fail
