@@ -29,6 +29,11 @@ CV_GROUPS_GRAD_SYMBOLS = ["gpak_cv_groups_grad"]
 CV_FOLDS_GRAD_SYMBOLS = ["gpak_cv_folds_grad"]
 # every symbol include/gpak_dev_cv_mix.h declares (the same test)
 DEV_CV_MIX_SYMBOLS = ["gpak_dev_mix_cols"]
+# every symbol include/gpak_dev_cv_kernels.h declares (tests/test_cv_kernels.py checks the header and this list agree)
+DEV_CV_KERNELS_SYMBOLS = ["gpak_dev_cvg_gram", "gpak_dev_cvg_solve", "gpak_dev_cvg_mix", "gpak_dev_cvf_pad", "gpak_dev_cvf_w",
+                          "gpak_dev_cvf_ev", "gpak_dev_cvf_sums", "gpak_dev_cvf_beta", "gpak_dev_cvf_q", "gpak_dev_cvf_gather",
+                          "gpak_dev_cvf_unmix", "gpak_dev_loo_rowsumsq", "gpak_dev_loo_finish", "gpak_dev_loo_vectors",
+                          "gpak_dev_loo_mirror_scale", "gpak_dev_loo_rank2", "gpak_dev_lgo_colscale"]
 # every symbol include/gpak_design.h / include/gpak_dev_design.h declares (tests/test_design.py checks the headers and these lists agree)
 DESIGN_SYMBOLS = ["gpak_design"]
 DEV_DESIGN_SYMBOLS = ["gpak_dev_design_score"]
@@ -92,13 +97,13 @@ def load():
     lib = C.CDLL(LIB_PATH)
     missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS
                + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DESIGN_SYMBOLS + DEV_DESIGN_SYMBOLS + CONDITION_SYMBOLS + DEV_CONDITION_SYMBOLS
-               + DEV_F32_SYMBOLS + LOCAL_SYMBOLS + DEV_LOCAL_SYMBOLS
+               + DEV_F32_SYMBOLS + LOCAL_SYMBOLS + DEV_LOCAL_SYMBOLS + DEV_CV_KERNELS_SYMBOLS
                if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
                            "gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_cv_folds_grad.h / "
                            "gpak_dev_cv_mix.h / gpak_design.h / gpak_dev_design.h / gpak_condition.h / gpak_dev_condition.h / "
-                           f"gpak_dev_f32.h / gpak_local.h / gpak_dev_local.h: {missing}")
+                           f"gpak_dev_f32.h / gpak_local.h / gpak_dev_local.h / gpak_dev_cv_kernels.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -172,5 +177,24 @@ def load():
                                        C.POINTER(LocalSummary)]
     lib.gpak_dev_local_krige.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, dp, C.c_double, C.c_int,
                                          C.c_double, C.c_double, vp, C.c_int, C.c_int, vp, vp, vp]
+    # include/gpak_dev_cv_kernels.h: the stream first, every pointer a device pointer
+    i, l, d = C.c_int, C.c_long, C.c_double
+    lib.gpak_dev_cvg_gram.argtypes = [vp, vp, l, i, vp, vp, i, vp, vp]
+    lib.gpak_dev_cvg_solve.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp, d, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gpak_dev_cvg_mix.argtypes = [vp, vp, l, i, vp, vp, i, vp]
+    lib.gpak_dev_cvf_pad.argtypes = [vp, vp, l, i]
+    lib.gpak_dev_cvf_w.argtypes = [vp, vp, l, i, vp, vp, vp]
+    lib.gpak_dev_cvf_ev.argtypes = [vp, vp, l, i, vp, vp, vp, d, vp, vp, vp, vp, vp]
+    lib.gpak_dev_cvf_sums.argtypes = [vp, vp, l, i, vp, vp, vp, vp, d, vp, vp, vp]
+    lib.gpak_dev_cvf_beta.argtypes = [vp, vp, i, d, vp]
+    lib.gpak_dev_cvf_q.argtypes = [vp, i, vp, l, i, vp, vp, vp, vp, vp, l, vp]
+    lib.gpak_dev_cvf_gather.argtypes = [vp, vp, l, i, vp, i, vp, l]
+    lib.gpak_dev_cvf_unmix.argtypes = [vp, vp, l, i, vp, i, vp, l]
+    lib.gpak_dev_loo_rowsumsq.argtypes = [vp, vp, l, i, i, i, vp, vp]
+    lib.gpak_dev_loo_finish.argtypes = [vp, i, vp, vp, vp, d, vp, vp, vp, vp]
+    lib.gpak_dev_loo_vectors.argtypes = [vp, i, i, vp, vp, d, vp, vp]
+    lib.gpak_dev_loo_mirror_scale.argtypes = [vp, i, i, vp, l, vp, vp, l]
+    lib.gpak_dev_loo_rank2.argtypes = [vp, i, vp, l, vp, vp]
+    lib.gpak_dev_lgo_colscale.argtypes = [vp, i, i, d, vp]
     _lib = lib
     return lib

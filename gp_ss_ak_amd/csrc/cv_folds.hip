@@ -33,6 +33,7 @@
 
 #include "../../include/gpak_cv_folds.h"
 #include "../../include/gpak_dev_cv.h"
+#include "../../include/gpak_dev_cv_kernels.h"
 #include "../../include/gpak_dev_cv_mix.h"
 #include "gpak_internal.h"
 
@@ -102,6 +103,13 @@ __global__ __launch_bounds__(256) void gpak_cvf_pad_f64(double *__restrict__ S, 
     if (i >= j) S[(size_t)i + (size_t)j * lds] = i == j ? 1.0 : 0.0;
   }
 }
+// the launches of the stage kernels on explicit arguments: what gpak_cvf_run_group / the column mix and the entries of
+// gpak_dev_cv_kernels.h both run
+static void cvf_launch_pad(hipStream_t st, double *S, long lds, int m) {
+  const int mp = cvf_pad128(m);
+  if (mp == m) return;   // nothing to pad
+  hipLaunchKernelGGL(gpak_cvf_pad_f64, dim3(1), dim3(256), 0, st, S, lds, m, mp);
+}
 
 // w_j = sum_{i <= j} T_ij alpha_I,i: workgroup j.  Thread t adds the rows t, t + 256, ... in ascending order, then the tree.
 __global__ __launch_bounds__(256) void gpak_cvf_w_f64(const double *__restrict__ T, long ldt, const int *__restrict__ rows,
@@ -118,6 +126,9 @@ __global__ __launch_bounds__(256) void gpak_cvf_w_f64(const double *__restrict__
     __syncthreads();
   }
   if (t == 0) wv[j] = red[0];
+}
+static void cvf_launch_w(hipStream_t st, const double *T, long ldt, int m, const int *rows, const double *alpha, double *wv) {
+  hipLaunchKernelGGL(gpak_cvf_w_f64, dim3(m), dim3(256), 0, st, T, ldt, rows, alpha, wv);
 }
 
 // e_i = sn2 sum_{j >= i} T_ij w_j and var_i = sn2 sum_{j >= i} T_ij^2 in one pass over the upper triangle of T, then
@@ -157,6 +168,10 @@ __global__ __launch_bounds__(256) void gpak_cvf_ev_f64(const double *__restrict_
     var[n] = v;
   }
 }
+static void cvf_launch_ev(hipStream_t st, const double *T, long ldt, int m, const double *wv, const int *rows, const double *y,
+                          double sn2, const int *info, double *ev, double *vv, double *mean, double *var) {
+  hipLaunchKernelGGL(gpak_cvf_ev_f64, dim3((m + 63) / 64), dim3(256), 0, st, T, ldt, m, wv, rows, y, sn2, info, ev, vv, mean, var);
+}
 
 // one workgroup: gsum[0..2] = sum e_i^2, sum e_i^2 / var_i, alpha_I . e_I and logp from those and sum log R_ii.  Thread t
 // adds i = t, t + 256, ... in ascending order, then the tree.
@@ -192,6 +207,10 @@ __global__ __launch_bounds__(256) void gpak_cvf_sums_f64(const double *__restric
     logp[0] = bad ? nan : -0.5 * red[2][0] - 0.5 * (m * log(sn2) - 2.0 * red[3][0]) - 0.5 * m * 1.8378770664093454836;   // log 2 pi
   }
 }
+static void cvf_launch_sums(hipStream_t st, const double *R, long ldr, int m, const double *ev, const double *vv, const int *rows,
+                            const double *alpha, double sn2, const int *info, double *logp, double *gsum) {
+  hipLaunchKernelGGL(gpak_cvf_sums_f64, dim3(1), dim3(256), 0, st, R, ldr, m, ev, vv, rows, alpha, sn2, info, logp, gsum);
+}
 
 // the substitution, the batched small groups, and pack / product / factor + inverse + finish summed over the other groups
 // of the context's last gpak_cv_folds, in ms.  Not part of the C-ABI (no header declares it): tools/time_cv_folds.py
@@ -226,6 +245,9 @@ __global__ __launch_bounds__(256) void gpak_cvf_beta_f64(const double *__restric
     sc[1] = sn2 / (1.0 + sqrt(fma(sn2, red[0], 1.0))) / rs;
   }
 }
+static void cvf_launch_beta(hipStream_t st, const double *wv, int m, double sn2, double *sc) {
+  hipLaunchKernelGGL(gpak_cvf_beta_f64, dim3(1), dim3(256), 0, st, wv, m, sn2, sc);
+}
 
 // Q[i, j] = sc[0] T_ij + sc[1] e_i w_j for i, j < m (T_ij = 0 for j < i) and 0 on the rest of m_p x m_p, column-major with
 // leading dimension ldq -- or, TRANSPOSED, Q^T so stored: the B operand of the GEMM that mixes a wide group; e_I scattered
@@ -247,6 +269,13 @@ __global__ __launch_bounds__(256) void gpak_cvf_q_f64(const double *__restrict__
     Q[TRANSPOSED ? (size_t)j + (size_t)i * ldq : (size_t)i + (size_t)j * ldq] = q;
   }
   if (blockIdx.y == 0 && jh == 0 && live) E[rows[i]] = ev[i];
+}
+static void cvf_launch_q(hipStream_t st, bool transposed, const double *T, long ldt, int m, const double *wv, const double *ev,
+                         const double *sc, const int *rows, double *Q, long ldq, double *E) {
+  const int mp = cvf_pad128(m);
+  const dim3 grid(mp / CVF_TB, mp / 16);
+  if (transposed) hipLaunchKernelGGL(gpak_cvf_q_f64<true>, grid, dim3(256), 0, st, T, ldt, m, wv, ev, sc, rows, Q, ldq, E);
+  else hipLaunchKernelGGL(gpak_cvf_q_f64<false>, grid, dim3(256), 0, st, T, ldt, m, wv, ev, sc, rows, Q, ldq, E);
 }
 
 // Z[:, c] = sum_{k < m} H[:, cols[k]] Q[k, c] for c < m: the mix for a column set of any width, out of place (block column J
@@ -356,13 +385,16 @@ __global__ __launch_bounds__(256) void gpak_cvf_unmix_f64(double *__restrict__ H
   const double *z = Z + (size_t)c * ldz;
   for (int r = blockIdx.y * 512 + threadIdx.x; r < min(Np, (int)(blockIdx.y + 1) * 512); r += 256) h[r] = z[r];
 }
+static void cvf_launch_unmix(hipStream_t st, double *H, long ld, int Np, const int *cols, int m, const double *Z, long ldz) {
+  hipLaunchKernelGGL(gpak_cvf_unmix_f64, dim3(m, (Np + 511) / 512), dim3(256), 0, st, H, ld, Np, cols, Z, ldz);
+}
 
 // the product, then -- stream-ordered behind every workgroup of it -- the write-back
 void gpak_launch_mix_cols(hipStream_t st, double *H, long ld, int Np, const int *cols, int m, const double *Q, long ldq,
                           double *Z, long ldz) {
   hipLaunchKernelGGL(gpak_cvf_mix_f64, dim3((Np + CVF_TB - 1) / CVF_TB, (m + CVF_TB - 1) / CVF_TB), dim3(256), 0, st, H, ld, Np,
                      cols, m, Q, ldq, Z, ldz);
-  hipLaunchKernelGGL(gpak_cvf_unmix_f64, dim3(m, (Np + 511) / 512), dim3(256), 0, st, H, ld, Np, cols, Z, ldz);
+  cvf_launch_unmix(st, H, ld, Np, cols, m, Z, ldz);
 }
 
 // The same mix from existing parts, for a group wide enough that the bulk GEMM's rate pays for two more passes over the
@@ -376,13 +408,16 @@ __global__ __launch_bounds__(256) void gpak_cvf_gather_f64(const double *__restr
   double *a = A + (size_t)c * lda;
   for (int r = blockIdx.y * 512 + threadIdx.x; r < min(Np, (int)(blockIdx.y + 1) * 512); r += 256) a[r] = h ? h[r] : 0.0;
 }
+static void cvf_launch_gather(hipStream_t st, const double *H, long ld, int Np, const int *cols, int m, double *A, long lda) {
+  hipLaunchKernelGGL(gpak_cvf_gather_f64, dim3(cvf_pad128(m), (Np + 511) / 512), dim3(256), 0, st, H, ld, Np, cols, m, A, lda);
+}
 
 static void cvf_mix_cols_gemm(hipStream_t st, double *H, long ld, int Np, const int *cols, int m, const double *Qt, long ldq,
                               double *A, double *Cw) {
   const int mp = cvf_pad128(m);
-  hipLaunchKernelGGL(gpak_cvf_gather_f64, dim3(mp, (Np + 511) / 512), dim3(256), 0, st, H, ld, Np, cols, m, A, (long)Np);
+  cvf_launch_gather(st, H, ld, Np, cols, m, A, (long)Np);
   gpak_launch_gemm_nt(st, Np / CVF_TB, mp / CVF_TB, mp, 1.0, A, (long)Np, Qt, ldq, 0.0, Cw, (long)Np, 0, 0, false, false);
-  hipLaunchKernelGGL(gpak_cvf_unmix_f64, dim3(m, (Np + 511) / 512), dim3(256), 0, st, H, ld, Np, cols, Cw, (long)Np);
+  cvf_launch_unmix(st, H, ld, Np, cols, m, Cw, (long)Np);
 }
 
 // which of the two a one-at-a-time group of m samples takes: measured, the fused kernel is ahead up
@@ -401,6 +436,61 @@ extern "C" int gpak_dev_mix_cols(void *stream, double *H, long ld, int Np, const
   if (!H || !cols || !Q || !Z || m < 1 || m > Np || ld < Np || ldq < m || ldz < Np) return GPAK_EINVAL;
   gpak_launch_mix_cols((hipStream_t)stream, H, ld, Np, cols, m, Q, ldq, Z, ldz);
   return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP;
+}
+
+// ---- include/gpak_dev_cv_kernels.h: the stage kernels of a one-at-a-time group alone on caller-owned device buffers ----
+static int cvf_status() { return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP; }
+
+extern "C" int gpak_dev_cvf_pad(void *stream, double *S, long lds, int m) {
+  if (!S || m < 1 || lds < cvf_pad128(m)) return GPAK_EINVAL;
+  cvf_launch_pad((hipStream_t)stream, S, lds, m);
+  return cvf_status();
+}
+
+extern "C" int gpak_dev_cvf_w(void *stream, const double *T, long ldt, int m, const int *rows, const double *alpha, double *wv) {
+  if (!T || !rows || !alpha || !wv || m < 1 || ldt < m) return GPAK_EINVAL;
+  cvf_launch_w((hipStream_t)stream, T, ldt, m, rows, alpha, wv);
+  return cvf_status();
+}
+
+extern "C" int gpak_dev_cvf_ev(void *stream, const double *T, long ldt, int m, const double *wv, const int *rows, const double *y,
+                               double sn2, const int *info, double *ev, double *vv, double *mean, double *var) {
+  if (!T || !wv || !rows || !y || !info || !ev || !vv || !mean || !var || m < 1 || ldt < m) return GPAK_EINVAL;
+  cvf_launch_ev((hipStream_t)stream, T, ldt, m, wv, rows, y, sn2, info, ev, vv, mean, var);
+  return cvf_status();
+}
+
+extern "C" int gpak_dev_cvf_sums(void *stream, const double *R, long ldr, int m, const double *ev, const double *vv,
+                                 const int *rows, const double *alpha, double sn2, const int *info, double *logp,
+                                 double *gsum) {
+  if (!R || !ev || !vv || !rows || !alpha || !info || !logp || !gsum || m < 1 || ldr < m) return GPAK_EINVAL;
+  cvf_launch_sums((hipStream_t)stream, R, ldr, m, ev, vv, rows, alpha, sn2, info, logp, gsum);
+  return cvf_status();
+}
+
+extern "C" int gpak_dev_cvf_beta(void *stream, const double *wv, int m, double sn2, double *sc) {
+  if (!wv || !sc || m < 1) return GPAK_EINVAL;
+  cvf_launch_beta((hipStream_t)stream, wv, m, sn2, sc);
+  return cvf_status();
+}
+
+extern "C" int gpak_dev_cvf_q(void *stream, int transposed, const double *T, long ldt, int m, const double *wv, const double *ev,
+                              const double *sc, const int *rows, double *Q, long ldq, double *E) {
+  if (!T || !wv || !ev || !sc || !rows || !Q || !E || m < 1 || ldt < m || ldq < cvf_pad128(m)) return GPAK_EINVAL;
+  cvf_launch_q((hipStream_t)stream, transposed != 0, T, ldt, m, wv, ev, sc, rows, Q, ldq, E);
+  return cvf_status();
+}
+
+extern "C" int gpak_dev_cvf_gather(void *stream, const double *H, long ld, int Np, const int *cols, int m, double *A, long lda) {
+  if (!H || !cols || !A || m < 1 || m > Np || ld < Np || lda < Np) return GPAK_EINVAL;
+  cvf_launch_gather((hipStream_t)stream, H, ld, Np, cols, m, A, lda);
+  return cvf_status();
+}
+
+extern "C" int gpak_dev_cvf_unmix(void *stream, double *H, long ld, int Np, const int *cols, int m, const double *Z, long ldz) {
+  if (!H || !cols || !Z || m < 1 || m > Np || ld < Np || ldz < Np) return GPAK_EINVAL;
+  cvf_launch_unmix((hipStream_t)stream, H, ld, Np, cols, m, Z, ldz);
+  return cvf_status();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -480,7 +570,7 @@ int gpak_cvf_run_group(gpak_ctx *ctx, const gpak_cvf_plan &pl, size_t k, const i
   GPAK_HIP(hipEventRecord(ctx->ev_cvf[3 * k], st));
   gpak_launch_gemm_nt(st, mt, mt, Np - k0, 1.0, P, ldp, P, ldp, 0.0, S, lds, 0, 0, true, false);
   GPAK_HIP(hipEventRecord(ctx->ev_cvf[3 * k + 1], st));
-  if (mp > m) hipLaunchKernelGGL(gpak_cvf_pad_f64, dim3(1), dim3(256), 0, st, S, lds, m, mp);
+  cvf_launch_pad(st, S, lds, m);
   for (int J = 0; J < mp; J += 512) {
     const int W = std::min(512, mp - J), c0 = J + W, rest = (mp - c0) / CVF_TB;
     gpak_factor_panel(st, S, lds, mp, J, W, inv, info, true, false, ctx->sched.potrf_co);
@@ -492,18 +582,13 @@ int gpak_cvf_run_group(gpak_ctx *ctx, const gpak_cvf_plan &pl, size_t k, const i
   double *T = P;                                          // the product is done with P
   const long ldt = mp;
   gpak_grad_g_of(st, mp, S, lds, inv, T, ldt);
-  hipLaunchKernelGGL(gpak_cvf_w_f64, dim3(m), dim3(256), 0, st, T, ldt, rows, ctx->dAlpha, wv);
-  hipLaunchKernelGGL(gpak_cvf_ev_f64, dim3((m + 63) / 64), dim3(256), 0, st, T, ldt, m, wv, rows, ctx->dy, ctx->sn2, info, ev,
-                     vv, dmean, dvar);
-  hipLaunchKernelGGL(gpak_cvf_sums_f64, dim3(1), dim3(256), 0, st, S, lds, m, ev, vv, rows, ctx->dAlpha, ctx->sn2, info,
-                     dlogp, dgsum);
+  cvf_launch_w(st, T, ldt, m, rows, ctx->dAlpha, wv);
+  cvf_launch_ev(st, T, ldt, m, wv, rows, ctx->dy, ctx->sn2, info, ev, vv, dmean, dvar);
+  cvf_launch_sums(st, S, lds, m, ev, vv, rows, ctx->dAlpha, ctx->sn2, info, dlogp, dgsum);
   if (dE) {                                               // the gradient's weights of this group
     double *sc = vv + mp_max, *Q = ctx->dCvfQ + pl.qoff[k];
-    hipLaunchKernelGGL(gpak_cvf_beta_f64, dim3(1), dim3(256), 0, st, wv, m, ctx->sn2, sc);
-    if (cvf_mix_by_gemm(m))                               // as gpak_cvf_mix_group will read it
-      hipLaunchKernelGGL(gpak_cvf_q_f64<true>, dim3(mt, mp / 16), dim3(256), 0, st, T, ldt, m, wv, ev, sc, rows, Q, (long)mp, dE);
-    else
-      hipLaunchKernelGGL(gpak_cvf_q_f64<false>, dim3(mt, mp / 16), dim3(256), 0, st, T, ldt, m, wv, ev, sc, rows, Q, (long)mp, dE);
+    cvf_launch_beta(st, wv, m, ctx->sn2, sc);
+    cvf_launch_q(st, cvf_mix_by_gemm(m), T, ldt, m, wv, ev, sc, rows, Q, (long)mp, dE);   // as gpak_cvf_mix_group will read it
   }
   GPAK_HIP(hipEventRecord(ctx->ev_cvf[3 * k + 2], st));
   return GPAK_OK;

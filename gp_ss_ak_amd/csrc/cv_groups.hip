@@ -24,6 +24,7 @@
 #include <limits>
 #include <vector>
 
+#include "../../include/gpak_dev_cv_kernels.h"
 #include "gpak_internal.h"
 
 #define CVG_MAX GPAK_CV_GROUP_MAX   // 128: rows of a group, 8 MFMA tiles of 16
@@ -326,40 +327,87 @@ extern "C" int gpak_cv_groups_last_split(gpak_ctx *ctx, double *ms3) {
 // The two passes on device lists, on the context's stream (gpak_cv_folds runs them on its groups of at most CVG_MAX
 // samples): perm / offs / soff as the kernels take them, soff[g + 1] - soff[g] = gpak_cvg_s_elems(size of group g)
 long long gpak_cvg_s_elems(int s) { return (long long)cvg_pad16(s) * cvg_pad16(s); }
-void gpak_cvg_launch_gram(gpak_ctx *ctx, const double *G, long ld, int n_groups, const int *dperm, const int *doffs,
-                          const long long *dsoff, double *dS) {
-  hipLaunchKernelGGL(gpak_cvg_gram_f64, dim3(n_groups), dim3(256), 0, ctx->stream, G, ld, ctx->Np, dperm, doffs, dsoff, dS);
+// The launches themselves, on explicit arguments: what the context's calls and the entries of gpak_dev_cv_kernels.h both run
+static void cvg_gram_on(hipStream_t st, const double *G, long ld, int Np, int n_groups, const int *dperm, const int *doffs,
+                        const long long *dsoff, double *dS) {
+  hipLaunchKernelGGL(gpak_cvg_gram_f64, dim3(n_groups), dim3(256), 0, st, G, ld, Np, dperm, doffs, dsoff, dS);
 }
 template <bool kWeights>
-static void cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
-                             const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
-                             int *dinfo, double *dE, double *dQb, const long long *dqoff) {
+static void cvg_solve_on(hipStream_t st, int device, const double *y, const double *alpha, double sn2, int n_groups,
+                         int max_size, const double *dS, const long long *dsoff, const int *dperm, const int *doffs,
+                         double *dmean, double *dvar, double *dlogp, double *dgsum, int *dinfo, double *dE, double *dQb,
+                         const long long *dqoff) {
   // more than 64 KiB of dynamic LDS needs the opt-in, once per kernel and per device
   {
     static std::atomic<unsigned long long> done_mask{0};
-    const unsigned long long bit = 1ull << (ctx->device & 63);
+    const unsigned long long bit = 1ull << (device & 63);
     if (!(done_mask.load(std::memory_order_acquire) & bit)) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gpak_cvg_solve_f64<kWeights>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)cvg_solve_lds(CVG_MAX));
       done_mask.fetch_or(bit, std::memory_order_release);
     }
   }
-  hipLaunchKernelGGL(gpak_cvg_solve_f64<kWeights>, dim3(n_groups), dim3(256), cvg_solve_lds(max_size), ctx->stream, dS, dsoff,
-                     dperm, doffs, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, dlogp, dgsum, dinfo, dE, dQb, dqoff);
+  hipLaunchKernelGGL(gpak_cvg_solve_f64<kWeights>, dim3(n_groups), dim3(256), cvg_solve_lds(max_size), st, dS, dsoff, dperm,
+                     doffs, y, alpha, sn2, dmean, dvar, dlogp, dgsum, dinfo, dE, dQb, dqoff);
+}
+static void cvg_mix_on(hipStream_t st, double *H, long ld, int Np, int n_bins, const int *dperm, const int *dbstart,
+                       const double *dQb) {
+  hipLaunchKernelGGL(gpak_cvg_mix_f64, dim3(Np / CVG_MAX, n_bins), dim3(256), 0, st, H, ld, dperm, dbstart, dQb);
+}
+void gpak_cvg_launch_gram(gpak_ctx *ctx, const double *G, long ld, int n_groups, const int *dperm, const int *doffs,
+                          const long long *dsoff, double *dS) {
+  cvg_gram_on(ctx->stream, G, ld, ctx->Np, n_groups, dperm, doffs, dsoff, dS);
 }
 void gpak_cvg_launch_solve(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
                            const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp, double *dgsum,
                            int *dinfo) {
-  cvg_launch_solve<false>(ctx, n_groups, max_size, dS, dsoff, dperm, doffs, dmean, dvar, dlogp, dgsum, dinfo, nullptr, nullptr,
-                          nullptr);
+  cvg_solve_on<false>(ctx->stream, ctx->device, ctx->dy, ctx->dAlpha, ctx->sn2, n_groups, max_size, dS, dsoff, dperm, doffs,
+                      dmean, dvar, dlogp, dgsum, dinfo, nullptr, nullptr, nullptr);
 }
 void gpak_cvg_launch_solve_weights(gpak_ctx *ctx, int n_groups, int max_size, const double *dS, const long long *dsoff,
                                    const int *dperm, const int *doffs, double *dmean, double *dvar, double *dlogp,
                                    double *dgsum, int *dinfo, double *dE, double *dQb, const long long *dqoff) {
-  cvg_launch_solve<true>(ctx, n_groups, max_size, dS, dsoff, dperm, doffs, dmean, dvar, dlogp, dgsum, dinfo, dE, dQb, dqoff);
+  cvg_solve_on<true>(ctx->stream, ctx->device, ctx->dy, ctx->dAlpha, ctx->sn2, n_groups, max_size, dS, dsoff, dperm, doffs,
+                     dmean, dvar, dlogp, dgsum, dinfo, dE, dQb, dqoff);
 }
 void gpak_cvg_launch_mix(gpak_ctx *ctx, double *H, long ld, int n_bins, const int *dperm, const int *dbstart, const double *dQb) {
-  hipLaunchKernelGGL(gpak_cvg_mix_f64, dim3(ctx->Np / CVG_MAX, n_bins), dim3(256), 0, ctx->stream, H, ld, dperm, dbstart, dQb);
+  cvg_mix_on(ctx->stream, H, ld, ctx->Np, n_bins, dperm, dbstart, dQb);
+}
+
+// ---- include/gpak_dev_cv_kernels.h: the three kernels alone on caller-owned device buffers ---------------------------
+static int cvg_status() { return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP; }
+
+extern "C" int gpak_dev_cvg_gram(void *stream, const double *G, long ld, int Np, const int *perm, const int *offs,
+                                 int n_groups, const long long *soff, double *S) {
+  if (!G || !perm || !offs || !soff || !S || n_groups < 1 || Np < CVG_MAX || Np % CVG_MAX || ld < Np) return GPAK_EINVAL;
+  cvg_gram_on((hipStream_t)stream, G, ld, Np, n_groups, perm, offs, soff, S);
+  return cvg_status();
+}
+
+extern "C" int gpak_dev_cvg_solve(void *stream, const double *S, const long long *soff, const int *perm, const int *offs,
+                                  int n_groups, int max_size, const double *y, const double *alpha, double sn2,
+                                  double *mean, double *var, double *logp, double *gsum, int *info, double *E, double *Qb,
+                                  const long long *qoff) {
+  const int n_w = (E != nullptr) + (Qb != nullptr) + (qoff != nullptr);
+  if (!S || !soff || !perm || !offs || !y || !alpha || !mean || !var || !logp || !gsum || !info || n_groups < 1 ||
+      max_size < 1 || max_size > CVG_MAX || !(sn2 > 0.0) || (n_w != 0 && n_w != 3))
+    return GPAK_EINVAL;
+  int device = 0;
+  if (hipGetDevice(&device) != hipSuccess) return GPAK_EHIP;
+  if (n_w)
+    cvg_solve_on<true>((hipStream_t)stream, device, y, alpha, sn2, n_groups, max_size, S, soff, perm, offs, mean, var, logp,
+                       gsum, info, E, Qb, qoff);
+  else
+    cvg_solve_on<false>((hipStream_t)stream, device, y, alpha, sn2, n_groups, max_size, S, soff, perm, offs, mean, var, logp,
+                        gsum, info, nullptr, nullptr, nullptr);
+  return cvg_status();
+}
+
+extern "C" int gpak_dev_cvg_mix(void *stream, double *H, long ld, int Np, const int *perm, const int *bstart, int n_bins,
+                                const double *Qb) {
+  if (!H || !perm || !bstart || !Qb || n_bins < 1 || Np < CVG_MAX || Np % CVG_MAX || ld < Np) return GPAK_EINVAL;
+  cvg_mix_on((hipStream_t)stream, H, ld, Np, n_bins, perm, bstart, Qb);
+  return cvg_status();
 }
 
 // The bins of the column mix: consecutive groups of the (group, sample) order packed greedily into bins of at most

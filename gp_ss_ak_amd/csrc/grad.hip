@@ -28,6 +28,7 @@
 
 #include "../../include/gpak_cv_folds.h"
 #include "../../include/gpak_dev.h"
+#include "../../include/gpak_dev_cv_kernels.h"
 #include "gpak_internal.h"
 
 #define PB 128
@@ -782,6 +783,24 @@ __global__ __launch_bounds__(256) void gpak_loo_finish_f64(int N, const double *
     part[(size_t)blockIdx.x * NSUM + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
+// The launches of the two steps on explicit arguments: what gpak_loo, gpak_loo_grad and the entries of
+// gpak_dev_cv_kernels.h all run.  Pass a of P on a slab with Ta = my_tiles(Np, P, a) > 0 row tiles: part takes
+// nch * Ta * 128 doubles (nch = the 512-column chunks of Np), d the Ta * 128 entries of the pass's rows.
+static int loo_chunks(int Np) { return (Np + LOO_CHUNK - 1) / LOO_CHUNK; }
+static void loo_launch_rowsumsq(hipStream_t st, const double *slab, long lds, int Np, int P, int a, double *part, double *d) {
+  const int Ta = my_tiles(Np, P, a), nch = loo_chunks(Np);
+  const long rows = (long)Ta * PB;
+  hipLaunchKernelGGL(gpak_loo_sumsq_f64, dim3(Ta, nch), dim3(256), 0, st, slab, lds, Np, P, a, rows, part);
+  hipLaunchKernelGGL(gpak_loo_rowsum_f64, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, part, rows, nch, P, a, d);
+}
+// mean, var and the three sums in out[0..2]; fin takes ceil(N / 256) * NSUM doubles
+static void loo_launch_finish(hipStream_t st, int N, const double *d, const double *y, const double *alpha, double sn2,
+                              double *mean, double *var, double *fin, double *out) {
+  const int nfin = (N + 255) / 256;
+  hipLaunchKernelGGL(gpak_loo_finish_f64, dim3(nfin), dim3(256), 0, st, N, d, y, alpha, sn2, mean, var, fin);
+  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(3), dim3(256), 0, st, fin, nfin, out);
+}
+
 // the summary from the three sums of gpak_loo_finish_f64 (gpak_loo and gpak_loo_grad: the same expressions, so the same bytes)
 static void loo_fill_summary(gpak_loo_summary *summary, const double *red, int N, double ms, int P) {
   if (!summary) return;
@@ -825,18 +844,14 @@ int gpak_loo_impl(gpak_ctx *ctx, double *mean, double *var, gpak_loo_summary *su
   GPAK_HIP(hipEventRecord(ctx->ev[7], st));
   const int GNB = 512;
   for (int a = 0; a < P; a++) {
-    const int Ta = my_tiles(Np, P, a);
-    if (Ta == 0) continue;
-    const long rows = (long)Ta * PB;
+    if (my_tiles(Np, P, a) == 0) continue;
     grad_g_subst(st, Np, GNB, P, a, [&](int b) {
       const size_t J = (size_t)b * GNB;
       return LBlockCol{ctx->dM + J + J * ctx->ld, ctx->ld, ctx->dInv + J / PB * 2 * PB * PB};
     }, slab, lds);
-    hipLaunchKernelGGL(gpak_loo_sumsq_f64, dim3(Ta, nch), dim3(256), 0, st, slab, lds, Np, P, a, rows, part);
-    hipLaunchKernelGGL(gpak_loo_rowsum_f64, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, part, rows, nch, P, a, dd);
+    loo_launch_rowsumsq(st, slab, lds, Np, P, a, part, dd);
   }
-  hipLaunchKernelGGL(gpak_loo_finish_f64, dim3(nfin), dim3(256), 0, st, N, dd, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, fin);
-  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(3), dim3(256), 0, st, fin, nfin, out);
+  loo_launch_finish(st, N, dd, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, fin, out);
   double red[3];
   GPAK_HIP(hipMemcpyAsync(red, out, sizeof(red), hipMemcpyDeviceToHost, st));
   GPAK_HIP(hipEventRecord(ctx->ev[9], st));
@@ -957,6 +972,19 @@ __global__ __launch_bounds__(256) void gpak_loo_rank2_f64(double *__restrict__ W
   }
 }
 
+// The launches of the three on explicit arguments: what the gradients and the entries of gpak_dev_cv_kernels.h both run
+static void loo_launch_vectors(hipStream_t st, int N, int Np, const double *d, const double *alpha, double sn2, double *s,
+                               double *r) {
+  hipLaunchKernelGGL(gpak_loo_vectors_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, d, alpha, sn2, s, r);
+}
+static void loo_launch_mirror_scale(hipStream_t st, int N, int Np, const double *Binv, long ldb, const double *s, double *H,
+                                    long ldh) {
+  hipLaunchKernelGGL(gpak_loo_mirror_scale_f64, dim3(Np / LM_T, Np / LM_T), dim3(256), 0, st, N, Binv, ldb, s, H, ldh);
+}
+static void loo_launch_rank2(hipStream_t st, int Np, double *W, long ld, const double *v, const double *alpha) {
+  hipLaunchKernelGGL(gpak_loo_rank2_f64, dim3(Np / LM_T, Np / LM_T), dim3(256), 0, st, W, ld, v, alpha);
+}
+
 // gpak_loo_grad on a single-GPU context whose factor and alpha are current.  Everything goes to the context's stream
 // and the host waits once, at the end.  Afterwards dG holds H and dBinv holds W: no claim is left behind, because
 // gpak_grad / gpak_grad_hyb / gpak_grad_exact run grad_binv (G and B^-1 anew) and gpak_loo runs grad_g_subst (G anew)
@@ -993,21 +1021,18 @@ int gpak_loo_grad_impl(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summa
   rc = grad_binv(ctx);
   if (rc) return rc;
   // 2. the LOO diagonal and summary: what gpak_loo launches on dG (P = 1)
-  hipLaunchKernelGGL(gpak_loo_sumsq_f64, dim3(T, nch), dim3(256), 0, st, ctx->dG, ld, Np, 1, 0, (long)Np, part);
-  hipLaunchKernelGGL(gpak_loo_rowsum_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, part, (long)Np, nch, 1, 0, dd);
-  hipLaunchKernelGGL(gpak_loo_finish_f64, dim3(nfin), dim3(256), 0, st, N, dd, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, fin);
-  hipLaunchKernelGGL(gpak_grad_reduce_f64, dim3(3), dim3(256), 0, st, fin, nfin, ctx->dRed + 32);
+  loo_launch_rowsumsq(st, ctx->dG, ld, Np, 1, 0, part, dd);
+  loo_launch_finish(st, N, dd, ctx->dy, ctx->dAlpha, ctx->sn2, dmean, dvar, fin, ctx->dRed + 32);
   // 3. s, r and v = B^-1 r by two substitutions on scratch vectors
-  hipLaunchKernelGGL(gpak_loo_vectors_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, dd, ctx->dAlpha, ctx->sn2, vs, vr);
+  loo_launch_vectors(st, N, Np, dd, ctx->dAlpha, ctx->sn2, vs, vr);
   gpak_launch_trsv_fwd(st, Np, ctx->dM, ld, ctx->dInv, vr, vz);
   gpak_backsolve(ctx, st, vz, vv, bs_scratch);
   // 4. H into dG (G has been consumed)
-  const dim3 lt(Np / LM_T, Np / LM_T);
-  hipLaunchKernelGGL(gpak_loo_mirror_scale_f64, lt, dim3(256), 0, st, N, ctx->dBinv, ld, vs, ctx->dG, ld);
+  loo_launch_mirror_scale(st, N, Np, ctx->dBinv, ld, vs, ctx->dG, ld);
   // 5. 2 M = 2 H H^T, lower tiles, into dBinv; H is full: the k-loop runs over all of Np
   gpak_launch_gemm_nt(st, T, T, Np, 2.0, ctx->dG, ld, ctx->dG, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, false);
   // 6. W = 2 M - v alpha^T - alpha v^T
-  hipLaunchKernelGGL(gpak_loo_rank2_f64, lt, dim3(256), 0, st, ctx->dBinv, ld, vv, ctx->dAlpha);
+  loo_launch_rank2(st, Np, ctx->dBinv, ld, vv, ctx->dAlpha);
   // 7. the exact pass with W for its weight
   GPAK_HIP(hipMemsetAsync(zero, 0, sizeof(double) * Np, st));
   pair_sums<ExactPass>(st, ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode, ctx->d, ctx->U.base, ctx->U.cap,
@@ -1044,6 +1069,9 @@ int gpak_loo_grad_impl(gpak_ctx *ctx, double *g, int ng, gpak_loo_summary *summa
 __global__ __launch_bounds__(256) void gpak_lgo_colscale_f64(int N, int Np, double c, double *__restrict__ s) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < Np) s[i] = i < N ? c : 0.0;
+}
+static void lgo_launch_colscale(hipStream_t st, int N, int Np, double c, double *s) {
+  hipLaunchKernelGGL(gpak_lgo_colscale_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, c, s);
 }
 
 int gpak_cv_groups_grad_layout(gpak_ctx *ctx, int ng) {
@@ -1118,15 +1146,14 @@ int gpak_cv_groups_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, in
   gpak_launch_trsv_fwd(st, Np, ctx->dM, ld, ctx->dInv, vr, vz);
   gpak_backsolve(ctx, st, vz, vv, bs_scratch);
   // 4. Kinv, full and zero on the padding, into dG (G has been consumed)
-  hipLaunchKernelGGL(gpak_lgo_colscale_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, 1.0 / ctx->sn2, vs);
-  const dim3 lt(Np / LM_T, Np / LM_T);
-  hipLaunchKernelGGL(gpak_loo_mirror_scale_f64, lt, dim3(256), 0, st, N, ctx->dBinv, ld, vs, ctx->dG, ld);
+  lgo_launch_colscale(st, N, Np, 1.0 / ctx->sn2, vs);
+  loo_launch_mirror_scale(st, N, Np, ctx->dBinv, ld, vs, ctx->dG, ld);
   // 5. H = Kinv[:, perm] blockdiag(Q_I), in place
   gpak_cvg_launch_mix(ctx, ctx->dG, ld, n_bins, dperm, dbstart, dQb);
   // 6. H H^T, lower tiles, into dBinv; H is full: the k-loop runs over all of Np
   gpak_launch_gemm_nt(st, T, T, Np, 1.0, ctx->dG, ld, ctx->dG, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, false);
   // 7. W = H H^T - v alpha^T - alpha v^T
-  hipLaunchKernelGGL(gpak_loo_rank2_f64, lt, dim3(256), 0, st, ctx->dBinv, ld, vv, ctx->dAlpha);
+  loo_launch_rank2(st, Np, ctx->dBinv, ld, vv, ctx->dAlpha);
   // 8. the exact pass with W for its weight
   GPAK_HIP(hipMemsetAsync(zero, 0, sizeof(double) * Np, st));
   pair_sums<ExactPass>(st, ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode, ctx->d, ctx->U.base, ctx->U.cap,
@@ -1259,9 +1286,8 @@ int gpak_cv_folds_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, int
   gpak_launch_trsv_fwd(st, Np, ctx->dM, ld, ctx->dInv, vr, vz);
   gpak_backsolve(ctx, st, vz, vv, bs_scratch);
   // 5. Kinv, full and zero on the padding, into dG (G has been consumed)
-  hipLaunchKernelGGL(gpak_lgo_colscale_f64, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, N, Np, 1.0 / ctx->sn2, vs);
-  const dim3 lt(Np / LM_T, Np / LM_T);
-  hipLaunchKernelGGL(gpak_loo_mirror_scale_f64, lt, dim3(256), 0, st, N, ctx->dBinv, ld, vs, ctx->dG, ld);
+  lgo_launch_colscale(st, N, Np, 1.0 / ctx->sn2, vs);
+  loo_launch_mirror_scale(st, N, Np, ctx->dBinv, ld, vs, ctx->dG, ld);
   // 6. H = Kinv[:, I] Q_I: the bins of the small groups in place,
   if (nSm) gpak_cvg_launch_mix(ctx, ctx->dG, ld, n_bins, dsperm, dbstart, dQb);
   // 7. every other group through dCvfP (the group sequences are done with it)
@@ -1271,7 +1297,7 @@ int gpak_cv_folds_grad_impl(gpak_ctx *ctx, const int *perm, const int *offs, int
   }
   // 8. W = H H^T - v alpha^T - alpha v^T (lower tiles, into dBinv) and the exact pass with W for its weight
   gpak_launch_gemm_nt(st, T, T, Np, 1.0, ctx->dG, ld, ctx->dG, ld, 0.0, ctx->dBinv, ld, 0, 0, true, true, false);
-  hipLaunchKernelGGL(gpak_loo_rank2_f64, lt, dim3(256), 0, st, ctx->dBinv, ld, vv, ctx->dAlpha);
+  loo_launch_rank2(st, Np, ctx->dBinv, ld, vv, ctx->dAlpha);
   GPAK_HIP(hipMemsetAsync(zero, 0, sizeof(double) * Np, st));
   pair_sums<ExactPass>(st, ctx->kp, ctx->kinds, te, ctx->expans, ctx->bias, ctx->dist_mode, ctx->d, ctx->U.base, ctx->U.cap,
                        ctx->dX, Np, N, Np, zero, ctx->dBinv, ld, 0, 0, 1.0, part, ctx->dRed + 8);
@@ -1409,4 +1435,56 @@ extern "C" int gpak_dev_grad_finish_d(const double *expans, double bias, double 
 }
 extern "C" int gpak_dev_grad_finish(const double *expans, double bias, double sn2, int n, const double *red, double *g) {
   return gpak_dev_grad_finish_d(expans, bias, sn2, n, 3, red, g);
+}
+
+// ---------------------------------------------------------------------------------------
+// include/gpak_dev_cv_kernels.h: the leave-one-out kernels alone on caller-owned device buffers, through the launches the
+// calls above run
+// ---------------------------------------------------------------------------------------
+static bool loo_misaligned(const void *p) { return (reinterpret_cast<size_t>(p) & 15) != 0; }
+static bool loo_bad_np(int Np) { return Np < PB || Np % PB != 0; }
+
+extern "C" int gpak_dev_loo_rowsumsq(void *stream, const double *slab, long lds, int Np, int P, int a, double *part, double *d) {
+  if (!slab || !part || !d || loo_bad_np(Np) || P < 1 || a < 0 || a >= P) return GPAK_EINVAL;
+  const int Ta = my_tiles(Np, P, a);
+  if (Ta == 0 || lds < (long)Ta * PB || (lds & 1) || loo_misaligned(slab)) return GPAK_EINVAL;
+  loo_launch_rowsumsq((hipStream_t)stream, slab, lds, Np, P, a, part, d);
+  return status();
+}
+
+extern "C" int gpak_dev_loo_finish(void *stream, int N, const double *d, const double *y, const double *alpha, double sn2,
+                                   double *mean, double *var, double *part, double *sums) {
+  if (!d || !y || !alpha || !mean || !var || !part || !sums || N < 1 || !(sn2 > 0.0)) return GPAK_EINVAL;
+  loo_launch_finish((hipStream_t)stream, N, d, y, alpha, sn2, mean, var, part, sums);
+  return status();
+}
+
+extern "C" int gpak_dev_loo_vectors(void *stream, int N, int Np, const double *d, const double *alpha, double sn2, double *s,
+                                    double *r) {
+  if (!d || !alpha || !s || !r || N < 1 || N > Np || !(sn2 > 0.0)) return GPAK_EINVAL;
+  loo_launch_vectors((hipStream_t)stream, N, Np, d, alpha, sn2, s, r);
+  return status();
+}
+
+extern "C" int gpak_dev_loo_mirror_scale(void *stream, int N, int Np, const double *Binv, long ldb, const double *s, double *H,
+                                         long ldh) {
+  if (!Binv || !s || !H || N < 1 || N > Np || loo_bad_np(Np) || ldb < Np || ldh < Np || (ldb & 1) || (ldh & 1) ||
+      loo_misaligned(Binv) || loo_misaligned(H))
+    return GPAK_EINVAL;
+  loo_launch_mirror_scale((hipStream_t)stream, N, Np, Binv, ldb, s, H, ldh);
+  return status();
+}
+
+extern "C" int gpak_dev_loo_rank2(void *stream, int Np, double *W, long ld, const double *v, const double *alpha) {
+  if (!W || !v || !alpha || loo_bad_np(Np) || ld < Np || (ld & 1) || loo_misaligned(W) || loo_misaligned(v) ||
+      loo_misaligned(alpha))
+    return GPAK_EINVAL;
+  loo_launch_rank2((hipStream_t)stream, Np, W, ld, v, alpha);
+  return status();
+}
+
+extern "C" int gpak_dev_lgo_colscale(void *stream, int N, int Np, double c, double *s) {
+  if (!s || N < 0 || N > Np || Np < 1) return GPAK_EINVAL;
+  lgo_launch_colscale((hipStream_t)stream, N, Np, c, s);
+  return status();
 }
