@@ -43,6 +43,9 @@ DEV_CONDITION_SYMBOLS = ["gpak_dev_kmm", "gpak_dev_kmm_slabs", "gpak_dev_kmm_sla
 # every symbol include/gpak_local.h / include/gpak_dev_local.h declares (tests/test_local.py checks the headers and these lists agree)
 LOCAL_SYMBOLS = ["gpak_local_metric", "gpak_local_neighbours", "gpak_predict_local"]
 DEV_LOCAL_SYMBOLS = ["gpak_dev_local_krige"]
+# every symbol include/gpak_local_ok.h / include/gpak_dev_local_ok.h declares (tests/test_local_ok.py checks the headers and these lists agree)
+LOCAL_OK_SYMBOLS = ["gpak_predict_local_ok", "gpak_local_neighbours_octant"]
+DEV_LOCAL_OK_SYMBOLS = ["gpak_dev_local_krige_ok"]
 # every symbol include/gpak_dev_f32.h declares (tests/test_dev_ops.py checks the header and this list agree)
 DEV_F32_SYMBOLS = ["gpak_dev_gemm_nt_f32", "gpak_dev_fill_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32",
                    "gpak_dev_rowsumsq_f32", "gpak_dev_fwd_subst_f32"]
@@ -98,12 +101,14 @@ def load():
     missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS
                + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DESIGN_SYMBOLS + DEV_DESIGN_SYMBOLS + CONDITION_SYMBOLS + DEV_CONDITION_SYMBOLS
                + DEV_F32_SYMBOLS + LOCAL_SYMBOLS + DEV_LOCAL_SYMBOLS + DEV_CV_KERNELS_SYMBOLS
+               + LOCAL_OK_SYMBOLS + DEV_LOCAL_OK_SYMBOLS
                if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
                            "gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_cv_folds_grad.h / "
                            "gpak_dev_cv_mix.h / gpak_design.h / gpak_dev_design.h / gpak_condition.h / gpak_dev_condition.h / "
-                           f"gpak_dev_f32.h / gpak_local.h / gpak_dev_local.h / gpak_dev_cv_kernels.h: {missing}")
+                           "gpak_dev_f32.h / gpak_local.h / gpak_dev_local.h / gpak_dev_cv_kernels.h / gpak_local_ok.h / "
+                           f"gpak_dev_local_ok.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -177,6 +182,13 @@ def load():
                                        C.POINTER(LocalSummary)]
     lib.gpak_dev_local_krige.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, dp, C.c_double, C.c_int,
                                          C.c_double, C.c_double, vp, C.c_int, C.c_int, vp, vp, vp]
+    # include/gpak_local_ok.h; include/gpak_dev_local_ok.h: the stream first, every pointer but kern a device pointer
+    lib.gpak_predict_local_ok.argtypes = [vp, dp, dp, C.c_long, C.c_int, dp, C.c_long, C.c_int, ip, C.c_int, dp, dp, dp, C.c_int,
+                                          C.POINTER(LocalSummary)]
+    lib.gpak_local_neighbours_octant.argtypes = [dp, C.c_long, C.c_int, dp, C.c_long, dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                 ip, ip]
+    lib.gpak_dev_local_krige_ok.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, dp, C.c_double, C.c_int,
+                                            C.c_double, C.c_double, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     # include/gpak_dev_cv_kernels.h: the stream first, every pointer a device pointer
     i, l, d = C.c_int, C.c_long, C.c_double
     lib.gpak_dev_cvg_gram.argtypes = [vp, vp, l, i, vp, vp, i, vp, vp]

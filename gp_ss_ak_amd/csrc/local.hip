@@ -15,6 +15,14 @@
 // eliminated column in ascending column order, and the two final dot products are summed by the first 64 threads of the
 // node -- element j by lane j mod 64 in ascending j, then one xor-butterfly over the 64 lanes.  Nothing depends on the
 // grid, on the batch or on the node's neighbours in it.
+//
+// Ordinary kriging (include/gpak_local_ok.h, include/gpak_dev_local_ok.h) is the same kernel body with OKM = true: a THIRD
+// extra row, the ones vector, under y_I^T and kbar^T, so that the factorisation leaves w_1 = L^-1 1 beside w_y and w_k, three
+// more dot products summed by the same scheme, and an epilogue of one lane (the order is stated in gpak_dev_local_ok.h).
+// The fill, the gather and the factorisation loop are shared; the simple-kriging instantiation is the code it was.
+// The LDS image is NOT larger: the gathered coordinates q are dead once K_II and kbar are filled, so the third row is
+// written after the fill, where a full list (s = smax) lets it run into the head of q; a shorter list keeps it inside the
+// smax + 2 rows.  Ordinary kriging therefore has simple kriging's LDS size and occupancy in every tier.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -26,6 +34,8 @@
 #include "../../include/gpak_dev.h"
 #include "../../include/gpak_dev_local.h"
 #include "../../include/gpak_local.h"
+#include "../../include/gpak_dev_local_ok.h"
+#include "../../include/gpak_local_ok.h"
 #include "gpak_internal.h"
 
 #define PARR GPAK_PARR
@@ -48,13 +58,16 @@ __device__ __forceinline__ double loc_wave_sum(double v) {
   return v;
 }
 
+template <bool OKM>
 __global__ __launch_bounds__(256) void gpak_local_krige_f64(const double *__restrict__ P, int cap, int nB, int nd,
                                                              const double *__restrict__ U, int capU, int nU,
                                                              const double *__restrict__ ys, KernParams kp, double inv_nd,
                                                              double white_nd, double noise, double var_add,
                                                              const int *__restrict__ nbr, int k, int smax, int wave_nodes,
                                                              int region, double *__restrict__ mean, double *__restrict__ var,
-                                                             int *info, int *nfail) {
+                                                             double *__restrict__ mu, int *info, int *nfail) {
+  constexpr int XR = OKM ? 3 : 2;   // the rows under the triangle: y_I^T, kbar^T and, for ordinary kriging, 1^T
+  static_assert(LOC_NC >= 2, "the third row of a full list lies in the first smax + 1 doubles of q");
   extern __shared__ double loc_lds[];
   const int t = threadIdx.x;
   const bool wn = wave_nodes != 0;
@@ -62,15 +75,24 @@ __global__ __launch_bounds__(256) void gpak_local_krige_f64(const double *__rest
   const int b = wn ? (int)blockIdx.x * LOC_WAVE_NODES + (t >> 6) : (int)blockIdx.x;
   if (b >= nB) return;   // a whole wave of a one-wave tier: that tier has no workgroup barrier
   const int nterms = kp.nterms, pitch = smax + 1;
-  double *A = loc_lds + (wn ? (size_t)(t >> 6) * region : 0);   // s + 2 rows of `pitch`
-  double *q = A + (size_t)(smax + 2) * pitch;                   // [term][LOC_NC][smax]
+  double *A = loc_lds + (wn ? (size_t)(t >> 6) * region : 0);   // s + XR rows of `pitch`: smax + 2 of them are A's own
+  double *q = A + (size_t)(smax + 2) * pitch;                   // [term][LOC_NC][smax]; dead after the fill
   int *ridx = reinterpret_cast<int *>(q + (size_t)nterms * LOC_NC * smax);
 
   for (int e = tid; e < k; e += nt) ridx[e] = nbr[e + (size_t)k * b];
   loc_sync(wn);
   int s = 0;   // the list ends at the first entry that names no sample
   while (s < k && (unsigned)ridx[s] < (unsigned)nU) s++;
-  const int R = s + 2;
+  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+  if (OKM && s == 0) {   // no sample, no local mean: not an estimate, and not a failure of the factorisation either
+    if (tid == 0) {
+      mean[b] = qnan;
+      if (var) var[b] = qnan;
+      if (mu) mu[b] = qnan;
+    }
+    return;   // the whole node: every thread of it read the same list
+  }
+  const int R = s + XR;
   double *yrow = A + (size_t)s * pitch, *krow = yrow + pitch;
 
   for (int e = tid; e < s * nterms * LOC_NC; e += nt) {
@@ -130,8 +152,12 @@ __global__ __launch_bounds__(256) void gpak_local_krige_f64(const double *__rest
     A[i * pitch + j] = i == j ? acc + noise : acc;
   }
   loc_sync(wn);
+  if (OKM) {   // the ones row, only now: with s = smax it lies where q was, and q has been read for the last time
+    for (int i = tid; i < s; i += nt) krow[pitch + i] = 1.0;
+    loc_sync(wn);
+  }
 
-  // right-looking Cholesky over the s + 2 rows; the diagonal itself is not needed afterwards and is left as the pivot
+  // right-looking Cholesky over the s + XR rows; the diagonal itself is not needed afterwards and is left as the pivot
   bool ok = true;
   for (int j = 0; j < s; j++) {
     const double dj = A[j * pitch + j];   // every thread of the node reads the same value: the branch is uniform
@@ -139,7 +165,7 @@ __global__ __launch_bounds__(256) void gpak_local_krige_f64(const double *__rest
     const double ri = 1.0 / sqrt(dj);
     for (int i = j + 1 + tid; i < R; i += nt) A[i * pitch + j] *= ri;
     loc_sync(wn);
-    for (int c = j + 1 + (tid >> 4); c < s; c += nt / 16) {   // column c of the trailing block, rows c .. s + 1, 16 lanes each
+    for (int c = j + 1 + (tid >> 4); c < s; c += nt / 16) {   // column c of the trailing block, rows c .. R - 1, 16 lanes each
       const double acj = A[c * pitch + j];
       for (int i = c + (tid & 15); i < R; i += 16)
         A[i * pitch + c] = fma(-A[i * pitch + j], acj, A[i * pitch + c]);
@@ -148,9 +174,9 @@ __global__ __launch_bounds__(256) void gpak_local_krige_f64(const double *__rest
   }
   if (!ok) {
     if (tid == 0) {
-      const double nan = __longlong_as_double(0x7ff8000000000000LL);
-      mean[b] = nan;
-      if (var) var[b] = nan;
+      mean[b] = qnan;
+      if (var) var[b] = qnan;
+      if (OKM && mu) mu[b] = qnan;
       atomicMin(info, b + 1);
       if (nfail) atomicAdd(nfail, 1);   // an integer count: the same whatever the order
     }
@@ -165,9 +191,31 @@ __global__ __launch_bounds__(256) void gpak_local_krige_f64(const double *__rest
     }
     macc = loc_wave_sum(macc);
     qacc = loc_wave_sum(qacc);
-    if (tid == 0) {
-      mean[b] = macc;
-      if (var) var[b] = (kbb - qacc) + var_add;
+    if (!OKM) {
+      if (tid == 0) {
+        mean[b] = macc;
+        if (var) var[b] = (kbb - qacc) + var_add;
+      }
+    } else {
+      const double *orow = krow + pitch;   // w_1 = L^-1 1
+      double aacc = 0.0, byacc = 0.0, bkacc = 0.0;
+      for (int j = tid; j < s; j += 64) {
+        const double w = orow[j];
+        aacc = fma(w, w, aacc);
+        byacc = fma(w, yrow[j], byacc);
+        bkacc = fma(w, krow[j], bkacc);
+      }
+      aacc = loc_wave_sum(aacc);
+      byacc = loc_wave_sum(byacc);
+      bkacc = loc_wave_sum(bkacc);
+      if (tid == 0) {   // the epilogue, in the order gpak_dev_local_ok.h states
+        const double m = byacc / aacc;
+        const double r = 1.0 - bkacc;
+        const double tq = r / aacc;
+        mean[b] = fma(r, m, macc);
+        if (var) var[b] = fma(r, tq, kbb - qacc) + var_add;
+        if (mu) mu[b] = m;
+      }
     }
   }
 }
@@ -190,18 +238,19 @@ int local_region(int smax, int nterms) {   // doubles of one node's LDS image
   return (smax + 2) * (smax + 1) + nterms * LOC_NC * smax + (smax + 1) / 2;
 }
 
-// one batch: nB nodes, every argument checked by the caller
+// one batch: nB nodes, every argument checked by the caller; OKM: ordinary kriging (mu may be null), else mu is not read
+template <bool OKM>
 void local_launch(hipStream_t st, int device, const double *P, int cap, int nB, int nd, const DevPoints &Q, const double *ys,
                   KernParams kp, double white, double noise, const int *nbr, int k, int flags, double *mean, double *var,
-                  int *info, int *nfail) {
+                  double *mu, int *info, int *nfail) {
   const LocalTier tier = gpak_local_tier(k);
-  const int region = local_region(tier.smax, kp.nterms);
+  const int region = local_region(tier.smax, kp.nterms);   // the same image for both estimators
   const size_t lds = sizeof(double) * (size_t)region * (tier.wave_nodes ? LOC_WAVE_NODES : 1);
   {   // more than 64 KiB of dynamic LDS needs the opt-in, once per device
-    static std::atomic<unsigned long long> done_mask{0};
+    static std::atomic<unsigned long long> done_mask{0};   // one per instantiation
     const unsigned long long bit = 1ull << (device & 63);
     if (!(done_mask.load(std::memory_order_acquire) & bit)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gpak_local_krige_f64), hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gpak_local_krige_f64<OKM>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(sizeof(double) * local_region(GPAK_LOCAL_MAX, GPAK_MAX_TERMS)));
       done_mask.fetch_or(bit, std::memory_order_release);
     }
@@ -210,8 +259,8 @@ void local_launch(hipStream_t st, int device, const double *P, int cap, int nB, 
   const int grid = tier.wave_nodes ? (nB + LOC_WAVE_NODES - 1) / LOC_WAVE_NODES : nB;
   const double var_add = (flags & GPAK_LOCAL_LATENT) ? 0.0 : (noise - white) / nd;
   hipLaunchKernelGGL(gpak_local_info_f64, dim3(1), dim3(1), 0, st, info, 0, nfail);
-  hipLaunchKernelGGL(gpak_local_krige_f64, dim3(grid), dim3(256), lds, st, P, cap, nB, nd, Q.base, Q.cap, Q.n, ys, kp, 1.0 / nd,
-                     white / nd, noise, var_add, nbr, k, tier.smax, tier.wave_nodes ? 1 : 0, region, mean, var, info, nfail);
+  hipLaunchKernelGGL(gpak_local_krige_f64<OKM>, dim3(grid), dim3(256), lds, st, P, cap, nB, nd, Q.base, Q.cap, Q.n, ys, kp, 1.0 / nd,
+                     white / nd, noise, var_add, nbr, k, tier.smax, tier.wave_nodes ? 1 : 0, region, mean, var, mu, info, nfail);
   hipLaunchKernelGGL(gpak_local_info_f64, dim3(1), dim3(1), 0, st, info, 1, nfail);
 }
 
@@ -224,13 +273,12 @@ struct Timer {   // device ms between two points of a stream, added up over the 
   void collect() { float v = 0; if (hipEventElapsedTime(&v, a, b) == hipSuccess) ms += v; }
   ~Timer() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
 };
-}  // namespace
 
-extern "C" {
-
-int gpak_dev_local_krige(void *stream, const double *P, int cap, int nB, int nd, const double *u, int ucap, int n,
-                         const double *ys, const double *kern, double bias, int dist_mode, double white, double noise,
-                         const int *nbr, int k, int flags, double *mean, double *var, int *info) {
+// gpak_dev_local_krige and gpak_dev_local_krige_ok: one body, the estimator a template argument
+template <bool OKM>
+int dev_local_krige(void *stream, const double *P, int cap, int nB, int nd, const double *u, int ucap, int n, const double *ys,
+                    const double *kern, double bias, int dist_mode, double white, double noise, const int *nbr, int k, int flags,
+                    double *mean, double *var, double *mu, int *info) {
   if (!P || !u || !ys || !kern || !nbr || !mean || !info || nB < 1 || nd < 1 || n < 1 || cap < nB || ucap < n || k < 1 ||
       k > GPAK_LOCAL_MAX || (flags & ~GPAK_LOCAL_LATENT) || (size_t)cap * nd > ((size_t)1 << 30))
     return GPAK_EINVAL;
@@ -252,8 +300,26 @@ int gpak_dev_local_krige(void *stream, const double *P, int cap, int nB, int nd,
   if (hipGetDevice(&device) != hipSuccess) return GPAK_EHIP;
   DevPoints Q;
   Q.base = const_cast<double *>(u); Q.n = n; Q.cap = ucap;
-  local_launch((hipStream_t)stream, device, P, cap, nB, nd, Q, ys, kp, white, noise, nbr, k, flags, mean, var, info, nullptr);
+  local_launch<OKM>((hipStream_t)stream, device, P, cap, nB, nd, Q, ys, kp, white, noise, nbr, k, flags, mean, var, mu, info,
+                    nullptr);
   return hipGetLastError() == hipSuccess ? GPAK_OK : GPAK_EHIP;
+}
+}  // namespace
+
+extern "C" {
+
+int gpak_dev_local_krige(void *stream, const double *P, int cap, int nB, int nd, const double *u, int ucap, int n,
+                         const double *ys, const double *kern, double bias, int dist_mode, double white, double noise,
+                         const int *nbr, int k, int flags, double *mean, double *var, int *info) {
+  return dev_local_krige<false>(stream, P, cap, nB, nd, u, ucap, n, ys, kern, bias, dist_mode, white, noise, nbr, k, flags, mean,
+                                var, nullptr, info);
+}
+
+int gpak_dev_local_krige_ok(void *stream, const double *P, int cap, int nB, int nd, const double *u, int ucap, int n,
+                            const double *ys, const double *kern, double bias, int dist_mode, double white, double noise,
+                            const int *nbr, int k, int flags, double *mean, double *var, double *mu, int *info) {
+  return dev_local_krige<true>(stream, P, cap, nB, nd, u, ucap, n, ys, kern, bias, dist_mode, white, noise, nbr, k, flags, mean,
+                               var, mu, info);
 }
 
 int gpak_local_metric(const gpak_ctx *ctx, int term, double *G) {
@@ -273,10 +339,13 @@ int gpak_local_metric(const gpak_ctx *ctx, int term, double *G) {
   return GPAK_OK;
 }
 
-int gpak_predict_local(gpak_ctx *ctx, const double *Xs, const double *ys, long Ns, int d, const double *Xd, long M, int nd,
-                       const int *nbr, int k, double *mean, double *var, int flags, gpak_local_summary *summary) {
+// the host driver of gpak_predict_local (okm false; mu is not read) and gpak_predict_local_ok (okm true; mu may be NULL)
+static int predict_local_driver(gpak_ctx *ctx, const double *Xs, const double *ys, long Ns, int d, const double *Xd, long M,
+                                int nd, const int *nbr, int k, double *mean, double *var, double *mu, int flags,
+                                gpak_local_summary *summary, bool okm) {
   if (!ctx) return GPAK_EINVAL;
-  const std::string who = "gpak_predict_local: ";
+  const std::string who = okm ? "gpak_predict_local_ok: " : "gpak_predict_local: ";
+  if (!okm) mu = nullptr;
   auto refuse = [&](int rc, const std::string &what) { ctx->err = who + what; return rc; };
   if (!Xs || !ys || !Xd || !nbr || !mean)
     return refuse(GPAK_EINVAL, std::string(!Xs ? "Xs" : !ys ? "ys" : !Xd ? "Xd" : !nbr ? "nbr" : "mean") + " is NULL");
@@ -333,7 +402,7 @@ int gpak_predict_local(gpak_ctx *ctx, const double *Xs, const double *ys, long N
   DevBuf<int> dNbr, dInfo;
   const bool ok = Us.reserve(capS) && dRaw.reserve((size_t)d * Ns) && dYs.reserve((size_t)Ns) &&
                   dXblk.reserve((size_t)d * cap * nd) && dTblk.reserve((size_t)GPAK_PT * kp.nterms * cap * nd) &&
-                  dOut.reserve(2 * (size_t)cap) && dNbr.reserve((size_t)k * cap) && dInfo.reserve(2);
+                  dOut.reserve((okm ? 3 : 2) * (size_t)cap) && dNbr.reserve((size_t)k * cap) && dInfo.reserve(2);
   if (!ok) {
     (void)hipGetLastError();
     return refuse(GPAK_ENOMEM, "device allocation failed for the transformed samples (15 doubles each) or a node batch");
@@ -349,7 +418,7 @@ int gpak_predict_local(gpak_ctx *ctx, const double *Xs, const double *ys, long N
   GPAK_HIP(hipStreamSynchronize(st));
   dRaw.release();
 
-  double *dMean = dOut, *dVar = dOut + cap;
+  double *dMean = dOut, *dVar = dOut + cap, *dMu = okm ? dOut + 2 * (size_t)cap : nullptr;
   const long Mn = M * nd;
   long notpd = 0;
   int batches = 0;
@@ -362,11 +431,16 @@ int gpak_predict_local(gpak_ctx *ctx, const double *Xs, const double *ys, long N
                               hipMemcpyHostToDevice, st));
     GPAK_HIP(hipMemcpyAsync(dNbr, nbr + (size_t)k * b0, sizeof(int) * (size_t)k * mb, hipMemcpyHostToDevice, st));
     gpak_launch_transform_blocks(st, dXblk, xs, mb, nd, cap, kp, dTblk);
-    local_launch(st, ctx->device, dTblk, cap, mb, nd, Us, dYs, kp, white, noise, dNbr, k, flags, dMean, var ? dVar : nullptr,
-                 dInfo, dInfo + 1);
+    if (okm)
+      local_launch<true>(st, ctx->device, dTblk, cap, mb, nd, Us, dYs, kp, white, noise, dNbr, k, flags, dMean,
+                         var ? dVar : nullptr, mu ? dMu : nullptr, dInfo, dInfo + 1);
+    else
+      local_launch<false>(st, ctx->device, dTblk, cap, mb, nd, Us, dYs, kp, white, noise, dNbr, k, flags, dMean,
+                          var ? dVar : nullptr, nullptr, dInfo, dInfo + 1);
     int hinfo[2] = {0, 0};   // the smallest failing node + 1, the number of failing nodes
     GPAK_HIP(hipMemcpyAsync(mean + b0, dMean, sizeof(double) * mb, hipMemcpyDeviceToHost, st));
     if (var) GPAK_HIP(hipMemcpyAsync(var + b0, dVar, sizeof(double) * mb, hipMemcpyDeviceToHost, st));
+    if (mu) GPAK_HIP(hipMemcpyAsync(mu + b0, dMu, sizeof(double) * mb, hipMemcpyDeviceToHost, st));
     GPAK_HIP(hipMemcpyAsync(hinfo, dInfo, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     GPAK_HIP(hipStreamSynchronize(st));
     GPAK_HIP(hipGetLastError());
@@ -387,6 +461,17 @@ int gpak_predict_local(gpak_ctx *ctx, const double *Xs, const double *ys, long N
     summary->max_used = max_used;
   }
   return GPAK_OK;
+}
+
+int gpak_predict_local(gpak_ctx *ctx, const double *Xs, const double *ys, long Ns, int d, const double *Xd, long M, int nd,
+                       const int *nbr, int k, double *mean, double *var, int flags, gpak_local_summary *summary) {
+  return predict_local_driver(ctx, Xs, ys, Ns, d, Xd, M, nd, nbr, k, mean, var, nullptr, flags, summary, false);
+}
+
+int gpak_predict_local_ok(gpak_ctx *ctx, const double *Xs, const double *ys, long Ns, int d, const double *Xd, long M, int nd,
+                          const int *nbr, int k, double *mean, double *var, double *mu, int flags,
+                          gpak_local_summary *summary) {
+  return predict_local_driver(ctx, Xs, ys, Ns, d, Xd, M, nd, nbr, k, mean, var, mu, flags, summary, true);
 }
 
 }  // extern "C"

@@ -16,3 +16,14 @@
 // INT_MAX, or a coordinate (raw or transformed) that is not finite.
 extern "C" int gpak_local_neighbours(const double *Xs, long Ns, int d, const double *Xc, long M, const double *G, int k,
                                      double radius, int threads, int *nbr, int *used);
+
+// The octant search (gpak_local_neighbours_octant, include/gpak_local_ok.h): the same transform, distances, grid and rings.
+// The octant of a sample is the sign pattern of its first three transformed differences e_j = t(x)_j - t(c)_j: bit j is set
+// when e_j < 0, a zero counting as non-negative; a fourth column counts in dist2 only.  Of the samples with dist2 <=
+// radius^2 each octant keeps its per_octant nearest by (dist2, index) -- eight heaps filled in the one pass over the rings,
+// which ends when every octant's heap is settled or the rings have left the radius -- and of those the k nearest are written
+// in ascending (dist2, index), -1 after them.  Exact, and independent of `threads`; per_octant = k gives the lists of
+// gpak_local_neighbours.  Returns 2 also for a radius that is not positive and finite (it is required: it is what ends the
+// rings of a centre with an empty octant) and for per_octant outside 1..k.
+extern "C" int gpak_local_neighbours_octant(const double *Xs, long Ns, int d, const double *Xc, long M, const double *G, int k,
+                                            int per_octant, double radius, int threads, int *nbr, int *used);

@@ -78,11 +78,13 @@ def group_labels(labels, n=None):
     return np.ascontiguousarray(group.reshape(-1), dtype=np.int32), values
 
 
-def local_neighbours(Xs, Xc, k, G=None, radius=0.0, threads=0):
+def local_neighbours(Xs, Xc, k, G=None, radius=0.0, threads=0, octant=0):
     """The k nearest samples of every centre (gpak_local_neighbours; host code, no context): returns (nbr, used), nbr
     M x k int32 -- row b the sample indices of centre b by ascending distance |(x - c) G|, then ascending index, -1 in the
     unused slots -- and used (M) the counts.  G: d x d, or the 4 x 4 of Gpak.local_metric (its leading d x d part is
-    taken), or None for the identity; radius > 0 keeps only samples within it; threads <= 0: min(cores, 16)."""
+    taken), or None for the identity; radius > 0 keeps only samples within it; threads <= 0: min(cores, 16).
+    octant > 0: the octant search (gpak_local_neighbours_octant) -- at most `octant` samples from each of the eight octants
+    around a centre, of those the k nearest; it needs a positive radius and octant <= k."""
     Xs, Xc = _f(Xs), _f(Xc)
     if Xs.ndim != 2 or Xc.ndim != 2 or Xs.shape[1] != Xc.shape[1]:
         raise GpakError(EINVAL, "Xs and Xc must be matrices with as many columns")
@@ -97,6 +99,18 @@ def local_neighbours(Xs, Xc, k, G=None, radius=0.0, threads=0):
     nbr = np.full((max(M, 0), max(k, 0)), -1, dtype=np.int32)
     used = np.zeros(max(M, 0), dtype=np.int32)
     ip = C.POINTER(C.c_int)
+    octant = int(octant)
+    if octant < 0:
+        raise GpakError(EINVAL, "octant is a count of samples per octant, or 0 for the plain search")
+    if octant > 0:
+        if not float(radius) > 0.0:
+            raise GpakError(EINVAL, "the octant search needs a positive radius")
+        rc = _lib.load().gpak_local_neighbours_octant(_p(Xs), Xs.shape[0], d, _p(Xc), M, _p(G), k, octant, float(radius),
+                                                      int(threads), nbr.ctypes.data_as(ip), used.ctypes.data_as(ip))
+        if rc != OK:
+            raise GpakError(rc, "gpak_local_neighbours_octant refused its arguments (shapes, k outside 1..128, octant outside "
+                                "1..k, a radius or a coordinate that is not finite)")
+        return nbr, used
     rc = _lib.load().gpak_local_neighbours(_p(Xs), Xs.shape[0], d, _p(Xc), M, _p(G), k, float(radius), int(threads),
                                            nbr.ctypes.data_as(ip), used.ctypes.data_as(ip))
     if rc != OK:
@@ -360,6 +374,25 @@ class Gpak:
                                                  nbr.ctypes.data_as(C.POINTER(C.c_int)), nbr.shape[1], _p(mean), _p(var),
                                                  LOCAL_LATENT if latent else 0, C.byref(s)))
         return mean, var, {f: getattr(s, f) for f, _ in s._fields_}
+
+    def predict_local_ok(self, Xs, ys, Xd, nd, nbr, want_var=True, want_mu=False, latent=False):
+        """Ordinary kriging in a moving neighbourhood (gpak_predict_local_ok): the arguments of predict_local; the mean is
+        re-estimated from every node's own samples and the weights sum to one.  Returns (mean, var, mu, summary), mu the
+        local means; var and mu are None unless asked for.  A node without a sample gets NaN in all three."""
+        Xs = _f(Xs)
+        ys = np.ascontiguousarray(ys, dtype=np.float64).ravel()
+        Xd, M, nd = self._blocks(Xd, nd)
+        nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+        if Xs.ndim != 2 or ys.size != Xs.shape[0] or nbr.ndim != 2 or nbr.shape[0] != M or Xd.shape[1] != Xs.shape[1]:
+            raise GpakError(EINVAL, "Xs is Ns x d with Ns values ys, Xd has as many columns, nbr one row per node")
+        mean = np.zeros(M)
+        var = np.zeros(M) if want_var else None
+        mu = np.zeros(M) if want_mu else None
+        s = _lib.LocalSummary()
+        self._check(self._lib.gpak_predict_local_ok(self._h, _p(Xs), _p(ys), Xs.shape[0], Xs.shape[1], _p(Xd), M, nd,
+                                                    nbr.ctypes.data_as(C.POINTER(C.c_int)), nbr.shape[1], _p(mean), _p(var),
+                                                    _p(mu), LOCAL_LATENT if latent else 0, C.byref(s)))
+        return mean, var, mu, {f: getattr(s, f) for f, _ in s._fields_}
 
     def predict_joint(self, Xd, nd, want_cov=True, latent=False, prior=False):
         """Mean (M) and full covariance (M x M, exactly symmetric) of the block averages (gpak_predict_joint); the

@@ -84,6 +84,19 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       if (tok.empty() || *end != '\0') local_radius = -1.0;         // the `local` verb refuses what is not positive
       local_radius_set = true;
     }
+    else if (isArg("--kriging", "--kriging")) {
+      incArg();
+      local_kriging = getArgNo() < argc ? getArg() : std::string();   // the `local` verb refuses what is not simple or ordinary
+      local_kriging_set = true;
+    }
+    else if (isArg("--octant", "--octant")) {
+      incArg();
+      char *end = nullptr;
+      const std::string tok = getArgNo() < argc ? getArg() : std::string();
+      const long v = strtol(tok.c_str(), &end, 10);
+      local_octant = (tok.empty() || *end != '\0') ? -1 : v;           // the `local` verb refuses what is not 1..--neighbours
+      local_octant_set = true;
+    }
     else break;
     incArg();
   }

@@ -74,6 +74,10 @@ class Control {
   long local_neighbours = 0;
   double local_radius = 0.0;
   bool local_neighbours_set = false, local_radius_set = false;
+  // --kriging simple|ordinary (ordinary: gpak_predict_local_ok), --octant n (at most n samples per octant; needs --radius)
+  std::string local_kriging = "simple";
+  long local_octant = 0;
+  bool local_kriging_set = false, local_octant_set = false;
   std::string mode = "gp";
   mat params, MinData, MaxData, MeanData, StData;
   double MaxTotalin = 0, MinTotalin = 0, MaxTotalo = 0, MinTotalo = 0;

@@ -7,8 +7,8 @@
 //   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
 //   gp_ss_ak [-v n] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] [--nugget v] --realisations S (--seed n | --xi file)
 //            sim [--method joint|path [--features F]] nodes.txt model train.txt [out_file]
-//   gp_ss_ak [-v n] --neighbours k [--radius r] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent]
-//            local nodes.txt model train.txt [out_file]
+//   gp_ss_ak [-v n] --neighbours k [--radius r] [--octant n] [--kriging simple|ordinary]
+//            [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
 // (exact: GradLL returns the derivative of nlZ and -o LBFGS runs Opt_Algs::ProjectedLBFGSOptimise; one GPU only),
@@ -109,6 +109,9 @@ class GP_Cntrl : public Control {
   void sim();
   void design();
   void local();
+  void localOptionsOnlyWithLocal() const {
+    if (local_kriging_set || local_octant_set) ErrorTermination("--kriging and --octant are options of the local verb");
+  }
   void Help() const;
 };
 
@@ -118,7 +121,7 @@ void GP_Cntrl::Help() const {
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
             << "design :\n \t To rank candidate drill holes by the estimation variance they would remove from targets ([--block-size dx,dy,dz --block-disc nx,ny,nz] [--pick k] [--weights file] design --candidates file --holes file targets model train).\n"
-            << "local :\n \t To estimate nodes or blocks from the k nearest of any number of samples (--neighbours k [--radius r] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes model samples).\n"
+            << "local :\n \t To estimate nodes or blocks from the k nearest of any number of samples (--neighbours k [--radius r] [--octant n: at most n samples per octant, needs --radius] [--kriging simple|ordinary: ordinary re-estimates the mean from every node's own samples] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes model samples).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
             << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]; sim --method path [--features F] with --seed n: any number of nodes, the prior from F random frequencies per term).\n";
 }
@@ -631,11 +634,15 @@ void GP_Cntrl::block() {
 
 // local (not a reference verb): moving-neighbourhood kriging (gpak_predict_local; one GPU only) -- every node from its k
 // nearest samples, so train.txt may hold any number of them (train on a subsample, estimate from all the assays):
-//   gp_ss_ak --neighbours k [--radius r] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes.txt model train.txt [out]
+//   gp_ss_ak --neighbours k [--radius r] [--octant n] [--kriging simple|ordinary] [--block-size dx,dy,dz --block-disc nx,ny,nz]
+//            [--latent] local nodes.txt model train.txt [out]
 // nodes.txt is read as block reads its centres (without the two block options the nodes are points); train.txt is
 // standardised with the model's _Statistics.txt.  The neighbours are searched from the node centres in the metric of the
 // model's first stationary term (gpak_local_metric), in which --radius is measured: 1 is one range.  Everything is checked
-// before a context exists.  Written to <model>_local.txt in input order.
+// before a context exists.  Written to <model>_local.txt in input order.  --octant n keeps at most n samples from each of
+// the eight octants around a node (gpak_local_neighbours_octant; it needs --radius, and 1 <= n <= k).  --kriging ordinary
+// re-estimates the mean from every node's own samples (gpak_predict_local_ok) and adds the column LocalMean; a node
+// without a sample then has no estimate and prints nan.
 void GP_Cntrl::local() {
   incArg();
   setMode("local");
@@ -655,6 +662,12 @@ void GP_Cntrl::local() {
   if (local_radius_set && !(local_radius > 0.0)) ErrorTermination("--radius takes a positive distance (1 is one range of the model's first term)");
   if (block_size_set != block_disc_set)
     ErrorTermination("local takes --block-size and --block-disc together (neither: the nodes are points)");
+  if (local_kriging != "simple" && local_kriging != "ordinary") ErrorTermination("--kriging takes simple or ordinary");
+  if (local_octant_set && !local_radius_set)
+    ErrorTermination("--octant needs --radius: the octant search looks for samples inside a radius only");
+  if (local_octant_set && (local_octant < 1 || local_octant > local_neighbours))
+    ErrorTermination("--octant takes the samples per octant, between 1 and --neighbours");
+  const bool ordinary = local_kriging == "ordinary";
   if (getArgNo() + 2 >= argc)
     ErrorTermination("There are not enough input parameters: local needs the nodes, the model and the samples.");
   std::string ndFile = getArg(), modelName = argv[getArgNo() + 1], trFile = argv[getArgNo() + 2];
@@ -687,23 +700,34 @@ void GP_Cntrl::local() {
   GPModel->LocalMetric(G);
   std::vector<int> nbr, used;
   const auto t0 = std::chrono::steady_clock::now();
-  GP_utils::LocalNeighbours(Xtr, C, G, k, local_radius_set ? local_radius : 0.0, nbr, used);
+  if (local_octant_set) GP_utils::LocalNeighboursOctant(Xtr, C, G, k, (int)local_octant, local_radius, nbr, used);
+  else GP_utils::LocalNeighbours(Xtr, C, G, k, local_radius_set ? local_radius : 0.0, nbr, used);
   const double search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  mat LocalVals(y.n_rows, 1), LocalVals_Var(y.n_rows, 1);
+  mat LocalVals(y.n_rows, 1), LocalVals_Var(y.n_rows, 1), LocalMu(ordinary ? y.n_rows : 0, 1);
   gpak_local_summary s;
-  GPModel->LocalMeanVar(LocalVals, LocalVals_Var, Xtr, ytr, Xd, nd, nbr, k, block_latent, s);
+  if (ordinary) GPModel->LocalMeanVarOk(LocalVals, LocalVals_Var, LocalMu, Xtr, ytr, Xd, nd, nbr, k, block_latent, s);
+  else GPModel->LocalMeanVar(LocalVals, LocalVals_Var, Xtr, ytr, Xd, nd, nbr, k, block_latent, s);
   postData(C, LocalVals, yscale, modelName);
   postData_var(LocalVals_Var, yscale, modelName);
   postData(y, yscale, modelName);
+  if (ordinary) postData(LocalMu, yscale, modelName);
   if (getVerbose() > 0)
     std::cout << "Nodes: " << s.nodes << " of " << nd << " points from " << Xtr.n_rows << " samples, " << k << " neighbours at most"
+              << (local_octant_set ? ", " + std::to_string(local_octant) + " per octant" : std::string())
+              << (ordinary ? ", ordinary kriging" : "")
               << (block_latent ? ", latent variance" : "") << "; without a neighbour " << s.empty << ", not positive definite "
               << s.notpd << "; search " << search_ms << " ms, device " << (s.upload_ms + s.krige_ms) << " ms\n";
   // rows in input order; the fourth column is what postData_var returns, as StdYblock of _block.txt
   std::ofstream out(LocalOut.c_str());
-  out << "# NodeNo, Y, Ylocal, StdYlocal, Neighbours, Inputs" << "\n";
+  out << (ordinary ? "# NodeNo, Y, Ylocal, StdYlocal, Neighbours, LocalMean, Inputs" : "# NodeNo, Y, Ylocal, StdYlocal, Neighbours, Inputs")
+      << "\n";
   for (size_t i = 0; i < y.n_elem; i++) {
-    out << (i + 1) << "\t" << y[i] << "\t" << LocalVals[i] << "\t" << LocalVals_Var[i] << "\t" << used[i] << "\t";
+    if (ordinary && std::isnan(LocalVals[i])) {   // no sample or no factor: `nan` whatever sign the NaN carries
+      out << (i + 1) << "\t" << y[i] << "\tnan\tnan\t" << used[i] << "\tnan\t";
+    } else {
+      out << (i + 1) << "\t" << y[i] << "\t" << LocalVals[i] << "\t" << LocalVals_Var[i] << "\t" << used[i] << "\t";
+      if (ordinary) out << LocalMu[i] << "\t";
+    }
     for (size_t j = 0; j < C.n_cols; j++) out << C(i, j) << "\t";
     out << "\n";
   }
@@ -986,6 +1010,7 @@ int main(int argc, char **argv) {
   GP_Cntrl ctl(argc, argv);
   if (ctl.getArgNo() >= argc) { ctl.Help(); return 1; }
   std::string verb = ctl.getArg();
+  if (verb != "local" && verb != "-h" && verb != "--help" && verb != "-?") ctl.localOptionsOnlyWithLocal();
   if (verb == "train") ctl.train();
   else if (verb == "test") ctl.test();
   else if (verb == "cv") ctl.cv();

@@ -279,6 +279,33 @@ void GP_utils::LocalMeanVar(mat &mean, mat &var, const mat &Xs, const mat &ys, c
   if (rc != GPAK_OK) gpak_host_fatal("gpak_predict_local", ctx);
 }
 
+void GP_utils::LocalNeighboursOctant(const mat &Xs, const mat &Xc, const double G[16], int k, int per_octant, double radius,
+                                     std::vector<int> &nbr, std::vector<int> &used) {
+  const int d = (int)Xs.n_cols;
+  std::vector<double> Gd((size_t)d * d);   // the leading d x d part
+  for (int c = 0; c < d; c++)
+    for (int r = 0; r < d; r++) Gd[r + (size_t)d * c] = G[r + 4 * c];
+  nbr.assign((size_t)k * Xc.n_rows, -1);
+  used.assign(Xc.n_rows, 0);
+  if (gpak_local_neighbours_octant(Xs.memptr(), (long)Xs.n_rows, d, Xc.memptr(), (long)Xc.n_rows, Gd.data(), k, per_octant, radius, 0,
+                                   nbr.data(), used.data()) != GPAK_OK) {
+    std::cerr << "gpak_local_neighbours_octant refused the samples or the nodes (a coordinate that is not finite?)" << std::endl;
+    exit(1);
+  }
+}
+
+void GP_utils::LocalMeanVarOk(mat &mean, mat &var, mat &mu, const mat &Xs, const mat &ys, const mat &Xd, int nd,
+                              const std::vector<int> &nbr, int k, bool latent, gpak_local_summary &summary) const {
+  sync_params();
+  const size_t M = nd > 0 ? Xd.n_rows / nd : 0;
+  if (mean.n_elem != M) mean.resize(M, 1);
+  if (var.n_elem != M) var.resize(M, 1);
+  if (mu.n_elem != M) mu.resize(M, 1);
+  int rc = gpak_predict_local_ok(ctx, Xs.memptr(), ys.memptr(), (long)Xs.n_rows, (int)Xs.n_cols, Xd.memptr(), (long)M, nd,
+                                 nbr.data(), k, mean.memptr(), var.memptr(), mu.memptr(), latent ? GPAK_LOCAL_LATENT : 0, &summary);
+  if (rc != GPAK_OK) gpak_host_fatal("gpak_predict_local_ok", ctx);
+}
+
 void GP_utils::JointMeanCov(mat &mean, mat &cov, const mat &Xd, int nd, bool latent) const {
   sync_params();
   const size_t M = nd > 0 ? Xd.n_rows / nd : 0;

@@ -15,6 +15,7 @@
 #include "../../include/gpak_condition.h"
 #include "../../include/gpak_design.h"
 #include "../../include/gpak_local.h"
+#include "../../include/gpak_local_ok.h"
 #include "kernels.hpp"
 
 class ModelInfo {
@@ -159,6 +160,12 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
                               std::vector<int> &used);
   void LocalMeanVar(mat &mean, mat &var, const mat &Xs, const mat &ys, const mat &Xd, int nd, const std::vector<int> &nbr, int k,
                     bool latent, gpak_local_summary &summary) const;
+  // the same with ordinary kriging (gpak_predict_local_ok), mu the local means; LocalNeighboursOctant: at most per_octant
+  // samples from each octant around a centre inside the radius, of those the k nearest (gpak_local_neighbours_octant)
+  static void LocalNeighboursOctant(const mat &Xs, const mat &Xc, const double G[16], int k, int per_octant, double radius,
+                                    std::vector<int> &nbr, std::vector<int> &used);
+  void LocalMeanVarOk(mat &mean, mat &var, mat &mu, const mat &Xs, const mat &ys, const mat &Xd, int nd, const std::vector<int> &nbr,
+                      int k, bool latent, gpak_local_summary &summary) const;
   // infill drilling design (gpak_design): the gain of each of the H candidate holes (hole[i] in [0, H) for candidate point i
   // of Xc) on the target blocks Xd (nd points each; wt: one weight per block, or null) and a greedy plan of k of them;
   // false when the A_h of some hole is not positive definite; everything NaN on Chol_fail
