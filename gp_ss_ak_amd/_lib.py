@@ -46,6 +46,9 @@ DEV_LOCAL_SYMBOLS = ["gpak_dev_local_krige"]
 # every symbol include/gpak_local_ok.h / include/gpak_dev_local_ok.h declares (tests/test_local_ok.py checks the headers and these lists agree)
 LOCAL_OK_SYMBOLS = ["gpak_predict_local_ok", "gpak_local_neighbours_octant"]
 DEV_LOCAL_OK_SYMBOLS = ["gpak_dev_local_krige_ok"]
+# every symbol include/gpak_local_search.h / include/gpak_dev_local_search.h declares (tests/test_local_search.py checks the headers and these lists agree)
+LOCAL_SEARCH_SYMBOLS = ["gpak_local_neighbours_dev"]
+DEV_LOCAL_SEARCH_SYMBOLS = ["gpak_dev_local_search"]
 # every symbol include/gpak_dev_f32.h declares (tests/test_dev_ops.py checks the header and this list agree)
 DEV_F32_SYMBOLS = ["gpak_dev_gemm_nt_f32", "gpak_dev_fill_f32", "gpak_dev_lower_to_f32", "gpak_dev_vec_to_f32",
                    "gpak_dev_rowsumsq_f32", "gpak_dev_fwd_subst_f32"]
@@ -85,6 +88,11 @@ class LocalSummary(C.Structure):
                 ("notpd", C.c_long), ("batches", C.c_int), ("max_used", C.c_int)]
 
 
+class LocalSearchSummary(C.Structure):
+    _fields_ = [("grid_ms", C.c_double), ("upload_ms", C.c_double), ("search_ms", C.c_double), ("centres", C.c_long),
+                ("cells", C.c_long), ("visited", C.c_ulonglong), ("batches", C.c_int), ("max_used", C.c_int)]
+
+
 _lib = None
 
 
@@ -101,14 +109,14 @@ def load():
     missing = [s for s in SYMBOLS + LOO_GRAD_SYMBOLS + CV_GROUPS_SYMBOLS + CV_FOLDS_SYMBOLS + CV_GROUPS_GRAD_SYMBOLS
                + CV_FOLDS_GRAD_SYMBOLS + DEV_CV_MIX_SYMBOLS + DESIGN_SYMBOLS + DEV_DESIGN_SYMBOLS + CONDITION_SYMBOLS + DEV_CONDITION_SYMBOLS
                + DEV_F32_SYMBOLS + LOCAL_SYMBOLS + DEV_LOCAL_SYMBOLS + DEV_CV_KERNELS_SYMBOLS
-               + LOCAL_OK_SYMBOLS + DEV_LOCAL_OK_SYMBOLS
+               + LOCAL_OK_SYMBOLS + DEV_LOCAL_OK_SYMBOLS + LOCAL_SEARCH_SYMBOLS + DEV_LOCAL_SEARCH_SYMBOLS
                if not hasattr(lib, s)]
     if missing:
         raise RuntimeError("libgpak_hip.so lacks symbols declared in include/gpak.h / gpak_loo_grad.h / "
                            "gpak_cv_groups.h / gpak_cv_folds.h / gpak_cv_groups_grad.h / gpak_cv_folds_grad.h / "
                            "gpak_dev_cv_mix.h / gpak_design.h / gpak_dev_design.h / gpak_condition.h / gpak_dev_condition.h / "
                            "gpak_dev_f32.h / gpak_local.h / gpak_dev_local.h / gpak_dev_cv_kernels.h / gpak_local_ok.h / "
-                           f"gpak_dev_local_ok.h: {missing}")
+                           f"gpak_dev_local_ok.h / gpak_local_search.h / gpak_dev_local_search.h: {missing}")
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
     lib.gpak_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
@@ -189,6 +197,11 @@ def load():
                                                  ip, ip]
     lib.gpak_dev_local_krige_ok.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, dp, C.c_double, C.c_int,
                                             C.c_double, C.c_double, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    # include/gpak_local_search.h; include/gpak_dev_local_search.h: the stream first, every pointer a device pointer
+    lib.gpak_local_neighbours_dev.argtypes = [vp, dp, C.c_long, C.c_int, dp, C.c_long, dp, C.c_int, C.c_double, ip, ip, dp,
+                                              C.POINTER(LocalSearchSummary)]
+    lib.gpak_dev_local_search.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]
     # include/gpak_dev_cv_kernels.h: the stream first, every pointer a device pointer
     i, l, d = C.c_int, C.c_long, C.c_double
     lib.gpak_dev_cvg_gram.argtypes = [vp, vp, l, i, vp, vp, i, vp, vp]

@@ -1,5 +1,6 @@
 // local_search.cpp -- gpak_local_neighbours and gpak_local_neighbours_octant: see local_search.h.  No HIP in this file.
 #include "local_search.h"
+#include "local_grid.h"   // transform_point, Grid, build_grid: shared with the device search
 
 #include <algorithm>
 #include <climits>
@@ -10,92 +11,9 @@
 
 namespace {
 
-// t = x G, the arithmetic local_search.h states (a test restates it in NumPy and expects the same bytes)
-inline void transform_point(const double *X, long n, long i, int d, const double *G, double *t) {
-  if (!G) {
-    for (int j = 0; j < d; j++) t[j] = X[i + (size_t)j * n];
-    return;
-  }
-  for (int j = 0; j < d; j++) {
-    double s = X[i] * G[(size_t)d * j];
-    for (int r = 1; r < d; r++) s = s + X[i + (size_t)r * n] * G[r + (size_t)d * j];
-    t[j] = s;
-  }
-}
-
-struct Grid {
-  int d = 3;
-  double lo[3] = {0, 0, 0}, h = 1.0, scale = 0.0;
-  int n[3] = {1, 1, 1};
-  std::vector<long> start;     // n0 n1 n2 + 1
-  std::vector<double> pts;     // the transformed samples in cell order, d per sample
-  std::vector<int> ids;        // their indices: ascending inside a cell
-  int cell_of(const double *t, int i) const {
-    const double f = std::floor((t[i] - lo[i]) / h);
-    return f <= 0.0 ? 0 : (f >= (double)(n[i] - 1) ? n[i] - 1 : (int)f);
-  }
-  size_t cell_index(int a0, int a1, int a2) const { return ((size_t)a0 * n[1] + a1) * n[2] + a2; }
-};
-
-bool build_grid(const double *Xs, long Ns, int d, const double *G, Grid &g) {
-  g.d = d;
-  std::vector<double> T((size_t)Ns * d);
-  double hi[3] = {0, 0, 0};
-  for (long i = 0; i < Ns; i++) {
-    double *t = &T[(size_t)i * d];
-    transform_point(Xs, Ns, i, d, G, t);
-    for (int j = 0; j < d; j++)
-      if (!std::isfinite(t[j])) return false;
-    for (int j = 0; j < 3; j++) {
-      if (i == 0 || t[j] < g.lo[j]) g.lo[j] = t[j];
-      if (i == 0 || t[j] > hi[j]) hi[j] = t[j];
-    }
-  }
-  double ext[3], vol = 1.0;
-  int m = 0;
-  for (int j = 0; j < 3; j++) {
-    ext[j] = hi[j] - g.lo[j];
-    if (!std::isfinite(ext[j])) return false;
-    if (ext[j] > 0.0) { vol *= ext[j]; m++; }
-    g.scale = std::max(g.scale, std::max(std::fabs(g.lo[j]), std::fabs(hi[j])));
-  }
-  // about four samples per cell over the dimensions that have an extent
-  const double cells = std::max(1.0, (double)Ns / 4.0);
-  g.h = m ? std::pow(vol / cells, 1.0 / m) : 1.0;
-  if (!(g.h > 0.0) || !std::isfinite(g.h)) g.h = 1.0;
-  // the cells grow until no dimension has more than 4096 of them and the grid no more than about 8 per sample.  No count is
-  // ever capped: a sample's cell is floor((t - lo) / h) in every dimension, which the ring bound of search_one relies on
-  for (;;) {
-    double total = 1.0, most = 1.0;
-    for (int j = 0; j < 3; j++) {
-      const double c = ext[j] > 0.0 ? std::floor(ext[j] / g.h) + 1.0 : 1.0;
-      most = std::max(most, c);
-      total *= c;
-      g.n[j] = c <= 4096.0 ? (int)c : 4096;
-    }
-    if (most <= 4096.0 && total <= 8.0 * (double)Ns + 64.0) break;
-    g.h *= 1.26;
-  }
-  const size_t nc = (size_t)g.n[0] * g.n[1] * g.n[2];
-  g.start.assign(nc + 1, 0);
-  std::vector<size_t> cell((size_t)Ns);
-  for (long i = 0; i < Ns; i++) {
-    const double *t = &T[(size_t)i * d];
-    const size_t c = g.cell_index(g.cell_of(t, 0), g.cell_of(t, 1), g.cell_of(t, 2));
-    cell[i] = c;
-    g.start[c + 1]++;
-  }
-  for (size_t c = 0; c < nc; c++) g.start[c + 1] += g.start[c];
-  std::vector<long> at(g.start.begin(), g.start.end() - 1);
-  g.pts.resize((size_t)Ns * d);
-  g.ids.resize((size_t)Ns);
-  for (long i = 0; i < Ns; i++) {   // ascending i: a cell's samples stay in index order
-    const long p = at[cell[i]]++;
-    g.ids[p] = (int)i;
-    for (int j = 0; j < d; j++) g.pts[(size_t)p * d + j] = T[(size_t)i * d + j];
-  }
-  return true;
-}
+using gpak_local_grid::Grid;
+using gpak_local_grid::build_grid;
+using gpak_local_grid::transform_point;
 
 // Every sample inside `radius` (all of them when radius <= 0) is handed to take(dist2, index, octant), ring by ring of
 // cells around the centre's cell, until stop(lb) says that no sample at least lb >= 0 away is wanted any more.  The octant

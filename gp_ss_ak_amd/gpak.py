@@ -375,6 +375,31 @@ class Gpak:
                                                  LOCAL_LATENT if latent else 0, C.byref(s)))
         return mean, var, {f: getattr(s, f) for f, _ in s._fields_}
 
+    def local_neighbours_dev(self, Xs, Xc, k, G=None, radius=0.0, want_dist2=False):
+        """local_neighbours with the search on this context's device (gpak_local_neighbours_dev): the same lists, byte for
+        byte.  Returns (nbr, used, dist2, summary): nbr and used as local_neighbours returns them, dist2 (M x k, None
+        unless asked for) the squared distance of every listed sample and 0.0 in the unused slots, summary a dict of
+        gpak_local_search_summary.  The context needs neither parameters nor a training set."""
+        Xs, Xc = _f(Xs), _f(Xc)
+        if Xs.ndim != 2 or Xc.ndim != 2 or Xs.shape[1] != Xc.shape[1]:
+            raise GpakError(EINVAL, "Xs and Xc must be matrices with as many columns")
+        d, M, k = Xs.shape[1], Xc.shape[0], int(k)
+        if G is not None:
+            G = np.asarray(G, dtype=np.float64)
+            if G.shape == (4, 4) and d == 3:
+                G = G[:3, :3]
+            if G.shape != (d, d):
+                raise GpakError(EINVAL, "G must be d x d (or the 4 x 4 of local_metric)")
+            G = np.asfortranarray(G)
+        nbr = np.full((max(M, 0), max(k, 0)), -1, dtype=np.int32)
+        used = np.zeros(max(M, 0), dtype=np.int32)
+        dist2 = np.zeros((max(M, 0), max(k, 0))) if want_dist2 else None
+        ip = C.POINTER(C.c_int)
+        s = _lib.LocalSearchSummary()
+        self._check(self._lib.gpak_local_neighbours_dev(self._h, _p(Xs), Xs.shape[0], d, _p(Xc), M, _p(G), k, float(radius),
+                                                        nbr.ctypes.data_as(ip), used.ctypes.data_as(ip), _p(dist2), C.byref(s)))
+        return nbr, used, dist2, {f: getattr(s, f) for f, _ in s._fields_}
+
     def predict_local_ok(self, Xs, ys, Xd, nd, nbr, want_var=True, want_mu=False, latent=False):
         """Ordinary kriging in a moving neighbourhood (gpak_predict_local_ok): the arguments of predict_local; the mean is
         re-estimated from every node's own samples and the weights sum to one.  Returns (mean, var, mu, summary), mu the

@@ -89,6 +89,11 @@ Control::Control(int arc, char **arv) : argc(arc), argv(arv) {
       local_kriging = getArgNo() < argc ? getArg() : std::string();   // the `local` verb refuses what is not simple or ordinary
       local_kriging_set = true;
     }
+    else if (isArg("--search", "--search")) {
+      incArg();
+      local_search = getArgNo() < argc ? getArg() : std::string();    // the `local` verb refuses what is not host or device
+      local_search_set = true;
+    }
     else if (isArg("--octant", "--octant")) {
       incArg();
       char *end = nullptr;

@@ -78,6 +78,9 @@ class Control {
   std::string local_kriging = "simple";
   long local_octant = 0;
   bool local_kriging_set = false, local_octant_set = false;
+  // --search host|device (device: the lists come from gpak_local_neighbours_dev; the octant search stays on the host)
+  std::string local_search = "host";
+  bool local_search_set = false;
   std::string mode = "gp";
   mat params, MinData, MaxData, MeanData, StData;
   double MaxTotalin = 0, MinTotalin = 0, MaxTotalo = 0, MinTotalo = 0;

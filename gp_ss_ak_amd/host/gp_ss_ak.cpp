@@ -7,7 +7,7 @@
 //   gp_ss_ak [-v n] --block-size dx,dy,dz --block-disc nx,ny,nz [--latent] block blocks.txt model train.txt [out_file]
 //   gp_ss_ak [-v n] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] [--nugget v] --realisations S (--seed n | --xi file)
 //            sim [--method joint|path [--features F]] nodes.txt model train.txt [out_file]
-//   gp_ss_ak [-v n] --neighbours k [--radius r] [--octant n] [--kriging simple|ordinary]
+//   gp_ss_ak [-v n] --neighbours k [--radius r] [--octant n] [--kriging simple|ordinary] [--search host|device]
 //            [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes.txt model train.txt [out_file]
 // device options (not reference flags): --gpus n (multi-GPU context), --precision f64|f32
 // (fp32 prediction work), --timing file|- (JSON of the context's phase times after the verb), --gradient reference|exact
@@ -111,6 +111,7 @@ class GP_Cntrl : public Control {
   void local();
   void localOptionsOnlyWithLocal() const {
     if (local_kriging_set || local_octant_set) ErrorTermination("--kriging and --octant are options of the local verb");
+    if (local_search_set) ErrorTermination("--search is an option of the local verb");
   }
   void Help() const;
 };
@@ -121,7 +122,7 @@ void GP_Cntrl::Help() const {
             << "test :\n \t To estimate test data set and plot the results.\n"
             << "cv :\n \t To cross-validate a trained model on its training data, leaving one sample out at a time (--groups file: one group of samples at a time; --folds file / --kfold K [--seed n]: groups of any size, k folds).\n"
             << "design :\n \t To rank candidate drill holes by the estimation variance they would remove from targets ([--block-size dx,dy,dz --block-disc nx,ny,nz] [--pick k] [--weights file] design --candidates file --holes file targets model train).\n"
-            << "local :\n \t To estimate nodes or blocks from the k nearest of any number of samples (--neighbours k [--radius r] [--octant n: at most n samples per octant, needs --radius] [--kriging simple|ordinary: ordinary re-estimates the mean from every node's own samples] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes model samples).\n"
+            << "local :\n \t To estimate nodes or blocks from the k nearest of any number of samples (--neighbours k [--radius r] [--octant n: at most n samples per octant, needs --radius] [--kriging simple|ordinary: ordinary re-estimates the mean from every node's own samples] [--search host|device: device searches the neighbours on the GPU, the same lists; not with --octant] [--block-size dx,dy,dz --block-disc nx,ny,nz] [--latent] local nodes model samples).\n"
             << "block :\n \t To estimate the average over blocks (--block-size dx,dy,dz --block-disc nx,ny,nz [--latent]) and its standard deviation.\n"
             << "sim :\n \t To draw realisations at nodes or blocks given the data (--realisations S and --seed n or --xi file; [--nugget v] [--latent]; sim --method path [--features F] with --seed n: any number of nodes, the prior from F random frequencies per term).\n";
 }
@@ -634,7 +635,8 @@ void GP_Cntrl::block() {
 
 // local (not a reference verb): moving-neighbourhood kriging (gpak_predict_local; one GPU only) -- every node from its k
 // nearest samples, so train.txt may hold any number of them (train on a subsample, estimate from all the assays):
-//   gp_ss_ak --neighbours k [--radius r] [--octant n] [--kriging simple|ordinary] [--block-size dx,dy,dz --block-disc nx,ny,nz]
+//   gp_ss_ak --neighbours k [--radius r] [--octant n] [--kriging simple|ordinary] [--search host|device]
+//            [--block-size dx,dy,dz --block-disc nx,ny,nz]
 //            [--latent] local nodes.txt model train.txt [out]
 // nodes.txt is read as block reads its centres (without the two block options the nodes are points); train.txt is
 // standardised with the model's _Statistics.txt.  The neighbours are searched from the node centres in the metric of the
@@ -642,7 +644,8 @@ void GP_Cntrl::block() {
 // before a context exists.  Written to <model>_local.txt in input order.  --octant n keeps at most n samples from each of
 // the eight octants around a node (gpak_local_neighbours_octant; it needs --radius, and 1 <= n <= k).  --kriging ordinary
 // re-estimates the mean from every node's own samples (gpak_predict_local_ok) and adds the column LocalMean; a node
-// without a sample then has no estimate and prints nan.
+// without a sample then has no estimate and prints nan.  --search device takes the lists from the device search
+// (gpak_local_neighbours_dev): the same lists, so the same file; the octant search stays on the host.
 void GP_Cntrl::local() {
   incArg();
   setMode("local");
@@ -667,7 +670,10 @@ void GP_Cntrl::local() {
     ErrorTermination("--octant needs --radius: the octant search looks for samples inside a radius only");
   if (local_octant_set && (local_octant < 1 || local_octant > local_neighbours))
     ErrorTermination("--octant takes the samples per octant, between 1 and --neighbours");
-  const bool ordinary = local_kriging == "ordinary";
+  if (local_search != "host" && local_search != "device") ErrorTermination("--search takes host or device");
+  if (local_search == "device" && local_octant_set)
+    ErrorTermination("--search device does not take --octant: the octant search runs on the host");
+  const bool ordinary = local_kriging == "ordinary", search_dev = local_search == "device";
   if (getArgNo() + 2 >= argc)
     ErrorTermination("There are not enough input parameters: local needs the nodes, the model and the samples.");
   std::string ndFile = getArg(), modelName = argv[getArgNo() + 1], trFile = argv[getArgNo() + 2];
@@ -700,7 +706,9 @@ void GP_Cntrl::local() {
   GPModel->LocalMetric(G);
   std::vector<int> nbr, used;
   const auto t0 = std::chrono::steady_clock::now();
-  if (local_octant_set) GP_utils::LocalNeighboursOctant(Xtr, C, G, k, (int)local_octant, local_radius, nbr, used);
+  gpak_local_search_summary ss;
+  if (search_dev) GPModel->LocalNeighboursDev(Xtr, C, G, k, local_radius_set ? local_radius : 0.0, nbr, used, ss);
+  else if (local_octant_set) GP_utils::LocalNeighboursOctant(Xtr, C, G, k, (int)local_octant, local_radius, nbr, used);
   else GP_utils::LocalNeighbours(Xtr, C, G, k, local_radius_set ? local_radius : 0.0, nbr, used);
   const double search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   mat LocalVals(y.n_rows, 1), LocalVals_Var(y.n_rows, 1), LocalMu(ordinary ? y.n_rows : 0, 1);
@@ -716,7 +724,11 @@ void GP_Cntrl::local() {
               << (local_octant_set ? ", " + std::to_string(local_octant) + " per octant" : std::string())
               << (ordinary ? ", ordinary kriging" : "")
               << (block_latent ? ", latent variance" : "") << "; without a neighbour " << s.empty << ", not positive definite "
-              << s.notpd << "; search " << search_ms << " ms, device " << (s.upload_ms + s.krige_ms) << " ms\n";
+              << s.notpd << "; search " << search_ms << " ms"
+              << (search_dev ? " on the device (grid " + std::to_string(ss.grid_ms) + " ms, upload " + std::to_string(ss.upload_ms) +
+                                   " ms, search " + std::to_string(ss.search_ms) + " ms)"
+                             : std::string())
+              << ", device " << (s.upload_ms + s.krige_ms) << " ms\n";
   // rows in input order; the fourth column is what postData_var returns, as StdYblock of _block.txt
   std::ofstream out(LocalOut.c_str());
   out << (ordinary ? "# NodeNo, Y, Ylocal, StdYlocal, Neighbours, LocalMean, Inputs" : "# NodeNo, Y, Ylocal, StdYlocal, Neighbours, Inputs")

@@ -268,6 +268,19 @@ void GP_utils::LocalNeighbours(const mat &Xs, const mat &Xc, const double G[16],
   }
 }
 
+void GP_utils::LocalNeighboursDev(const mat &Xs, const mat &Xc, const double G[16], int k, double radius, std::vector<int> &nbr,
+                                  std::vector<int> &used, gpak_local_search_summary &summary) const {
+  const int d = (int)Xs.n_cols;
+  std::vector<double> Gd((size_t)d * d);   // the leading d x d part
+  for (int c = 0; c < d; c++)
+    for (int r = 0; r < d; r++) Gd[r + (size_t)d * c] = G[r + 4 * c];
+  nbr.assign((size_t)k * Xc.n_rows, -1);
+  used.assign(Xc.n_rows, 0);
+  if (gpak_local_neighbours_dev(ctx, Xs.memptr(), (long)Xs.n_rows, d, Xc.memptr(), (long)Xc.n_rows, Gd.data(), k, radius, nbr.data(),
+                                used.data(), nullptr, &summary) != GPAK_OK)
+    gpak_host_fatal("gpak_local_neighbours_dev", ctx);
+}
+
 void GP_utils::LocalMeanVar(mat &mean, mat &var, const mat &Xs, const mat &ys, const mat &Xd, int nd, const std::vector<int> &nbr,
                             int k, bool latent, gpak_local_summary &summary) const {
   sync_params();

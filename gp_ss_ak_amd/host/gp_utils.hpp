@@ -16,6 +16,7 @@
 #include "../../include/gpak_design.h"
 #include "../../include/gpak_local.h"
 #include "../../include/gpak_local_ok.h"
+#include "../../include/gpak_local_search.h"
 #include "kernels.hpp"
 
 class ModelInfo {
@@ -158,6 +159,9 @@ class GP_utils : public Modeling, public Opt_Algs, public StreamIntfce {
   void LocalMetric(double G[16]) const;
   static void LocalNeighbours(const mat &Xs, const mat &Xc, const double G[16], int k, double radius, std::vector<int> &nbr,
                               std::vector<int> &used);
+  // LocalNeighboursDev: the same lists from the context's device (gpak_local_neighbours_dev)
+  void LocalNeighboursDev(const mat &Xs, const mat &Xc, const double G[16], int k, double radius, std::vector<int> &nbr,
+                          std::vector<int> &used, gpak_local_search_summary &summary) const;
   void LocalMeanVar(mat &mean, mat &var, const mat &Xs, const mat &ys, const mat &Xd, int nd, const std::vector<int> &nbr, int k,
                     bool latent, gpak_local_summary &summary) const;
   // the same with ordinary kriging (gpak_predict_local_ok), mu the local means; LocalNeighboursOctant: at most per_octant
