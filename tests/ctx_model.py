@@ -2,7 +2,8 @@
 
 ModelGpak has the method names of gp_ss_ak_amd.gpak.Gpak and no memory beyond the last training set, the last kernel call
 and the options: every answer is computed from those alone, on the CPU, from the references the suite already holds the
-single features to (the CPU checker in oracle/, exact_grad_ref, loo_ref, block_ref, joint_ref).  Results are cached by
+single features to (the CPU checker in oracle/, exact_grad_ref, loo_ref, block_ref, joint_ref; for the feature calls
+loo_grad_ref, cvg_ref, lgo_grad_ref, design_ref, path_ref, local_ref, local_ok_ref, local_search_ref).  Results are cached by
 (training set, kernel, operation), so a long sequence costs each distinct state once.  It restates the statuses the header
 promises (GPAK_ESTATE before a training set or parameters, GPAK_ENOTIMPL, GPAK_EINVAL, GPAK_ENOTPD with quiet NaN).
 
@@ -12,6 +13,7 @@ question from the state its flags point at.  Unmutated it equals ModelGpak step 
 one invalidation; tests/test_ctx_sequences.py proves on the CPU that every one of them is caught by a named sequence, i.e.
 that the sequences would notice the corresponding slip.  It logs the events it passes through under the names of
 CtxState's members: tests/test_ctx_state.py replays them through the C++ struct itself and compares the two, flag by flag.
+FEATURE_MUTATIONS (after the class) do the same for the feature calls, with FEATURE_REDUNDANT for a reset another one covers.
 
 GroupCaching does the same for a group (gpak_create_multi): the flags of csrc/multi.hip, RankCore::have_result of
 csrc/dist.hip and the replica contexts' flags, with GROUP_MUTATIONS; it also counts the evaluations gpak_timing reports.
@@ -258,7 +260,12 @@ class ModelGpak:
 
     def loo_grad(self, ng=10):
         self._single_only("gpak_loo_grad")
-        raise AssertionError("the sequences ask gpak_loo_grad of groups only (tests/test_loo_grad_gpu.py holds it to its reference)")
+        self._need()
+        self._grad_checks(ng)
+        nan = float("nan")
+        if self._fit()["col"]:
+            return np.full(int(ng), nan), dict(mse=nan, mssr=nan, log_pl=nan, ms=0.0, passes=0, status=ENOTPD)
+        return self._loo_grad()[0].copy(), self.loo()[2]
 
     def GradLL_exact(self, ng=10):
         self._single_only("gpak_grad_exact")
@@ -334,6 +341,213 @@ class ModelGpak:
     def timing(self):
         return None      # how often a context factored is not a function of its state: CachingModel counts
 
+    # -- the feature calls (include/gpak_loo_grad.h, gpak_cv_groups*.h, gpak_cv_folds*.h, gpak_design.h, gpak_condition.h,
+    # gpak_local*.h): stateless, on the references their own tests hold them to; the statuses in the order of csrc/api.hip --
+    def _loo_grad(self):
+        """(gradient, 1/2 sum |W|) of loo_grad_ref, as tests/loo_grad_model.py"""
+        import loo_grad_ref
+        k = self.kern
+
+        def build():
+            g, W = loo_grad_ref.grad_loo(self.X, self.y, self._terms(), k["bias"], k["sn2"], want_w=True)
+            return g, 0.5 * float(np.abs(W).sum())
+        return self._cached("loo_grad", build)
+
+    def _labels(self, labels, limit, what="group"):
+        values, group = np.unique(np.asarray(labels), return_inverse=True)
+        group = group.reshape(-1)
+        sizes = np.bincount(group)
+        if limit and sizes.max() > limit:
+            raise ModelError(EINVAL, f"a {what} has more than {limit} members")
+        return values, group, sizes
+
+    def _cv(self, name, labels, limit):
+        import cvg_ref
+        self._single_only(name)
+        self._need()
+        values, group, sizes = self._labels(labels, limit)
+        nan = float("nan")
+        if self._fit()["col"]:
+            return (np.full(self.N, nan), np.full(self.N, nan), np.full(sizes.size, nan),
+                    dict(mse=nan, mssr=nan, msmd=nan, log_pl=nan, ms=0.0, groups=int(sizes.size), max_size=0, status=ENOTPD, labels=values))
+
+        def build():
+            mean, var, logp, md = cvg_ref.cv_groups(self._fit()["K"], self.y, self.kern["sn2"], group)
+            return mean, var, logp, cvg_ref.summary(self.y, mean, var, logp, md)
+        mean, var, logp, s = self._cached(("cv", _digest(group)), build)
+        return mean.copy(), var.copy(), logp.copy(), dict(s, ms=0.0, groups=int(sizes.size), max_size=int(sizes.max()), status=OK, labels=values)
+
+    def cv_groups(self, labels):
+        return self._cv("gpak_cv_groups", labels, 128)
+
+    def cv_folds(self, labels, no_batch=False):
+        return self._cv("gpak_cv_folds", labels, 0)
+
+    def _cv_grad_ref(self, group):
+        """(gradient, 1/2 sum |W|) of lgo_grad_ref on the direct-form Gram matrix, as tests/lgo_grad_model.py"""
+        import lgo_grad_ref
+        k = self.kern
+
+        def build():
+            g, W = lgo_grad_ref.grad_lgo(self.X, self.y, self._terms(), k["bias"], k["sn2"], group, want_w=True)
+            return g, 0.5 * float(np.abs(W).sum())
+        return self._cached(("cv_grad", _digest(group)), build)
+
+    def _cv_grad(self, name, labels, ng, limit):
+        self._single_only(name)
+        self._need()
+        self._grad_checks(ng)
+        values, group, sizes = self._labels(labels, limit)
+        nan = float("nan")
+        if self._fit()["col"]:
+            return np.full(int(ng), nan), dict(mse=nan, mssr=nan, msmd=nan, log_pl=nan, ms=0.0, groups=int(sizes.size), max_size=0,
+                                               status=ENOTPD, labels=values)
+        return self._cv_grad_ref(group)[0].copy(), self._cv(name, labels, 0)[3]
+
+    def cv_groups_grad(self, labels, ng=10):
+        return self._cv_grad("gpak_cv_groups_grad", labels, ng, 128)
+
+    def cv_folds_grad(self, labels, ng=10, no_batch=False):
+        return self._cv_grad("gpak_cv_folds_grad", labels, ng, 0)
+
+    def design(self, Xt, nd, Xc, holes, weights=None, pick=0, want_reduction=False):
+        import design_ref
+        self._single_only("gpak_design")
+        self._need()
+        Xt, Xc, nd, k = np.asfortranarray(Xt, dtype=float), np.asfortranarray(Xc, dtype=float), int(nd), int(pick)
+        if Xc.shape[1] != Xt.shape[1] or Xt.shape[1] != self.d:
+            raise ModelError(EINVAL, "target and candidate points must have as many columns as the training set")
+        values, hole, sizes = self._labels(holes, 128, "hole")
+        T, H = Xt.shape[0] // nd, int(sizes.size)
+        wt = None if weights is None else np.asarray(weights, dtype=float).ravel()
+        if wt is not None and not np.all(np.isfinite(wt) & (wt >= 0.0)):
+            raise ModelError(EINVAL, "a weight is negative or not finite")
+        if not 0 <= k <= H:
+            raise ModelError(EINVAL, "k is outside [0, H]")
+        nan = float("nan")
+        if self._fit()["col"]:
+            s = dict(var_before=nan, var_after=nan, ms=0.0, holes=H, max_size=0, picks=0, status=ENOTPD, labels=values)
+            return (np.full(H, nan), np.full(k, -1, dtype=np.int32), np.full(k, nan),
+                    {"reduction": np.full((T, H), nan) if want_reduction else None, "var": np.full(T, nan), "var_after": np.full(T, nan),
+                     "summary": s})
+        kn = self.kern
+        r = self._cached(("design", _digest(Xt), nd, _digest(Xc), _digest(hole), None if wt is None else _digest(wt), k),
+                         lambda: design_ref.design(self.X, Xt, nd, Xc, hole, self._terms(), kn["bias"], kn["white"], kn["sn2"], wt=wt, k=k))
+        f = lambda a: np.asarray(a).astype(float)      # noqa: E731
+        s = dict(var_before=float(r["var_before"]), var_after=float(r["var_after_sum"]), ms=0.0, holes=H, max_size=int(sizes.max()), picks=k,
+                 status=OK, labels=values)
+        return (f(r["gain"]), np.array(r["picked"], dtype=np.int32), f(r["pick_gain"]).reshape(k),
+                {"reduction": f(r["reduction"]) if want_reduction else None, "var": f(r["var"]), "var_after": f(r["var_after"]), "summary": s,
+                 "gaps": design_ref.pick_gaps(r["rounds"]), "weight_sum": float(T if wt is None else wt.sum())})
+
+    def _nodes(self, name, Xd, nd):
+        """the prologue of gpak_condition / gpak_sample_path: a training set, then the columns (parameters: ensure_nlz)"""
+        self._single_only(name)
+        Xd = np.asfortranarray(Xd, dtype=float)
+        if self.X is None:
+            raise ModelError(ESTATE, "no training set")
+        if Xd.shape[1] != self.d:
+            raise ModelError(EINVAL, "block points must have as many columns as the training set")
+        return Xd, Xd.shape[0] // int(nd), int(nd)
+
+    def path_model(self, Xd, nd):
+        import path_ref
+        k = self.kern
+        return self._cached(("path", _digest(Xd), int(nd)), lambda: path_ref.Model(self.X, self.y, Xd, int(nd), self._terms(), k["bias"],
+                                                                                  k["white"], k["sn2"]))
+
+    def _conditioned(self, Xd, M, nd, S, unfused, key, fn):
+        nan = float("nan")
+        s = dict(solve_ms=0.0, prior_ms=0.0, product_ms=0.0, batches=0, fused=0 if unfused else 1)
+        if self._fit()["col"]:
+            return np.full((M, S), nan), np.full(M, nan), dict(s, status=ENOTPD)
+        Z, mean = self._cached(key, lambda: tuple(np.asarray(a).astype(float) for a in fn(self.path_model(Xd, nd))))
+        return Z.copy(), mean.copy(), dict(s, status=OK)
+
+    def condition(self, Xd, nd, Ysim, Fsim=None, unfused=False):
+        Xd, M, nd = self._nodes("gpak_condition", Xd, nd)
+        self._need()
+        Ysim = np.asarray(Ysim, dtype=float).reshape(self.N, -1)
+        key = ("condition", _digest(Xd), nd, _digest(Ysim), None if Fsim is None else _digest(Fsim))
+        return self._conditioned(Xd, M, nd, Ysim.shape[1], unfused, key, lambda pm: pm.condition(Ysim, Fsim))
+
+    def sample_path(self, Xd, nd, feat_term, omega, ab, b0, E, unfused=False):
+        Xd, M, nd = self._nodes("gpak_sample_path", Xd, nd)
+        self._need()
+        ft = np.asarray(feat_term).ravel()
+        if ft.min() < 0 or ft.max() >= len(self.kern["terms"]):
+            raise ModelError(EINVAL, "a feature names a term outside the composition")
+        if b0 is None and self.kern["bias"] != 0.0:
+            raise ModelError(EINVAL, "b0 is NULL and the constant is not 0")
+        ab = np.asarray(ab, dtype=float).reshape(2 * ft.size, -1)
+        key = ("path draw", _digest(Xd), nd, _digest(ft), _digest(omega), _digest(ab), None if b0 is None else _digest(b0), _digest(E))
+        return self._conditioned(Xd, M, nd, ab.shape[1], unfused, key, lambda pm: pm.sample_path(ft, omega, ab, b0, E))
+
+    def _local_pre(self, name, Xs, Xd):
+        self._single_only(name)
+        Xs, Xd = np.asfortranarray(Xs, dtype=float), np.asfortranarray(Xd, dtype=float)
+        if Xd.shape[1] != Xs.shape[1]:
+            raise ModelError(EINVAL, "Xd has as many columns as Xs")
+        if Xs.shape[1] not in (3, 4) or (self.X is not None and Xs.shape[1] != self.d):
+            raise ModelError(ENOTIMPL, "the samples have 3 or 4 columns, as many as the context's training set")
+        if self.kern is None:
+            raise ModelError(ESTATE, "no parameters")
+        return Xs, Xd
+
+    def _local_cached(self, what, Xs, ys, Xd, nd, nbr, fn):
+        k = self.kern
+        key = (None, self.kkey[:4], (what, _digest(Xs), _digest(ys), _digest(Xd), int(nd), _digest(nbr)))   # the direct form whatever the mode
+        if key not in self.cache:
+            self.cache[key] = fn(Xs, ys, Xd, int(nd), nbr, self._terms(), k["bias"], k["white"], k["sn2"])
+        return self.cache[key]
+
+    def local_metric(self, term=0):
+        """G with |(x - x') G|^2 = D2 of the term (any such G: the answers are compared through D2, see cs.model_errors)"""
+        import path_ref
+        self._single_only("gpak_local_metric")
+        if self.kern is None:
+            raise ModelError(ESTATE, "no parameters")
+        if not 0 <= int(term) < len(self.kern["terms"]):
+            raise ModelError(EINVAL, "term is outside the composition")
+        kind, p = self.kern["terms"][int(term)]
+        G = np.zeros((4, 4))
+        if kind == xref.EXPANS:
+            G[:3, :3] = np.asarray(xref.expans_metric([float(v) for v in p])[0], dtype=float)
+            G[3, 3] = p[7]
+        else:
+            G[np.arange(4), np.arange(4)] = 1.0 / p[0]
+        return G
+
+    def predict_local(self, Xs, ys, Xd, nd, nbr, want_var=True, latent=False):
+        import local_ref
+        Xs, Xd = self._local_pre("gpak_predict_local", Xs, Xd)
+        r = self._local_cached("local", Xs, ys, Xd, nd, nbr, local_ref.local_predict)
+        f = lambda a: np.asarray(a).astype(float)      # noqa: E731
+        s = dict(nodes=int(r["used"].size), empty=int((r["used"] == 0).sum()), notpd=int(r["notpd"].sum()), max_used=int(r["used"].max()))
+        return f(r["mean"]), (f(r["latent"] if latent else r["var"]) if want_var else None), s
+
+    def predict_local_ok(self, Xs, ys, Xd, nd, nbr, want_var=True, want_mu=False, latent=False):
+        import local_ok_ref
+        Xs, Xd = self._local_pre("gpak_predict_local_ok", Xs, Xd)
+        r = self._local_cached("local ok", Xs, ys, Xd, nd, nbr, local_ok_ref.local_predict_ok)
+        f = lambda a: np.asarray(a).astype(float)      # noqa: E731
+        s = dict(nodes=int(r["used"].size), empty=int((r["used"] == 0).sum()), notpd=int(r["notpd"].sum()), max_used=int(r["used"].max()))
+        return f(r["mean"]), (f(r["latent"] if latent else r["var"]) if want_var else None), (f(r["mu"]) if want_mu else None), s
+
+    def local_neighbours_dev(self, Xs, Xc, k, G=None, radius=0.0, want_dist2=False):
+        import local_ref
+        import local_search_ref as sr
+        self._single_only("gpak_local_neighbours_dev")
+        Xs, Xc = np.asfortranarray(Xs, dtype=float), np.asfortranarray(Xc, dtype=float)
+        if Xs.shape[1] != Xc.shape[1] or Xs.shape[1] not in (3, 4) or not 1 <= int(k) <= 128:
+            raise ModelError(EINVAL, "the samples have 3 or 4 columns, k is in 1..128")
+        key = (None, None, ("search", _digest(Xs), _digest(Xc), int(k), None if G is None else _digest(G), float(radius)))
+        if key not in self.cache:
+            nbr, used = local_ref.brute_neighbours(Xs, Xc, int(k), G, radius)
+            self.cache[key] = (nbr, used, sr.dist2_lists(sr.transform(Xs, G), sr.transform(Xc, G), nbr))
+        nbr, used, d2 = self.cache[key]
+        return nbr.copy(), used.copy(), (d2.copy() if want_dist2 else None), dict(max_used=int(used.max()))
+
 
 # -------------------------------------------------------------------------------------------------------------------------
 def _spoil(out):
@@ -342,8 +556,8 @@ def _spoil(out):
         return tuple(_spoil(o) for o in out)
     if isinstance(out, dict):
         return {k: (v if k in ("status", "passes", "ms") else _spoil(v)) for k, v in out.items()}
-    if out is None or isinstance(out, (bool, np.bool_)):
-        return out
+    if out is None or isinstance(out, (bool, np.bool_, int, np.integer, list)) or (isinstance(out, np.ndarray) and out.dtype.kind in "iu"):
+        return out                                # counts, labels, lists of hole numbers: the wrong buffer does not change them
     return np.asarray(out, dtype=float) * (1.0 + 1e-3) if isinstance(out, np.ndarray) else out * (1.0 + 1e-3)
 
 
@@ -357,7 +571,7 @@ class CachingModel(ModelGpak):
 
     def __init__(self, precision=F64, cache=None, mut=()):
         super().__init__(precision, cache)
-        unknown = [m for m in mut if m not in MUTATIONS]
+        unknown = [m for m in mut if m not in MUTATIONS + FEATURE_MUTATIONS + FEATURE_REDUNDANT]
         assert not unknown, unknown
         self.mut = set(mut)
         self.states = {}
@@ -647,8 +861,67 @@ class CachingModel(ModelGpak):
             return ModelGpak.sample_joint(self, Xd, nd, xi, nugget, latent)
         return self._answer("sample_joint", "nlz", ("aS", "fS"), ("alpha", "factor"), Xd, nd, xi, nugget, latent)
 
+    # -- the feature calls: csrc/api.hip refuses from the current state alone (single_gpu_call, the layout of the gradient, the
+    # labels, the columns), then ensure_nlz, then the _impl, which reads the factor, alpha and the training points and raises no
+    # event -- but gpak_condition_impl, whose solve runs through dWork (work_vectors_overwritten, csrc/condition.hip) ---------
+    def _feature(self, name, *a, **k):
+        probe = getattr(ModelGpak, name)(self._at(self._cur()), *a, **k)      # a refusal raises here, before anything is built
+        mutation = f"{name} answers from the factor as it stands"
+        if mutation in self.mut and self.nS is None:
+            # no ensure_nlz: the _impl reads dM / dAlpha as the last call that built them left them
+            self.dropped.append((mutation, self.bufA))
+            if self.bufA is None or self.states[self.bufA][0] is None or self.states[self.bufA][0].shape != self.X.shape:
+                return _spoil(probe)              # nothing there, or of another size: not the right numbers
+            return getattr(ModelGpak, name)(self._at(self.bufA), *a, **k)
+        rc = self._ensure_nlz()
+        out = self._answer(name, "nlz", ("aS", "fS"), ("alpha", "factor"), *a, rc=rc, **k)
+        if rc == OK and self.kern["mode"] == DIST_EXPANSION and f"{name} leaks pooled mean" in self.mut and self.uS is not None:
+            self.dropped.append((f"{name} leaks pooled mean", self.uS))
+            self.taint.add("U")                   # U re-centred on the mean pooled with the call's own points
+        if rc == OK and name in ("condition", "sample_path"):
+            if "condition keeps z" in self.mut:
+                self.dropped.append(("condition keeps z", self.fS))
+                self.z_clobbered = self.z_ok      # alpha is built first and has consumed z: z_ok is down already
+            else:
+                self.z_ok = False
+                self.events.append("work_vectors_overwritten")
+        return out
+
+    def loo_grad(self, ng=10):
+        return self._feature("loo_grad", ng)
+
+    def cv_groups(self, labels):
+        return self._feature("cv_groups", labels)
+
+    def cv_groups_grad(self, labels, ng=10):
+        return self._feature("cv_groups_grad", labels, ng)
+
+    def cv_folds(self, labels, no_batch=False):
+        return self._feature("cv_folds", labels, no_batch)
+
+    def cv_folds_grad(self, labels, ng=10, no_batch=False):
+        return self._feature("cv_folds_grad", labels, ng, no_batch)
+
+    def design(self, Xt, nd, Xc, holes, weights=None, pick=0, want_reduction=False):
+        return self._feature("design", Xt, nd, Xc, holes, weights, pick, want_reduction)
+
+    def condition(self, Xd, nd, Ysim, Fsim=None, unfused=False):
+        return self._feature("condition", Xd, nd, Ysim, Fsim, unfused)
+
+    def sample_path(self, Xd, nd, feat_term, omega, ab, b0, E, unfused=False):
+        return self._feature("sample_path", Xd, nd, feat_term, omega, ab, b0, E, unfused)
+
     def timing(self):
         return {"evaluations": self.evals}
+
+
+# Each name drops the bring-up-to-date (ensure_nlz) of ONE factor-dependent feature call, or lets a call that pools a mean with
+# its own points write the re-centred training points into U (EXPANSION form).  FEATURE_REDUNDANT: gpak_condition's
+# work_vectors_overwritten comes after ensure_nlz, whose back substitution has consumed z already: dropping it changes nothing.
+FEATURE_FACTOR_CALLS = ("cv_groups", "cv_groups_grad", "cv_folds", "cv_folds_grad", "design", "condition", "sample_path")
+FEATURE_MUTATIONS = tuple(f"{m} answers from the factor as it stands" for m in FEATURE_FACTOR_CALLS) + \
+    ("design leaks pooled mean", "condition leaks pooled mean")
+FEATURE_REDUNDANT = ("condition keeps z",)
 
 
 # -------------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE: runs the sequences of one group of tests/ctx_sequences.py on libgpak_hip.so in THIS process.
 
     python tests/ctx_seq_worker.py --group {memo,gram,walk,...} --out FILE.npz
+    python tests/ctx_seq_worker.py --group {f-cv,f-scratch,...} --out FILE.npz                      (cs.FEATURE_SEQUENCES)
     python tests/ctx_seq_worker.py --group {g-count,g-late2,...} --ranks P --out FILE.npz          (groups of up to P ranks on device 0)
     python tests/ctx_seq_worker.py --group {g-count,...} --ranks P --engine numpy --out FILE.npz   (no GPU: see below)
 
@@ -53,7 +54,7 @@ def engine_group(P):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--group", choices=cs.GROUPS + list(cs.WORKER_GROUPS), required=True)
+    ap.add_argument("--group", choices=cs.GROUPS + list(cs.WORKER_GROUPS) + cs.FEATURE_GROUPS, required=True)
     ap.add_argument("--ranks", type=int, default=0)
     ap.add_argument("--engine", choices=["hip", "numpy"], default="hip")
     ap.add_argument("--out", required=True)
@@ -76,7 +77,8 @@ def main():
             return gpak.Gpak(0, precision) if ranks == 1 else gpak.Gpak(devices=[0] * ranks, precision=precision)
         if a.ranks:
             assert a.group in cs.WORKER_GROUPS and a.ranks == cs.WORKER_GROUPS[a.group], "--ranks is the group's largest rank count"
-        sequences = [(si, s) for si, s in enumerate(cs.GROUP_SEQUENCES if a.ranks else cs.SEQUENCES) if s["group"] == a.group]
+        pool = cs.GROUP_SEQUENCES if a.ranks else cs.FEATURE_SEQUENCES if a.group in cs.FEATURE_GROUPS else cs.SEQUENCES
+        sequences = [(si, s) for si, s in enumerate(pool) if s["group"] == a.group]
     assert sequences, "nothing to run"
 
     t0 = time.time()

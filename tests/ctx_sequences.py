@@ -22,6 +22,12 @@ must) and Track does not hear of it, so every later answer is compared with a co
 GROUP_SEQUENCES (further down) are the sequences on a multi-GPU context: `ranks` per context, make(precision, ranks), a
 fresh answer from a fresh group of the same rank count; engine_sequence cuts them down to what a group over caller-supplied
 engines answers, for the run of the group's host code on the CPU.
+
+FEATURE_SEQUENCES (last part) bring the calls of the ten feature headers (gpak_loo_grad.h, gpak_cv_groups(_grad).h,
+gpak_cv_folds(_grad).h, gpak_design.h, gpak_condition.h, gpak_local.h, gpak_local_ok.h, gpak_local_search.h) into the same
+vocabulary: FEATURE_INVOKE, feature_errors, lists of their own beside SEQUENCES.  They run at T129 and T300 (the long-double
+references of the design, the simulation and the local calls are cubic in N); T700 and T1100 appear in `cv workspace` alone,
+for the second 512-column block and the leading-dimension change T1100 -> T300, where the float64 restatements suffice.
 """
 import functools
 import os
@@ -158,8 +164,11 @@ LEAKED = []               # ... and kept referenced here, so that no destructor 
 
 def invoke(obj, method, kw, n_train):
     """Call obj.method with the data the keys name; returns (status, [arrays or None])."""
+    status = None
     try:
-        if method == "set_option":
+        if method in FEATURE_INVOKE:
+            status, out = FEATURE_INVOKE[method](obj, kw, n_train)
+        elif method == "set_option":
             out = obj.set_option(OPTS[kw["opt"]], kw["value"])
         elif method == "set_train":
             out = obj.set_train(*train(kw["train"]))
@@ -179,9 +188,6 @@ def invoke(obj, method, kw, n_train):
             out = obj.posteriorMeanVar(points(kw["X"]), want_var=kw.get("want_var", True), compat=kw.get("compat", 0))
         elif method in ("GradLL_hyb", "GradLL_exact"):
             out = getattr(obj, method)(kw["ng"])
-        elif method == "loo_grad":
-            g, s = obj.loo_grad(kw["ng"])
-            out = (g, np.array([s[k] for k in ("mse", "mssr", "log_pl")]))
         elif method == "transport":
             name = obj.transport()
             out = np.array([[name.startswith(t) for t in TRANSPORTS].index(True)])
@@ -206,7 +212,7 @@ def invoke(obj, method, kw, n_train):
             DEVICE_ERROR.append(f"{method} {kw}: {e}")
             raise
         return int(e.status), []
-    status = OK
+    status = OK if status is None else int(status)
     if method == "loo":
         status = int(out[2]["status"])
         out = (out[0], out[1], np.array([out[2][k] for k in ("mse", "mssr", "log_pl")]))
@@ -362,6 +368,8 @@ def model_errors(method, kw, got, want, m, precision=F64):
         if len(g) > 1 and g[1] is not None:
             out.append(("D2", float(np.abs(g[1] - w[1]).max()), (1e-14 if direct else 1e-13) if plain else 1e-12))
         return out
+    if method in FEATURE_INVOKE:
+        return feature_errors(method, kw, g, w, m, t8, direct)
     if method in ("factor", "n_gpus", "transport"):   # yes / no, a count, a name: equal or not
         return [(method, float(g[0][0] != w[0][0]), 0.5)]
     if method == "failed_column":                     # the column itself: an integer, equal or not (tests/failcol_ref.py)
@@ -924,3 +932,531 @@ def engine_sequence(seq, ranks):
     if not any(m not in SETTERS + ("timing",) for _c, m, _kw in steps):
         return None
     return dict(seq, steps=steps, ranks=ranks)
+
+
+# ======== the feature calls: DESIGN.md section 8, "Call sequences across the feature calls" ====================================
+# gpak_loo_grad, gpak_cv_groups(_grad), gpak_cv_folds(_grad), gpak_design, gpak_condition, gpak_sample_path and the four local
+# calls share dGpart, dG / dLoo, the prediction buffers, Upred and the dCond* buffers with each other and with the calls above.
+# The data the keys name, built from what each feature's own tests use:
+#   labels      cvg_ref.holes / mixed_sizes (1, 2, 127, 128) / singletons, cvf_cases.random_folds(3), and "big": contiguous folds
+#               with one above 128 samples (129 + 171 at T300, 256 + 257 + 187 at T700, 129 + 971 at T1100, all of T129);
+#               "over": groups of 129, which gpak_cv_groups(_grad) refuses;
+#   designs     the two smallest 3-column entries of design_cases.CASES (T17 nd1 "six" weighted with 3 picks, T17 nd8 "twins"
+#               with 2) and, as the large footprint in dGpart, "sizes" (T130 nd8, 344 candidates in holes of 1 .. 128);
+#   draws       Ysim / Fsim as test_path_gpu.draws, S = 3 and S = 130 (one past the 128-realisation tile of gpak_kmm_f64);
+#   priors      nfeat = 96 and 1100 (one past FEAT_CHUNK = 1024), frequencies as test_path_gpu.features, every feature on term 0
+#               (valid under every composition), S = 3;
+#   local       N300-M37-nd1-defaults and N513-M130-nd8-defaults of local_cases (lists of 1 .. 128 samples: every tier edge in
+#               one call); the search over the same samples and centres with k = 17 and k = 128.
+# The binding numbers labels by rank, so "a label out of range" cannot reach the library through it: the label refusal the
+# sequences meet is the group above 128.  gpak_predict_local(_ok) are not asked at the failing parameters (sn2 < 0 makes every
+# node's own matrix borderline; whether a pivot fails there is no property of the context).
+import cvf_cases  # noqa: E402
+import cvg_ref  # noqa: E402
+
+# Compositions of the prediction-buffer sequences.  gpak_condition's own bound in the EXPANSION form is wide (2e-7 max|Kbar| sum_j
+# |A_js|, and alpha grows as sn2 shrinks), so E / EXR / T2 at sn2 = 0.016 .. 0.05 lie only 100 to 1000 of those bounds apart; with a
+# noise of 0.2 .. 0.4 and plainly different widths and amplitudes every pair is at least 1400 bounds apart (the separation test).
+E2 = [E[0], 0.5 * E[1], E[2], 0.5 * E[3], E[4], 0.5 * E[5], 1.4, E[7]]
+KERN.update({"En": ([(EXPANS, E)], synth.DEFAULT_BIAS, 0.0, 0.4), "E2n": ([(EXPANS, E2)], 0.05, 0.0, 0.3),
+             "T2XRn": ([(EXPANS, THETA2), (EXP, [0.5, 0.9]), (RBF, [0.5, 0.9, 0.5])], 0.35, 0.0, 0.2)})
+NG.update({name: sum(cm.NPARS[k] for k, _ in KERN[name][0]) + 2 for name in ("En", "E2n", "T2XRn")})
+BIG_FOLDS = {129: (129,), 300: (129, 171), 700: (256, 257, 187), 1100: (129, 971)}
+LABELS = {"holes": cvg_ref.holes, "mixed": cvg_ref.mixed_sizes, "singles": cvg_ref.singletons, "folds": cvf_cases.random_folds(3),
+          "big": lambda n: cvf_cases.contiguous(*BIG_FOLDS[n])(n), "over": lambda n: cvg_ref.holes(n, 129)}
+SMALL_GROUPS = ("holes", "mixed", "singles")          # no group above 128: what gpak_cv_groups takes
+DESIGNS = {"six": ("N200-theta2-T17-nd1-six", True, 3), "twins8": ("N200-defaults-T17-nd8-twins", False, 2),
+           "sizes": ("N513-defaults-T130-nd8-sizes", False, 1)}
+PRIORS = {"F96": 96, "F1100": 1100}
+PRIOR_S = 3
+LOCAL = {"L37x1": "N300-M37-nd1-defaults", "L130x8": "N513-M130-nd8-defaults",
+         "L37x8d4": "N300-M37-nd8-d4-defaults"}      # four columns: refused (GPAK_ENOTIMPL) by a context whose training set has three
+CV_SUMMARY = ("mse", "mssr", "msmd", "log_pl")
+LD = np.longdouble
+
+
+@functools.lru_cache(maxsize=None)
+def labels(key, n):
+    a = np.asarray(LABELS[key](int(n)), dtype=np.int64)
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def design_args(key, bad_columns=False):
+    """(Xt, nd, Xc, hole, weights, picks); bad_columns: a fourth column on both point sets (refused on a 3-column set)"""
+    import design_cases as dc
+    name, weighted, k = DESIGNS[key]
+    T, nd = dc.CASES[name][2], dc.CASES[name][3]
+    _X, _y, Xt, Xc, hole = dc.inputs(name)
+    if bad_columns:
+        Xt, Xc = np.asfortranarray(np.hstack([Xt, Xt[:, :1]])), np.asfortranarray(np.hstack([Xc, Xc[:, :1]]))
+    return Xt, nd, Xc, hole, (dc.weights(T) if weighted else None), k
+
+
+@functools.lru_cache(maxsize=None)
+def draws(n, m, s):
+    rng = np.random.default_rng(17 * n + m + s)
+    return np.asfortranarray(0.7 * rng.standard_normal((n, s))), np.asfortranarray(1.3 * rng.standard_normal((m, s)))
+
+
+@functools.lru_cache(maxsize=None)
+def prior(key, n):
+    """(feat_term, omega, ab, b0, E) of a spectral prior with PRIORS[key] features and PRIOR_S realisations"""
+    nfeat = PRIORS[key]
+    rng = np.random.default_rng(900 + nfeat + n)
+    om = rng.standard_normal((nfeat, 4)) / np.abs(rng.standard_normal((nfeat, 1)))
+    om[:, 3] = 0.0
+    om[5] *= 1e4 / np.abs(om[5]).max()                # one frequency of order 1e4
+    return (np.zeros(nfeat, dtype=np.int32), om, np.asfortranarray(rng.standard_normal((2 * nfeat, PRIOR_S))), rng.standard_normal(PRIOR_S),
+            np.asfortranarray(rng.standard_normal((n, PRIOR_S))))
+
+
+@functools.lru_cache(maxsize=None)
+def local_inputs(key):
+    """(Xs, ys, Xd, nd, nbr, centres) of a case of local_cases"""
+    import local_cases as lc
+    Xs, ys, Xd, nbr = lc.inputs(LOCAL[key])
+    nd = lc.CASES[LOCAL[key]][2]
+    return Xs, ys, Xd, nd, nbr, np.asfortranarray(lc.centres(Xd, nd))
+
+
+class _sized:
+    """The binding sizes its label and realisation checks by Gpak.N; before a training set the library refuses first, so
+    the data is made for `n` samples and N says so for the length of the call."""
+
+    def __init__(self, obj, n_train, n):
+        self.obj, self.on = obj, (not n_train) and hasattr(obj, "_h")
+        self.n = n
+
+    def __enter__(self):
+        if self.on:
+            # only ever on a binding object that holds no training set; anything else would hide a stale size
+            assert self.obj.N == 0, self.obj.N       # Gpak.__init__ sets N = 0 (and no d) until gpak_set_train is accepted
+            self.obj.N = self.n
+
+    def __exit__(self, *exc):
+        if self.on:
+            assert self.obj.N == self.n, (self.obj.N, self.n)        # the call itself must not have moved it
+            self.obj.N = 0
+
+
+def _cv_out(out):
+    s = out[-1]
+    return int(s["status"]), tuple(out[:-1]) + (np.array([s[k] for k in CV_SUMMARY]), np.array([s["groups"], s["max_size"]], dtype=float))
+
+
+def _ask_cv(method):
+    def ask(obj, kw, n_train):
+        n = n_train or 300
+        args = [labels(kw["labels"], n)] + ([kw["ng"]] if method.endswith("_grad") else [])
+        opts = dict(no_batch=kw["no_batch"]) if "no_batch" in kw else {}
+        with _sized(obj, n_train, n):
+            return _cv_out(getattr(obj, method)(*args, **opts))
+    return ask
+
+
+def _ask_loo_grad(obj, kw, n_train):
+    g, s = obj.loo_grad(kw["ng"])
+    return int(s["status"]), (g, np.array([s[k] for k in ("mse", "mssr", "log_pl")]))
+
+
+def _ask_design(obj, kw, n_train):
+    Xt, nd, Xc, hole, wt, k = design_args(kw["design"], kw.get("bad_columns", False))
+    gain, picked, pick_gain, ex = obj.design(Xt, nd, Xc, hole, wt, k, True)
+    s = ex["summary"]
+    return int(s["status"]), (gain, picked, pick_gain, ex["reduction"], ex["var"], ex["var_after"], np.array([s["var_before"], s["var_after"]]),
+                              np.array([s["holes"], s["max_size"], s["picks"]], dtype=float))
+
+
+def _ask_condition(obj, kw, n_train):
+    Xd, nd = blocks(kw["blocks"])
+    n = n_train or 300
+    Y, F = draws(n, Xd.shape[0] // nd, kw["S"])
+    with _sized(obj, n_train, n):
+        Z, mean, s = obj.condition(Xd, nd, Y, F if kw.get("fsim", True) else None, unfused=kw.get("unfused", False))
+    return int(s["status"]), (Z, mean, np.array([s["fused"]], dtype=float))
+
+
+def _ask_sample_path(obj, kw, n_train):
+    Xd, nd = blocks(kw["blocks"])
+    n = n_train or 300
+    with _sized(obj, n_train, n):
+        Z, mean, s = obj.sample_path(Xd, nd, *prior(kw["prior"], n), unfused=kw.get("unfused", False))
+    return int(s["status"]), (Z, mean, np.array([s["fused"]], dtype=float))
+
+
+def _local_counts(s):
+    return np.array([s[k] for k in ("nodes", "empty", "notpd", "max_used")], dtype=float)
+
+
+def _ask_predict_local(obj, kw, n_train):
+    Xs, ys, Xd, nd, nbr, _c = local_inputs(kw["local"])
+    mean, var, s = obj.predict_local(Xs, ys, Xd, nd, nbr, latent=kw.get("latent", False))
+    return OK, (mean, var, _local_counts(s))
+
+
+def _ask_predict_local_ok(obj, kw, n_train):
+    Xs, ys, Xd, nd, nbr, _c = local_inputs(kw["local"])
+    mean, var, mu, s = obj.predict_local_ok(Xs, ys, Xd, nd, nbr, want_mu=True, latent=kw.get("latent", False))
+    return OK, (mean, var, mu, _local_counts(s))
+
+
+def _ask_search(obj, kw, n_train):
+    Xs, _ys, _Xd, _nd, _nbr, centres = local_inputs(kw["local"])
+    nbr, used, d2, _s = obj.local_neighbours_dev(Xs, centres, kw["k"], want_dist2=True)
+    return OK, (nbr, used, d2)
+
+
+FEATURE_INVOKE = {"loo_grad": _ask_loo_grad, "cv_groups": _ask_cv("cv_groups"), "cv_groups_grad": _ask_cv("cv_groups_grad"),
+                  "cv_folds": _ask_cv("cv_folds"), "cv_folds_grad": _ask_cv("cv_folds_grad"), "design": _ask_design,
+                  "condition": _ask_condition, "sample_path": _ask_sample_path,
+                  "local_metric": lambda obj, kw, n_train: (OK, obj.local_metric(kw.get("term", 0))),
+                  "predict_local": _ask_predict_local, "predict_local_ok": _ask_predict_local_ok, "local_neighbours_dev": _ask_search}
+FEATURE_ENTRY = {"cv_groups": "gpak_cv_groups", "cv_groups_grad": "gpak_cv_groups_grad", "cv_folds": "gpak_cv_folds",
+                 "cv_folds_grad": "gpak_cv_folds_grad", "design": "gpak_design", "condition": "gpak_condition",
+                 "sample_path": "gpak_sample_path", "local_metric": "gpak_local_metric", "predict_local": "gpak_predict_local",
+                 "predict_local_ok": "gpak_predict_local_ok", "local_neighbours_dev": "gpak_local_neighbours_dev"}
+ENTRY.update(FEATURE_ENTRY)
+FEATURE_HEADERS = ("gpak_cv_groups.h", "gpak_cv_groups_grad.h", "gpak_cv_folds.h", "gpak_cv_folds_grad.h", "gpak_design.h", "gpak_condition.h",
+                   "gpak_local.h", "gpak_local_ok.h", "gpak_local_search.h", "gpak_loo_grad.h")
+
+
+def _equal(label, a, b):
+    return (label, 0.0 if np.array_equal(a, b) else float("inf"), 1.0)
+
+
+def _gradient_errors(g, w, half, b):
+    """test_group_gradient_matches_numpy_restatement / test_fold_gradient_matches_numpy_restatement / test_loo_gradient_...: per
+    block; the bias entry (1/2 sum W) also on the condition of its own sum"""
+    nk = len(w) - 2
+    return [("kernel block", float(np.abs(g[:nk] - w[:nk]).max() / np.abs(w[:nk]).max()), b),
+            ("bias", abs(g[nk] - w[nk]), b * abs(w[nk]) + 1e-15 * half), ("sn2", abs(g[nk + 1] - w[nk + 1]) / abs(w[nk + 1]), b)]
+
+
+def feature_errors(method, kw, g, w, m, t8, direct):
+    """model_errors for the feature calls.  b: 1e-8, the bound of every one of their GPU tests in the DIRECT form
+    (cvf_cases.BOUND, test_cv_groups_gpu.BOUND, test_design_gpu.BOUND, test_path_gpu.BOUND, test_block_gpu.BOUND for the local
+    calls).  In the EXPANSION form: gpak_design and gpak_condition have tests of their own there
+    (test_design_in_the_expansion_form: the same bound; test_condition_in_the_expansion_form: the fill tolerance through
+    sum_j |A_js|), the local calls use the direct distance whatever the form (test_predict_local_matches_...: the same bytes),
+    and the cross-validation calls and gpak_loo_grad, whose tests run the DIRECT form only, BORROW the prediction's 1e-5 as loo
+    and the block calls do above."""
+    import path_ref
+    b = 1e-8 if direct else t8
+    if method == "local_neighbours_dev":              # test_local_search_gpu: bytes
+        return [_equal("lists", g[0], w[0]), _equal("used", g[1], w[1]), _equal("dist2", g[2], w[2])]
+    if method == "local_metric":
+        # test_local_metric_is_the_distance_of_the_term: exp(-sqrt(D2)) var2 + bias within 1e-12 of its largest value, D2 from G.
+        # Here with var2 = 1 and bias = 0 (they scale and shift both sides alike) on the first 64 points of P300.
+        P = points("P300")[:64]
+
+        def kernel(G):
+            T = P @ G[:3, :3]
+            return np.exp(-np.sqrt(((T[:, None, :] - T[None, :, :]) ** 2).sum(axis=2)))
+        return [("exp(-|(x - x') G|)", float(np.abs(kernel(g[0]) - kernel(w[0])).max()), 1e-12)]
+    pv = m.prior_variance()
+    if method in ("predict_local", "predict_local_ok"):       # test_predict_local(_ok)_matches_the_long_double_reference
+        ys = local_inputs(kw["local"])[1]
+        smax = float(np.abs(ys).max())
+        out = [("mean", float(np.abs(g[0] - w[0]).max() / smax), 1e-8), ("var", float(np.abs(g[1] - w[1]).max() / pv), 1e-8)]
+        if method == "predict_local_ok":
+            out.append(("mu", float(np.abs(g[2] - w[2]).max() / smax), 1e-8))
+        return out + [_equal("counts", g[-1], w[-1])]
+    ymax = float(np.abs(m.y).max())
+    if method in ("cv_groups", "cv_folds"):           # test_cv_groups_matches_numpy_restatement, test_cv_folds_matches_numpy_restatement
+        return [("mean", float(np.abs(g[0] - w[0]).max() / ymax), b), ("var", float((np.abs(g[1] - w[1]) / np.abs(w[1])).max()), b),
+                ("logp", float((np.abs(g[2] - w[2]) / np.abs(w[2])).max()), b),
+                ("summary", float((np.abs(g[3] - w[3]) / np.abs(w[3])).max()), b), _equal("counts", g[4], w[4])]
+    if method == "loo_grad":                          # test_loo_gradient_matches_numpy_restatement; the summary: test_loo_matches_...
+        return _gradient_errors(g[0], w[0], m._loo_grad()[1], b) + [("summary", float((np.abs(g[1] - w[1]) / np.abs(w[1])).max()), b)]
+    if method in ("cv_groups_grad", "cv_folds_grad"):
+        group = np.unique(labels(kw["labels"], m.N), return_inverse=True)[1].reshape(-1)
+        return _gradient_errors(g[0], w[0], m._cv_grad_ref(group)[1], b) + \
+            [("summary", float((np.abs(g[1] - w[1]) / np.abs(w[1])).max()), b), _equal("counts", g[2], w[2])]
+    if method == "design":                            # test_design_matches_long_double, test_design_in_the_expansion_form
+        Xt, nd, _Xc, _hole, wt, k = design_args(kw["design"])
+        sw = float(Xt.shape[0] // nd if wt is None else wt.sum())
+        out = [("gain", float(np.abs(g[0] - w[0]).max()), 1e-8 * pv * sw), _equal("picked", g[1], w[1]),
+               ("reduction", float(np.abs(g[3] - w[3]).max()), 1e-8 * pv), ("var", float(np.abs(g[4] - w[4]).max()), 1e-8 * pv),
+               ("var_after", float(np.abs(g[5] - w[5]).max()), 1e-8 * pv), ("sums", float(np.abs(g[6] - w[6]).max()), 1e-8 * pv * sw),
+               _equal("counts", g[7], w[7])]
+        return out + ([("pick_gain", float(np.abs(g[2] - w[2]).max()), 1e-8 * pv * sw)] if k else [])
+    # gpak_condition / gpak_sample_path: test_condition_against_long_double, test_sample_path_is_the_reference_linear_map: 1e-8 of
+    # max|y| + max|Ysim| + max|Fsim| (an absent Fsim adds nothing), the sampler also the rounding of theta,
+    # 8 u sum_f |amp_f| (1 + sum_k |omega_fk u_k|).  EXPANSION (test_condition_in_the_expansion_form): per element also
+    # 2e-7 max|Kbar| sum_j |A_js|, A = alpha 1' - Ky^-1 Ysim; the mean is the column A = alpha.  gpak_sample_path has no test in
+    # that form and borrows gpak_condition's.
+    Xd, nd = blocks(kw["blocks"])
+    pm = m.path_model(Xd, nd)
+    theta = 0.0
+    if method == "condition":
+        Y, F = draws(m.N, Xd.shape[0] // nd, kw["S"])
+        F = F if kw.get("fsim", True) else None
+    else:
+        ft, om, ab, b0, E = prior(kw["prior"], m.N)
+        F, Y = pm.prior_draw(ft, om, ab, b0, E)
+        _, amp, arg = pm.features(pm.Xd, nd, ft, om)
+        _, _, argx = pm.features(pm.X, 1, ft, om)
+        theta = 8 * U * float((amp.astype(float) * (1 + np.maximum(arg, argx))).sum())
+    scale = ymax + float(np.abs(Y).max()) + (float(np.abs(F).max()) if F is not None else 0.0)
+    bz = bm = 1e-8 * scale + theta
+    if not direct:
+        A = pm.alpha[:, None] - path_ref.solve_ky(pm.L, np.asarray(Y, dtype=LD))
+        kmax = float(np.abs(pm.Kbar).max())
+        bz = bz + 2e-7 * kmax * np.abs(A).sum(axis=0).astype(float)[None, :]
+        bm = bm + 2e-7 * kmax * float(np.abs(pm.alpha).sum())
+    return [("Z", float((np.abs(g[0] - w[0]) / bz).max()), 1.0), ("mean", float(np.abs(g[1] - w[1]).max() / bm), 1.0), _equal("fused", g[2], w[2])]
+
+
+# ---- the named feature sequences ---------------------------------------------------------------------------------------------
+def cv_all(small, any_size, ng=10, ctx=0):
+    c = dict(ctx=ctx)
+    return [S("cv_groups", labels=small, **c), S("cv_groups_grad", labels=small, ng=ng, **c), S("cv_folds", labels=any_size, **c),
+            S("cv_folds_grad", labels=any_size, ng=ng, **c)]
+
+
+def seq_cv_workspace():
+    """G = L^-T of the four cross-validation calls goes into dG when a gradient has allocated one, else into dLoo
+    (csrc/cv_folds.hip, csrc/cv_groups.hip): each call before any gradient, then GradLL_exact and loo_grad (dG / dBinv exist from
+    here on), then each again with loo, GradLL and GradLL_hyb between; then T1100 (leading-dimension pad 32) -> T300 -> T700 with
+    one question of each after every change: every shared buffer holds the larger set's numbers at another leading dimension."""
+    s = [S("set_train", train="T300"), S("set_params", kern="E")] + cv_all("mixed", "big")
+    s += [S("GradLL_exact", ng=10), S("loo_grad", ng=10)]
+    s += [S("cv_groups", labels="mixed"), S("loo"), S("cv_groups_grad", labels="holes", ng=10), S("GradLL"),
+          S("cv_folds", labels="big", no_batch=True), S("GradLL_hyb", ng=10), S("cv_folds_grad", labels="folds", ng=10),
+          S("cv_folds_grad", labels="big", ng=10, no_batch=True)]
+    s += [S("timing"), S("set_train", train="T1100")] + cv_all("holes", "big")
+    s += [S("timing"), S("set_train", train="T300")] + cv_all("holes", "big")
+    s += [S("timing"), S("set_train", train="T700")] + cv_all("mixed", "big")
+    return s + [S("timing")]
+
+
+def seq_scratch():
+    """dGpart: gpak_design carves four arrays out of it (csrc/design.hip), gpak_cv_groups five, gpak_cv_folds three, the
+    gradients their partial sums.  The footprint grows and shrinks from call to call: the large design, then singletons, then
+    the reverse, with the gradients between."""
+    return [S("set_train", train="T300"), S("set_params", kern="E"), S("design", design="sizes"), S("cv_groups", labels="singles"),
+            S("cv_folds_grad", labels="big", ng=10), S("GradLL_exact", ng=10), S("loo_grad", ng=10), S("design", design="six"),
+            S("cv_groups", labels="mixed"), S("timing"), S("set_params", kern="E13"), S("cv_groups", labels="singles"), S("design", design="sizes"),
+            S("cv_folds_grad", labels="folds", ng=10), S("loo_grad", ng=10), S("GradLL_exact", ng=10), S("design", design="twins8"),
+            S("cv_groups_grad", labels="singles", ng=10), S("timing")]
+
+
+def seq_feature_prediction(mode):
+    """dWt / dC / dTblk / dXblk / Upred serve the point, block and joint predictions, gpak_design and gpak_condition; dTblk is
+    sized by the number of terms, gpak_design and gpak_condition transform the training points again into Upred under a mean
+    pooled with their own points.  n_d = 1 and 8; M small, 300 in two batches, small; one term, three, one.  In the EXPANSION
+    form every call that pools a mean is followed by logLikelihood and gram, which read the training points' own transform."""
+    def pooled(step):
+        return [step] + ([S("logLikelihood"), S("gram")] if mode == EXPANSION else [])
+    s = [S("set_train", train="T300"), S("set_params", kern="En", mode=mode)]
+    s += pooled(S("posteriorMeanVar", X="P5")) + [S("predict_block", blocks="B12x8")] + pooled(S("design", design="twins8"))
+    s += pooled(S("condition", blocks="B40x1", S=3)) + [S("predict_joint", blocks="B40x1"), S("sample_joint", blocks="B12x8")]
+    s += [opt("PRED_BATCH", 256)] + pooled(S("condition", blocks="B300x1", S=3)) + [S("predict_joint", blocks="B300x1")]
+    s += pooled(S("posteriorMeanVar", X="P300")) + pooled(S("design", design="six")) + [opt("PRED_BATCH", 0)]
+    s += pooled(S("condition", blocks="B12x8", S=3))
+    s += [S("timing"), S("set_kernel", kern="T2XRn", mode=mode), S("predict_block", blocks="B12x8")] + pooled(S("condition", blocks="B40x8", S=3))
+    s += pooled(S("design", design="six")) + [S("predict_joint", blocks="B40x1"), S("sample_joint", blocks="B40x1")]
+    s += pooled(S("condition", blocks="B300x1", S=3))
+    s += [S("set_params", kern="E2n", mode=mode)] + pooled(S("condition", blocks="B12x8", S=3)) + [S("predict_block", blocks="B40x8")]
+    s += pooled(S("design", design="twins8")) + pooled(S("posteriorMeanVar", X="P5"))
+    return s + [S("timing")]
+
+
+def seq_simulation():
+    """The dCond* buffers grow only: S = 130 (one past the 128-realisation tile) then S = 3, fused then unfused, 1100 features
+    (one past FEAT_CHUNK) then 96; then T300 -> T129 -> T300: dCondY and dCondA take N rows per column of an N_p pitch, the rows
+    N .. N_p keep the larger set's numbers.  gpak_condition solves through dWork: solve_chol, set_params and solve_alpha after each
+    part.  No step follows a change of INV512 / BWD_FUSED."""
+    after = lambda kern: [S("solve_chol", k=2), S("timing"), S("set_params", kern=kern), S("solve_alpha")]        # noqa: E731
+    s = [S("set_train", train="T300"), S("set_params", kern="E"), S("condition", blocks="B40x8", S=130), S("condition", blocks="B40x8", S=3),
+         S("condition", blocks="B40x8", S=3, unfused=True), S("condition", blocks="B40x8", S=130, fsim=False)] + after("E13")
+    s += [S("sample_path", blocks="B40x1", prior="F1100"), S("sample_path", blocks="B40x1", prior="F96"),
+          S("sample_path", blocks="B40x1", prior="F96", unfused=True)] + after("E")
+    s += [S("set_train", train="T129"), S("condition", blocks="B40x8", S=130), S("sample_path", blocks="B40x1", prior="F96")] + after("E13")
+    s += [S("set_train", train="T300"), S("condition", blocks="B40x8", S=3), S("condition", blocks="B40x8", S=130, unfused=True),
+          S("sample_path", blocks="B12x8", prior="F96"), S("solve_alpha"), S("logLikelihood"), S("timing")]
+    return s
+
+
+def factor_calls(ctx=0):
+    """every feature call that needs the factor, once"""
+    c = dict(ctx=ctx)
+    return cv_all("holes", "big", 10, ctx) + [S("loo_grad", ng=10, **c), S("design", design="six", **c), S("condition", blocks="B12x8", S=3, **c),
+                                              S("sample_path", blocks="B12x8", prior="F96", **c)]
+
+
+def factorless_calls(ctx=0):
+    """the local calls that read neither the factor nor sn2"""
+    c = dict(ctx=ctx)
+    return [S("local_metric", **c), S("local_neighbours_dev", local="L37x1", k=17, **c)]
+
+
+def local_calls(a="L37x1", b="L37x1", k=17, ctx=0):
+    c = dict(ctx=ctx)
+    return [S("local_metric", **c), S("predict_local", local=a, **c), S("predict_local_ok", local=b, **c),
+            S("local_neighbours_dev", local=a, k=k, **c)]
+
+
+def seq_feature_fail():
+    """sn2 < 0 (from column 1, then from column 200): every feature call that needs the factor answers GPAK_ENOTPD with quiet
+    NaN, the local calls that need none answer as before, and after good parameters everything has a fresh context's bits."""
+    return ([S("set_train", train="T300"), S("set_params", kern="E"), S("cv_groups", labels="holes"), S("set_params", kern="BAD")] +
+            factor_calls() + factorless_calls() + [S("failed_column"), S("timing"), S("set_params", kern="BAD200")] + factor_calls() +
+            [S("failed_column"), S("timing"), S("set_params", kern="E13")] + factor_calls() + local_calls() + [S("failed_column"), S("timing")])
+
+
+def seq_feature_f32():
+    """GPAK_F32: the feature calls are fp64 whatever the context's precision; between fp32 predictions they must leave the fp32
+    image of the factor alone and find the fp64 factor."""
+    return [S("set_train", train="T300"), S("set_params", kern="E"), S("posteriorMeanVar", X="P300"), S("cv_groups", labels="holes"),
+            S("posteriorMeanVar", X="P5"), S("design", design="six"), S("condition", blocks="B12x8", S=3), S("posteriorMeanVar", X="P300"),
+            S("cv_folds_grad", labels="big", ng=10), S("loo_grad", ng=10), S("predict_local", local="L37x1"), S("posteriorMeanVar", X="P300"),
+            S("set_params", kern="T2"), S("posteriorMeanVar", X="P300"), S("sample_path", blocks="B40x1", prior="F96"),
+            S("cv_folds", labels="big"), S("cv_groups_grad", labels="mixed", ng=10), S("predict_local_ok", local="L37x1"),
+            S("posteriorMeanVar", X="P5"), S("timing")]
+
+
+def seq_feature_refused():
+    """Each call's cheapest refusals (a group above 128, a gradient of the wrong length, a fourth column -- for the local
+    predictions too: GPAK_ENOTIMPL --, k = 129 for the search, a White child for the gradients, no parameters, no training set) are
+    results, and the answers after them are those of a context that never saw
+    the call: nothing is factored for them (timing)."""
+    early = cv_all("holes", "big", 10, 1) + [S("loo_grad", ctx=1, ng=10), S("design", ctx=1, design="six"),
+                                             S("condition", ctx=1, blocks="B12x8", S=3), S("sample_path", ctx=1, blocks="B12x8", prior="F96")]
+    return ([S("set_train", train="T300"), S("set_params", kern="E"), S("logLikelihood"), S("timing"),
+             S("cv_groups", labels="over"), S("cv_groups_grad", labels="over", ng=10), S("logLikelihood"),
+             S("cv_groups_grad", labels="holes", ng=11), S("cv_folds_grad", labels="big", ng=9), S("loo_grad", ng=13),
+             S("design", design="six", bad_columns=True), S("condition", blocks="C12x8", S=3), S("sample_path", blocks="C12x8", prior="F96"),
+             S("predict_local", local="L37x8d4"), S("predict_local_ok", local="L37x8d4"), S("local_neighbours_dev", local="L37x1", k=129),
+             S("predict_local", local="L37x1"), S("solve_alpha"), S("GradLL"), S("timing"),
+             S("set_kernel", kern="EW"), S("cv_groups_grad", labels="holes", ng=10), S("cv_folds_grad", labels="big", ng=10),
+             S("loo_grad", ng=10), S("timing"), S("cv_groups", labels="holes"), S("logLikelihood"), S("timing")] +
+            early + local_calls(ctx=1)[:3] + [S("local_neighbours_dev", ctx=1, local="L37x1", k=129),
+                                              S("local_neighbours_dev", ctx=1, local="L37x1", k=17), S("set_params", ctx=1, kern="E")] + early +
+            local_calls(ctx=1) +
+            [S("set_train", ctx=1, train="T129"), S("cv_groups", ctx=1, labels="holes"), S("logLikelihood", ctx=1), S("timing", ctx=1)])
+
+
+def seq_local_between():
+    """The local calls need parameters only: before a training set, with one, between two gpak_condition calls (which share the
+    block staging buffers), and after gpak_set_kernel to another composition."""
+    cond = S("condition", blocks="B12x8", S=3)
+    return ([S("set_params", kern="E")] + local_calls() + [S("set_train", train="T300")] + local_calls("L130x8", "L130x8", 128) +
+            [cond, S("predict_local", local="L37x1"), S("predict_local_ok", local="L130x8", latent=True), cond, S("logLikelihood"),
+             S("timing"), S("set_kernel", kern="EXR"), S("local_metric", term=2)] + local_calls("L37x1", "L130x8", 128) +
+            [cond, S("solve_alpha"), S("timing")])
+
+
+def seq_feature_two():
+    """Two live contexts with different training sets and compositions, advanced alternately."""
+    a = [S("set_train", train="T300"), S("set_params", kern="E"), S("cv_folds", labels="big"), S("design", design="six"),
+         S("condition", blocks="B12x8", S=3), S("cv_groups_grad", labels="holes", ng=10), S("sample_path", blocks="B40x1", prior="F96"),
+         S("predict_local", local="L37x1"), S("loo_grad", ng=10), S("timing")]
+    b = [S("set_train", ctx=1, train="T129"), S("set_kernel", ctx=1, kern="EXR"), S("condition", ctx=1, blocks="B40x1", S=130),
+         S("cv_groups", ctx=1, labels="mixed"), S("cv_folds_grad", ctx=1, labels="folds", ng=15), S("design", ctx=1, design="twins8"),
+         S("loo_grad", ctx=1, ng=15), S("cv_folds", ctx=1, labels="holes"), S("predict_local_ok", ctx=1, local="L37x1"), S("timing", ctx=1)]
+    return alternate(a, b)
+
+
+FEATURE_RANDOM_COUNT, FEATURE_RANDOM_LENGTH = 3, 30
+
+
+def seq_feature_random(k):
+    """30 steps over the whole vocabulary, old and new, at N in {129, 300}; the generator keeps the preconditions: the gradient's
+    length, no gradient with a White child, labels of the current N (no group above 128 for gpak_cv_groups), matching columns."""
+    rng = np.random.default_rng(RANDOM_SEED + 200 + k)
+    pick = lambda a: a[int(rng.integers(len(a)))]   # noqa: E731
+    cur = dict(kern=None)
+
+    def set_kern():
+        cur["kern"] = pick(["E", "E13", "T2", "ER", "EXR", "EW"])
+        return S("set_kernel" if cur["kern"] in ("ER", "EXR", "EW") else "set_params", kern=cur["kern"])
+
+    steps = [S("set_train", train=pick(["T129", "T300"])), set_kern()]
+    old = ["gram", "solve_alpha", "solve_chol", "logLikelihood", "nlz_terms", "posteriorMeanVar", "GradLL_exact", "loo", "predict_block",
+           "predict_joint", "sample_joint", "chol_upper", "timing"]
+    new = ["cv_groups", "cv_groups_grad", "cv_folds", "cv_folds_grad", "loo_grad", "design", "condition", "sample_path", "local_metric",
+           "predict_local", "predict_local_ok", "local_neighbours_dev"]
+    while len(steps) < FEATURE_RANDOM_LENGTH:
+        r = rng.random()
+        if r < 0.07:
+            steps.append(S("set_train", train=pick(["T129", "T300"])))
+        elif r < 0.2:
+            steps.append(set_kern())
+        elif r < 0.25:
+            steps.append(opt(*pick([("PRED_BATCH", 256), ("PRED_BATCH", 0), ("LOO_ROWS", 128), ("LOO_ROWS", 0)])))
+        else:
+            m = pick(new) if r < 0.8 else pick(old)
+            ng = NG[cur["kern"]]
+            if m in ("GradLL_exact", "loo_grad", "cv_groups_grad", "cv_folds_grad") and cur["kern"] == "EW":
+                continue
+            if m in ("cv_groups", "cv_groups_grad"):
+                steps.append(S(m, labels=pick(list(SMALL_GROUPS)), **(dict(ng=ng) if m.endswith("_grad") else {})))
+            elif m in ("cv_folds", "cv_folds_grad"):
+                steps.append(S(m, labels=pick(["big", "folds", "mixed"]), no_batch=bool(rng.integers(2)), **(dict(ng=ng) if m.endswith("_grad") else {})))
+            elif m in ("GradLL_exact", "loo_grad"):
+                steps.append(S(m, ng=ng))
+            elif m == "design":
+                steps.append(S(m, design=pick(["six", "twins8"])))
+            elif m == "condition":
+                steps.append(S(m, blocks=pick(["B12x8", "B40x1"]), S=pick([3, 130]), fsim=bool(rng.integers(2)), unfused=bool(rng.integers(2))))
+            elif m == "sample_path":
+                steps.append(S(m, blocks=pick(["B12x8", "B40x1"]), prior="F96"))
+            elif m in ("predict_local", "predict_local_ok"):
+                steps.append(S(m, local="L37x1", latent=bool(rng.integers(2))))
+            elif m == "local_neighbours_dev":
+                steps.append(S(m, local="L37x1", k=pick([17, 128])))
+            elif m == "solve_chol":
+                steps.append(S(m, k=int(rng.integers(1, 4))))
+            elif m == "posteriorMeanVar":
+                steps.append(S(m, X=pick(["P5", "P300"])))
+            elif m in ("predict_block", "predict_joint", "sample_joint"):
+                steps.append(S(m, blocks=pick(["B12x8", "B40x1"])))
+            else:
+                steps.append(S(m))
+    return steps
+
+
+# `group`: one worker process each (tests/ctx_seq_worker.py --group NAME: the worker finds the list by the group's name)
+FEATURE_SEQUENCES = [
+    _seq("cv workspace", "f-cv", seq_cv_workspace()),
+    _seq("scratch", "f-scratch", seq_scratch()),
+    _seq("feature prediction buffers [direct]", "f-pred-direct", seq_feature_prediction(DIRECT)),
+    _seq("feature prediction buffers [expansion]", "f-pred-expansion", seq_feature_prediction(EXPANSION)),
+    _seq("simulation", "f-sim", seq_simulation()),
+    _seq("feature fail and recover", "f-fail", seq_feature_fail()),
+    _seq("feature f32", "f-f32", seq_feature_f32(), F32),
+    _seq("feature refused", "f-refused", seq_feature_refused()),
+    _seq("local between", "f-local", seq_local_between()),
+    _seq("feature two contexts", "f-two", seq_feature_two()),
+] + [_seq(f"feature random {k}", f"f-random{k}", seq_feature_random(k)) for k in range(FEATURE_RANDOM_COUNT)]
+FEATURE_GROUPS = []
+for _s in FEATURE_SEQUENCES:
+    if _s["group"] not in FEATURE_GROUPS:
+        FEATURE_GROUPS.append(_s["group"])
+FEATURE_BY_NAME = {s["name"]: s for s in FEATURE_SEQUENCES}
+
+
+# ---- the feature calls on a group: every one of them is built for the single-GPU context (all ten headers: GPAK_ENOTIMPL) ------
+def feature_refusals(ctx=0):
+    c = dict(ctx=ctx)
+    return [S("cv_groups", labels="holes", **c), S("cv_groups_grad", labels="holes", ng=10, **c), S("cv_folds", labels="big", **c),
+            S("cv_folds_grad", labels="big", ng=10, **c), S("design", design="six", **c), S("condition", blocks="B12x8", S=3, **c),
+            S("sample_path", blocks="B12x8", prior="F96", **c), S("local_metric", **c), S("predict_local", local="L37x1", **c),
+            S("predict_local_ok", local="L37x1", **c), S("local_neighbours_dev", local="L37x1", k=17, **c)]
+
+
+def seq_g_feature_refusals():
+    """Between logLikelihood, solve_alpha and a sharded prediction (P300 at P = 2: 256 + 44) each feature call is asked of a group
+    and refused; nothing changes and nothing is factored again."""
+    r = feature_refusals()
+    return ([S("set_train", train="T300"), S("set_params", kern="E"), S("logLikelihood"), S("timing")] + r[:4] +
+            [S("logLikelihood"), S("solve_alpha")] + r[4:7] + [S("posteriorMeanVar", X="P300"), S("timing")] + r[7:] +
+            [S("solve_alpha"), S("posteriorMeanVar", X="P300"), S("logLikelihood"), S("timing")])
+
+
+GROUP_SEQUENCES.append(_gseq("g feature refusals", "g-feature", seq_g_feature_refusals(), 2))
+GROUP_BY_NAME["g feature refusals"] = GROUP_SEQUENCES[-1]
+WORKER_GROUPS["g-feature"] = 2

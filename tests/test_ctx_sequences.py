@@ -13,6 +13,10 @@ DESIGN.md section 8, "Call sequences on one context".
 Groups (gpak_create_multi; second half of the module): the same on cs.GROUP_SEQUENCES with GroupCaching; on the CPU also
 the group's own host code over NumPy engines in a worker process; on the GPU one worker per worker group, which asks every
 fresh question of two fresh groups.  DESIGN.md section 8, "Call sequences on a multi-GPU context".
+
+Feature calls (last part of the module): the same three halves on cs.FEATURE_SEQUENCES -- models, FEATURE_MUTATIONS, separation,
+coverage of the ten feature headers on the CPU; test_feature_sequences_on_the_device on the GPU -- and `g feature refusals` among
+the group sequences.  DESIGN.md section 8, "Call sequences across the feature calls".
 """
 import json
 import os
@@ -50,7 +54,7 @@ def model_run(seq, mut=None):
     if mut is None:
         make = lambda p, r=1: cm.ModelGpak(p, CACHE, r)                                                        # noqa: E731
     else:      # a mutation belongs to one of the two restatements: the other kind of context of the sequence runs unmutated
-        single = [m for m in mut if m in cm.MUTATIONS]
+        single = [m for m in mut if m in cm.MUTATIONS + cm.FEATURE_MUTATIONS + cm.FEATURE_REDUNDANT]
         make = lambda p, r=1: cm.CachingModel(p, CACHE, single) if r == 1 else cm.GroupCaching(p, CACHE, r, [m for m in mut if m not in single])  # noqa: E731
     return list(cs.run(seq, make))
 
@@ -306,6 +310,7 @@ def test_every_declared_function_is_called_in_some_sequence():
     assert all(max(np.atleast_1d(s["ranks"])) >= 2 for s in cs.GROUP_SEQUENCES)
     called |= {"gpak_create_multi"} | {cs.ENTRY[m] for s in cs.GROUP_SEQUENCES if not s["name"].startswith("random") for _c, m, _kw in s["steps"]}
     called.discard("gpak_loo_grad")
+    called -= set(cs.FEATURE_ENTRY.values())      # `g feature refusals`: declared in the feature headers (test_the_feature_sequences_cover_...)
     declared = set(header_functions())
     assert EXCLUDED <= declared
     missing = declared - called - EXCLUDED
@@ -335,9 +340,7 @@ def _worker(group, out):
                           env=dict(os.environ, PYTHONPATH=ROOT), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=TIMEOUT)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("group", cs.GROUPS)
-def test_sequences_on_the_device(group, tmp_path):
+def _sequences_on_the_device(group, tmp_path, sequences):
     if _DEVICE_TROUBLE:
         pytest.fail(f"not started: {_DEVICE_TROUBLE[0]}")
     out = str(tmp_path / "results.npz")
@@ -353,18 +356,24 @@ def test_sequences_on_the_device(group, tmp_path):
         _DEVICE_TROUBLE.append(f"the worker of group {group} ended with status {r.returncode}: {err[-1500:]}")
         pytest.fail(_DEVICE_TROUBLE[0])
     lines = [json.loads(l) for l in r.stdout.decode().splitlines() if l.startswith("{")]
-    failures, summary = judge_group(group, lines, np.load(out))
+    failures, summary = judge_group(group, lines, np.load(out), sequences)
     print(summary)
     assert not failures, "\n".join(failures)
 
 
-def judge_group(group, lines, arrays):
+@pytest.mark.gpu
+@pytest.mark.parametrize("group", cs.GROUPS)
+def test_sequences_on_the_device(group, tmp_path):
+    _sequences_on_the_device(group, tmp_path, cs.SEQUENCES)
+
+
+def judge_group(group, lines, arrays, sequences=cs.SEQUENCES):
     """The worker's records and arrays of one group against fresh contexts (a) and the model (b): (failures, summary)."""
     done = lines.pop()
     assert done["done"] == group
     failures, bit_equal, compared, worst = [], 0, 0, (0.0, None)
-    index = {s["name"]: k for k, s in enumerate(cs.SEQUENCES)}
-    for seq in (s for s in cs.SEQUENCES if s["group"] == group):
+    index = {s["name"]: k for k, s in enumerate(sequences)}
+    for seq in (s for s in sequences if s["group"] == group):
         mine = [x for x in lines if x["seq"] == seq["name"]]
         want = expected(seq)
         counts = model_run(seq, mut=())
@@ -381,7 +390,7 @@ def judge_group(group, lines, arrays):
                     failures.append(f"{where}: {int(vals[0][0])} factorisations since set_train, {int(c['res'][1][0][0])} expected")
                 continue
             compared += 1
-            if (seq["name"], x["i"]) not in MODEL_ONLY:
+            if (seq["name"], x["i"]) not in MODEL_ONLY and (seq["name"], x["i"]) not in FEATURE_MODEL_ONLY:
                 if x["bits"]:
                     bit_equal += 1
                 else:
@@ -537,7 +546,7 @@ def test_the_group_mutation_tables_are_the_models():
 
 
 # sequences whose group goes through one state only (or none): nothing to separate
-ONE_STATE = ("refusals (group)", "out of order (group)")
+ONE_STATE = ("refusals (group)", "out of order (group)", "g feature refusals")
 
 
 @pytest.mark.parametrize("name", GROUP_NAMES)
@@ -665,3 +674,214 @@ def test_group_sequences_on_the_device(group, tmp_path):
     failures, _unrepeatable, summary = _group_run(group, tmp_path)
     print(summary)
     assert not failures, "\n".join(failures)
+
+
+# ======== the feature calls (cs.FEATURE_SEQUENCES): DESIGN.md section 8, "Call sequences across the feature calls" ===============
+FEATURE_NAMES = [s["name"] for s in cs.FEATURE_SEQUENCES]
+FEATURE_NAMED = [s for s in cs.FEATURE_SEQUENCES if not s["name"].startswith("feature random")]
+TWELVE = ("gpak_cv_groups", "gpak_cv_groups_grad", "gpak_cv_folds", "gpak_cv_folds_grad", "gpak_design", "gpak_condition", "gpak_sample_path",
+          "gpak_local_metric", "gpak_predict_local", "gpak_predict_local_ok", "gpak_local_neighbours_dev")
+# declared in the feature headers and out of scope: the two host searches take no context
+FEATURE_EXCLUDED = {"gpak_local_neighbours": "host code, no context", "gpak_local_neighbours_octant": "host code, no context"}
+# (sequence, step) -> why the step's bits legitimately depend on earlier calls (a code line, never a failure)
+FEATURE_MODEL_ONLY = {}
+
+
+@pytest.mark.parametrize("name", FEATURE_NAMES)
+def test_feature_sequence_on_the_models(name):
+    seq = cs.FEATURE_BY_NAME[name]
+    want = expected(seq)
+    caching = model_run(seq, mut=())
+    counted = 0
+    for w, c in zip(want, caching):
+        if w["method"] == "timing":
+            assert w["res"][1] == [None] and c["res"][1][0].shape == (1,)
+            continue
+        assert cs.same_bits(w["res"], c["res"]), (name, w["i"], w["method"], w["kw"], w["res"][0], c["res"][0])
+        counted += w["method"] not in cs.SETTERS
+    assert len(want) == len(caching) == len(seq["steps"]) and counted > 0
+    print(f"{name}: {len(want)} steps, {counted} compared, statuses {sorted({w['res'][0] for w in want})}")
+
+
+def test_the_feature_sequences_meet_the_statuses_the_headers_promise():
+    seen = {}
+    for seq in FEATURE_NAMED:
+        for w in expected(seq):
+            seen.setdefault(w["res"][0], set()).add((seq["name"], w["method"]))
+    factor_calls = set(cm.FEATURE_FACTOR_CALLS) | {"loo_grad"}
+    assert {("feature fail and recover", m) for m in factor_calls} <= seen[cs.ENOTPD]
+    assert {("feature refused", m) for m in factor_calls} <= seen[cs.ESTATE]
+    # the local calls: no parameters (GPAK_ESTATE), a column count other than the training set's (GPAK_ENOTIMPL), k = 129 (GPAK_EINVAL)
+    assert {("feature refused", m) for m in ("local_metric", "predict_local", "predict_local_ok")} <= seen[cs.ESTATE]
+    assert {("feature refused", m) for m in ("predict_local", "predict_local_ok")} <= seen[cs.ENOTIMPL]
+    assert ("feature refused", "local_neighbours_dev") in seen[cs.EINVAL]
+    refused = expected(cs.FEATURE_BY_NAME["feature refused"])
+    for m in cs.FEATURE_ENTRY:                     # every one of the eleven is refused somewhere, and answers somewhere after it
+        at = [w["i"] for w in refused if w["method"] == m and w["res"][0] != cs.OK]
+        assert at and any(w["res"][0] == cs.OK and w["i"] > at[0] and w["method"] not in cs.SETTERS + ("timing",) for w in refused), m
+    assert [w["res"][0] for w in refused if w["method"] == "local_neighbours_dev"] == [cs.EINVAL, cs.EINVAL, cs.OK, cs.OK]
+    assert {("feature refused", m) for m in ("cv_groups", "cv_groups_grad", "cv_folds_grad", "loo_grad", "design", "condition", "sample_path")} <= seen[cs.EINVAL]
+    assert {("feature refused", m) for m in ("cv_groups_grad", "cv_folds_grad", "loo_grad")} <= seen[cs.ENOTIMPL]
+    fail = expected(cs.FEATURE_BY_NAME["feature fail and recover"])
+    for w in fail:                                 # quiet NaN in every floating-point output of a failed call
+        if w["res"][0] == cs.ENOTPD:
+            nan = [np.isnan(v).all() for v in w["res"][1]]
+            assert sum(nan) >= len(nan) - 2, (w["i"], w["method"])          # design: picked and the counts; the others: the counts
+    assert [int(w["res"][1][0][0]) for w in fail if w["method"] == "failed_column"] == [1, cs.BAD200_COLUMN, 0]
+    # at the column-200 failure too, every factor-dependent call
+    late = [w["method"] for w in fail if w["res"][0] == cs.ENOTPD and w["kern"][1] == "BAD200"]
+    assert set(late) == factor_calls and len(late) == 8
+    # the counts the device run is held to: a failing ask factors (and counts) every time, a refusal and a local call never;
+    # every named sequence carries them
+    assert [int(c["res"][1][0][0]) for c in model_run(cs.FEATURE_BY_NAME["feature fail and recover"], mut=()) if c["method"] == "timing"] == [9, 17, 18]
+    assert all(any(m == "timing" for _c, m, _kw in s["steps"]) for s in FEATURE_NAMED)
+    assert sum(m == "timing" for s in cs.FEATURE_SEQUENCES for _c, m, _kw in s["steps"]) >= 25
+    # the local calls that need no factor answer at the failing parameters, with numbers
+    assert all(w["res"][0] == cs.OK and np.isfinite(w["res"][1][0]).all() for w in fail if w["method"] in ("local_metric", "local_neighbours_dev"))
+    # nothing is factored for a refusal
+    counts = [int(c["res"][1][0][0]) for c in model_run(cs.FEATURE_BY_NAME["feature refused"], mut=()) if c["method"] == "timing"]
+    assert counts == [1, 1, 1, 2, 1], counts
+
+
+# mutation -> (the named feature sequence that catches it, index and method of its first step off the model): the call itself,
+# as the first reader of a factor after new parameters or a new training set
+FEATURE_CAUGHT_BY = {
+    "cv_groups answers from the factor as it stands": ("cv workspace", 2, "cv_groups"),
+    "cv_groups_grad answers from the factor as it stands": ("feature fail and recover", 5, "cv_groups_grad"),
+    "cv_folds answers from the factor as it stands": ("feature two contexts", 4, "cv_folds"),
+    "cv_folds_grad answers from the factor as it stands": ("feature fail and recover", 7, "cv_folds_grad"),
+    "design answers from the factor as it stands": ("scratch", 2, "design"),
+    "condition answers from the factor as it stands": ("simulation", 2, "condition"),
+    "sample_path answers from the factor as it stands": ("feature fail and recover", 11, "sample_path"),
+    # the design at 6 (the condition at 9); logLikelihood after it reads the factor, which stands; the Gram matrix two steps on is
+    # the first thing built from U again, as for `predict leaks pooled mean`
+    "design leaks pooled mean": ("feature prediction buffers [expansion]", 8, "gram"),
+    "condition leaks pooled mean": ("feature prediction buffers [expansion]", 11, "gram"),
+}
+
+
+def test_the_feature_mutation_table_is_the_models():
+    assert set(FEATURE_CAUGHT_BY) == set(cm.FEATURE_MUTATIONS) and len(cm.FEATURE_MUTATIONS) == 9 and cm.FEATURE_REDUNDANT == ("condition keeps z",)
+    assert {v[0] for v in FEATURE_CAUGHT_BY.values()} <= {s["name"] for s in FEATURE_NAMED}
+    assert not set(cm.FEATURE_MUTATIONS) & set(cm.MUTATIONS) and len(cm.MUTATIONS) == 9
+
+
+@pytest.mark.parametrize("mutation", cm.FEATURE_MUTATIONS)
+def test_each_feature_mutation_is_caught(mutation):
+    name, index, method = FEATURE_CAUGHT_BY[mutation]
+    seq = cs.FEATURE_BY_NAME[name]
+    rec, ratio, dropped = first_divergence(seq, [mutation])
+    assert rec is not None, f"{mutation}: the sequence '{name}' runs on the mutated model without a difference"
+    print(f"{mutation}: '{name}' step {rec['i']} ({rec['method']} {rec['kw']}) is {ratio:.3g} bounds off the model")
+    assert dropped and all(d[0] == mutation for d in dropped)
+    assert (rec["i"], rec["method"]) == (index, method), (rec["i"], rec["method"])
+
+
+@pytest.mark.parametrize("mutation", cm.FEATURE_REDUNDANT)
+def test_a_feature_reset_that_another_covers_changes_nothing(mutation):
+    """gpak_condition's work_vectors_overwritten follows ensure_nlz, whose back substitution has consumed L^-1 y / sn2 and lowered
+    the flag already: no sequence can tell whether the event is raised."""
+    hit = 0
+    for seq in cs.FEATURE_SEQUENCES:
+        rec, _ratio, dropped = first_divergence(seq, [mutation])
+        assert rec is None, (mutation, seq["name"], rec["i"], rec["method"])
+        hit += len(dropped)
+    assert hit > 0
+
+
+# sequences whose contexts with a training set go through one state only
+FEATURE_ONE_STATE = ()
+
+
+@pytest.mark.parametrize("name", FEATURE_NAMES)
+def test_distinct_feature_states_are_a_thousand_bounds_apart(name):
+    """test_distinct_states_are_a_thousand_bounds_apart for the feature sequences."""
+    separation(cs.FEATURE_BY_NAME[name], single_state=FEATURE_ONE_STATE)
+
+
+def test_sizing_the_binding_before_a_training_set_is_undone_and_guarded():
+    """cs._sized lends Gpak.N the size the no-training-set data was made for (the binding checks labels and realisations against N
+    before the library can answer GPAK_ESTATE; tests/lgo_grad_model.py does the same): only on a binding object without a
+    training set, undone after the call, also when the call raises; a model is left alone."""
+    from gp_ss_ak_amd import gpak
+    b = gpak.Gpak.__new__(gpak.Gpak)               # the binding's own class without a device, as Gpak.__init__ leaves it
+    b._h, b.N = None, 0
+    with cs._sized(b, 0, 300):
+        assert b.N == 300
+    assert b.N == 0
+    with pytest.raises(RuntimeError):
+        with cs._sized(b, 0, 300):
+            raise RuntimeError("refused")
+    assert b.N == 0
+    with cs._sized(b, 129, 129):                   # with a training set: nothing to lend
+        assert b.N == 0
+    b.N = 129
+    with pytest.raises(AssertionError):            # a stale size would be hidden
+        with cs._sized(b, 0, 300):
+            pass
+    m = cm.ModelGpak()
+    with cs._sized(m, 0, 300):
+        assert m.N == 0
+
+
+def test_every_pick_of_a_design_is_decided_beyond_its_bound():
+    """`picked` is compared for equality: in every state a sequence asks a design in, the gain a pick was taken by leads the
+    runner-up by more than 1000 times the bound on a gain (1e-8 prior variance sum of weights), or the two are the same hole
+    twice (the tie of layout "twins", which the header gives to the smaller number)."""
+    asked = 0
+    for seq in cs.FEATURE_SEQUENCES:
+        for w in expected(seq):
+            if w["method"] != "design" or w["res"][0] != cs.OK:
+                continue
+            m = cs.model_at(w, CACHE, seq["precision"])
+            Xt, nd, Xc, hole, wt, k = cs.design_args(w["kw"]["design"])
+            gain, _picked, _pg, ex = m.design(Xt, nd, Xc, hole, wt, k, True)
+            for gap in ex["gaps"]:
+                assert gap == 0.0 or gap * float(np.nanmax(gain)) > SEPARATION * 1e-8 * m.prior_variance() * ex["weight_sum"], (seq["name"], w["i"], gap)
+            asked += 1
+    assert asked >= 10
+
+
+def test_the_feature_sequences_cover_the_feature_headers():
+    assert [s["steps"] for s in cs.FEATURE_SEQUENCES if s["name"].startswith("feature random")] == \
+        [cs.seq_feature_random(k) for k in range(cs.FEATURE_RANDOM_COUNT)]
+    assert cs.FEATURE_RANDOM_COUNT == 3 and all(len(cs.seq_feature_random(k)) == 30 for k in range(3))
+    random_methods = {m for s in cs.FEATURE_SEQUENCES if s["name"].startswith("feature random") for _c, m, _kw in s["steps"]}
+    assert set(cs.FEATURE_ENTRY) | {"loo_grad"} <= random_methods, sorted(set(cs.FEATURE_ENTRY) - random_methods)
+    assert len(random_methods - set(cs.FEATURE_ENTRY) - set(cs.SETTERS)) >= 8          # and the old vocabulary
+    named = {cs.ENTRY[m] for s in FEATURE_NAMED for _c, m, _kw in s["steps"]}
+    assert set(TWELVE) | {"gpak_loo_grad"} <= named, sorted(set(TWELVE) - named)
+    declared = set()
+    for h in cs.FEATURE_HEADERS:
+        declared |= set(header_functions(h))
+    assert set(FEATURE_EXCLUDED) <= declared
+    missing = declared - named - set(FEATURE_EXCLUDED)
+    assert not missing, sorted(missing)
+    assert set(cs.FEATURE_ENTRY.values()) | {"gpak_loo_grad"} == declared - set(FEATURE_EXCLUDED)
+    # both forms of the calls that have two
+    kws = [(m, kw) for s in FEATURE_NAMED for _c, m, kw in s["steps"]]
+    assert any(m == "cv_folds" and kw.get("no_batch") for m, kw in kws) and any(m == "cv_folds_grad" and kw.get("no_batch") for m, kw in kws)
+    assert any(m == "condition" and kw.get("unfused") for m, kw in kws) and any(m == "condition" and kw.get("fsim") is False for m, kw in kws)
+    assert {kw["S"] for m, kw in kws if m == "condition"} == {3, 130} and {kw["prior"] for m, kw in kws if m == "sample_path"} == {"F96", "F1100"}
+    assert {kw["k"] for m, kw in kws if m == "local_neighbours_dev"} == {17, 128, 129}          # 129: the refusal
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group", cs.FEATURE_GROUPS)
+def test_feature_sequences_on_the_device(group, tmp_path):
+    """One fresh process per group; every non-setter step (a) bit-equal to a fresh context and (b) within the bound of the model;
+    the count of factorisations that of the unmutated CachingModel.  Shares _DEVICE_TROUBLE with the groups above."""
+    _sequences_on_the_device(group, tmp_path, cs.FEATURE_SEQUENCES)
+
+
+def test_a_group_refuses_every_feature_call():
+    """`g feature refusals`: GPAK_ENOTIMPL from each of the eleven calls of the feature headers that take a context (gpak_loo_grad:
+    `refusals (group)`), one factorisation over the whole sequence, and the NumPy-engine run asks none of them."""
+    seq = cs.GROUP_BY_NAME["g feature refusals"]
+    want = expected(seq)
+    refused = {w["method"] for w in want if w["res"][0] == cs.ENOTIMPL}
+    assert refused == set(cs.FEATURE_ENTRY) and len(refused) == 11
+    assert all(w["res"][0] == cs.OK for w in want if w["method"] not in cs.FEATURE_ENTRY)
+    assert set(counts_of(seq).values()) == {1}
+    cut = cs.engine_sequence(seq, 2)
+    assert cut is not None and not {m for _c, m, _kw in cut["steps"]} & set(cs.FEATURE_ENTRY)

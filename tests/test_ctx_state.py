@@ -6,7 +6,7 @@ tests/ctx_state_driver.cpp includes the header alone and is built with plain g++
 the events it passes through; the driver replays them, and after every step its state -- points, rung, z, backsolve,
 image, failed_col, factorisations -- must be the model's flags.  Then the comparison is shown to be able to fail: for each
 of the nine MUTATIONS the driver, fed the UNMUTATED events, must part from the mutated model's flags at or before the step
-at which tests/test_ctx_sequences.py catches that mutation.
+at which tests/test_ctx_sequences.py catches that mutation.  The same for cs.FEATURE_SEQUENCES and the FEATURE_MUTATIONS.
 """
 import os
 import subprocess
@@ -17,7 +17,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ctx_model as cm  # noqa: E402
 import ctx_sequences as cs  # noqa: E402
-from test_ctx_sequences import CACHE, CAUGHT_BY  # noqa: E402
+from test_ctx_sequences import CACHE, CAUGHT_BY, FEATURE_CAUGHT_BY  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gp_ss_ak_amd", "csrc")
@@ -103,6 +103,38 @@ def test_the_comparison_can_fail(replay, mutation):
     name, index, _method = CAUGHT_BY[mutation]
     seq = cs.BY_NAME[name]
     want = driver_states(replay, trace(seq))                  # the struct, fed what the unmutated model passes through
+    mutated = trace(seq, [mutation])
+    off = [i for i, (state, (_c, _ev, flags)) in enumerate(zip(want, mutated)) if state != flags]
+    assert off, f"{mutation}: the mutated model's flags are the struct's over all of '{name}'"
+    print(f"{mutation}: '{name}' step {off[0]} ({seq['steps'][off[0]][1]}): struct {want[off[0]]}, mutated model {mutated[off[0]][2]}; "
+          f"test_ctx_sequences catches it at step {index}")
+    assert off[0] <= index
+
+
+# ---- the feature calls (cs.FEATURE_SEQUENCES) ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [s["name"] for s in cs.FEATURE_SEQUENCES])
+def test_the_struct_is_the_model_over_the_feature_sequences(replay, name):
+    seq = cs.FEATURE_BY_NAME[name]
+    steps = trace(seq)
+    got = driver_states(replay, steps)
+    for i, ((c, ev, flags), state) in enumerate(zip(steps, got)):
+        assert state == flags, (name, i, seq["steps"][i][1], ev, "driver", state, "model", flags)
+    assert [e for _c, ev, _fl in steps for e in ev]
+
+
+def test_a_condition_call_raises_work_vectors_overwritten():
+    """gpak_condition_impl solves through dWork (csrc/condition.hip): the event follows the call's own bring-up-to-date."""
+    seq = cs.FEATURE_BY_NAME["simulation"]
+    for (_c, method, _kw), (_ctx, ev, _fl) in zip(seq["steps"], trace(seq)):
+        if method in ("condition", "sample_path"):
+            assert ev and ev[-1] == "work_vectors_overwritten", (method, ev)
+
+
+@pytest.mark.parametrize("mutation", cm.FEATURE_MUTATIONS)
+def test_the_feature_comparison_can_fail(replay, mutation):
+    name, index, _method = FEATURE_CAUGHT_BY[mutation]
+    seq = cs.FEATURE_BY_NAME[name]
+    want = driver_states(replay, trace(seq))
     mutated = trace(seq, [mutation])
     off = [i for i, (state, (_c, _ev, flags)) in enumerate(zip(want, mutated)) if state != flags]
     assert off, f"{mutation}: the mutated model's flags are the struct's over all of '{name}'"
